@@ -12,7 +12,9 @@ N x 4096 batch and one RCCL int32 sum all-reduce per step gives every rank every
 Started plainly with --gpus N > 1 (no torchrun), the script launches its N ranks itself -- before the parent
 has made any GPU call -- and relays rank 0's line; it never falls back to fewer ranks than asked for.
 
-One JSON line on rank 0.  Extra objects: `roofline` (the dominant score kernel against the bound it really
+One JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps, writes the last step's counts with
+--dump-outputs DIR and prints the line.  With --full it also runs the legs that fill the extra objects: `roofline`
+(the dominant score kernel against the bound it really
 hits: FP64 vector-ALU issue slots; live HIP-event time, counter values replayed from profiles/rN and labelled
 so), `roofline_refit` (the HBM-bound full-cloud scan, everything measured live), `masks_out` (the same step
 with inlier masks written), `cpu_baseline` (the oracle, 1 thread, bounded sample; `cpu_baseline_mt`: OpenMP
@@ -44,10 +46,10 @@ FLOPS_PER_TEST = {"plane": 13, "sphere": 20, "cylinder": 34, "cone": 140}
 KINDS = ["plane", "sphere", "cylinder", "cone"]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--prewarm-ms", type=float, default=40.0,
                     help="before the W warm-up steps, repeat the step for about this many ms so that the GPU has settled at "
@@ -66,9 +68,17 @@ def parse():
     ap.add_argument("--lists", choices=["auto", "on", "off"], default="auto",
                     help="rh_set_option st_cull on the scored cloud: super-tile candidate lists in front of the score kernel by the "
                          "library's own rule (auto), always, never.  Profiling passes that run one batch at a time pass what the default run took")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline step, run every other leg: the spread regions, one batch in flight, per-kind launches "
+                         "and rooflines, masks, refit, Float32, HBM probe, CPU baselines, end to end, the cfg2 / cfg5 children and, "
+                         "at N > 1, the per-rank and sharded end-to-end legs.  A plain run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the int32 score of every candidate "
+                         "of the batch, all ranks' after the all-reduce) as DIR/counts.npy in float64")
     ap.add_argument("--spread-regions", type=int, default=5,
-                    help="after the timed region, repeat the same K-step region this many times and report min / median / max of the "
-                         "metric as `value_spread` (the headline `value` stays the first region)")
+                    help="--full: after the timed region, repeat the same K-step region this many times and report min / median / max "
+                         "of the metric as `value_spread` (the headline `value` stays the first region)")
     ap.add_argument("--no-cfg5", action="store_true", help="skip the 50M-point / cones leg (a child process at N = 1)")
     ap.add_argument("--no-cfg2", action="store_true", help="skip the 1M-point / 6-primitive leg (a child process at N = 1)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
@@ -88,10 +98,14 @@ def parse():
                          "library itself (rh_comm_* of the C ABI: librccl directly, the path a Julia / C host uses)")
     ap.add_argument("--no-e2e-octree", action="store_true", help="skip the octree-sampling end-to-end leg")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the cpu_baseline legs of the score step (the end-to-end prefix check stays)")
-    ap.add_argument("--detail-out", default=DETAIL_DEFAULT,
+    ap.add_argument("--detail-out", default=None,
                     help="where rank 0 writes the full result document (notes, per-kind diagnostics, nested cfg2/cfg5 legs, counter "
-                         "provenance); stdout carries only the compact line (< 4 KB)")
-    return ap.parse_args()
+                         "provenance); stdout carries only the compact line (< 4 KB).  Default: none for a plain run; with --full "
+                         "bench_detail.json beside this script, or in the temporary directory when the checkout is read-only")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def _newest_profile(fname):
@@ -156,7 +170,14 @@ def pmc_replay(kernel_key, enabled, suffix=""):
     return out
 
 
-DETAIL_DEFAULT = os.path.join(ROOT, "bench_detail.json")
+def detail_default():
+    """--full without --detail-out: bench_detail.json beside this script, where the checkout is writable"""
+    if os.access(ROOT, os.W_OK):
+        return os.path.join(ROOT, "bench_detail.json")
+    import tempfile
+    return os.path.join(tempfile.gettempdir(), "bench_detail_%d.json" % os.getpid())
+
+
 LINE_MAX_BYTES = 4096        # the driver keeps a bounded tail of stdout: the line it parses must fit with room to spare
 LINE_MAX_STR = 120
 
@@ -335,6 +356,8 @@ def shapes_to_c(R, L, cands):
 
 def main():
     args = parse()
+    if args.full and args.detail_out is None:
+        args.detail_out = detail_default()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ:
@@ -529,10 +552,13 @@ def main():
         dt = float(tmax.item())
     ms_per_step = 1e3 * dt / args.steps
     value = b_global * args.steps / dt
+    # what the last timed step handed its caller: every candidate's count (after the all-reduce at N > 1)
+    counts_h = (lib_bufs[(lib_k[0] - 1) & 1] if libcomm is not None else
+                scorer.result(scorer.k - 1) if scorer is not None else ring[(ring_k[0] - 1) % in_flight]).cpu().numpy()
     # the same K-step region a few more times (each with its own fence on both sides): the spread of `value` on this box.
     # `value` itself is the FIRST region above, exactly as the contract times it.
     spread_vals = []
-    for _ in range(max(0, args.spread_regions)):
+    for _ in range(max(0, args.spread_regions) if args.full else 0):
         fence()
         ring_k[0] = 0
         t1 = time.perf_counter()
@@ -550,7 +576,7 @@ def main():
     L.check(lib.rh_score_launch_info(pc._h, linfo))
     launch_R, lists_used = int(linfo[0]), bool(linfo[1])
     one_in_flight = None
-    if in_flight > 1:   # every buffer of the ring holds the same batch's counts; then the same region one batch at a time
+    if in_flight > 1 and args.full:   # every buffer of the ring holds the same batch's counts; then the same region one batch at a time
         for r in ring[1:]:
             if args.steps >= in_flight and not torch.equal(r, counts):
                 raise SystemExit("PARITY FAILURE: count buffers of the batches in flight differ")
@@ -566,8 +592,6 @@ def main():
         one_in_flight = {"ms_per_step": sorted(vals)[1], "value": b_global / (1e-3 * sorted(vals)[1]),
                          "note": "the same K-step region with batches_in_flight = 1 (median of 3): one batch's prepare + score launches at a time"}
         R.set_option("batches_in_flight", in_flight, cloud=pc)
-    counts_h = (lib_bufs[(lib_k[0] - 1) & 1] if libcomm is not None else
-                scorer.result(scorer.k - 1) if scorer is not None else counts).cpu().numpy()
 
     out = {
         "metric": "candidates_scored_per_sec", "value": value, "unit": "candidates/s", "n_gpus": world,
@@ -596,7 +620,7 @@ def main():
     # ---- N > 1: what each rank saw, so that the first run on a real multi-GPU node can be read -- per rank the timed region's
     # step, the score launch alone, the all-reduce alone (both with a host wait each: latencies, not the pipelined step)
     per_rank = None
-    if multi:
+    if multi and args.full:
         try:
             kd = max(5, min(20, args.steps))
             fence()
@@ -631,7 +655,7 @@ def main():
     # dealt round-robin to the ranks, windows' candidate lists exchanged through host shared memory, extractions
     # replicated).  Strong scaling: the same scene, the same result as one GPU, bit for bit.
     e2e_sharded = None
-    if world > 1 and not args.no_e2e:
+    if world > 1 and args.full and not args.no_e2e:
         try:
             import hashlib
             rp = R.ransacparameters(types, iteration={"minsubsetN": 4096, "itermax": args.e2e_iters, "τ": 900, "prob_det": 0.9})
@@ -691,7 +715,7 @@ def main():
             fence()
 
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- per-kind kernel time (HIP events) and rooflines -----------------------------
         per_kind = {}
         reps = 30
@@ -1074,31 +1098,6 @@ def main():
             out["oracle_checked"] = int(max(nb, nb_mt))
             del oc
 
-        if args.oracle_check > 0 and world == 1:
-            from oracle import oracle as orc
-            k_chk = min(args.oracle_check, b_global)
-            sel = sorted({int(round(i * (b_global - 1) / max(1, k_chk - 1))) for i in range(k_chk)})
-            oc = orc.Cloud(xyz, nrm, subs[0])
-            oarr_c = (orc.Shape * len(sel))()
-            for j, i in enumerate(sel):
-                oarr_c[j] = orc.Shape.from_buffer_copy(bytes(arr[i]))
-            try:
-                avail = len(os.sched_getaffinity(0))
-            except AttributeError:
-                avail = os.cpu_count() or 1
-            t0 = time.perf_counter()
-            chk = oc.score_batch_mt(oarr_c, orc.Params.from_buffer_copy(bytes(cp)), max(1, min(16, avail)))
-            t_chk = time.perf_counter() - t0
-            if not np.array_equal(chk, counts_h[sel]):
-                bad = [sel[j] for j in range(len(sel)) if chk[j] != counts_h[sel[j]]]
-                raise SystemExit("PARITY FAILURE: GPU counts differ from the oracle on candidates %s" % bad[:10])
-            kinds_chk = sorted({cands[i][0] for i in sel}, key=KINDS.index)
-            out["oracle_checked"] = max(int(out.get("oracle_checked", 0)), len(sel))
-            out["oracle_check"] = {"candidates": len(sel), "kinds": kinds_chk, "seconds": t_chk,
-                                   "inliers": int(chk.sum()), "note": "counts of %d candidates spread evenly over the batch, "
-                                   "oracle (OpenMP) vs the timed launch's: identical" % len(sel)}
-            del oc
-
         # ---- end to end: shapes / s of the whole ransac() loop on the same cloud ----------
         if not args.no_e2e:
             e2e = R.ransacparameters(types,
@@ -1202,7 +1201,7 @@ def main():
                 dpath = os.path.splitext(args.detail_out)[0] + "_%s.json" % name
                 if os.path.exists(dpath):
                     os.remove(dpath)
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", name, "--no-cfg5", "--no-cfg2", "--no-f32",
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--workload", name, "--no-cfg5", "--no-cfg2", "--no-f32",
                                     "--detail-out", dpath] +
                                    ([] if "--e2e-iters" in extra else ["--no-e2e", "--no-cpu"]) + extra, capture_output=True, text=True, timeout=900)
                 if r.returncode != 0:
@@ -1238,9 +1237,38 @@ def main():
                                     "this GPU, S = 1 562 500, cones in the batch; 1024 candidates of all four kinds (spread evenly over the timed batch) checked against the "
                                     "oracle; the refit scan streams 2.4 GB; a bounded end-to-end leg (4096 iterations, the oracle's loop "
                                     "compared on a 48-iteration prefix)")
-        write_detail(out, args.detail_out)
-        sys.stderr.write("bench.py: full result document -> %s\n" % args.detail_out)
-        sys.stderr.flush()
+    if rank == 0 and args.oracle_check > 0 and world == 1:
+        from oracle import oracle as orc
+        k_chk = min(args.oracle_check, b_global)
+        sel = sorted({int(round(i * (b_global - 1) / max(1, k_chk - 1))) for i in range(k_chk)})
+        oc = orc.Cloud(xyz, nrm, subs[0])
+        oarr_c = (orc.Shape * len(sel))()
+        for j, i in enumerate(sel):
+            oarr_c[j] = orc.Shape.from_buffer_copy(bytes(arr[i]))
+        try:
+            avail = len(os.sched_getaffinity(0))
+        except AttributeError:
+            avail = os.cpu_count() or 1
+        t0 = time.perf_counter()
+        chk = oc.score_batch_mt(oarr_c, orc.Params.from_buffer_copy(bytes(cp)), max(1, min(16, avail)))
+        t_chk = time.perf_counter() - t0
+        if not np.array_equal(chk, counts_h[sel]):
+            bad = [sel[j] for j in range(len(sel)) if chk[j] != counts_h[sel[j]]]
+            raise SystemExit("PARITY FAILURE: GPU counts differ from the oracle on candidates %s" % bad[:10])
+        kinds_chk = sorted({cands[i][0] for i in sel}, key=KINDS.index)
+        out["oracle_checked"] = max(int(out.get("oracle_checked", 0)), len(sel))
+        out["oracle_check"] = {"candidates": len(sel), "kinds": kinds_chk, "seconds": t_chk,
+                               "inliers": int(chk.sum()), "note": "counts of %d candidates spread evenly over the batch, "
+                               "oracle (OpenMP) vs the timed launch's: identical" % len(sel)}
+        del oc
+    if rank == 0:
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "counts.npy"), counts_h.astype(np.float64))
+        if args.detail_out:
+            write_detail(out, args.detail_out)
+            sys.stderr.write("bench.py: full result document -> %s\n" % args.detail_out)
+            sys.stderr.flush()
         print(compact_line(out, args.detail_out), flush=True)
     batch.free()
     if points_mode:

@@ -26,14 +26,15 @@ vectors are derived BY HAND from the source text, two kinds of them:
 
 tests/test_compat_exact_vectors.py runs them through the oracle, through every rounding-order variant of the
 oracle (CPU) and through the HIP kernels (score, both paths, and refit; -m gpu).
-Run once: python tests/golden/make_compat_exact_vectors.py; the JSON is committed.
+Run once: python tests/golden/make_compat_exact_vectors.py; the JSON is committed.  An argument writes the JSON there instead.
 """
 import json
 import math
 import os
+import sys
 from fractions import Fraction as Fr
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "compat_exact_vectors.json")
+OUT = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "compat_exact_vectors.json")
 NAN = "nan"
 
 

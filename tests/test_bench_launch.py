@@ -59,3 +59,44 @@ def test_self_launch_on_one_gpu_box(tmp_path):
     line = json.loads(last)
     assert json.load(open(tmp_path / "detail.json"))["n_gpus"] == 2     # the full document went to the side file
     assert line["n_gpus"] == 2 and line["rccl_ranks_seen"] == 2 and line["config"]["candidates_per_step"] == 8192
+
+
+def test_plain_and_full_options_parse():
+    """--steps sets the timed steps and must be >= 1; --full and --dump-outputs are off unless given."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench_mod", BENCH)
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = b.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        b.parse(["--steps", "0"])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_steps_counts(tmp_path):
+    """A plain run prints the headline keys without the --full legs and writes the last timed step's counts and nothing
+    else (a read-only checkout must do); the same arguments give the same counts (seeded inputs), and --oracle-check holds
+    the dumped counts against the oracle."""
+    import numpy as np
+    detail = os.path.join(ROOT, "bench_detail.json")
+    before = os.stat(detail).st_mtime_ns if os.path.exists(detail) else None
+    base = ["--workload", "cfg2", "--warmup", "2"]
+    lines = []
+    for k, extra in enumerate((["--steps", "5", "--oracle-check", "64"], ["--steps", "3"])):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--dump-outputs", str(tmp_path / ("d%d" % k))] + base + extra,
+                           env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for line, steps in zip(lines, (5, 3)):
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["metric"] == "candidates_scored_per_sec"
+        assert line["value"] > 0 and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert line["roofline"]["kernel"] is None and line["cpu_baseline"] is None and "masks_ms" not in line
+        assert "detail" not in line
+    assert (os.stat(detail).st_mtime_ns if os.path.exists(detail) else None) == before
+    assert lines[0]["oracle_checked"] == 64
+    c0, c1 = (np.load(tmp_path / ("d%d" % k) / "counts.npy") for k in (0, 1))
+    assert c0.dtype == np.float64 and c0.shape == (4096,) and np.array_equal(c0, np.round(c0)) and c0.sum() > 4096 * 100
+    assert np.array_equal(c0, c1)

@@ -723,7 +723,7 @@ def test_full_size_properties(cfg):
     assert np.array_equal(R.score_batch(pc, arr, cp), counts)
     assert counts.max() <= subs[0].size and counts.sum() > 4096 * 100
     oc = orc.Cloud(c["xyz"], c["nrm"], subs[0])
-    # oracle on: the whole batch (cfg2), every second candidate (cfg3; bench.py checks all 4096 on every run), every fourth
+    # oracle on: the whole batch (cfg2), every second candidate (cfg3; bench.py --full checks all 4096 on every run), every fourth
     # (cfg5: 1024 candidates, 170 of them cones; ~5 s on 16 threads at S = 1 562 500)
     sel = list(range(0, 4096, {"cfg2": 1, "cfg3": 2, "cfg5": 4}[cfg]))
     kinds_in = {cands[i].kind for i in sel}

@@ -1,8 +1,9 @@
 #!/bin/bash
 # per-kernel average durations of the bench's Float32-cloud leg under rocprofv3 (every kernel, sorted by total time)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/kstats_f32; rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -- python3 $GRAFT_REPO_ROOT/bench.py --workload cfg3 --no-cpu --no-cfg5 --no-cfg2 --no-e2e --detail-out "$OUT/detail.json" "$@" > "$OUT/line.json" 2> "$OUT/err.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -- python3 "$ROOT/bench.py" --full --workload cfg3 --no-cpu --no-cfg5 --no-cfg2 --no-e2e --detail-out "$OUT/detail.json" "$@" > "$OUT/line.json" 2> "$OUT/err.log"
 f=$(find "$OUT" -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<PY
 import csv,sys

@@ -47,14 +47,14 @@ if [ "$WHAT" = "stats" ]; then
 fi
 if [ "$ONLY" = "sq3" ]; then
     cd /tmp && export TMPDIR=/tmp
-    if [ "$WHAT" = "default" ]; then LI=$(lists_of cfg3); B="$ROOT/bench.py --no-cpu --no-cfg5 --no-cfg2 --no-f32 --no-per-kind"; SFX=""; else LI=$(lists_of $WHAT); B="$ROOT/bench.py --workload $WHAT --no-cpu --no-cfg5 --no-cfg2 --no-f32 --no-per-kind"; SFX="_$WHAT"; fi
+    if [ "$WHAT" = "default" ]; then LI=$(lists_of cfg3); B="$ROOT/bench.py --full --no-cpu --no-cfg5 --no-cfg2 --no-f32 --no-per-kind"; SFX=""; else LI=$(lists_of $WHAT); B="$ROOT/bench.py --full --workload $WHAT --no-cpu --no-cfg5 --no-cfg2 --no-f32 --no-per-kind"; SFX="_$WHAT"; fi
 elif [ "$WHAT" = "default" ]; then
-    python bench.py --detail-out "$OUT/bench_default_detail.json" > "$OUT/bench_default_unprofiled.json" 2> "$OUT/bench_default.err"
+    python bench.py --full --detail-out "$OUT/bench_default_detail.json" > "$OUT/bench_default_unprofiled.json" 2> "$OUT/bench_default.err"
     echo "bench done"
     LI=$(lists_of cfg3)
     echo "lists: $LI"
     cd /tmp && export TMPDIR=/tmp
-    B="$ROOT/bench.py --no-cpu --no-cfg5 --no-cfg2 --no-f32 --no-per-kind"
+    B="$ROOT/bench.py --full --no-cpu --no-cfg5 --no-cfg2 --no-f32 --no-per-kind"
     SFX=""
     rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/score_only" -- python3 $B --no-e2e --in-flight 1 --lists $LI --detail-out "$OUT/bench_score_only_under_rocprof_detail.json" > "$OUT/bench_score_only_under_rocprof.json" 2> "$OUT/score_only.err"
     echo "stats 1 done"
@@ -64,7 +64,7 @@ else
     LI=$(lists_of $WHAT)
     echo "lists: $LI"
     cd /tmp && export TMPDIR=/tmp
-    B="$ROOT/bench.py --workload $WHAT --no-cpu --no-cfg5 --no-cfg2 --no-f32 --no-per-kind"
+    B="$ROOT/bench.py --full --workload $WHAT --no-cpu --no-cfg5 --no-cfg2 --no-f32 --no-per-kind"
     SFX="_$WHAT"
     rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/score_only$SFX" -- python3 $B --no-e2e --in-flight 1 --lists $LI --steps 60 --warmup 10 --detail-out "$OUT/bench_score_only_under_rocprof${SFX}_detail.json" > "$OUT/bench_score_only_under_rocprof$SFX.json" 2> "$OUT/score_only$SFX.err"
     echo "stats $WHAT done"
