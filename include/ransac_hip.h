@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 109
+#define RH_VERSION 110
 
 enum {
     RH_OK = 0,
@@ -376,6 +376,34 @@ int rh_octree_node_info(const rh_octree *t, int32_t cell, double *origin3, doubl
 int rh_octree_node_points(const rh_octree *t, int32_t cell, int64_t *idx_out_1based, int64_t cap);   /* cell.data.incellpoints */
 /* cell.data.incellpoints[pc.isenabled[cell.data.incellpoints]] (fitting.jl:405-407) on the device, against cloud c's bits */
 int rh_octree_cell_enabled(rh_cloud *c, rh_octree *t, int32_t cell, int64_t *idx_out_1based, int64_t cap, int64_t *n_out);
+
+/* ---- point normals for a cloud without them (no counterpart in the reference, which starts from clouds with
+ *      normals: "If normal information is not available, there are algorithms to approximate it (PCA for example)",
+ *      docs/src/ransac.md:13) ----
+ * For every point p_i (0-based i):
+ *  1. neighbours: p_i itself first, then the other points ordered by d^2 = (dx*dx + dy*dy) + dz*dz (binary64,
+ *     dx = q.x - p.x), ties to the smaller index; the first k of that order; with radius > 0 those with
+ *     d^2 > radius*radius dropped.  m = what remains (1 <= m <= min(k, n));
+ *  2. C = sum (q - c)(q - c)^T / m over them, c their mean (binary64); eigenvalues l0 <= l1 <= l2;
+ *  3. normal = the unit eigenvector of l0; curvature = l0 / (l0 + l1 + l2);
+ *  4. degenerate (m < 3, l2 == 0 or l1 <= 1e-12 * l2): normal (0, 0, 0), curvature 0, flag 1; otherwise flag 0;
+ *  5. sign: the component of largest magnitude positive (the first on a tie), then
+ *     orient 0: kept; 1: negated if dot(n, viewpoint - p) < 0; 2: negated if dot(n, hint_i) < 0.
+ * The same bits on every run.  A zero normal never passes isparallel (src/utilities.jl:115-117), so a degenerate
+ * point never becomes an inlier; the result feeds rh_cloud_create as its nrm_aos.  hints_aos_or_null: n x 3
+ * (orient = 2 only).  curv / flags outputs are optional.  RH_E_INVALID: k outside 3..64, orient outside 0..2,
+ * orient = 2 without hints, radius negative or not finite, a coordinate not finite, n < 1. */
+typedef struct {
+    int32_t k;               /* 3..64 */
+    int32_t orient;          /* 0 canonical sign, 1 towards viewpoint, 2 along hints */
+    double radius;           /* 0 = no limit */
+    double viewpoint[3];     /* orient = 1 */
+} rh_normals_params;
+int rh_estimate_normals(const double *xyz_aos, int64_t n, const rh_normals_params *p, const double *hints_aos_or_null,
+                        int device, double *nrm_out_aos, double *curv_out_or_null, int32_t *flags_out_or_null);
+/* Julia's Vector{SVector{3,Float32}} in and out: the binary64 result on the widened coordinates, rounded once */
+int rh_estimate_normals_f32(const float *xyz_aos, int64_t n, const rh_normals_params *p, const float *hints_aos_or_null,
+                            int device, float *nrm_out_aos, float *curv_out_or_null, int32_t *flags_out_or_null);
 
 /* ---- tuning options ----
  * The library reads NO environment variable: what a caller may tune goes through this call, for one cloud or, with

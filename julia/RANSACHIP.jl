@@ -382,4 +382,45 @@ function scorecounts_sharded(h::HIPCloud, comm::Ptr{Cvoid}, candidates::Vector{<
     return counts
 end
 
+# ---- point normals for a cloud without them (rh_estimate_normals; docs/src/ransac.md:13 "PCA for example") ----
+# typedef struct { int32_t k; int32_t orient; double radius; double viewpoint[3]; } rh_normals_params;   (40 bytes)
+struct RhNormalsParams
+    k::Cint
+    orient::Cint
+    radius::Cdouble
+    viewpoint::NTuple{3,Cdouble}
+end
+
+"""
+    estimatenormals(vertices; k = 16, radius = 0.0, viewpoint = nothing, hints = nothing) -> normals
+
+PCA normals of the k nearest neighbours (the point itself first, ties to the smaller index), computed on the GPU.
+`viewpoint` turns every normal towards it, `hints` (one vector per point) along them, neither: the largest component
+positive.  Degenerate points get a zero normal.  Float32 vertices give Float32 normals; the result goes into
+`RANSACCloud(vertices, normals, subsets)` as is.
+"""
+function estimatenormals(vertices::AbstractVector{SVector{3,T}}; k::Integer = 16, radius::Real = 0.0,
+                         viewpoint = nothing, hints = nothing, device::Integer = 0) where {T<:Union{Float32,Float64}}
+    viewpoint !== nothing && hints !== nothing && error("estimatenormals: a viewpoint or hints, not both")
+    orient = viewpoint !== nothing ? 1 : (hints !== nothing ? 2 : 0)
+    vp = viewpoint === nothing ? (0.0, 0.0, 0.0) : ntuple(i -> Cdouble(viewpoint[i]), 3)
+    p = RhNormalsParams(k, orient, radius, vp)
+    vs = convert(Vector{SVector{3,T}}, vertices)
+    hs = hints === nothing ? nothing : convert(Vector{SVector{3,T}}, hints)
+    out = Vector{SVector{3,T}}(undef, length(vs))
+    hp = hs === nothing ? Ptr{T}(C_NULL) : pointer(reinterpret(T, hs))
+    GC.@preserve vs hs out begin
+        if T == Float32
+            check(ccall((:rh_estimate_normals_f32, LIB), Cint,
+                (Ptr{Cfloat}, Int64, Ref{RhNormalsParams}, Ptr{Cfloat}, Cint, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Int32}),
+                pointer(reinterpret(Float32, vs)), length(vs), p, hp, device, pointer(reinterpret(Float32, out)), C_NULL, C_NULL))
+        else
+            check(ccall((:rh_estimate_normals, LIB), Cint,
+                (Ptr{Cdouble}, Int64, Ref{RhNormalsParams}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                pointer(reinterpret(Float64, vs)), length(vs), p, hp, device, pointer(reinterpret(Float64, out)), C_NULL, C_NULL))
+        end
+    end
+    return out
+end
+
 end # module

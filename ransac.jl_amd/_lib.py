@@ -54,6 +54,10 @@ class Result(C.Structure):
                 ("seconds_to_last_extraction", C.c_double), ("arena", C.c_void_p)]
 
 
+class NormalsParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("orient", C.c_int32), ("radius", C.c_double), ("viewpoint", C.c_double * 3)]
+
+
 class RansacHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libransac_hip error %d: %s" % (code, msg))
@@ -138,6 +142,9 @@ SIGNATURES = {
     "rh_score_batch_allreduce_dev": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _pp, _vp]),
     "rh_comm_fence": (C.c_int, [_vp, _vp]),
     "rh_comm_sync": (C.c_int, [_vp]),
+    "rh_estimate_normals": (C.c_int, [_dp, C.c_int64, C.POINTER(NormalsParams), _dp, C.c_int, _dp, _dp, _i32p]),
+    "rh_estimate_normals_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(NormalsParams), C.POINTER(C.c_float),
+                                          C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32p]),
 }
 
 # include/ransac_hip_diag.h: exported by the diag build only

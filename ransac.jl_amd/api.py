@@ -734,6 +734,40 @@ def refit_lsq(s, pc, params, max_iter=10):
     return shape_from_c(out), n.value, rms.value, it.value
 
 
+def estimatenormals(vertices, k=16, radius=0.0, viewpoint=None, hints=None, device=0, return_curvature=False,
+                    return_flags=False):
+    """Oriented normals for a cloud without them (rh_estimate_normals: PCA of the k nearest neighbours, the step
+    docs/src/ransac.md:13 leaves to the user).  vertices: (n, 3) float64 or float32; the result has that dtype and
+    feeds RANSACCloud(vertices, normals, subsets) as is.  radius > 0 drops neighbours farther than it; viewpoint
+    (3-vector) turns every normal towards it, hints ((n, 3), e.g. scanner directions or rough normals) along them;
+    neither: the largest component positive.  Degenerate points get (0, 0, 0) and flag 1.
+    Returns normals, then curvature and / or flags when asked for."""
+    if viewpoint is not None and hints is not None:
+        raise ValueError("estimatenormals: give a viewpoint or hints, not both")
+    f32 = np.asarray(vertices).dtype == np.float32
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    xyz = np.ascontiguousarray(vertices, dtype=t).reshape(-1, 3)
+    n = xyz.shape[0]
+    prm = L.NormalsParams(k=int(k), orient=0, radius=float(radius))
+    h = None
+    if viewpoint is not None:
+        prm.orient = 1
+        prm.viewpoint[:] = [float(x) for x in np.asarray(viewpoint, dtype=np.float64).reshape(3)]
+    if hints is not None:
+        prm.orient = 2
+        h = np.ascontiguousarray(hints, dtype=t).reshape(-1, 3)
+        if h.shape[0] != n:
+            raise ValueError("estimatenormals: %d hints for %d points" % (h.shape[0], n))
+    nrm = np.zeros((n, 3), dtype=t)
+    curv = np.zeros(n, dtype=t) if return_curvature else None
+    flags = np.zeros(n, dtype=np.int32) if return_flags else None
+    fn = lib().rh_estimate_normals_f32 if f32 else lib().rh_estimate_normals
+    check(fn(_p(xyz, ct), n, C.byref(prm), None if h is None else _p(h, ct), device, _p(nrm, ct),
+             None if curv is None else _p(curv, ct), None if flags is None else _p(flags, C.c_int32)))
+    out = (nrm,) + ((curv,) if return_curvature else ()) + ((flags,) if return_flags else ())
+    return out[0] if len(out) == 1 else out
+
+
 def invalidate_indexes(pc, indexlist):  # invalidate_indexes!: fitting.jl:197-202
     idx = np.ascontiguousarray(indexlist, dtype=np.int64)
     check(lib().rh_invalidate(pc._h, _p(idx, C.c_int64), idx.size))
