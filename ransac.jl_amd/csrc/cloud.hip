@@ -81,82 +81,64 @@ int rh_ensure_pin(rh_cloud *c, int64_t bytes)
     return RH_OK;
 }
 
-int rh_ensure_batch(rh_cloud *c, int64_t b)
+int rh_grow_buffer(rh_cloud *c, void **buf, int64_t *cap, int64_t new_cap, size_t bytes)
 {
-    if (b <= c->batch_cap) return RH_OK;
     RH_HIP(hipStreamSynchronize(c->stream));
-    int64_t cap = std::max<int64_t>(b, std::max<int64_t>(1024, c->batch_cap * 2));
-    (void)hipFree(c->d_shapes); (void)hipFree(c->d_prep); (void)hipFree(c->d_orig); (void)hipFree(c->d_counts);
-    c->d_shapes = nullptr; c->d_prep = nullptr; c->d_orig = nullptr; c->d_counts = nullptr;
-    c->batch_cap = 0;
-    RH_TRY(dev_alloc(&c->d_shapes, cap));
-    RH_TRY(dev_alloc(&c->d_prep, 4 * cap));
-    (void)hipFree(c->d_qpre);
-    c->d_qpre = nullptr;
-    RH_HIP(hipMalloc(&c->d_qpre, (size_t)(4 * cap) * 64));   // rhdev::rh_pre (40 B) or rh4::rh_cls (64 B) per slot
-    (void)hipFree(c->d_box);
-    c->d_box = nullptr;
-    RH_TRY(dev_alloc(&c->d_box, (int64_t)rh4::RH_BOX_FIELDS * 4 * cap));
-    RH_TRY(dev_alloc(&c->d_orig, 4 * cap));
-    RH_TRY(dev_alloc(&c->d_counts, cap));
-    if (c->f32) {
-        (void)hipFree(c->d_prep32);
-        c->d_prep32 = nullptr;
-        RH_HIP(hipMalloc(&c->d_prep32, (size_t)(4 * cap) * 12 * sizeof(float)));
-    }
-    c->batch_cap = cap;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    if (cap) *cap = 0;
+    RH_TRY(dev_alloc((char **)buf, (int64_t)bytes));
+    if (cap) *cap = new_cap;
     return RH_OK;
 }
 
-int rh_ensure_masks(rh_cloud *c, int64_t words)
+int rh_ensure_batch(rh_cloud *c, rh_batch_ws &w, int64_t b)
 {
-    if (words <= c->masks_cap) return RH_OK;
-    RH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_masks);
-    c->d_masks = nullptr;
-    c->masks_cap = 0;
-    RH_TRY(dev_alloc(&c->d_masks, words));
-    c->masks_cap = words;
+    if (b <= w.batch_cap) return RH_OK;
+    const int64_t cap = std::max<int64_t>(b, std::max<int64_t>(1024, w.batch_cap * 2));
+    w.batch_cap = 0;
+    RH_TRY(rh_grow_buffer(c, (void **)&w.d_shapes, nullptr, 0, sizeof(rh_shape) * (size_t)cap));
+    RH_TRY(rh_grow_buffer(c, (void **)&w.d_prep, nullptr, 0, sizeof(rh_prep) * (size_t)(4 * cap)));
+    RH_TRY(rh_grow_buffer(c, &w.d_qpre, nullptr, 0, (size_t)(4 * cap) * 64));   // rh4::rh_cls (64 B) per slot
+    RH_TRY(rh_grow_buffer(c, (void **)&w.d_box, nullptr, 0, sizeof(float) * (size_t)rh4::RH_BOX_FIELDS * (size_t)(4 * cap)));
+    RH_TRY(rh_grow_buffer(c, (void **)&w.d_orig, nullptr, 0, sizeof(int32_t) * (size_t)(4 * cap)));
+    RH_TRY(rh_grow_buffer(c, (void **)&w.d_counts, nullptr, 0, sizeof(int32_t) * (size_t)cap));
+    if (c->f32) RH_TRY(rh_grow_buffer(c, &w.d_prep32, nullptr, 0, (size_t)(4 * cap) * 12 * sizeof(float)));
+    w.batch_cap = cap;
     return RH_OK;
 }
 
-// v4 score kernel with masks: per candidate row a list of (internal word number, inlier word) entries, 16 bytes each,
-// at most one per group (mstride4 of them), and one int32 cursor per row, zero between batches
-static int ensure_masks4(rh_cloud *c, int64_t b)
+// Where a batch's masks go before they are un-permuted.  The culled kernel (the batch has classifier records) leaves entry
+// lists: nothing to zero but, once, the new cursors.  The brute-force kernels OR into dense rows in internal order.
+static int rh_masks_begin(rh_cloud *c, rh_batch_ws &w, int32_t b, bool culled)
 {
-    c->mstride4 = (c->ngroups + 7) / 8 * 8;
-    const int64_t words = 2 * b * c->mstride4;      // (two 64-bit words per entry)
-    if (words > c->masks_int_cap) {
-        RH_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_masks_int);
-        c->d_masks_int = nullptr;
-        c->masks_int_cap = 0;
-        RH_TRY(dev_alloc(&c->d_masks_int, words));
-        c->masks_int_cap = words;
+    w.masks4 = false;
+    if (culled) {
+        w.mstride4 = (c->ngroups + 7) / 8 * 8;
+        const int64_t words = 2 * b * w.mstride4;      // (two 64-bit words per entry)
+        if (words > w.masks_int_cap) RH_TRY(rh_grow_buffer(c, (void **)&w.d_masks_int, &w.masks_int_cap, words, sizeof(uint64_t) * (size_t)words));
+        const int64_t cur_bytes = 4 * (int64_t)b;
+        if (cur_bytes > w.occ_cap) {
+            w.occ_cap = 0;
+            RH_TRY(rh_grow_buffer(c, (void **)&w.d_occ, nullptr, 0, (size_t)cur_bytes));
+            RH_HIP(hipMemsetAsync(w.d_occ, 0, (size_t)cur_bytes, c->stream));
+            w.occ_cap = cur_bytes;
+        }
+        w.masks4 = true;
+        return RH_OK;
     }
-    const int64_t cur_bytes = 4 * b;
-    if (cur_bytes > c->occ_cap) {
-        RH_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_occ);
-        c->d_occ = nullptr;
-        c->occ_cap = 0;
-        RH_TRY(dev_alloc(&c->d_occ, cur_bytes));
-        RH_HIP(hipMemsetAsync(c->d_occ, 0, (size_t)cur_bytes, c->stream));
-        c->occ_cap = cur_bytes;
-    }
+    const int64_t words = (int64_t)b * c->swords;
+    if (words > w.masks_int_cap) RH_TRY(rh_grow_buffer(c, (void **)&w.d_masks_int, &w.masks_int_cap, words, sizeof(uint64_t) * (size_t)words));
+    RH_HIP(hipMemsetAsync(w.d_masks_int, 0, sizeof(uint64_t) * (size_t)words, c->stream));
     return RH_OK;
 }
 
-static int ensure_masks_int(rh_cloud *c, int64_t words)
+// ... and from there to d_masks: dense rows in subset order
+static int rh_masks_finish(rh_cloud *c, rh_batch_ws &w, int32_t b, uint64_t *d_masks)
 {
-    if (words <= c->masks_int_cap) return RH_OK;
-    RH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_masks_int);
-    c->d_masks_int = nullptr;
-    c->masks_int_cap = 0;
-    RH_TRY(dev_alloc(&c->d_masks_int, words));
-    c->masks_int_cap = words;
-    return RH_OK;
+    const bool lists = w.masks4;
+    w.masks4 = false;
+    return lists ? rhk_unpermute_masks4(c, w, b, d_masks) : rhk_unpermute_masks(c, w.d_masks_int, b, d_masks);
 }
 
 // 63-bit Morton code of a point inside the subset's bounding box (21 bits per axis)
@@ -171,6 +153,19 @@ static inline uint64_t spread21(uint64_t v)
     return v;
 }
 
+// everything a batch workspace owns (and nothing else does): the one list of its buffers
+static void batch_ws_free(rh_batch_ws &w)
+{
+    if (w.stream) (void)hipStreamSynchronize(w.stream);
+    (void)hipFree(w.d_shapes); (void)hipFree(w.d_prep); (void)hipFree(w.d_orig); (void)hipFree(w.d_counts); (void)hipFree(w.d_nk2);
+    (void)hipFree(w.d_qpre); (void)hipFree(w.d_prep32); (void)hipFree(w.d_box); (void)hipFree(w.d_masks_int); (void)hipFree(w.d_occ);
+    (void)hipFree(w.d_stlist); (void)hipFree(w.d_stcount);
+    if (w.done) (void)hipEventDestroy(w.done);
+    if (w.start) (void)hipEventDestroy(w.start);
+    if (w.stream) (void)hipStreamDestroy(w.stream);
+    w = rh_batch_ws();
+}
+
 static void cloud_free(rh_cloud *c)
 {
     if (!c) return;
@@ -178,18 +173,12 @@ static void cloud_free(rh_cloud *c)
     // a caller's stream (rh_cloud_set_stream) may be gone by now: wait for the device instead of the handle
     if (c->stream != c->own_stream) (void)hipDeviceSynchronize();
     else if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    for (rh_batch_slot &s : c->alt) {
-        if (!s.stream) continue;
-        (void)hipStreamSynchronize(s.stream);
-        (void)hipFree(s.d_shapes); (void)hipFree(s.d_prep); (void)hipFree(s.d_orig); (void)hipFree(s.d_counts); (void)hipFree(s.d_nk2);
-        (void)hipFree(s.d_qpre); (void)hipFree(s.d_prep32); (void)hipFree(s.d_box); (void)hipFree(s.d_masks_int); (void)hipFree(s.d_occ); (void)hipFree(s.d_stlist); (void)hipFree(s.d_stcount);
-        (void)hipEventDestroy(s.done); (void)hipEventDestroy(s.start); (void)hipStreamDestroy(s.stream);
-    }
+    for (rh_batch_ws &w : c->ws) batch_ws_free(w);
     (void)hipFree(c->full); (void)hipFree(c->rec); (void)hipFree(c->crec); (void)hipFree(c->sel_list); (void)hipFree(c->set_ws); (void)hipFree(c->set_level); (void)hipFree(c->sub); (void)hipFree(c->dis);
     (void)hipFree(c->sub_idx0); (void)hipFree(c->enabled); (void)hipFree(c->sub_enabled);
-    (void)hipFree(c->sub_perm); (void)hipFree(c->gb); (void)hipFree(c->d_masks_int);
-    (void)hipFree(c->full32); (void)hipFree(c->sub32); (void)hipFree(c->d_prep32); (void)hipFree(c->d_qpre); (void)hipFree(c->d_zero);
-    (void)hipFree(c->s4_stats); (void)hipFree(c->d_box); (void)hipFree(c->gb32); (void)hipFree(c->st32); (void)hipFree(c->d_stlist); (void)hipFree(c->d_stcount); (void)hipFree(c->d_occ); (void)hipFree(c->unp_segmask);
+    (void)hipFree(c->sub_perm); (void)hipFree(c->gb);
+    (void)hipFree(c->full32); (void)hipFree(c->sub32); (void)hipFree(c->d_zero);
+    (void)hipFree(c->s4_stats); (void)hipFree(c->gb32); (void)hipFree(c->st32); (void)hipFree(c->unp_segmask);
     (void)hipFree(c->oct_code); (void)hipFree(c->oct_perm); (void)hipFree(c->oct_pos); (void)hipFree(c->oct_men);
     (void)hipFree(c->oct_prefix); (void)hipFree(c->oct_P); (void)hipFree(c->oct_tab); (void)hipFree(c->oct_code_o);
     (void)hipFree(c->oct_state); (void)hipFree(c->oct_adv_tab); (void)hipFree(c->oct_adv_bits); (void)hipFree(c->oct_adv_E);
@@ -197,8 +186,7 @@ static void cloud_free(rh_cloud *c)
     (void)hipFree(c->en_block_sums); (void)hipFree(c->dis_gb); (void)hipFree(c->dis_gb32);
     (void)hipFree(c->d_ndis); (void)hipFree(c->refit_mask); (void)hipFree(c->block_sums);
     (void)hipFree(c->word_prefix); (void)hipFree(c->idx_out); (void)hipFree(c->d_total);
-    (void)hipFree(c->d_shapes); (void)hipFree(c->d_prep); (void)hipFree(c->d_orig); (void)hipFree(c->d_nk); (void)hipFree(c->d_nk2);
-    (void)hipFree(c->d_counts); (void)hipFree(c->d_masks); (void)hipFree(c->d_ranks); (void)hipFree(c->d_stage);
+    (void)hipFree(c->d_nk); (void)hipFree(c->d_masks); (void)hipFree(c->d_ranks); (void)hipFree(c->d_stage);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -429,7 +417,7 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
     CK(dev_alloc(&c->idx_out, n));
     CK(dev_alloc(&c->d_total, 1));
     CK(dev_alloc(&c->d_nk, 4));
-    CK(dev_alloc(&c->d_nk2, 8));
+    CK(dev_alloc(&c->ws[0].d_nk2, 8));
     CKH(hipMemsetAsync(c->full, 0, sizeof(double) * 6 * (size_t)c->n_pad, c->stream));
     CKH(hipMemsetAsync(c->sub, 0, sizeof(double) * 6 * (size_t)c->s_pad, c->stream));
     CKH(hipMemsetAsync(c->dis, 0, sizeof(double) * 6 * (size_t)c->dis_stride, c->stream));
@@ -682,12 +670,13 @@ static int enter_nojoin(rh_cloud *c)
 // still have in flight ("batches_in_flight" > 1), so everything else sees one stream's order
 int rh_join_batches(rh_cloud *c)
 {
-    for (int i = 0; i < RH_MAX_IN_FLIGHT - 1; i++) {
-        if (c->alt_dirty[i]) RH_HIP(hipStreamWaitEvent(c->stream, c->alt[i].done, 0));
-        c->alt_dirty[i] = false;
-        c->alt_started[i] = false;
+    for (rh_batch_ws &w : c->ws) {
+        if (w.dirty) RH_HIP(hipStreamWaitEvent(c->stream, w.done, 0));
+        w.dirty = false;
+        w.started = false;
+        w.out_counts = nullptr;
+        w.out_masks = nullptr;
     }
-    for (int i = 0; i < RH_MAX_IN_FLIGHT; i++) { c->slot_counts[i] = nullptr; c->slot_masks[i] = nullptr; }
     c->pipe_k = 0;
     return RH_OK;
 }
@@ -763,10 +752,10 @@ static inline const uint64_t *enabled_for_kind(const rh_cloud *c, int kind, cons
 // all four kind bins (bin k at prep/orig + off[k], its size in d_nk[k]) against subset 1.
 // Culled path (subsets of RH_G2_MIN_POINTS points and more): ONE launch of score4.hip's kernel over all kinds, reading the
 // bins' classifier / culling records d_cls / d_box (64 B per slot at the same offsets / fields bstride apart); masks leave
-// it as entry lists (c->masks4).  ms_kind (the bench's per-kind leg): one launch per kind instead, the other kinds' bin
+// it as entry lists (w.masks4).  ms_kind (the bench's per-kind leg): one launch per kind instead, the other kinds' bin
 // sizes read as zero, an event before each.  Small subsets: the brute-force kernel, one launch per kind, masks in internal
 // order.  Float32 clouds: the same two paths with the exact tests in binary32.
-static int score_bins_subset(rh_cloud *c, const rh_params *p, const rh_prep *d_prep, const int32_t *d_orig,
+static int score_bins_subset(rh_cloud *c, rh_batch_ws &w, const rh_params *p, const rh_prep *d_prep, const int32_t *d_orig,
                              const int64_t off[4], const int32_t *d_nk, const int32_t nk_bound[4], int32_t total_bound,
                              int32_t *d_counts, uint64_t *d_masks_int, float *ms_kind, const void *d_cls = nullptr,
                              const float *d_box = nullptr, int64_t bstride = 0)
@@ -775,19 +764,11 @@ static int score_bins_subset(rh_cloud *c, const rh_params *p, const rh_prep *d_p
     for (int k = 0; k < 4; k++) en[k] = enabled_for_kind(c, k, p);
     if (rh_score_v4_enabled(c)) {
         if (d_cls == nullptr || d_box == nullptr) { rh_set_error("internal: culled scoring without the bins' classifier records"); return RH_E_INTERNAL; }
-        const rh_prep *pr[4];
-        const int32_t *og[4], *nk[4];
-        const void *cl[4];
-        const float *bx[4];
-        for (int k = 0; k < 4; k++) {
-            pr[k] = d_prep + off[k];
-            og[k] = d_orig + off[k];
-            nk[k] = d_nk + k;
-            cl[k] = (const char *)d_cls + (size_t)off[k] * 64;
-            bx[k] = d_box + off[k];
-        }
+        const rh_bins B = rh_bins_at(d_prep, d_orig, d_cls, d_box, off);
+        const int32_t *nk[4];
+        for (int k = 0; k < 4; k++) nk[k] = d_nk + k;
         if (!ms_kind)
-            return rhk_score_all_groups(c, en, pr, og, nk, total_bound, p->eps, p->cos_alpha, d_counts, d_masks_int, cl, bx, bstride);
+            return rhk_score_all_groups(c, w, en, B.prep, B.orig, nk, total_bound, p->eps, p->cos_alpha, d_counts, d_masks_int, B.cls, B.box, bstride);
         if (c->d_zero == nullptr) {
             RH_HIP(hipMalloc((void **)&c->d_zero, 64));
             RH_HIP(hipMemsetAsync(c->d_zero, 0, 64, c->stream));
@@ -797,16 +778,15 @@ static int score_bins_subset(rh_cloud *c, const rh_params *p, const rh_prep *d_p
             if (nk_bound[k] == 0) continue;
             const int32_t *nk1[4];
             for (int q = 0; q < 4; q++) nk1[q] = q == k ? nk[q] : c->d_zero;
-            RH_TRY(rhk_score_all_groups(c, en, pr, og, nk1, nk_bound[k], p->eps, p->cos_alpha, d_counts, d_masks_int, cl, bx, bstride));
+            RH_TRY(rhk_score_all_groups(c, w, en, B.prep, B.orig, nk1, nk_bound[k], p->eps, p->cos_alpha, d_counts, d_masks_int, B.cls, B.box, bstride));
         }
         return RH_OK;
     }
     if (c->f32) {   // Float32 cloud, small subset: float records from the batch's shapes, brute-force float kernel (f32.hip)
-        if (c->f32_shapes == nullptr) { rh_set_error("internal: Float32 scoring without the batch's shapes"); return RH_E_INTERNAL; }
+        if (w.f32_shapes == nullptr) { rh_set_error("internal: Float32 scoring without the batch's shapes"); return RH_E_INTERNAL; }
         for (int k = 0; k < 4; k++)
             if (ms_kind) RH_HIP(hipEventRecord(c->evk[k], c->stream));
-        return rhk_score_all_f32(c, c->f32_shapes, c->f32_via_orig, en, d_orig, off, d_nk, nk_bound, p->eps, p->cos_alpha,
-                                 d_counts, d_masks_int);
+        return rhk_score_all_f32(c, w, en, d_orig, off, d_nk, nk_bound, p->eps, p->cos_alpha, d_counts, d_masks_int);
     }
     for (int k = 0; k < 4; k++) {
         if (ms_kind) RH_HIP(hipEventRecord(c->evk[k], c->stream));
@@ -832,7 +812,8 @@ extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, co
         }
         nk[shapes[i].kind]++;
     }
-    RH_TRY(rh_ensure_batch(c, b));
+    rh_batch_ws &w = c->ws[0];
+    RH_TRY(rh_ensure_batch(c, w, b));
     // Pinned staging: [records | original positions | bin sizes | counts] -- every transfer of the call is
     // asynchronous and the call waits once.  Batches of the size scorecandidates! sees per iteration (a few
     // candidates; here: up to 32) go as ONE small transfer into a device block of the same layout, carrying the
@@ -875,12 +856,12 @@ extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, co
         h_orig[fill[k]] = i;
         fill[k]++;
     }
-    const rh_prep *d_prep_use = c->d_prep;
+    const rh_prep *d_prep_use = w.d_prep;
     const void *d_cls_use = nullptr;
     const float *d_box_use = nullptr;
     int64_t bstride_use = 0;
-    const int32_t *d_orig_use = c->d_orig, *d_nk_use = c->d_nk;
-    int32_t *d_counts_use = c->d_counts;
+    const int32_t *d_orig_use = w.d_orig, *d_nk_use = c->d_nk;
+    int32_t *d_counts_use = w.d_counts;
     if (staged) {
         memset(h_counts, 0, sizeof(int32_t) * (size_t)b);
         RH_HIP(hipMemcpyAsync(dp, hp, stage_bytes, hipMemcpyHostToDevice, c->stream));
@@ -890,33 +871,25 @@ extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, co
         d_counts_use = (int32_t *)(dp + o_counts);
         if (staged_cls) { d_cls_use = dp + o_cls; d_box_use = (const float *)(dp + o_box); bstride_use = b; }
     } else {
-        RH_HIP(hipMemcpyAsync(c->d_shapes, h_sorted, sizeof(rh_shape) * (size_t)b, hipMemcpyHostToDevice, c->stream));
-        RH_HIP(hipMemcpyAsync(c->d_orig, h_orig, sizeof(int32_t) * (size_t)b, hipMemcpyHostToDevice, c->stream));
+        RH_HIP(hipMemcpyAsync(w.d_shapes, h_sorted, sizeof(rh_shape) * (size_t)b, hipMemcpyHostToDevice, c->stream));
+        RH_HIP(hipMemcpyAsync(w.d_orig, h_orig, sizeof(int32_t) * (size_t)b, hipMemcpyHostToDevice, c->stream));
         RH_HIP(hipMemcpyAsync(c->d_nk, h_nk, 4 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        RH_TRY(rhk_prep_sorted(c, c->d_shapes, b, c->d_prep, c->d_counts, p->eps, p->cos_alpha));   // zeroes d_counts as well
-        if (c->qpre_v4) { d_cls_use = c->d_qpre; d_box_use = c->d_box; bstride_use = 4 * c->batch_cap; }
+        RH_TRY(rhk_prep_sorted(c, w, b, w.d_counts, p->eps, p->cos_alpha));   // zeroes d_counts as well
+        if (w.qpre_v4) { d_cls_use = w.d_qpre; d_box_use = w.d_box; bstride_use = 4 * w.batch_cap; }
     }
     uint64_t *d_masks = nullptr, *d_masks_int = nullptr;
-    c->masks4 = false;
     if (masks_out && c->swords > 0) {
-        RH_TRY(rh_ensure_masks(c, (int64_t)b * c->swords));
+        const int64_t words = (int64_t)b * c->swords;
+        if (words > c->masks_cap) RH_TRY(rh_grow_buffer(c, (void **)&c->d_masks, &c->masks_cap, words, sizeof(uint64_t) * (size_t)words));
         d_masks = c->d_masks;
-        if (d_cls_use != nullptr) {   // the culled kernel leaves entry lists: nothing to zero
-            RH_TRY(ensure_masks4(c, b));
-            c->masks4 = true;
-        } else {                      // the brute-force kernel ORs into dense rows in internal order
-            RH_TRY(ensure_masks_int(c, (int64_t)b * c->swords));
-            RH_HIP(hipMemsetAsync(c->d_masks_int, 0, sizeof(uint64_t) * (size_t)b * (size_t)c->swords, c->stream));
-        }
-        d_masks_int = c->d_masks_int;
+        RH_TRY(rh_masks_begin(c, w, b, d_cls_use != nullptr));
+        d_masks_int = w.d_masks_int;
     }
     const int64_t off64[4] = { off[0], off[1], off[2], off[3] };
-    c->f32_shapes = c->d_shapes;   // sorted like the bins
-    c->f32_via_orig = 0;
-    RH_TRY(score_bins_subset(c, p, d_prep_use, d_orig_use, off64, d_nk_use, nk, b, d_counts_use, d_masks_int, nullptr, d_cls_use, d_box_use, bstride_use));
-    if (d_masks_int && c->masks4) RH_TRY(rhk_unpermute_masks4(c, d_masks_int, c->d_occ, c->mstride4, b, d_masks));
-    else if (d_masks_int) RH_TRY(rhk_unpermute_masks(c, d_masks_int, b, d_masks));
-    c->masks4 = false;
+    w.f32_shapes = w.d_shapes;     // sorted like the bins
+    w.f32_via_orig = 0;
+    RH_TRY(score_bins_subset(c, w, p, d_prep_use, d_orig_use, off64, d_nk_use, nk, b, d_counts_use, d_masks_int, nullptr, d_cls_use, d_box_use, bstride_use));
+    if (d_masks_int) RH_TRY(rh_masks_finish(c, w, b, d_masks));
     RH_HIP(hipMemcpyAsync(h_counts, d_counts_use, sizeof(int32_t) * (size_t)b, hipMemcpyDeviceToHost, c->stream));
     if (d_masks)
         RH_HIP(hipMemcpyAsync(masks_out, d_masks, sizeof(uint64_t) * (size_t)b * (size_t)c->swords,
@@ -972,19 +945,35 @@ static int pick_concurrent_stream(const hipStream_t *busy, int nbusy, hipStream_
     return RH_OK;
 }
 
-static void swap_batch_slot(rh_cloud *c, rh_batch_slot &s)
+// What makes c->ws[slot] (slot >= 1) a slot of the pipeline: a stream beside the cloud's and the other slots', two events and
+// the bin-size buffer.  Made into locals and published only when all four exist, so a slot is never half made.
+static int batch_slot_create(rh_cloud *c, int slot)
 {
-    std::swap(c->stream, s.stream);
-    std::swap(c->batch_cap, s.batch_cap);
-    std::swap(c->d_shapes, s.d_shapes); std::swap(c->d_prep, s.d_prep); std::swap(c->d_orig, s.d_orig); std::swap(c->d_counts, s.d_counts);
-    std::swap(c->d_nk2, s.d_nk2); std::swap(c->d_qpre, s.d_qpre); std::swap(c->d_prep32, s.d_prep32); std::swap(c->d_box, s.d_box);
-    std::swap(c->nk2_flip, s.nk2_flip); std::swap(c->nk2_ready, s.nk2_ready); std::swap(c->qpre_v4, s.qpre_v4);
-    std::swap(c->d_masks_int, s.d_masks_int); std::swap(c->masks_int_cap, s.masks_int_cap); std::swap(c->d_occ, s.d_occ);
-    std::swap(c->occ_cap, s.occ_cap); std::swap(c->mstride4, s.mstride4);
-    std::swap(c->d_stlist, s.d_stlist); std::swap(c->d_stcount, s.d_stcount); std::swap(c->stlist_cap, s.stlist_cap); std::swap(c->stlist_nst, s.stlist_nst);
+    hipStream_t busy[RH_MAX_IN_FLIGHT];
+    int nbusy = 0;
+    busy[nbusy++] = c->stream;
+    for (int q = 1; q < RH_MAX_IN_FLIGHT; q++) if (q != slot && c->ws[q].stream != nullptr) busy[nbusy++] = c->ws[q].stream;
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr, start = nullptr;
+    int32_t *d_nk2 = nullptr;
+    RH_TRY(pick_concurrent_stream(busy, nbusy, &stream));
+    hipError_t e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&start, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_nk2, 8 * sizeof(int32_t));
+    if (e != hipSuccess) {   // (d_nk2 came last: there is none)
+        if (done) (void)hipEventDestroy(done);
+        if (start) (void)hipEventDestroy(start);
+        (void)hipStreamDestroy(stream);
+        rh_set_error("rh_score_batch_dev: batch slot %d: %s", slot, hipGetErrorString(e));
+        return RH_E_NODEVICE;
+    }
+    rh_batch_ws &w = c->ws[slot];
+    w.stream = stream; w.done = done; w.start = start; w.d_nk2 = d_nk2;
+    return RH_OK;
 }
 
-static int score_batch_dev_impl(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const rh_params *p,
+// one batch on workspace c->ws[slot]; c->stream is that workspace's stream (slot > 0: rh_score_batch_dev)
+static int score_batch_dev_impl(rh_cloud *c, int slot, const rh_shape *d_shapes, int32_t b, const rh_params *p,
                                 int32_t *d_counts, uint64_t *d_masks, float *ms_kind, bool joined = true)
 {
     RH_TRY(joined ? enter(c) : enter_nojoin(c));
@@ -993,40 +982,34 @@ static int score_batch_dev_impl(rh_cloud *c, const rh_shape *d_shapes, int32_t b
     const bool product_only = ms_kind && ms_kind[0] < 0.f;   // (profiling passes: no per-kind launches beside the product's)
     if (ms_kind) for (int k = 0; k < 5; k++) ms_kind[k] = 0.f;
     if (b == 0) return RH_OK;
-    RH_TRY(rh_ensure_batch(c, b));
+    rh_batch_ws &w = c->ws[slot];
+    RH_TRY(rh_ensure_batch(c, w, b));
     // bin sizes: two halves of d_nk2 used alternately; the prep kernel zeroes the counts and the other half,
     // so a step is two launches and no memset
-    if (!c->nk2_ready) {
-        RH_HIP(hipMemsetAsync(c->d_nk2, 0, 8 * sizeof(int32_t), c->stream));
-        c->nk2_ready = true;
+    if (!w.nk2_ready) {
+        RH_HIP(hipMemsetAsync(w.d_nk2, 0, 8 * sizeof(int32_t), c->stream));
+        w.nk2_ready = true;
     }
-    int32_t *nk_cur = c->d_nk2 + 4 * c->nk2_flip, *nk_next = c->d_nk2 + 4 * (1 - c->nk2_flip);
-    c->nk2_flip = 1 - c->nk2_flip;
-    RH_TRY(rhk_prep_binned(c, d_shapes, b, c->d_prep, c->d_orig, nk_cur, c->batch_cap, d_counts, nk_next, 1, p->eps, p->cos_alpha));
+    int32_t *nk_cur = w.d_nk2 + 4 * w.nk2_flip, *nk_next = w.d_nk2 + 4 * (1 - w.nk2_flip);
+    w.nk2_flip = 1 - w.nk2_flip;
+    RH_TRY(rhk_prep_binned(c, w, d_shapes, b, nk_cur, d_counts, nk_next, 1, p->eps, p->cos_alpha));
     uint64_t *d_masks_int = nullptr;
-    c->masks4 = false;
     if (d_masks && c->swords > 0) {
-        if (c->qpre_v4) {   // the culled kernel leaves entry lists: nothing to zero
-            RH_TRY(ensure_masks4(c, b));
-            c->masks4 = true;
-        } else {
-            RH_TRY(ensure_masks_int(c, (int64_t)b * c->swords));
-            RH_HIP(hipMemsetAsync(c->d_masks_int, 0, sizeof(uint64_t) * (size_t)b * (size_t)c->swords, c->stream));
-        }
-        d_masks_int = c->d_masks_int;
+        RH_TRY(rh_masks_begin(c, w, b, w.qpre_v4));
+        d_masks_int = w.d_masks_int;
     }
-    const int64_t off[4] = { 0, c->batch_cap, 2 * (int64_t)c->batch_cap, 3 * (int64_t)c->batch_cap };
+    const int64_t off[4] = { 0, w.batch_cap, 2 * w.batch_cap, 3 * w.batch_cap };
     const int32_t bound[4] = { b, b, b, b };
-    const void *d_cls = c->qpre_v4 ? c->d_qpre : nullptr;   // (made by rhk_prep_binned above)
-    c->f32_shapes = d_shapes;      // the caller's order: the float records go through d_orig
-    c->f32_via_orig = 1;
+    const void *d_cls = w.qpre_v4 ? w.d_qpre : nullptr;   // (made by rhk_prep_binned above)
+    w.f32_shapes = d_shapes;       // the caller's order: the float records go through d_orig
+    w.f32_via_orig = 1;
     if (ms_kind) {   // the product launch (all kinds in one kernel) first, then the per-kind launches
         ms_kind[4] = 0.f;
         if (c->ev_cull == nullptr) RH_HIP(hipEventCreate(&c->ev_cull));
         RH_HIP(hipEventRecord(c->evk[0], c->stream));
         c->time_cull = true;
         c->last_s4[1] = 0;
-        const int rc_s = score_bins_subset(c, p, c->d_prep, c->d_orig, off, nk_cur, bound, b, d_counts, d_masks_int, nullptr, d_cls, c->d_box, 4 * c->batch_cap);
+        const int rc_s = score_bins_subset(c, w, p, w.d_prep, w.d_orig, off, nk_cur, bound, b, d_counts, d_masks_int, nullptr, d_cls, w.d_box, 4 * w.batch_cap);
         c->time_cull = false;
         RH_TRY(rc_s);
         RH_HIP(hipEventRecord(c->evk[1], c->stream));
@@ -1040,15 +1023,13 @@ static int score_batch_dev_impl(rh_cloud *c, const rh_shape *d_shapes, int32_t b
         }
         if (!product_only) {
             RH_HIP(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * (size_t)b, c->stream));
-            if (d_masks_int && c->masks4) RH_HIP(hipMemsetAsync(c->d_occ, 0, sizeof(int32_t) * (size_t)b, c->stream));   // (the lists' cursors)
+            if (d_masks_int && w.masks4) RH_HIP(hipMemsetAsync(w.d_occ, 0, sizeof(int32_t) * (size_t)b, c->stream));   // (the lists' cursors)
             else if (d_masks_int) RH_HIP(hipMemsetAsync(d_masks_int, 0, sizeof(uint64_t) * (size_t)b * (size_t)c->swords, c->stream));
         }
     }
     if (!product_only)
-        RH_TRY(score_bins_subset(c, p, c->d_prep, c->d_orig, off, nk_cur, bound, b, d_counts, d_masks_int, ms_kind, d_cls, c->d_box, 4 * c->batch_cap));
-    if (d_masks_int && c->masks4) RH_TRY(rhk_unpermute_masks4(c, d_masks_int, c->d_occ, c->mstride4, b, d_masks));
-    else if (d_masks_int) RH_TRY(rhk_unpermute_masks(c, d_masks_int, b, d_masks));
-    c->masks4 = false;
+        RH_TRY(score_bins_subset(c, w, p, w.d_prep, w.d_orig, off, nk_cur, bound, b, d_counts, d_masks_int, ms_kind, d_cls, w.d_box, 4 * w.batch_cap));
+    if (d_masks_int) RH_TRY(rh_masks_finish(c, w, b, d_masks));
     if (ms_kind && !product_only) {
         RH_HIP(hipEventRecord(c->evk[4], c->stream));
         RH_HIP(hipEventSynchronize(c->evk[4]));
@@ -1067,46 +1048,35 @@ extern "C" int rh_score_batch_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t
     // next; with masks the un-permutation of one batch, HBM-bound, runs under the next batch's score launch, issue-bound); any other call on the cloud (and rh_cloud_sync /
     // rh_timer_stop) first makes the cloud's stream wait for the others.
     const int in_flight = c != nullptr && b > 0 && c->stream == c->own_stream ? rh_opt_int(c, RH_OPT_BATCHES_IN_FLIGHT, 1) : 1;
-    if (in_flight > 1) {
-        RH_TRY(enter_nojoin(c));
-        int slot = (int)(c->pipe_k % (uint32_t)in_flight);
-        // a caller whose buffers are not F apart (the same count buffer call after call, say): never two batches in flight on
-        // one buffer -- the streams are joined first and the batch runs alone (correct, only not overlapped)
-        for (int t = 0; t < RH_MAX_IN_FLIGHT; t++)
-            if (t != slot && ((c->slot_counts[t] != nullptr && c->slot_counts[t] == d_counts) || (d_masks != nullptr && c->slot_masks[t] == d_masks))) {
-                RH_TRY(rh_join_batches(c));
-                slot = 0;
-                break;
-            }
-        c->pipe_k++;
-        c->slot_counts[slot] = d_counts;
-        c->slot_masks[slot] = d_masks;
-        if (slot == 0) return score_batch_dev_impl(c, d_shapes, b, p, d_counts, d_masks, nullptr, false);
-        rh_batch_slot &s = c->alt[slot - 1];
-        if (s.stream == nullptr) {
-            hipStream_t busy[RH_MAX_IN_FLIGHT];
-            int nbusy = 0;
-            busy[nbusy++] = c->stream;
-            for (int q = 0; q < RH_MAX_IN_FLIGHT - 1; q++) if (q != slot - 1 && c->alt[q].stream != nullptr) busy[nbusy++] = c->alt[q].stream;
-            RH_TRY(pick_concurrent_stream(busy, nbusy, &s.stream));
-            RH_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-            RH_HIP(hipEventCreateWithFlags(&s.start, hipEventDisableTiming));
-            RH_HIP(hipMalloc((void **)&s.d_nk2, 8 * sizeof(int32_t)));
+    if (in_flight <= 1) return score_batch_dev_impl(c, 0, d_shapes, b, p, d_counts, d_masks, nullptr);
+    RH_TRY(enter_nojoin(c));
+    int slot = (int)(c->pipe_k % (uint32_t)in_flight);
+    // a caller whose buffers are not F apart (the same count buffer call after call, say): never two batches in flight on
+    // one buffer -- the streams are joined first and the batch runs alone (correct, only not overlapped)
+    for (int t = 0; t < RH_MAX_IN_FLIGHT; t++)
+        if (t != slot && ((c->ws[t].out_counts != nullptr && c->ws[t].out_counts == d_counts) || (d_masks != nullptr && c->ws[t].out_masks == d_masks))) {
+            RH_TRY(rh_join_batches(c));
+            slot = 0;
+            break;
         }
-        if (!c->alt_started[slot - 1]) {   // once per pipelined stretch: the stream starts behind what the cloud's stream holds so far
-            RH_HIP(hipEventRecord(s.start, c->stream));
-            RH_HIP(hipStreamWaitEvent(s.stream, s.start, 0));
-            c->alt_started[slot - 1] = true;
-        }
-        swap_batch_slot(c, s);
-        const int rc = score_batch_dev_impl(c, d_shapes, b, p, d_counts, d_masks, nullptr, false);
-        swap_batch_slot(c, s);
-        // (also behind a failed call: whatever it did enqueue on the slot's stream is waited for at the next join)
-        RH_HIP(hipEventRecord(s.done, s.stream));
-        c->alt_dirty[slot - 1] = true;
-        return rc;
+    c->pipe_k++;
+    rh_batch_ws &w = c->ws[slot];
+    w.out_counts = d_counts;
+    w.out_masks = d_masks;
+    if (slot == 0) return score_batch_dev_impl(c, 0, d_shapes, b, p, d_counts, d_masks, nullptr, false);
+    if (w.stream == nullptr) RH_TRY(batch_slot_create(c, slot));
+    if (!w.started) {   // once per pipelined stretch: the stream starts behind what the cloud's stream holds so far
+        RH_HIP(hipEventRecord(w.start, c->stream));
+        RH_HIP(hipStreamWaitEvent(w.stream, w.start, 0));
+        w.started = true;
     }
-    return score_batch_dev_impl(c, d_shapes, b, p, d_counts, d_masks, nullptr);
+    c->stream = w.stream;        // the one redirection: every launcher below enqueues on c->stream and takes its buffers from w
+    const int rc = score_batch_dev_impl(c, slot, d_shapes, b, p, d_counts, d_masks, nullptr, false);
+    c->stream = c->own_stream;   // (in_flight > 1 only on the cloud's own stream)
+    // (also behind a failed call: whatever it did enqueue on the slot's stream is waited for at the next join)
+    RH_HIP(hipEventRecord(w.done, w.stream));
+    w.dirty = true;
+    return rc;
 }
 
 extern "C" int rh_last_list_launch_ms(rh_cloud *c, float *ms_out)
@@ -1127,7 +1097,7 @@ extern "C" int rh_score_batch_dev_timed(rh_cloud *c, const rh_shape *d_shapes, i
                                         int32_t *d_counts, uint64_t *d_masks, float *ms_kind_out)
 {
     if (!ms_kind_out) { rh_set_error("rh_score_batch_dev_timed: ms_kind_out is NULL"); return RH_E_INVALID; }
-    return score_batch_dev_impl(c, d_shapes, b, p, d_counts, d_masks, ms_kind_out);
+    return score_batch_dev_impl(c, 0, d_shapes, b, p, d_counts, d_masks, ms_kind_out);
 }
 
 // ------------------------------------------------------------------ refit ----

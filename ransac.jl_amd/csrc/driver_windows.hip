@@ -86,19 +86,14 @@ int Driver::run_chained_windows(const size_t status_bytes)
             RUN(rhk_oct_window_begin(c, c->oct_state));   // the list of this window starts at position 0
         }
         RUNH(hipMemsetAsync(w.d_status, 0, status_bytes, c->stream));
-        RUN(rh_ensure_batch(c, w.entries_cap));
+        rh_batch_ws &ws = c->ws[0];
+        RUN(rh_ensure_batch(c, ws, w.entries_cap));
+        const rh_bins B = rh_ws_bins(ws);
         const uint64_t *enw[4];
-        const rh_prep *pr[4];
-        const int32_t *og[4], *nkp[4];
-        const void *clsw[4];
-        const float *boxw[4];
+        const int32_t *nkp[4];
         for (int q = 0; q < 4; q++) {
             enw[q] = (q == RH_SPHERE && !p->sphere_uses_enabled) ? nullptr : c->sub_enabled;
-            pr[q] = c->d_prep + (int64_t)q * c->batch_cap;
-            og[q] = c->d_orig + (int64_t)q * c->batch_cap;
             nkp[q] = c->d_nk + q;
-            clsw[q] = (const char *)c->d_qpre + (size_t)q * (size_t)c->batch_cap * 64;
-            boxw[q] = c->d_box + (int64_t)q * c->batch_cap;
         }
         c->s4_stop = &c->oct_state->stop;
         c->s4_open_count = true;
@@ -106,10 +101,10 @@ int Driver::run_chained_windows(const size_t status_bytes)
         for (int32_t it = 0; it < W && rc == RH_OK; it++) {
             rc = rhk_sample_fit(c, p, rng->s[0], k0 + it, 1, (int32_t)en.count, c->oct_state->P, w.d_entries, w.entries_cap, w.d_status, 1,
                                 c->d_nk, it, c->oct_state);
-            if (rc == RH_OK) rc = rhk_prep_entries(c, w.d_entries, (const int32_t *)w.d_status, w.entries_cap, per_it, w.d_counts, 1, p->eps,
+            if (rc == RH_OK) rc = rhk_prep_entries(c, ws, w.d_entries, (const int32_t *)w.d_status, w.entries_cap, per_it, w.d_counts, 1, p->eps,
                                                    p->cos_alpha, c->oct_state);
-            if (rc == RH_OK) rc = rhk_score_all_groups(c, enw, pr, og, nkp, std::min<int32_t>(per_it, std::max<int32_t>((int32_t)((int64_t)cnt_est * bound_pct / 100) + 64, 1024)), p->eps,
-                                                       p->cos_alpha, w.d_counts, nullptr, clsw, boxw, 4 * c->batch_cap);
+            if (rc == RH_OK) rc = rhk_score_all_groups(c, ws, enw, B.prep, B.orig, nkp, std::min<int32_t>(per_it, std::max<int32_t>((int32_t)((int64_t)cnt_est * bound_pct / 100) + 64, 1024)), p->eps,
+                                                       p->cos_alpha, w.d_counts, nullptr, B.cls, B.box, 4 * ws.batch_cap);
             if (rc == RH_OK) rc = rhk_oct_advance(c, p, c->oct_state, w.d_entries, w.d_status, w.entries_cap, w.d_counts, it, k0 + it, w.h_list,
                                                   w.h_list_counts, w.h_list_rank, w.h_list_slot, w.h_hdr);
             if (rc == RH_OK && hipEventRecord(w.ev_it[it], c->stream) != hipSuccess) { rh_set_error("hipEventRecord failed"); rc = RH_E_NODEVICE; }
@@ -300,29 +295,22 @@ int Driver::run_streams_device()
                            fused_score ? c->d_nk : nullptr));
         w.scored = false;
         if (fused_score) {
-            RUN(rh_ensure_batch(c, w.entries_cap));
+            rh_batch_ws &ws = c->ws[0];
+            RUN(rh_ensure_batch(c, ws, w.entries_cap));
             // launch sizes from the previous windows' list lengths; any length is handled (the
             // kernels read the true count), a longer list only gets fewer blocks per candidate
             const int32_t bound = std::min<int32_t>(w.entries_cap, std::max<int32_t>(4 * cnt_est, 1024));
-            RUN(rhk_prep_entries(c, w.d_entries, (const int32_t *)w.d_status, w.entries_cap, w.entries_cap, w.d_counts, 1, p->eps, p->cos_alpha));
+            RUN(rhk_prep_entries(c, ws, w.d_entries, (const int32_t *)w.d_status, w.entries_cap, w.entries_cap, w.d_counts, 1, p->eps, p->cos_alpha));
+            const rh_bins B = rh_ws_bins(ws);
             const uint64_t *enw[4];
-            const rh_prep *pr[4];
-            const int32_t *og[4], *nkp[4];
+            const int32_t *nkp[4];
             for (int q = 0; q < 4; q++) {
                 enw[q] = (q == RH_SPHERE && !p->sphere_uses_enabled) ? nullptr : c->sub_enabled;
-                pr[q] = c->d_prep + (int64_t)q * c->batch_cap;
-                og[q] = c->d_orig + (int64_t)q * c->batch_cap;
                 nkp[q] = c->d_nk + q;
             }
-            const void *clsw[4];
-            const float *boxw[4];
-            for (int q = 0; q < 4; q++) {
-                clsw[q] = (const char *)c->d_qpre + (size_t)q * (size_t)c->batch_cap * 64;
-                boxw[q] = c->d_box + (int64_t)q * c->batch_cap;
-            }
             c->s4_open_count = true;   // (bound is a guess: the kernel's tail launch covers a longer list)
-            const int rcs = rhk_score_all_groups(c, enw, pr, og, nkp, bound, p->eps, p->cos_alpha, w.d_counts, nullptr,
-                                                 clsw, boxw, 4 * c->batch_cap);
+            const int rcs = rhk_score_all_groups(c, ws, enw, B.prep, B.orig, nkp, bound, p->eps, p->cos_alpha, w.d_counts, nullptr,
+                                                 B.cls, B.box, 4 * ws.batch_cap);
             c->s4_open_count = false;
             if (rcs != RH_OK) return rcs;
             w.scored = true;

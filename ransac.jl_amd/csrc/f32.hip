@@ -172,29 +172,28 @@ int rhk_f32_build(rh_cloud *c)
     return RH_OK;
 }
 
-int rhk_prep_f32(rh_cloud *c, const rh_shape *d_shapes, int via_orig, const int32_t *d_orig, const int64_t off[4],
-                 const int32_t *d_nk, int32_t nmax)
+int rhk_prep_f32(rh_cloud *c, rh_batch_ws &w, const int32_t *d_orig, const int64_t off[4], const int32_t *d_nk, int32_t nmax)
 {
     if (nmax <= 0) return RH_OK;
     Off4 o4;
     for (int k = 0; k < 4; k++) o4.o[k] = off[k];
-    hipLaunchKernelGGL(prep32_kernel, dim3(cdiv32(nmax, 256)), dim3(256), 0, c->stream, d_shapes, via_orig, d_orig, o4, d_nk,
-                       (rh_prepf *)c->d_prep32);
+    hipLaunchKernelGGL(prep32_kernel, dim3(cdiv32(nmax, 256)), dim3(256), 0, c->stream, w.f32_shapes, w.f32_via_orig, d_orig, o4, d_nk,
+                       (rh_prepf *)w.d_prep32);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
 
 // all kinds of a binned batch (the Float64 path's bins: orig / nk, bin k at off[k]) against subset 1; masks (optional) in
 // INTERNAL order like the other scorers
-int rhk_score_all_f32(rh_cloud *c, const rh_shape *d_shapes, int via_orig, const uint64_t *const en[4], const int32_t *d_orig,
+int rhk_score_all_f32(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const int32_t *d_orig,
                       const int64_t off[4], const int32_t *d_nk, const int32_t nk_bound[4], const double eps[4],
                       const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int)
 {
     int nmax = 0;
     for (int k = 0; k < 4; k++) nmax = std::max(nmax, (int)nk_bound[k]);
     if (nmax == 0 || c->s == 0) return RH_OK;
-    rh_prepf *prep32 = (rh_prepf *)c->d_prep32;
-    RH_TRY(rhk_prep_f32(c, d_shapes, via_orig, d_orig, off, d_nk, nmax));
+    rh_prepf *prep32 = (rh_prepf *)w.d_prep32;
+    RH_TRY(rhk_prep_f32(c, w, d_orig, off, d_nk, nmax));
     const int64_t ntiles = (c->s + RH_SC_TILE - 1) / RH_SC_TILE;
     for (int k = 0; k < 4; k++) {
         if (nk_bound[k] == 0) continue;

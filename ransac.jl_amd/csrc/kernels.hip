@@ -969,44 +969,43 @@ bool rh_score_v4_enabled(const rh_cloud *c)
     return c->f32 ? c->f32_groups : c->use_groups;
 }
 
-// eps + cosa given (and the bins are the cloud's own): the prep kernel also leaves the classifier and culling records of
-// the bins in c->d_qpre / c->d_box; c->qpre_v4 says so to the score dispatch
-static PreArgs pre_args(rh_cloud *c, const double *eps, const double *cosa)
+// eps + cosa given: the prep kernel also leaves the classifier and culling records of the workspace's bins in
+// w.d_qpre / w.d_box; w.qpre_v4 says so to the score dispatch
+static PreArgs pre_args(rh_cloud *c, rh_batch_ws &w, const double *eps, const double *cosa)
 {
     PreArgs QA;
     for (int k = 0; k < 4; k++) { QA.eps[k] = eps ? eps[k] : 0.0; QA.cosa[k] = cosa ? cosa[k] : 0.0; }
     QA.coord_mag = c->coord_mag;
     QA.nrm_mag = c->nrm_mag;
     QA.f32 = c->f32 ? 1 : 0;
-    QA.box = c->d_box;
-    QA.bstride = 4 * c->batch_cap;
-    c->qpre_v4 = eps != nullptr && cosa != nullptr && rh_score_v4_enabled(c) && c->d_box != nullptr && c->d_qpre != nullptr;
+    QA.box = w.d_box;
+    QA.bstride = 4 * w.batch_cap;
+    w.qpre_v4 = eps != nullptr && cosa != nullptr && rh_score_v4_enabled(c) && w.d_box != nullptr && w.d_qpre != nullptr;
     return QA;
 }
 
-int rhk_prep_sorted(rh_cloud *c, const rh_shape *d_shapes_sorted, int32_t b, rh_prep *d_prep, int32_t *d_counts_to_zero,
-                    const double *eps, const double *cosa)
+int rhk_prep_sorted(rh_cloud *c, rh_batch_ws &w, int32_t b, int32_t *d_counts_to_zero, const double *eps, const double *cosa)
 {
-    const bool own = d_prep == c->d_prep && eps != nullptr && cosa != nullptr;
-    const PreArgs QA = pre_args(c, own ? eps : nullptr, own ? cosa : nullptr);
+    const bool both = eps != nullptr && cosa != nullptr;
+    const PreArgs QA = pre_args(c, w, both ? eps : nullptr, both ? cosa : nullptr);
     if (b == 0) return RH_OK;
-    hipLaunchKernelGGL(prep_sorted_kernel, dim3(cdiv(b, 256)), dim3(256), 0, c->stream, d_shapes_sorted, b, d_prep,
-                       d_counts_to_zero, c->qpre_v4 ? (rh4::rh_cls *)c->d_qpre : (rh4::rh_cls *)nullptr, QA);
+    hipLaunchKernelGGL(prep_sorted_kernel, dim3(cdiv(b, 256)), dim3(256), 0, c->stream, (const rh_shape *)w.d_shapes, b, w.d_prep,
+                       d_counts_to_zero, w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre : (rh4::rh_cls *)nullptr, QA);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
 
-// prep + bin the first min(*d_count, cap_entries) entries into c->d_prep / c->d_orig / c->d_nk (batch_cap >= cap_entries)
-int rhk_prep_entries(rh_cloud *c, const rh_cand_entry *d_entries, const int32_t *d_count, int32_t cap_entries,
+// prep + bin the first min(*d_count, cap_entries) entries into w.d_prep / w.d_orig / c->d_nk (w.batch_cap >= cap_entries)
+int rhk_prep_entries(rh_cloud *c, rh_batch_ws &w, const rh_cand_entry *d_entries, const int32_t *d_count, int32_t cap_entries,
                      int32_t launch_bound, int32_t *d_counts, int nk_is_zero, const double *eps, const double *cosa,
                      const rh_oct_state *ost)
 {
     if (!nk_is_zero) RH_HIP(hipMemsetAsync(c->d_nk, 0, 4 * sizeof(int32_t), c->stream));
-    const PreArgs QA = pre_args(c, eps, cosa);
+    const PreArgs QA = pre_args(c, w, eps, cosa);
     if (launch_bound <= 0) return RH_OK;
     hipLaunchKernelGGL(prep_entries_kernel, dim3(cdiv(launch_bound, 256)), dim3(256), 0, c->stream, d_entries, d_count,
-                       cap_entries, c->d_prep, c->d_orig, c->d_nk, c->batch_cap, d_counts,
-                       c->qpre_v4 ? (rh4::rh_cls *)c->d_qpre : (rh4::rh_cls *)nullptr, QA, ost);
+                       cap_entries, w.d_prep, w.d_orig, c->d_nk, w.batch_cap, d_counts,
+                       w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre : (rh4::rh_cls *)nullptr, QA, ost);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
@@ -1021,13 +1020,11 @@ int32_t rh_spread_multiplier(int32_t b)
     return (int32_t)(m % b);
 }
 
-int rhk_prep_binned(rh_cloud *c, const rh_shape *d_shapes, int32_t b, rh_prep *d_prep, int32_t *d_orig,
-                    int32_t *d_nk, int64_t cap, int32_t *d_counts_to_zero, int32_t *d_nk_other, int nk_is_zero,
-                    const double *eps, const double *cosa)
+int rhk_prep_binned(rh_cloud *c, rh_batch_ws &w, const rh_shape *d_shapes, int32_t b, int32_t *d_nk, int32_t *d_counts_to_zero,
+                    int32_t *d_nk_other, int nk_is_zero, const double *eps, const double *cosa)
 {
     if (!nk_is_zero) RH_HIP(hipMemsetAsync(d_nk, 0, 4 * sizeof(int32_t), c->stream));
-    const bool own = d_prep == c->d_prep && cap == c->batch_cap;
-    PreArgs QA = pre_args(c, own ? eps : nullptr, own ? cosa : nullptr);
+    PreArgs QA = pre_args(c, w, eps, cosa);
     if (b == 0) return RH_OK;
     const int no_spread = rh_opt_on(c, RH_OPT_NO_SPREAD) ? 1 : 0;
     // (consumed by this launch: set by rh_score_batch_allreduce_dev around its score call)
@@ -1037,9 +1034,9 @@ int rhk_prep_binned(rh_cloud *c, const rh_shape *d_shapes, int32_t b, rh_prep *d
 #ifndef RH_PREP_BLOCK
 #define RH_PREP_BLOCK 64   // (one wave per block: the launch is a latency chain -- shape, bin reservation, divisions, records -- and 64 blocks spread it over 64 CUs: cfg3 step 0.0860 -> 0.0846 ms, cfg2 0.0431 -> 0.0421; 128: the same; 256: round 4)
 #endif
-    hipLaunchKernelGGL(prep_binned_kernel, dim3(cdiv(b, RH_PREP_BLOCK)), dim3(RH_PREP_BLOCK), 0, c->stream, d_shapes, b, d_prep, d_orig,
-                       d_nk, cap, d_counts_to_zero, d_nk_other, no_spread ? 1 : rh_spread_multiplier(b),
-                       c->qpre_v4 ? (rh4::rh_cls *)c->d_qpre : (rh4::rh_cls *)nullptr, QA, zx, zxn);
+    hipLaunchKernelGGL(prep_binned_kernel, dim3(cdiv(b, RH_PREP_BLOCK)), dim3(RH_PREP_BLOCK), 0, c->stream, d_shapes, b, w.d_prep, w.d_orig,
+                       d_nk, w.batch_cap, d_counts_to_zero, d_nk_other, no_spread ? 1 : rh_spread_multiplier(b),
+                       w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre : (rh4::rh_cls *)nullptr, QA, zx, zxn);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
@@ -1422,18 +1419,17 @@ int rhk_compact_generic(hipStream_t stream, const uint64_t *mask, int64_t nwords
 
 // all kinds against subset 1 in one launch of the culled kernel (score4.hip); cls / box: the bins' classifier and culling
 // records (prep kernels); nk_total_bound >= the number of candidates over all kinds
-int rhk_score_all_groups(rh_cloud *c, const uint64_t *const en[4], const rh_prep *const prep[4],
+int rhk_score_all_groups(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const rh_prep *const prep[4],
                          const int32_t *const orig[4], const int32_t *const nk[4], int32_t nk_total_bound,
                          const double eps[4], const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int,
                          const void *const cls[4], const float *const box[4], int64_t bstride)
 {
     if (c->ngroups == 0 || nk_total_bound <= 0) return RH_OK;
-    if (cls == nullptr || box == nullptr || !rh_score_v4_enabled(c) || c->gb32 == nullptr || (d_masks_int != nullptr && !c->masks4)) {
+    if (cls == nullptr || box == nullptr || !rh_score_v4_enabled(c) || c->gb32 == nullptr || (d_masks_int != nullptr && !w.masks4)) {
         rh_set_error("internal: the culled score kernel without its records (classifier, culling, group boxes, mask lists)");
         return RH_E_INTERNAL;
     }
-    return rhk_score4_all(c, en, prep, cls, box, bstride, orig, nk, nk_total_bound, eps, cosa, d_counts, d_masks_int,
-                          d_masks_int ? c->d_occ : nullptr, c->mstride4);
+    return rhk_score4_all(c, w, en, prep, cls, box, bstride, orig, nk, nk_total_bound, eps, cosa, d_counts, d_masks_int);
 }
 
 // liveness pass of a cloud without the culled path: candidates against dis[first, first + cnt) (counts only), brute force

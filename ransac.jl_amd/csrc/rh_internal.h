@@ -88,31 +88,75 @@ struct rh_s4_points {   // what the v4 score kernel runs over (score4.hip): poin
     int64_t stride, s, ngroups;
     const float *gb32;
 };
-// rh_score_batch_dev with two batches in flight (rh_set_option "batches_in_flight" = 2): batches take turns on the cloud's own
-// workspaces and stream and on these, so its prepare + score launches fill the chip while the previous batch's launch drains
+// Everything that belongs to ONE batch being prepared and scored: its buffers (grown on demand: rh_grow_buffer) and what the
+// launchers leave in them.  A cloud has RH_MAX_IN_FLIGHT of them (rh_cloud::ws).  ws[0] is the workspace of the cloud's own
+// stream: every path but the pipelined rh_score_batch_dev uses it alone.  With rh_set_option "batches_in_flight" = F > 1 the
+// batches of rh_score_batch_dev take turns on ws[0 .. F-1], slot k >= 1 on a stream of its own, so one batch's prepare + score
+// launches fill the chip while the previous batch's launch drains.  Whatever a launcher needs of a batch it gets as a
+// `rh_batch_ws &`; a buffer that is not in here is shared by all batches of the cloud (see "shared by the batches" below).
 #define RH_MAX_IN_FLIGHT 4
-struct rh_batch_slot {
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr, start = nullptr;
+struct rh_batch_ws {
+    // the slot in the pipeline (made by batch_slot_create for slots >= 1; null in ws[0], whose batches run on the cloud's stream)
+    hipStream_t stream = nullptr;      // rh_cloud::stream is this one while the slot's batch is queued
+    hipEvent_t done = nullptr, start = nullptr;   // behind the slot's last batch / where `stream` was ordered behind the cloud's
+    bool dirty = false;                // work on `stream` the cloud's own stream has not waited for yet
+    bool started = false;              // `stream` has been ordered behind the cloud's stream since the last join
+    const void *out_counts = nullptr, *out_masks = nullptr;   // (ws[0] too) the buffers the slot's batch in flight writes (null: none)
+    // the bins (rh_ensure_batch) and what the prep kernels leave in them
     int64_t batch_cap = 0;
-    rh_shape *d_shapes = nullptr;
-    rh_prep *d_prep = nullptr;
-    int32_t *d_orig = nullptr, *d_counts = nullptr, *d_nk2 = nullptr;
-    void *d_qpre = nullptr, *d_prep32 = nullptr;
-    float *d_box = nullptr;
-    uint16_t *d_stlist = nullptr;      // (the super-tile lists of the slot's batch)
+    rh_shape *d_shapes = nullptr;      // [batch_cap]
+    rh_prep *d_prep = nullptr;         // [4 * batch_cap], kind-major
+    int32_t *d_orig = nullptr, *d_counts = nullptr;   // [4 * batch_cap], [batch_cap]
+    void *d_prep32 = nullptr;          // [4 * batch_cap] float records (rh_prepf) of a Float32 cloud's bins (f32.hip)
+    void *d_qpre = nullptr;            // [4 * batch_cap] classifier records (rh4::rh_cls, 64 B) of the bins in d_prep; culling records: d_box
+    float *d_box = nullptr;            // [RH_BOX_FIELDS][4 * batch_cap] culling records of the same bins (v4 score kernel), structure of arrays
+    bool qpre_v4 = false;              // ... made by the last prep kernel (for the thresholds it was given)
+    int32_t *d_nk2 = nullptr;          // [8] rh_score_batch_dev's bin sizes: two halves used alternately, each batch zeroes the other
+    int nk2_flip = 0;
+    bool nk2_ready = false;
+    // masks in internal order, before un-permuting (rh_masks_begin / rh_masks_finish).  Culled kernel (masks4): per candidate
+    // row a list of (internal word number, inlier word) entries, 16 bytes each, at most one per group (mstride4 of them), and
+    // in d_occ one int32 cursor per row, zero between batches.  Brute-force kernels: dense rows.
+    uint64_t *d_masks_int = nullptr;
+    uint8_t *d_occ = nullptr;
+    int64_t masks_int_cap = 0, occ_cap = 0, mstride4 = 0;   // (in 64-bit words, bytes, entries)
+    bool masks4 = false;
+    // per-super-tile candidate lists of the batch being scored (score4.hip, st_cull_kernel): [nst][4 kinds][stlist_cap] slots, [nst][4] counts
+    uint16_t *d_stlist = nullptr;
     int32_t *d_stcount = nullptr;
     int64_t stlist_cap = 0, stlist_nst = 0;
-    uint64_t *d_masks_int = nullptr;   // (batches with mask output: the entry lists and their cursors)
-    uint8_t *d_occ = nullptr;
-    int64_t masks_int_cap = 0, occ_cap = 0, mstride4 = 0;
-    int nk2_flip = 0;
-    bool nk2_ready = false, qpre_v4 = false;
+    // Float32 clouds, brute-force kernel: the shapes of the batch being scored, on the device ...
+    const rh_shape *f32_shapes = nullptr;
+    int f32_via_orig = 0;              // ... indexed through d_orig (caller's order) or directly (sorted like the bins)
 };
+// the four kinds' bins of a prepared batch: candidate records, original positions, classifier and culling records
+struct rh_bins {
+    const rh_prep *prep[4];
+    const int32_t *orig[4];
+    const void *cls[4];
+    const float *box[4];
+};
+static inline rh_bins rh_bins_at(const rh_prep *prep, const int32_t *orig, const void *cls, const float *box, const int64_t off[4])
+{
+    rh_bins B;
+    for (int k = 0; k < 4; k++) {
+        B.prep[k] = prep + off[k];
+        B.orig[k] = orig + off[k];
+        B.cls[k] = cls ? (const char *)cls + (size_t)off[k] * 64 : nullptr;
+        B.box[k] = box ? box + off[k] : nullptr;
+    }
+    return B;
+}
+// ... of a workspace the prep kernels filled: bin k at k * batch_cap, the culling records' fields 4 * batch_cap apart
+static inline rh_bins rh_ws_bins(const rh_batch_ws &w)
+{
+    const int64_t off[4] = { 0, w.batch_cap, 2 * w.batch_cap, 3 * w.batch_cap };
+    return rh_bins_at(w.d_prep, w.d_orig, w.d_qpre, w.d_box, off);
+}
 struct rh_cloud {
     int64_t opt[RH_OPT_COUNT];         // rh_set_option on this cloud (RH_OPTION_UNSET: the process-wide value holds); rh_opt_init_cloud
     int device = -1;
-    hipStream_t stream = nullptr;      // the stream every launch / copy of this cloud goes to
+    hipStream_t stream = nullptr;      // the stream every launch / copy of this cloud goes to (a slot's own while its batch is queued: rh_score_batch_dev)
     hipStream_t own_stream = nullptr;  // created with the cloud; `stream` is this or the caller's (rh_cloud_set_stream)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t evk[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };   // per-kind launch brackets
@@ -150,16 +194,8 @@ struct rh_cloud {
     double nrm_mag = 0;                // max |normal component| over the subset (margins of the binary32 classifier)
     bool use_groups = false;           // culled scoring path available (s large enough)
     float *gb32 = nullptr;             // the same boxes in binary32, 8 floats per group (v4 score kernel: scalar loads)
-    hipEvent_t ev_cull = nullptr;      // timed launches (rh_score_batch_dev_timed): behind the list launch, in front of the score launch
-    bool time_cull = false;
-    float last_cull_ms = 0.f;
-    int32_t last_s4[4] = { 0, 0, 0, 0 };   // the last sized launch of the culled score kernel: R, lists taken (0 / 1), rows, tiles (rh_score_launch_info)
     float *st32 = nullptr;             // boxes of the super-tiles (16 consecutive groups = 4 tiles of the k-d leaf order), 8 floats each
     int64_t nst = 0;
-    // per-super-tile candidate lists of the batch being scored (score4.hip, st_cull_kernel): [nst][4 kinds][stlist_cap] slots, [nst][4] counts
-    uint16_t *d_stlist = nullptr;
-    int32_t *d_stcount = nullptr;
-    int64_t stlist_cap = 0, stlist_nst = 0;
     double *dis_gb = nullptr;          // boxes of the dis segment in use (7 x ng_pad)
     int32_t *d_ndis = nullptr;         // device counter: entries in dis
     int64_t n_dis = 0;                 // host mirror
@@ -187,13 +223,8 @@ struct rh_cloud {
     uint64_t *oct_men = nullptr;       // [nwords] enabled bits in Morton order
     int32_t *oct_prefix = nullptr;     // [nwords + 1]
     rh_oct_state *oct_state = nullptr; // chained octree windows: the window's state,
-    const int32_t *s4_stop = nullptr;  //   its stop flag as the score kernel sees it (null outside such windows),
-    const rh_s4_points *s4_points = nullptr;   // the launches being queued run over this set instead of subset 1 (rhk_score4_dis)
     float *dis_gb32 = nullptr;         // binary32 twins of dis_gb
-    int32_t *zero_extra = nullptr;     // the next rhk_prep_binned launch also zeroes zero_extra_n ints from here (then forgets it)
-    int32_t zero_extra_n = 0;
     void *s4_stats = nullptr;          // diag build: event counters of the score launches (rh_dbg_s4_stats), 128 x u64 on the device
-    bool s4_open_count = false;        // the candidate count of the score launches being queued is a guess (windows of the candidate loop)
     int32_t *oct_adv_tab = nullptr;    //   the (level, slot) table of rhk_oct_advance, its bitmap (kept zero) and the sorted scores
     unsigned long long *oct_adv_bits = nullptr;
     int64_t oct_adv_cells = 0;
@@ -216,41 +247,48 @@ struct rh_cloud {
     int64_t *idx_out = nullptr;        // [n] compacted indices
     int32_t *d_total = nullptr;        // scalar
 
-    // batch workspaces (grown on demand)
-    int64_t batch_cap = 0;
-    rh_shape *d_shapes = nullptr;      // [batch_cap]
-    rh_prep *d_prep = nullptr;         // [4 * batch_cap], kind-major
-    int32_t *d_orig = nullptr;         // [4 * batch_cap]
-    int32_t *d_nk = nullptr;           // [4]
-    int32_t *d_nk2 = nullptr;          // [8] rh_score_batch_dev: two halves used alternately, each batch zeroes the other
-    int nk2_flip = 0;
-    bool nk2_ready = false;
-    int32_t *d_counts = nullptr;       // [batch_cap]
-    uint64_t *d_masks = nullptr;       // grown on demand
+    // the batch workspaces: ws[0] the cloud's own, ws[1 ..] the other slots of rh_score_batch_dev's pipeline (rh_batch_ws)
+    rh_batch_ws ws[RH_MAX_IN_FLIGHT];
+    uint32_t pipe_k = 0;               // batches since the pipeline (re)started
+
+    // Shared by the batches: state of the scoring path that is per CLOUD, although batches on several streams go through the
+    // code that touches it.  Why each is safe to share today:
+    //   d_nk, d_masks, d_zero, ev_cull / time_cull / last_cull_ms: only touched by calls that join the slots first and run
+    //     on ws[0] (rh_score_batch, rh_score_batch_dev_timed, rh_ransac's windows) -- no other batch is in flight then.
+    //   s4_points, s4_stop, s4_open_count: hand-overs to the score launcher, set and reset within one such joined call (null /
+    //     false whenever a pipelined batch is queued).
+    //   zero_extra: set by rh_score_batch_allreduce_dev and consumed by the rhk_prep_binned launch of the rh_score_batch_dev
+    //     it calls next, within that one host call.
+    //   last_s4: host-side record of the last sized launch, whichever slot it was on (a cloud is used by one host thread at a time).
+    //   unp_segmask / unp_seg_words: NOT safe.  rhk_unpermute_masks4 builds the table on the stream of whichever batch needs it
+    //     first and other slots' streams then read it with no ordering behind that launch; a change of "unp_words" frees and
+    //     rebuilds it while un-permutations on the other streams may still read the old one.
+    //     TODO ("data race on the per-cloud segment-mask table"): build it on a joined cloud, or give every
+    //     rh_batch_ws a table of its own.
+    int32_t *d_nk = nullptr;           // [4] bin sizes of a batch whose sizes the host uploads (rh_score_batch) or the sampler leaves (rh_ransac)
+    uint64_t *d_masks = nullptr;       // rh_score_batch: the masks in subset order on their way to the host (grown on demand)
     int64_t masks_cap = 0;
-    uint64_t *d_masks_int = nullptr;   // masks in internal order (before un-permuting)
-    int64_t masks_int_cap = 0;
-    uint8_t *d_occ = nullptr;          // v4 score kernel with masks: one int32 cursor per candidate row of the entry lists in d_masks_int (zero between batches)
+    int32_t *d_zero = nullptr;         // 64 zero bytes: the bin size a kind left out of a launch reads (per-kind timing leg)
+    hipEvent_t ev_cull = nullptr;      // timed launches (rh_score_batch_dev_timed): behind the list launch, in front of the score launch
+    bool time_cull = false;
+    float last_cull_ms = 0.f;
+    const rh_s4_points *s4_points = nullptr;   // the launches being queued run over this set instead of subset 1 (rhk_score4_dis)
+    const int32_t *s4_stop = nullptr;  // chained octree windows: the window's stop flag as the score kernel sees it (null outside such windows)
+    bool s4_open_count = false;        // the candidate count of the score launches being queued is a guess (windows of the candidate loop)
+    int32_t *zero_extra = nullptr;     // the next rhk_prep_binned launch also zeroes zero_extra_n ints from here (then forgets it)
+    int32_t zero_extra_n = 0;
+    int32_t last_s4[4] = { 0, 0, 0, 0 };   // the last sized launch of the culled score kernel: R, lists taken (0 / 1), rows, tiles (rh_score_launch_info)
     uint64_t *unp_segmask = nullptr;   // mask un-permutation: per output segment and internal word, the bits that land in the segment
     int64_t unp_seg_words = 0;         //   ... made for this segment width
-    int64_t occ_cap = 0;
-    bool masks4 = false;               // the batch being scored leaves its masks in the v4 form (rows mstride4 apart)
-    int64_t mstride4 = 0;
+
     int64_t *d_ranks = nullptr;        // select in/out
     int64_t ranks_cap = 0;
 
-    // Float32 clouds (rh_cloud_create_f32; f32.hip): float copies of the two point sets and float candidate records
+    // Float32 clouds (rh_cloud_create_f32; f32.hip): float copies of the two point sets (the float candidate records: rh_batch_ws)
     bool f32 = false;
     bool f32_groups = false;           // scored by the culled kernel (exact test in binary32); else by the brute-force float kernel
     float *full32 = nullptr;           // 6 planes x n_pad, original order (the refit scan streams these: 24 B per point)
     float *sub32 = nullptr;            // 6 planes x s_pad, subset 1 in k-d leaf order
-    void *d_prep32 = nullptr;          // [4 * batch_cap] float records (rh_prepf), grown with the batch workspaces
-    void *d_qpre = nullptr;            // [4 * batch_cap] classifier records (rh4::rh_cls, 64 B) of the bins in d_prep; culling records: d_box
-    float *d_box = nullptr;            // [RH_BOX_FIELDS][4 * batch_cap] culling records of the same bins (v4 score kernel), structure of arrays
-    bool qpre_v4 = false;              // ... made by the last prep kernel (for the thresholds it was given)
-    int32_t *d_zero = nullptr;         // 64 zero bytes: the bin size a kind left out of a launch reads (per-kind timing leg)
-    const rh_shape *f32_shapes = nullptr;   // the batch being scored: its shapes on the device ...
-    int f32_via_orig = 0;                   // ... indexed through d_orig (caller's order) or directly (sorted like the bins)
 
     // rh_ransac_mp: this process's share of every iteration's minimal sets (set j belongs to rank j % world)
     int32_t mp_rank = 0, mp_world = 1;
@@ -261,13 +299,6 @@ struct rh_cloud {
 
     // rh_score_batch with host buffers: device twin of the pinned staging block of a small batch (one upload)
     void *d_stage = nullptr;
-
-    // two batches in flight (rh_score_batch_dev, "batches_in_flight" = 2)
-    rh_batch_slot alt[RH_MAX_IN_FLIGHT - 1];
-    uint32_t pipe_k = 0;               // batches since the pipeline (re)started
-    const void *slot_counts[RH_MAX_IN_FLIGHT] = {}, *slot_masks[RH_MAX_IN_FLIGHT] = {};   // the buffers the slots' batches in flight write (null: none)
-    bool alt_dirty[RH_MAX_IN_FLIGHT - 1] = {};     // work on alt[i].stream the cloud's own stream has not waited for yet
-    bool alt_started[RH_MAX_IN_FLIGHT - 1] = {};   // alt[i].stream has been ordered behind the cloud's stream since the last join
 
     // pinned staging
     void *h_pin = nullptr;
@@ -289,22 +320,24 @@ int rhk_transpose_aos(rh_cloud *c, const double *d_aos_xyz, const double *d_aos_
                       const int32_t *d_gather_or_null, int64_t count, double *dst, int64_t dst_stride);
 int rhk_fetch2_i32(rh_cloud *c, const int32_t *d_src0, const int32_t *d_src1, int32_t *h_pinned_dst);   // h[0..1] = *d0, *d1 in stream order (pinned h)
 int rhk_pack_records(rh_cloud *c, const double *d_xyz, const double *d_nrm, int64_t n, double *d_rec);
-int rhk_prep_sorted(rh_cloud *c, const rh_shape *d_shapes_sorted, int32_t b, rh_prep *d_prep,
-                    int32_t *d_counts_to_zero = nullptr, const double *eps = nullptr, const double *cosa = nullptr);
+// The prep launchers fill the bins of the workspace they are given (w.d_prep / w.d_orig, bin k at k * w.batch_cap); with eps +
+// cosa they also leave the bins' classifier / culling records in w.d_qpre / w.d_box and say so in w.qpre_v4.
+int rhk_prep_sorted(rh_cloud *c, rh_batch_ws &w, int32_t b, int32_t *d_counts_to_zero = nullptr, const double *eps = nullptr,
+                    const double *cosa = nullptr);   // w.d_shapes[0 .. b), sorted by kind -> w.d_prep, slot for slot
 struct rh_cand_entry;
 struct rh_oct_state;
-int rhk_prep_entries(rh_cloud *c, const rh_cand_entry *d_entries, const int32_t *d_count, int32_t cap_entries,
+int rhk_prep_entries(rh_cloud *c, rh_batch_ws &w, const rh_cand_entry *d_entries, const int32_t *d_count, int32_t cap_entries,
                      int32_t launch_bound, int32_t *d_counts, int nk_is_zero, const double *eps = nullptr,
-                     const double *cosa = nullptr, const rh_oct_state *ost = nullptr);   // eps + cosa: also leave the classifier / culling records in d_qpre / d_box
-int rhk_prep_binned(rh_cloud *c, const rh_shape *d_shapes, int32_t b, rh_prep *d_prep, int32_t *d_orig,
-                    int32_t *d_nk, int64_t cap, int32_t *d_counts_to_zero, int32_t *d_nk_other, int nk_is_zero,
-                    const double *eps = nullptr, const double *cosa = nullptr);   // eps + cosa: also leave the classifier / culling records (bins in c->d_prep only)
+                     const double *cosa = nullptr, const rh_oct_state *ost = nullptr);   // bin sizes: c->d_nk
+int rhk_prep_binned(rh_cloud *c, rh_batch_ws &w, const rh_shape *d_shapes, int32_t b, int32_t *d_nk, int32_t *d_counts_to_zero,
+                    int32_t *d_nk_other, int nk_is_zero, const double *eps = nullptr, const double *cosa = nullptr);
 bool rh_score_v4_enabled(const rh_cloud *c);
-int rhk_score4_all(rh_cloud *c, const uint64_t *const en[4], const rh_prep *const prep[4], const void *const cls[4],
+// (w: the super-tile lists of the launch; masks: the entry lists d_masks_int = w.d_masks_int with their cursors w.d_occ, rows w.mstride4 apart)
+int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const rh_prep *const prep[4], const void *const cls[4],
                    const float *const box[4], int64_t bstride, const int32_t *const orig[4], const int32_t *const nk[4],
                    int32_t nk_total_bound, const double eps[4], const double cosa[4], int32_t *d_counts,
-                   uint64_t *d_masks_int = nullptr, uint8_t *d_occ = nullptr, int64_t mstride = 0);   // masks: entry lists + row cursors
-int rhk_unpermute_masks4(rh_cloud *c, const uint64_t *d_in, uint8_t *d_occ, int64_t mstride, int32_t b, uint64_t *d_out);   // score4.hip
+                   uint64_t *d_masks_int = nullptr);
+int rhk_unpermute_masks4(rh_cloud *c, rh_batch_ws &w, int32_t b, uint64_t *d_out);   // score4.hip: w's entry lists -> dense rows
 // score nk candidates of one kind; nk_host < 0: count is only known on the device (d_nk),
 // launch for an upper bound of nk_bound candidates
 int rhk_score_kind(rh_cloud *c, int kind, const double *pts, int64_t stride, int64_t s,
@@ -313,7 +346,7 @@ int rhk_score_kind(rh_cloud *c, int kind, const double *pts, int64_t stride, int
                    uint64_t *d_masks_or_null, int64_t mask_stride);
 // culled path over c->sub (k-d leaf order + per-group boxes): all kinds in one launch of score4.hip's kernel; masks
 // (optional) leave it as entry lists (rhk_unpermute_masks4)
-int rhk_score_all_groups(rh_cloud *c, const uint64_t *const en[4], const rh_prep *const prep[4],
+int rhk_score_all_groups(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const rh_prep *const prep[4],
                          const int32_t *const orig[4], const int32_t *const nk[4], int32_t nk_total_bound,
                          const double eps[4], const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int,
                          const void *const cls[4],                 // cls / box: classifier and culling records (score4_device.h) of the
@@ -325,11 +358,11 @@ int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, const rh_prep *const
                    int64_t bstride, const int32_t *const orig[4], const int32_t *const nk[4], int32_t nk_total_bound, const double eps[4],
                    const double cosa[4], int32_t *d_counts);
 // (score4.hip: gb32 from gb)
-int rhk_prep_f32(rh_cloud *c, const rh_shape *d_shapes, int via_orig, const int32_t *d_orig, const int64_t off[4],
-                 const int32_t *d_nk, int32_t nmax);               // fills c->d_prep32 (f32.hip)
+int rhk_prep_f32(rh_cloud *c, rh_batch_ws &w, const int32_t *d_orig, const int64_t off[4], const int32_t *d_nk,
+                 int32_t nmax);                                    // w.f32_shapes -> w.d_prep32 (f32.hip)
 // Float32 clouds (f32.hip)
 int rhk_f32_build(rh_cloud *c);
-int rhk_score_all_f32(rh_cloud *c, const rh_shape *d_shapes, int via_orig, const uint64_t *const en[4], const int32_t *d_orig,
+int rhk_score_all_f32(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const int32_t *d_orig,
                       const int64_t off[4], const int32_t *d_nk, const int32_t nk_bound[4], const double eps[4],
                       const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int);
 int rhk_refit_mask_f32(rh_cloud *c, const rh_shape &shape, double eps, double cosa, bool apply = false);
@@ -461,9 +494,11 @@ void rh_prep_host(const rh_shape &s, rh_prep *out);
 int32_t rh_spread_multiplier(int32_t b);   // t -> (t * m) mod b: a permutation of the batch that separates neighbours
 
 // ---- host helpers (cloud.hip) -----------------------------------------------
-int rh_ensure_batch(rh_cloud *c, int64_t b);
+// the one way a device buffer of the cloud grows: c->stream (the stream of the workspace in use) is synchronised, the old buffer
+// freed, `bytes` allocated, and only then the capacity published (*cap = new_cap; cap may be null); a failure leaves null / 0
+int rh_grow_buffer(rh_cloud *c, void **buf, int64_t *cap, int64_t new_cap, size_t bytes);
+int rh_ensure_batch(rh_cloud *c, rh_batch_ws &w, int64_t b);
+int rh_join_batches(rh_cloud *c);   // the cloud's stream waits for what the other batch slots have in flight ("batches_in_flight")
 int rh_cloud_join(rh_cloud *c);     // the same with the cloud's device made current first (options.cpp)
-int rh_join_batches(rh_cloud *c);   // the cloud's stream waits for the second batch slot ("batches_in_flight")
-int rh_ensure_masks(rh_cloud *c, int64_t words);
 int rh_ensure_pin(rh_cloud *c, int64_t bytes);
 int rh_validate_params(const rh_params *p);

@@ -942,7 +942,7 @@ int rhk_oct_advance(rh_cloud *c, const rh_params *prm, rh_oct_state *ost, const 
     A.cap = cap; A.it = it; A.od = od; A.score_mode = prm->score_mode; A.extract_s = prm->extract_s; A.minsubsetN = prm->minsubsetN;
     A.drawN = prm->drawN; A.k = k; A.per_it = per_it; A.S1length = c->s; A.Plength = c->n; A.prob_det = prm->prob_det;
     A.Etab = (double *)c->oct_adv_tab; A.spref = (int32_t *)((double *)c->oct_adv_tab + cells); A.bits = c->oct_adv_bits; A.sbits = c->oct_adv_bits + nw; A.Esort = c->oct_adv_E;
-    A.bin_prep = c->d_prep; A.bin_orig = c->d_orig; A.bin_nk = c->d_nk; A.bin_cap = c->batch_cap;
+    A.bin_prep = c->ws[0].d_prep; A.bin_orig = c->ws[0].d_orig; A.bin_nk = c->d_nk; A.bin_cap = c->ws[0].batch_cap;
     A.h_entries = h_entries; A.h_counts = h_counts; A.h_rank = h_rank; A.h_slot = h_slot; A.h_hdr = h_hdr;
     hipLaunchKernelGGL(oct_advance_kernel, dim3(1), dim3(OA_THREADS), 0, c->stream, A);
     RH_HIP(hipGetLastError());

@@ -1033,26 +1033,22 @@ int rhk_gb32_build(rh_cloud *c)
     return RH_OK;
 }
 
-// the super-tile lists' workspace of the batch slot in place: [nst][4][cap] bin slots + [nst][4] counts
-static int ensure_stlists(rh_cloud *c, int64_t cap)
+// the super-tile lists of the workspace's batch: [nst][4][cap] bin slots + [nst][4] counts
+static int ensure_stlists(rh_cloud *c, rh_batch_ws &w, int64_t cap)
 {
-    if (c->d_stlist != nullptr && cap <= c->stlist_cap && c->stlist_nst == c->nst) return RH_OK;
-    RH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_stlist); (void)hipFree(c->d_stcount);
-    c->d_stlist = nullptr; c->d_stcount = nullptr; c->stlist_cap = 0;
+    if (w.d_stlist != nullptr && cap <= w.stlist_cap && w.stlist_nst == c->nst) return RH_OK;
     const int64_t ncap = std::max<int64_t>(cap, 1024);
-    RH_HIP(hipMalloc((void **)&c->d_stlist, sizeof(uint16_t) * (size_t)c->nst * 4 * (size_t)ncap));
-    RH_HIP(hipMalloc((void **)&c->d_stcount, sizeof(int32_t) * (size_t)c->nst * 4));
-    c->stlist_cap = ncap;
-    c->stlist_nst = c->nst;
+    w.stlist_cap = 0;
+    RH_TRY(rh_grow_buffer(c, (void **)&w.d_stcount, nullptr, 0, sizeof(int32_t) * (size_t)c->nst * 4));
+    RH_TRY(rh_grow_buffer(c, (void **)&w.d_stlist, &w.stlist_cap, ncap, sizeof(uint16_t) * (size_t)c->nst * 4 * (size_t)ncap));
+    w.stlist_nst = c->nst;
     return RH_OK;
 }
 
 // the v4 launch: cls[k] / box[k] = the classifier / culling records of bin prep[k], slot for slot, made for eps / cosa.
-int rhk_score4_all(rh_cloud *c, const uint64_t *const en[4], const rh_prep *const prep[4], const void *const cls[4],
+int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const rh_prep *const prep[4], const void *const cls[4],
                    const float *const box[4], int64_t bstride, const int32_t *const orig[4], const int32_t *const nk[4],
-                   int32_t nk_total_bound, const double eps[4], const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int,
-                   uint8_t *d_occ, int64_t mstride)
+                   int32_t nk_total_bound, const double eps[4], const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int)
 {
     const bool open_count = c->s4_open_count;
     const bool f32cloud = c->f32;   // the exact tests in binary32, on float records derived from `prep`
@@ -1072,8 +1068,8 @@ int rhk_score4_all(rh_cloud *c, const uint64_t *const en[4], const rh_prep *cons
     A.ngroups = PS.ngroups;
     A.gb32 = PS.gb32;
     A.masks = d_masks_int;
-    A.occ = d_occ;
-    A.mstride = mstride;
+    A.occ = d_masks_int ? w.d_occ : nullptr;
+    A.mstride = d_masks_int ? w.mstride4 : 0;
     A.stats = nullptr;
 #ifdef RH_DIAG
     A.stats = (unsigned long long *)c->s4_stats;   // (rh_dbg_s4_stats switched the counters on)
@@ -1096,12 +1092,12 @@ int rhk_score4_all(rh_cloud *c, const uint64_t *const en[4], const rh_prep *cons
     if (use_lists && st_opt == 0)
         use_lists = nk_total_bound >= 1024 && ntiles >= (rh_opt_int(c, RH_OPT_BATCHES_IN_FLIGHT, 1) > 1 ? 1000 : 3000);
     if (use_lists) {
-        RH_TRY(ensure_stlists(c, ((int64_t)nk_total_bound + 63) / 64 * 64));
+        RH_TRY(ensure_stlists(c, w, ((int64_t)nk_total_bound + 63) / 64 * 64));
         StCullArgs SA;
         for (int k = 0; k < 4; k++) { SA.box[k] = box[k]; SA.nk[k] = nk[k]; }
-        SA.bstride = bstride; SA.stcap = c->stlist_cap; SA.st32 = c->st32; SA.stlist = c->d_stlist; SA.stcount = c->d_stcount;
+        SA.bstride = bstride; SA.stcap = w.stlist_cap; SA.st32 = c->st32; SA.stlist = w.d_stlist; SA.stcount = w.d_stcount;
         hipLaunchKernelGGL(st_cull_kernel, dim3((unsigned)c->nst, 4), dim3(256), 0, c->stream, SA);
-        A.stlist = c->d_stlist; A.stcount = c->d_stcount; A.stcap = c->stlist_cap;
+        A.stlist = w.d_stlist; A.stcount = w.d_stcount; A.stcap = w.stlist_cap;
         if (c->time_cull && c->ev_cull != nullptr) RH_HIP(hipEventRecord(c->ev_cull, c->stream));
     }
     const int env_r = (int)rh_opt_int(c, RH_OPT_S4_ROWS, 0);   // rh_set_option(.., "s4_rows", ..), read on every launch: the fuzzers vary it from case to case
@@ -1242,7 +1238,7 @@ int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, const rh_prep *const
     const rh_s4_points PS = { c->dis + first, c->dis_stride, cnt, ng, c->dis_gb32 };
     const uint64_t *en[4] = { nullptr, nullptr, nullptr, nullptr };
     c->s4_points = &PS;
-    const int rc = rhk_score4_all(c, en, prep, cls, box, bstride, orig, nk, nk_total_bound, eps, cosa, d_counts, nullptr, nullptr, 0);
+    const int rc = rhk_score4_all(c, c->ws[0], en, prep, cls, box, bstride, orig, nk, nk_total_bound, eps, cosa, d_counts);   // (no lists over s4_points: w is not touched)
     c->s4_points = nullptr;
     return rc;
 }
@@ -1351,11 +1347,14 @@ extern "C" int rh_dbg_s4_stats(rh_cloud *c, int mode, uint64_t *out)
 }
 #endif   // RH_DIAG
 
-// the entry lists the v4 score kernel left (rows of mstride 16-byte entries, one cursor per row in d_occ) -> dense rows in
-// subset order; the cursors are zero again afterwards
-int rhk_unpermute_masks4(rh_cloud *c, const uint64_t *d_in, uint8_t *d_occ, int64_t mstride, int32_t b, uint64_t *d_out)
+// the entry lists the v4 score kernel left in the workspace (rows of mstride4 16-byte entries, one cursor per row in d_occ) ->
+// dense rows in subset order; the cursors are zero again afterwards
+int rhk_unpermute_masks4(rh_cloud *c, rh_batch_ws &w, int32_t b, uint64_t *d_out)
 {
     if (b == 0 || c->swords == 0) return RH_OK;
+    const uint64_t *d_in = w.d_masks_int;
+    uint8_t *d_occ = w.d_occ;
+    const int64_t mstride = w.mstride4;
     const int env_words = (int)rh_opt_int(c, RH_OPT_UNP_WORDS, 0);   // rh_set_option(.., "unp_words", n) (tests; read per call): segments of n words, so that a small cloud's rows span several / many
     const int64_t seg_words = std::min<int64_t>(c->swords, env_words > 0 ? std::min(env_words, 16384) : (c->swords <= S4_UNP_WORDS ? S4_UNP_WORDS : S4_UNP_WORDS_MULTI));
     const int nseg = cdiv4(c->swords, seg_words);
