@@ -159,7 +159,7 @@ static void batch_ws_free(rh_batch_ws &w)
     if (w.stream) (void)hipStreamSynchronize(w.stream);
     (void)hipFree(w.d_shapes); (void)hipFree(w.d_prep); (void)hipFree(w.d_orig); (void)hipFree(w.d_counts); (void)hipFree(w.d_nk2);
     (void)hipFree(w.d_qpre); (void)hipFree(w.d_prep32); (void)hipFree(w.d_box); (void)hipFree(w.d_masks_int); (void)hipFree(w.d_occ);
-    (void)hipFree(w.d_stlist); (void)hipFree(w.d_stcount);
+    (void)hipFree(w.d_stlist); (void)hipFree(w.d_stcount); (void)hipFree(w.d_segmask);
     if (w.done) (void)hipEventDestroy(w.done);
     if (w.start) (void)hipEventDestroy(w.start);
     if (w.stream) (void)hipStreamDestroy(w.stream);
@@ -178,7 +178,7 @@ static void cloud_free(rh_cloud *c)
     (void)hipFree(c->sub_idx0); (void)hipFree(c->enabled); (void)hipFree(c->sub_enabled);
     (void)hipFree(c->sub_perm); (void)hipFree(c->gb);
     (void)hipFree(c->full32); (void)hipFree(c->sub32); (void)hipFree(c->d_zero);
-    (void)hipFree(c->s4_stats); (void)hipFree(c->gb32); (void)hipFree(c->st32); (void)hipFree(c->unp_segmask);
+    (void)hipFree(c->s4_stats); (void)hipFree(c->gb32); (void)hipFree(c->st32);
     (void)hipFree(c->oct_code); (void)hipFree(c->oct_perm); (void)hipFree(c->oct_pos); (void)hipFree(c->oct_men);
     (void)hipFree(c->oct_prefix); (void)hipFree(c->oct_P); (void)hipFree(c->oct_tab); (void)hipFree(c->oct_code_o);
     (void)hipFree(c->oct_state); (void)hipFree(c->oct_adv_tab); (void)hipFree(c->oct_adv_bits); (void)hipFree(c->oct_adv_E);
@@ -742,59 +742,38 @@ extern "C" int rh_cloud_count_enabled(rh_cloud *c, int64_t *out)
 }
 
 // ---------------------------------------------------------------- scoring ----
-static inline const uint64_t *enabled_for_kind(const rh_cloud *c, int kind, const rh_params *p)
-{
-    // sphere.jl:121,131: the sphere scorer builds `ens` and never applies it
-    if (kind == RH_SPHERE && !p->sphere_uses_enabled) return nullptr;
-    return c->sub_enabled;
-}
-
-// all four kind bins (bin k at prep/orig + off[k], its size in d_nk[k]) against subset 1.
+// all four kind bins of the job against subset 1.
 // Culled path (subsets of RH_G2_MIN_POINTS points and more): ONE launch of score4.hip's kernel over all kinds, reading the
-// bins' classifier / culling records d_cls / d_box (64 B per slot at the same offsets / fields bstride apart); masks leave
-// it as entry lists (w.masks4).  ms_kind (the bench's per-kind leg): one launch per kind instead, the other kinds' bin
-// sizes read as zero, an event before each.  Small subsets: the brute-force kernel, one launch per kind, masks in internal
-// order.  Float32 clouds: the same two paths with the exact tests in binary32.
-static int score_bins_subset(rh_cloud *c, rh_batch_ws &w, const rh_params *p, const rh_prep *d_prep, const int32_t *d_orig,
-                             const int64_t off[4], const int32_t *d_nk, const int32_t nk_bound[4], int32_t total_bound,
-                             int32_t *d_counts, uint64_t *d_masks_int, float *ms_kind, const void *d_cls = nullptr,
-                             const float *d_box = nullptr, int64_t bstride = 0)
+// bins' classifier / culling records; masks leave it as entry lists (w.masks4).  ms_kind (the bench's per-kind leg): one
+// launch per kind instead, the other kinds' bin sizes read as zero, an event before each.  Small subsets: the brute-force
+// kernel, one launch per kind, masks in internal order.  Float32 clouds: the same two paths with the exact tests in binary32.
+// launch_info: what the last sized launch of the culled kernel chose (rhk_score4_all).
+static int score_bins_subset(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, const float *ms_kind, int32_t *launch_info = nullptr)
 {
-    const uint64_t *en[4];
-    for (int k = 0; k < 4; k++) en[k] = enabled_for_kind(c, k, p);
     if (rh_score_v4_enabled(c)) {
-        if (d_cls == nullptr || d_box == nullptr) { rh_set_error("internal: culled scoring without the bins' classifier records"); return RH_E_INTERNAL; }
-        const rh_bins B = rh_bins_at(d_prep, d_orig, d_cls, d_box, off);
-        const int32_t *nk[4];
-        for (int k = 0; k < 4; k++) nk[k] = d_nk + k;
-        if (!ms_kind)
-            return rhk_score_all_groups(c, w, en, B.prep, B.orig, nk, total_bound, p->eps, p->cos_alpha, d_counts, d_masks_int, B.cls, B.box, bstride);
+        if (!ms_kind) return rhk_score4_all(c, w, job, launch_info);
         if (c->d_zero == nullptr) {
             RH_HIP(hipMalloc((void **)&c->d_zero, 64));
             RH_HIP(hipMemsetAsync(c->d_zero, 0, 64, c->stream));
         }
         for (int k = 0; k < 4; k++) {
             RH_HIP(hipEventRecord(c->evk[k], c->stream));
-            if (nk_bound[k] == 0) continue;
-            const int32_t *nk1[4];
-            for (int q = 0; q < 4; q++) nk1[q] = q == k ? nk[q] : c->d_zero;
-            RH_TRY(rhk_score_all_groups(c, w, en, B.prep, B.orig, nk1, nk_bound[k], p->eps, p->cos_alpha, d_counts, d_masks_int, B.cls, B.box, bstride));
+            if (job.kind_bound[k] == 0) continue;
+            rh_score_job one = job;
+            for (int q = 0; q < 4; q++) if (q != k) one.nk[q] = c->d_zero;
+            one.bound = job.kind_bound[k];
+            RH_TRY(rhk_score4_all(c, w, one, launch_info));
         }
         return RH_OK;
     }
-    if (c->f32) {   // Float32 cloud, small subset: float records from the batch's shapes, brute-force float kernel (f32.hip)
-        if (w.f32_shapes == nullptr) { rh_set_error("internal: Float32 scoring without the batch's shapes"); return RH_E_INTERNAL; }
-        for (int k = 0; k < 4; k++)
-            if (ms_kind) RH_HIP(hipEventRecord(c->evk[k], c->stream));
-        return rhk_score_all_f32(c, w, en, d_orig, off, d_nk, nk_bound, p->eps, p->cos_alpha, d_counts, d_masks_int);
-    }
     for (int k = 0; k < 4; k++) {
         if (ms_kind) RH_HIP(hipEventRecord(c->evk[k], c->stream));
-        if (nk_bound[k] == 0) continue;
-        RH_TRY(rhk_score_kind(c, k, c->sub, c->s_pad, c->s, en[k], d_prep + off[k], d_orig + off[k], d_nk + k, nk_bound[k],
-                              p->eps[k], p->cos_alpha[k], d_counts, d_masks_int, c->swords));
+        if (c->f32 || job.kind_bound[k] == 0) continue;
+        RH_TRY(rhk_score_kind(c, k, c->sub, c->s_pad, c->s, job.en[k], job.bins.prep[k], job.bins.orig[k], job.nk[k], job.kind_bound[k],
+                              job.eps[k], job.cosa[k], job.d_counts, job.d_masks_int, c->swords));
     }
-    return RH_OK;
+    // Float32 cloud, small subset: float records from the batch's shapes, brute-force float kernel (f32.hip)
+    return c->f32 ? rhk_score_all_f32(c, w, job) : RH_OK;
 }
 
 extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, int32_t *counts_out,
@@ -886,9 +865,13 @@ extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, co
         d_masks_int = w.d_masks_int;
     }
     const int64_t off64[4] = { off[0], off[1], off[2], off[3] };
-    w.f32_shapes = w.d_shapes;     // sorted like the bins
-    w.f32_via_orig = 0;
-    RH_TRY(score_bins_subset(c, w, p, d_prep_use, d_orig_use, off64, d_nk_use, nk, b, d_counts_use, d_masks_int, nullptr, d_cls_use, d_box_use, bstride_use));
+    rh_score_job job = rh_subset_job(c, p, rh_bins_at(d_prep_use, d_orig_use, d_cls_use, d_box_use, off64), bstride_use, d_nk_use);
+    job.bound = b;
+    for (int k = 0; k < 4; k++) job.kind_bound[k] = nk[k];
+    job.d_counts = d_counts_use;
+    job.d_masks_int = d_masks_int;
+    job.shapes = w.d_shapes;   // sorted like the bins
+    RH_TRY(score_bins_subset(c, w, job, nullptr));
     if (d_masks_int) RH_TRY(rh_masks_finish(c, w, b, d_masks));
     RH_HIP(hipMemcpyAsync(h_counts, d_counts_use, sizeof(int32_t) * (size_t)b, hipMemcpyDeviceToHost, c->stream));
     if (d_masks)
@@ -973,8 +956,10 @@ static int batch_slot_create(rh_cloud *c, int slot)
 }
 
 // one batch on workspace c->ws[slot]; c->stream is that workspace's stream (slot > 0: rh_score_batch_dev)
+// (zero_extra: the prepare launch also zeroes zero_extra_n ints from there)
 static int score_batch_dev_impl(rh_cloud *c, int slot, const rh_shape *d_shapes, int32_t b, const rh_params *p,
-                                int32_t *d_counts, uint64_t *d_masks, float *ms_kind, bool joined = true)
+                                int32_t *d_counts, uint64_t *d_masks, float *ms_kind, bool joined = true,
+                                int32_t *zero_extra = nullptr, int32_t zero_extra_n = 0)
 {
     RH_TRY(joined ? enter(c) : enter_nojoin(c));
     RH_TRY(rh_validate_params(p));
@@ -992,30 +977,33 @@ static int score_batch_dev_impl(rh_cloud *c, int slot, const rh_shape *d_shapes,
     }
     int32_t *nk_cur = w.d_nk2 + 4 * w.nk2_flip, *nk_next = w.d_nk2 + 4 * (1 - w.nk2_flip);
     w.nk2_flip = 1 - w.nk2_flip;
-    RH_TRY(rhk_prep_binned(c, w, d_shapes, b, nk_cur, d_counts, nk_next, 1, p->eps, p->cos_alpha));
+    RH_TRY(rhk_prep_binned(c, w, d_shapes, b, nk_cur, d_counts, nk_next, 1, p->eps, p->cos_alpha, zero_extra, zero_extra_n));
     uint64_t *d_masks_int = nullptr;
     if (d_masks && c->swords > 0) {
         RH_TRY(rh_masks_begin(c, w, b, w.qpre_v4));
         d_masks_int = w.d_masks_int;
     }
     const int64_t off[4] = { 0, w.batch_cap, 2 * w.batch_cap, 3 * w.batch_cap };
-    const int32_t bound[4] = { b, b, b, b };
-    const void *d_cls = w.qpre_v4 ? w.d_qpre : nullptr;   // (made by rhk_prep_binned above)
-    w.f32_shapes = d_shapes;       // the caller's order: the float records go through d_orig
-    w.f32_via_orig = 1;
+    // (classifier + culling records: made by rhk_prep_binned above)
+    rh_score_job job = rh_subset_job(c, p, rh_bins_at(w.d_prep, w.d_orig, w.qpre_v4 ? w.d_qpre : nullptr, w.qpre_v4 ? w.d_box : nullptr, off), 4 * w.batch_cap, nk_cur);
+    job.bound = b;
+    for (int k = 0; k < 4; k++) job.kind_bound[k] = b;
+    job.d_counts = d_counts;
+    job.d_masks_int = d_masks_int;
+    job.shapes = d_shapes;     // the caller's order: the float records go through d_orig
+    job.shapes_via_orig = 1;
+    int32_t s4[4] = { 0, 0, 0, 0 };   // what the last sized launch below chose
     if (ms_kind) {   // the product launch (all kinds in one kernel) first, then the per-kind launches
         ms_kind[4] = 0.f;
         if (c->ev_cull == nullptr) RH_HIP(hipEventCreate(&c->ev_cull));
         RH_HIP(hipEventRecord(c->evk[0], c->stream));
-        c->time_cull = true;
-        c->last_s4[1] = 0;
-        const int rc_s = score_bins_subset(c, w, p, w.d_prep, w.d_orig, off, nk_cur, bound, b, d_counts, d_masks_int, nullptr, d_cls, w.d_box, 4 * w.batch_cap);
-        c->time_cull = false;
-        RH_TRY(rc_s);
+        rh_score_job timed = job;
+        timed.ev_listed = c->ev_cull;
+        RH_TRY(score_bins_subset(c, w, timed, nullptr, s4));
         RH_HIP(hipEventRecord(c->evk[1], c->stream));
         RH_HIP(hipEventSynchronize(c->evk[1]));
         c->last_cull_ms = 0.f;
-        if (c->last_s4[1] != 0) {   // super-tile lists: the list launch and the score launch apart (ms_kind[4] = the score launch alone)
+        if (s4[1] != 0) {   // super-tile lists: the list launch and the score launch apart (ms_kind[4] = the score launch alone)
             RH_HIP(hipEventElapsedTime(&c->last_cull_ms, c->evk[0], c->ev_cull));
             RH_HIP(hipEventElapsedTime(&ms_kind[4], c->ev_cull, c->evk[1]));
         } else {
@@ -1027,8 +1015,8 @@ static int score_batch_dev_impl(rh_cloud *c, int slot, const rh_shape *d_shapes,
             else if (d_masks_int) RH_HIP(hipMemsetAsync(d_masks_int, 0, sizeof(uint64_t) * (size_t)b * (size_t)c->swords, c->stream));
         }
     }
-    if (!product_only)
-        RH_TRY(score_bins_subset(c, w, p, w.d_prep, w.d_orig, off, nk_cur, bound, b, d_counts, d_masks_int, ms_kind, d_cls, w.d_box, 4 * w.batch_cap));
+    if (!product_only) RH_TRY(score_bins_subset(c, w, job, ms_kind, s4));
+    if (s4[0] != 0) memcpy(c->last_s4, s4, sizeof s4);
     if (d_masks_int) RH_TRY(rh_masks_finish(c, w, b, d_masks));
     if (ms_kind && !product_only) {
         RH_HIP(hipEventRecord(c->evk[4], c->stream));
@@ -1038,8 +1026,8 @@ static int score_batch_dev_impl(rh_cloud *c, int slot, const rh_shape *d_shapes,
     return RH_OK;
 }
 
-extern "C" int rh_score_batch_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const rh_params *p,
-                                  int32_t *d_counts, uint64_t *d_masks)
+int rh_score_batch_dev_zeroing(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const rh_params *p, int32_t *d_counts, uint64_t *d_masks,
+                               int32_t *zero_extra, int32_t zero_extra_n)
 {
     // "batches_in_flight" = F > 1 (rh_set_option): batches take turns on the cloud's stream and F - 1 more streams with
     // workspaces of their own, so batch k + 1's prepare and score launches fill the chip while batch k's launch drains (the
@@ -1048,7 +1036,7 @@ extern "C" int rh_score_batch_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t
     // next; with masks the un-permutation of one batch, HBM-bound, runs under the next batch's score launch, issue-bound); any other call on the cloud (and rh_cloud_sync /
     // rh_timer_stop) first makes the cloud's stream wait for the others.
     const int in_flight = c != nullptr && b > 0 && c->stream == c->own_stream ? rh_opt_int(c, RH_OPT_BATCHES_IN_FLIGHT, 1) : 1;
-    if (in_flight <= 1) return score_batch_dev_impl(c, 0, d_shapes, b, p, d_counts, d_masks, nullptr);
+    if (in_flight <= 1) return score_batch_dev_impl(c, 0, d_shapes, b, p, d_counts, d_masks, nullptr, true, zero_extra, zero_extra_n);
     RH_TRY(enter_nojoin(c));
     int slot = (int)(c->pipe_k % (uint32_t)in_flight);
     // a caller whose buffers are not F apart (the same count buffer call after call, say): never two batches in flight on
@@ -1063,7 +1051,7 @@ extern "C" int rh_score_batch_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t
     rh_batch_ws &w = c->ws[slot];
     w.out_counts = d_counts;
     w.out_masks = d_masks;
-    if (slot == 0) return score_batch_dev_impl(c, 0, d_shapes, b, p, d_counts, d_masks, nullptr, false);
+    if (slot == 0) return score_batch_dev_impl(c, 0, d_shapes, b, p, d_counts, d_masks, nullptr, false, zero_extra, zero_extra_n);
     if (w.stream == nullptr) RH_TRY(batch_slot_create(c, slot));
     if (!w.started) {   // once per pipelined stretch: the stream starts behind what the cloud's stream holds so far
         RH_HIP(hipEventRecord(w.start, c->stream));
@@ -1071,12 +1059,18 @@ extern "C" int rh_score_batch_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t
         w.started = true;
     }
     c->stream = w.stream;        // the one redirection: every launcher below enqueues on c->stream and takes its buffers from w
-    const int rc = score_batch_dev_impl(c, slot, d_shapes, b, p, d_counts, d_masks, nullptr, false);
+    const int rc = score_batch_dev_impl(c, slot, d_shapes, b, p, d_counts, d_masks, nullptr, false, zero_extra, zero_extra_n);
     c->stream = c->own_stream;   // (in_flight > 1 only on the cloud's own stream)
     // (also behind a failed call: whatever it did enqueue on the slot's stream is waited for at the next join)
     RH_HIP(hipEventRecord(w.done, w.stream));
     w.dirty = true;
     return rc;
+}
+
+extern "C" int rh_score_batch_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const rh_params *p,
+                                  int32_t *d_counts, uint64_t *d_masks)
+{
+    return rh_score_batch_dev_zeroing(c, d_shapes, b, p, d_counts, d_masks, nullptr, 0);
 }
 
 extern "C" int rh_last_list_launch_ms(rh_cloud *c, float *ms_out)

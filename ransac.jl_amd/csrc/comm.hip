@@ -152,21 +152,9 @@ extern "C" int rh_score_batch_allreduce_dev(rh_cloud *c, rh_comm *m, const rh_sh
     if (m->calls >= 2 && hipEventQuery(m->done[m->calls & 1]) != hipSuccess) RH_HIP(hipStreamWaitEvent(c->stream, m->done[m->calls & 1], 0));
     // the whole total is zeroed by the batch's prepare launch (no fill launch of its own); a rank without candidates, or a
     // batch that does not go through that launch (<= 32 candidates travel staged), fills it the plain way
-    bool zeroed = false;
-    if (b > 32) {
-        c->zero_extra = d_counts_total;
-        c->zero_extra_n = b_total;
-    } else {
-        RH_HIP(hipMemsetAsync(d_counts_total, 0, sizeof(int32_t) * (size_t)b_total, c->stream));
-        zeroed = true;
-    }
-    if (b > 0) {
-        const int rc = rh_score_batch_dev(c, d_shapes, b, p, d_counts_total + offset, nullptr);
-        const bool consumed = c->zero_extra == nullptr;
-        c->zero_extra = nullptr; c->zero_extra_n = 0;
-        if (rc != RH_OK) return rc;
-        if (!zeroed && !consumed) { rh_set_error("rh_score_batch_allreduce_dev: the batch did not pass the prepare launch"); return RH_E_INTERNAL; }
-    }
+    int32_t *const by_prepare = b > 32 ? d_counts_total : nullptr;
+    if (by_prepare == nullptr) RH_HIP(hipMemsetAsync(d_counts_total, 0, sizeof(int32_t) * (size_t)b_total, c->stream));
+    if (b > 0) RH_TRY(rh_score_batch_dev_zeroing(c, d_shapes, b, p, d_counts_total + offset, nullptr, by_prepare, by_prepare ? b_total : 0));
     RH_HIP(hipEventRecord(m->scored, c->stream));
     RH_HIP(hipStreamWaitEvent(m->stream, m->scored, 0));
     RH_NCCL(R->AllReduce(d_counts_total, d_counts_total, (size_t)b_total, ncclInt32, ncclSum, m->comm, m->stream));

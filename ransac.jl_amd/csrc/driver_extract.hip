@@ -62,24 +62,24 @@ int Driver::prune_managed_store(const size_t extracted_pos, const int64_t sum_n,
             RUN(rhk_store_cls(c, st.prep, st.n, pbase, p->eps, p->cos_alpha, st.d_cls, st.d_box, st.cls_cap));
             // kinds that look at the same stretch of the list go in one launch (faithful-mode spheres look at all of it)
             for (int pass = 0; pass < 2; pass++) {
-                const rh_prep *pr[4];
-                const void *cl[4];
-                const float *bx[4];
-                const int32_t *og[4], *nkp[4];
+                rh_score_job job;   // (every point of the stretch counts: no enabled words)
+                job.bstride = st.cls_cap;
+                job.eps = p->eps;
+                job.cosa = p->cos_alpha;
+                job.d_counts = st.counts;
                 int64_t first = -1;
-                int32_t bound = 0;
                 for (int q = 0; q < 4; q++) {
                     const bool all_disabled = (q == RH_SPHERE && !p->sphere_uses_enabled);
                     const bool in = st.n[q] > 0 && (pass == 0 ? !all_disabled : all_disabled);
-                    pr[q] = st.prep[q];
-                    cl[q] = (const char *)st.d_cls + 64 * (size_t)pbase[q];
-                    bx[q] = st.d_box + pbase[q];
-                    og[q] = st.iota + pbase[q];
-                    nkp[q] = st.d_nk + (in ? q : 4 + q);
-                    if (in) { first = all_disabled ? 0 : ndis_old; bound += st.n[q]; }
+                    job.bins.prep[q] = st.prep[q];
+                    job.bins.cls[q] = (const char *)st.d_cls + 64 * (size_t)pbase[q];
+                    job.bins.box[q] = st.d_box + pbase[q];
+                    job.bins.orig[q] = st.iota + pbase[q];
+                    job.nk[q] = st.d_nk + (in ? q : 4 + q);
+                    if (in) { first = all_disabled ? 0 : ndis_old; job.bound += st.n[q]; }
                 }
                 if (first < 0 || (int64_t)ndis_new - first <= 0) continue;
-                RUN(rhk_score4_dis(c, first, (int64_t)ndis_new - first, pr, cl, bx, st.cls_cap, og, nkp, bound, p->eps, p->cos_alpha, st.counts));
+                RUN(rhk_score4_dis(c, first, (int64_t)ndis_new - first, job));
             }
         } else {
             RUNH(hipMemcpyAsync(st.d_nk + 4, h_nk, 4 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));

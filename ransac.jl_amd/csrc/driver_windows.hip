@@ -4,6 +4,17 @@
 
 namespace rhdrv {
 
+// the score launch of a window of the candidate loop: the bins rhk_prep_entries left in ws (sizes: c->d_nk) against subset 1,
+// counts only; `bound` is a guess -- the window is queued before its list length is known
+static rh_score_job window_score_job(const rh_cloud *c, const rh_batch_ws &ws, const rh_params *p, int32_t bound, int32_t *d_counts)
+{
+    rh_score_job J = rh_subset_job(c, p, rh_ws_bins(ws), 4 * ws.batch_cap, c->d_nk);
+    J.bound = bound;
+    J.d_counts = d_counts;
+    J.open_count = true;
+    return J;
+}
+
 // Octree windows, one process: CHAINED.  Every iteration's scores change the level distribution the next
 // one samples from (fitting.jl:184, octree.jl:198-205), so nothing can be sampled ahead.  Instead the whole
 // iteration -- sampling, fits, scoring, the level update and the copy of its candidates to the host
@@ -88,29 +99,19 @@ int Driver::run_chained_windows(const size_t status_bytes)
         RUNH(hipMemsetAsync(w.d_status, 0, status_bytes, c->stream));
         rh_batch_ws &ws = c->ws[0];
         RUN(rh_ensure_batch(c, ws, w.entries_cap));
-        const rh_bins B = rh_ws_bins(ws);
-        const uint64_t *enw[4];
-        const int32_t *nkp[4];
-        for (int q = 0; q < 4; q++) {
-            enw[q] = (q == RH_SPHERE && !p->sphere_uses_enabled) ? nullptr : c->sub_enabled;
-            nkp[q] = c->d_nk + q;
-        }
-        c->s4_stop = &c->oct_state->stop;
-        c->s4_open_count = true;
+        rh_score_job job = window_score_job(c, ws, p, std::min<int32_t>(per_it, std::max<int32_t>((int32_t)((int64_t)cnt_est * bound_pct / 100) + 64, 1024)), w.d_counts);
+        job.stop = &c->oct_state->stop;
         int rc = RH_OK;
         for (int32_t it = 0; it < W && rc == RH_OK; it++) {
             rc = rhk_sample_fit(c, p, rng->s[0], k0 + it, 1, (int32_t)en.count, c->oct_state->P, w.d_entries, w.entries_cap, w.d_status, 1,
                                 c->d_nk, it, c->oct_state);
             if (rc == RH_OK) rc = rhk_prep_entries(c, ws, w.d_entries, (const int32_t *)w.d_status, w.entries_cap, per_it, w.d_counts, 1, p->eps,
                                                    p->cos_alpha, c->oct_state);
-            if (rc == RH_OK) rc = rhk_score_all_groups(c, ws, enw, B.prep, B.orig, nkp, std::min<int32_t>(per_it, std::max<int32_t>((int32_t)((int64_t)cnt_est * bound_pct / 100) + 64, 1024)), p->eps,
-                                                       p->cos_alpha, w.d_counts, nullptr, B.cls, B.box, 4 * ws.batch_cap);
+            if (rc == RH_OK) rc = rhk_score4_all(c, ws, job);
             if (rc == RH_OK) rc = rhk_oct_advance(c, p, c->oct_state, w.d_entries, w.d_status, w.entries_cap, w.d_counts, it, k0 + it, w.h_list,
                                                   w.h_list_counts, w.h_list_rank, w.h_list_slot, w.h_hdr);
             if (rc == RH_OK && hipEventRecord(w.ev_it[it], c->stream) != hipSuccess) { rh_set_error("hipEventRecord failed"); rc = RH_E_NODEVICE; }
         }
-        c->s4_stop = nullptr;
-        c->s4_open_count = false;
         if (rc != RH_OK) return rc;
         nwin++;
         return RH_OK;
@@ -301,18 +302,7 @@ int Driver::run_streams_device()
             // kernels read the true count), a longer list only gets fewer blocks per candidate
             const int32_t bound = std::min<int32_t>(w.entries_cap, std::max<int32_t>(4 * cnt_est, 1024));
             RUN(rhk_prep_entries(c, ws, w.d_entries, (const int32_t *)w.d_status, w.entries_cap, w.entries_cap, w.d_counts, 1, p->eps, p->cos_alpha));
-            const rh_bins B = rh_ws_bins(ws);
-            const uint64_t *enw[4];
-            const int32_t *nkp[4];
-            for (int q = 0; q < 4; q++) {
-                enw[q] = (q == RH_SPHERE && !p->sphere_uses_enabled) ? nullptr : c->sub_enabled;
-                nkp[q] = c->d_nk + q;
-            }
-            c->s4_open_count = true;   // (bound is a guess: the kernel's tail launch covers a longer list)
-            const int rcs = rhk_score_all_groups(c, ws, enw, B.prep, B.orig, nkp, bound, p->eps, p->cos_alpha, w.d_counts, nullptr,
-                                                 B.cls, B.box, 4 * ws.batch_cap);
-            c->s4_open_count = false;
-            if (rcs != RH_OK) return rcs;
+            RUN(rhk_score4_all(c, ws, window_score_job(c, ws, p, bound, w.d_counts)));
             w.scored = true;
         }
         // status + head of the list (+ counts) land in pinned host memory through one small kernel

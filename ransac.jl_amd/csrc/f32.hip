@@ -172,28 +172,32 @@ int rhk_f32_build(rh_cloud *c)
     return RH_OK;
 }
 
-int rhk_prep_f32(rh_cloud *c, rh_batch_ws &w, const int32_t *d_orig, const int64_t off[4], const int32_t *d_nk, int32_t nmax)
+// job.shapes -> the float records of the job's bins, in w.d_prep32 where the bins' `orig` lie in theirs
+int rhk_prep_f32(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t nmax)
 {
     if (nmax <= 0) return RH_OK;
+    if (job.shapes == nullptr) { rh_set_error("internal: Float32 scoring without the batch's shapes"); return RH_E_INTERNAL; }
     Off4 o4;
-    for (int k = 0; k < 4; k++) o4.o[k] = off[k];
-    hipLaunchKernelGGL(prep32_kernel, dim3(cdiv32(nmax, 256)), dim3(256), 0, c->stream, w.f32_shapes, w.f32_via_orig, d_orig, o4, d_nk,
-                       (rh_prepf *)w.d_prep32);
+    for (int k = 0; k < 4; k++) {
+        o4.o[k] = job.bins.orig[k] - job.bins.orig[0];
+        if (job.nk[k] != job.nk[0] + k) { rh_set_error("internal: Float32 scoring needs the bin sizes side by side"); return RH_E_INTERNAL; }
+    }
+    hipLaunchKernelGGL(prep32_kernel, dim3(cdiv32(nmax, 256)), dim3(256), 0, c->stream, job.shapes, job.shapes_via_orig, job.bins.orig[0], o4,
+                       job.nk[0], (rh_prepf *)w.d_prep32);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
 
-// all kinds of a binned batch (the Float64 path's bins: orig / nk, bin k at off[k]) against subset 1; masks (optional) in
-// INTERNAL order like the other scorers
-int rhk_score_all_f32(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const int32_t *d_orig,
-                      const int64_t off[4], const int32_t *d_nk, const int32_t nk_bound[4], const double eps[4],
-                      const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int)
+// all kinds of a binned batch (the Float64 path's bins: orig / nk) against subset 1; masks (optional) in INTERNAL order like
+// the other scorers
+int rhk_score_all_f32(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job)
 {
+    const int32_t *const nk_bound = job.kind_bound;
+    uint64_t *const d_masks_int = job.d_masks_int;
     int nmax = 0;
     for (int k = 0; k < 4; k++) nmax = std::max(nmax, (int)nk_bound[k]);
     if (nmax == 0 || c->s == 0) return RH_OK;
-    rh_prepf *prep32 = (rh_prepf *)w.d_prep32;
-    RH_TRY(rhk_prep_f32(c, w, d_orig, off, d_nk, nmax));
+    RH_TRY(rhk_prep_f32(c, w, job, nmax));
     const int64_t ntiles = (c->s + RH_SC_TILE - 1) / RH_SC_TILE;
     for (int k = 0; k < 4; k++) {
         if (nk_bound[k] == 0) continue;
@@ -204,8 +208,9 @@ int rhk_score_all_f32(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], 
         if (splits > ntiles) splits = ntiles;
         dim3 grid((unsigned)splits, (unsigned)ctiles);
 #define RH_S32(K, M)                                                                                                      \
-    hipLaunchKernelGGL((score32_kernel<K, M>), grid, dim3(RH_SC_THREADS), 0, c->stream, c->sub32, c->s_pad, c->s, en[k],    \
-                       prep32 + off[k], d_orig + off[k], d_nk + k, eps[k], cosa[k], d_counts, d_masks_int, c->swords)
+    hipLaunchKernelGGL((score32_kernel<K, M>), grid, dim3(RH_SC_THREADS), 0, c->stream, c->sub32, c->s_pad, c->s, job.en[k],                \
+                       (rh_prepf *)w.d_prep32 + (job.bins.orig[k] - job.bins.orig[0]), job.bins.orig[k], job.nk[k], job.eps[k], job.cosa[k], \
+                       job.d_counts, d_masks_int, c->swords)
         if (d_masks_int) {
             switch (k) {
             case RH_PLANE: RH_S32(RH_PLANE, true); break;

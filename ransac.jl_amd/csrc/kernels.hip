@@ -1021,22 +1021,18 @@ int32_t rh_spread_multiplier(int32_t b)
 }
 
 int rhk_prep_binned(rh_cloud *c, rh_batch_ws &w, const rh_shape *d_shapes, int32_t b, int32_t *d_nk, int32_t *d_counts_to_zero,
-                    int32_t *d_nk_other, int nk_is_zero, const double *eps, const double *cosa)
+                    int32_t *d_nk_other, int nk_is_zero, const double *eps, const double *cosa, int32_t *zero_extra, int32_t zero_extra_n)
 {
     if (!nk_is_zero) RH_HIP(hipMemsetAsync(d_nk, 0, 4 * sizeof(int32_t), c->stream));
     PreArgs QA = pre_args(c, w, eps, cosa);
     if (b == 0) return RH_OK;
     const int no_spread = rh_opt_on(c, RH_OPT_NO_SPREAD) ? 1 : 0;
-    // (consumed by this launch: set by rh_score_batch_allreduce_dev around its score call)
-    int32_t *zx = c->zero_extra;
-    const int32_t zxn = c->zero_extra_n;
-    c->zero_extra = nullptr; c->zero_extra_n = 0;
 #ifndef RH_PREP_BLOCK
 #define RH_PREP_BLOCK 64   // (one wave per block: the launch is a latency chain -- shape, bin reservation, divisions, records -- and 64 blocks spread it over 64 CUs: cfg3 step 0.0860 -> 0.0846 ms, cfg2 0.0431 -> 0.0421; 128: the same; 256: round 4)
 #endif
     hipLaunchKernelGGL(prep_binned_kernel, dim3(cdiv(b, RH_PREP_BLOCK)), dim3(RH_PREP_BLOCK), 0, c->stream, d_shapes, b, w.d_prep, w.d_orig,
                        d_nk, w.batch_cap, d_counts_to_zero, d_nk_other, no_spread ? 1 : rh_spread_multiplier(b),
-                       w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre : (rh4::rh_cls *)nullptr, QA, zx, zxn);
+                       w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre : (rh4::rh_cls *)nullptr, QA, zero_extra, zero_extra_n);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
@@ -1415,21 +1411,6 @@ int rhk_compact_generic(hipStream_t stream, const uint64_t *mask, int64_t nwords
                            idx_out, cap, (int32_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr);
     RH_HIP(hipGetLastError());
     return RH_OK;
-}
-
-// all kinds against subset 1 in one launch of the culled kernel (score4.hip); cls / box: the bins' classifier and culling
-// records (prep kernels); nk_total_bound >= the number of candidates over all kinds
-int rhk_score_all_groups(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const rh_prep *const prep[4],
-                         const int32_t *const orig[4], const int32_t *const nk[4], int32_t nk_total_bound,
-                         const double eps[4], const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int,
-                         const void *const cls[4], const float *const box[4], int64_t bstride)
-{
-    if (c->ngroups == 0 || nk_total_bound <= 0) return RH_OK;
-    if (cls == nullptr || box == nullptr || !rh_score_v4_enabled(c) || c->gb32 == nullptr || (d_masks_int != nullptr && !w.masks4)) {
-        rh_set_error("internal: the culled score kernel without its records (classifier, culling, group boxes, mask lists)");
-        return RH_E_INTERNAL;
-    }
-    return rhk_score4_all(c, w, en, prep, cls, box, bstride, orig, nk, nk_total_bound, eps, cosa, d_counts, d_masks_int);
 }
 
 // liveness pass of a cloud without the culled path: candidates against dis[first, first + cnt) (counts only), brute force

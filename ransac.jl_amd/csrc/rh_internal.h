@@ -125,9 +125,10 @@ struct rh_batch_ws {
     uint16_t *d_stlist = nullptr;
     int32_t *d_stcount = nullptr;
     int64_t stlist_cap = 0, stlist_nst = 0;
-    // Float32 clouds, brute-force kernel: the shapes of the batch being scored, on the device ...
-    const rh_shape *f32_shapes = nullptr;
-    int f32_via_orig = 0;              // ... indexed through d_orig (caller's order) or directly (sorted like the bins)
+    // mask un-permutation of rows that span 2..16 segments (rhk_unpermute_masks4): per output segment and internal word, the bits
+    // that land in the segment.  Built on the slot's own stream, so stream order alone puts it in front of the slot's readers.
+    uint64_t *d_segmask = nullptr;
+    int64_t segmask_words = 0;         // ... made for this segment width (0: none yet)
 };
 // the four kinds' bins of a prepared batch: candidate records, original positions, classifier and culling records
 struct rh_bins {
@@ -153,6 +154,24 @@ static inline rh_bins rh_ws_bins(const rh_batch_ws &w)
     const int64_t off[4] = { 0, w.batch_cap, 2 * w.batch_cap, 3 * w.batch_cap };
     return rh_bins_at(w.d_prep, w.d_orig, w.d_qpre, w.d_box, off);
 }
+// Everything ONE score launch is told: the launchers below take it whole, a call site fills it in once.
+struct rh_score_job {
+    rh_bins bins = {};                 // the four kinds' bins ...
+    int64_t bstride = 0;               // ... the fields of their culling records this far apart
+    const uint64_t *en[4] = { nullptr, nullptr, nullptr, nullptr };   // per kind the enabled words of the point set (null: every point counts): rh_subset_job
+    const int32_t *nk[4] = { nullptr, nullptr, nullptr, nullptr };    // per kind the bin's size, on the device
+    int32_t bound = 0;                 // >= the candidates of all kinds together (sizes the culled launch)
+    int32_t kind_bound[4] = { 0, 0, 0, 0 };   // >= those of each kind (brute-force kernels, the per-kind timing leg)
+    const double *eps = nullptr, *cosa = nullptr;   // [4] thresholds the bins' records were made for
+    int32_t *d_counts = nullptr;
+    uint64_t *d_masks_int = nullptr;   // null: counts only.  Culled kernel: the workspace's entry lists (w.d_occ, w.mstride4)
+    rh_s4_points points = { nullptr, 0, 0, 0, nullptr };   // pts null: subset 1 in internal order; else rhk_score4_dis' stretch of the disabled list
+    const int32_t *stop = nullptr;     // chained octree windows: the window's stop flag as the score kernel sees it
+    bool open_count = false;           // `bound` is a guess (windows of the candidate loop): a tail launch covers a longer list
+    hipEvent_t ev_listed = nullptr;    // timed launches: recorded behind the list launch, in front of the score launch
+    const rh_shape *shapes = nullptr;  // Float32 clouds, brute-force kernel: the batch's shapes on the device ...
+    int shapes_via_orig = 0;           // ... indexed through the bins' orig (caller's order) or directly (sorted like the bins)
+};
 struct rh_cloud {
     int64_t opt[RH_OPT_COUNT];         // rh_set_option on this cloud (RH_OPTION_UNSET: the process-wide value holds); rh_opt_init_cloud
     int device = -1;
@@ -252,34 +271,18 @@ struct rh_cloud {
     uint32_t pipe_k = 0;               // batches since the pipeline (re)started
 
     // Shared by the batches: state of the scoring path that is per CLOUD, although batches on several streams go through the
-    // code that touches it.  Why each is safe to share today:
-    //   d_nk, d_masks, d_zero, ev_cull / time_cull / last_cull_ms: only touched by calls that join the slots first and run
-    //     on ws[0] (rh_score_batch, rh_score_batch_dev_timed, rh_ransac's windows) -- no other batch is in flight then.
-    //   s4_points, s4_stop, s4_open_count: hand-overs to the score launcher, set and reset within one such joined call (null /
-    //     false whenever a pipelined batch is queued).
-    //   zero_extra: set by rh_score_batch_allreduce_dev and consumed by the rhk_prep_binned launch of the rh_score_batch_dev
-    //     it calls next, within that one host call.
-    //   last_s4: host-side record of the last sized launch, whichever slot it was on (a cloud is used by one host thread at a time).
-    //   unp_segmask / unp_seg_words: NOT safe.  rhk_unpermute_masks4 builds the table on the stream of whichever batch needs it
-    //     first and other slots' streams then read it with no ordering behind that launch; a change of "unp_words" frees and
-    //     rebuilds it while un-permutations on the other streams may still read the old one.
-    //     TODO ("data race on the per-cloud segment-mask table"): build it on a joined cloud, or give every
-    //     rh_batch_ws a table of its own.
+    // code that touches it.  Why each is safe to share:
+    //   d_nk, d_masks, d_zero, ev_cull / last_cull_ms: only touched by calls that join the slots first and run on ws[0]
+    //     (rh_score_batch, rh_score_batch_dev_timed, rh_ransac's windows) -- no other batch is in flight then.
+    //   last_s4: host-side record of the last sized batch launch, whichever slot it was on (a cloud is used by one host thread at a time).
+    // Whatever else a score launch is told travels in its rh_score_job.
     int32_t *d_nk = nullptr;           // [4] bin sizes of a batch whose sizes the host uploads (rh_score_batch) or the sampler leaves (rh_ransac)
     uint64_t *d_masks = nullptr;       // rh_score_batch: the masks in subset order on their way to the host (grown on demand)
     int64_t masks_cap = 0;
     int32_t *d_zero = nullptr;         // 64 zero bytes: the bin size a kind left out of a launch reads (per-kind timing leg)
     hipEvent_t ev_cull = nullptr;      // timed launches (rh_score_batch_dev_timed): behind the list launch, in front of the score launch
-    bool time_cull = false;
     float last_cull_ms = 0.f;
-    const rh_s4_points *s4_points = nullptr;   // the launches being queued run over this set instead of subset 1 (rhk_score4_dis)
-    const int32_t *s4_stop = nullptr;  // chained octree windows: the window's stop flag as the score kernel sees it (null outside such windows)
-    bool s4_open_count = false;        // the candidate count of the score launches being queued is a guess (windows of the candidate loop)
-    int32_t *zero_extra = nullptr;     // the next rhk_prep_binned launch also zeroes zero_extra_n ints from here (then forgets it)
-    int32_t zero_extra_n = 0;
-    int32_t last_s4[4] = { 0, 0, 0, 0 };   // the last sized launch of the culled score kernel: R, lists taken (0 / 1), rows, tiles (rh_score_launch_info)
-    uint64_t *unp_segmask = nullptr;   // mask un-permutation: per output segment and internal word, the bits that land in the segment
-    int64_t unp_seg_words = 0;         //   ... made for this segment width
+    int32_t last_s4[4] = { 0, 0, 0, 0 };   // the last sized batch launch of the culled score kernel: R, lists taken (0 / 1), rows, tiles (rh_score_launch_info)
 
     int64_t *d_ranks = nullptr;        // select in/out
     int64_t ranks_cap = 0;
@@ -304,6 +307,23 @@ struct rh_cloud {
     void *h_pin = nullptr;
     int64_t h_pin_cap = 0;
 };
+
+// the job of scoring prepared bins (sizes: d_nk[0 .. 3]) against subset 1 with p's thresholds; the caller adds the bounds, the
+// outputs and whatever else its launch is told.  The one place that says which enabled words a kind's scorer applies:
+// sphere.jl:121,131 -- the sphere scorer builds `ens` and never applies it, so faithful mode counts every point
+static inline rh_score_job rh_subset_job(const rh_cloud *c, const rh_params *p, const rh_bins &bins, int64_t bstride, const int32_t *d_nk)
+{
+    rh_score_job J;
+    J.bins = bins;
+    J.bstride = bstride;
+    for (int k = 0; k < 4; k++) {
+        J.en[k] = (k == RH_SPHERE && !p->sphere_uses_enabled) ? nullptr : c->sub_enabled;
+        J.nk[k] = d_nk + k;
+    }
+    J.eps = p->eps;
+    J.cosa = p->cos_alpha;
+    return J;
+}
 
 // liveness pass over a small store (rhk_liveness_small): per kind the prepared candidates, their number, where
 // their flags start, and the first entry of the disabled list they have to be tested against
@@ -330,13 +350,14 @@ int rhk_prep_entries(rh_cloud *c, rh_batch_ws &w, const rh_cand_entry *d_entries
                      int32_t launch_bound, int32_t *d_counts, int nk_is_zero, const double *eps = nullptr,
                      const double *cosa = nullptr, const rh_oct_state *ost = nullptr);   // bin sizes: c->d_nk
 int rhk_prep_binned(rh_cloud *c, rh_batch_ws &w, const rh_shape *d_shapes, int32_t b, int32_t *d_nk, int32_t *d_counts_to_zero,
-                    int32_t *d_nk_other, int nk_is_zero, const double *eps = nullptr, const double *cosa = nullptr);
+                    int32_t *d_nk_other, int nk_is_zero, const double *eps = nullptr, const double *cosa = nullptr,
+                    int32_t *zero_extra = nullptr, int32_t zero_extra_n = 0);   // the launch also zeroes zero_extra_n ints from zero_extra
 bool rh_score_v4_enabled(const rh_cloud *c);
-// (w: the super-tile lists of the launch; masks: the entry lists d_masks_int = w.d_masks_int with their cursors w.d_occ, rows w.mstride4 apart)
-int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const rh_prep *const prep[4], const void *const cls[4],
-                   const float *const box[4], int64_t bstride, const int32_t *const orig[4], const int32_t *const nk[4],
-                   int32_t nk_total_bound, const double eps[4], const double cosa[4], int32_t *d_counts,
-                   uint64_t *d_masks_int = nullptr);
+// culled path (k-d leaf order + per-group boxes): all kinds in one launch of score4.hip's kernel over job.points.  w: the
+// super-tile lists of the launch and, with masks, the entry lists they leave it as (job.d_masks_int = w.d_masks_int, cursors
+// w.d_occ, rows w.mstride4 apart: rhk_unpermute_masks4).  launch_info (optional): a sized launch (not open_count) leaves its
+// R, lists taken (0 / 1), rows and tiles there.
+int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t *launch_info = nullptr);
 int rhk_unpermute_masks4(rh_cloud *c, rh_batch_ws &w, int32_t b, uint64_t *d_out);   // score4.hip: w's entry lists -> dense rows
 // score nk candidates of one kind; nk_host < 0: count is only known on the device (d_nk),
 // launch for an upper bound of nk_bound candidates
@@ -344,27 +365,14 @@ int rhk_score_kind(rh_cloud *c, int kind, const double *pts, int64_t stride, int
                    const uint64_t *enabled_words_or_null, const rh_prep *d_prep, const int32_t *d_orig,
                    const int32_t *d_nk, int32_t nk_bound, double eps, double cosa, int32_t *d_counts,
                    uint64_t *d_masks_or_null, int64_t mask_stride);
-// culled path over c->sub (k-d leaf order + per-group boxes): all kinds in one launch of score4.hip's kernel; masks
-// (optional) leave it as entry lists (rhk_unpermute_masks4)
-int rhk_score_all_groups(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const rh_prep *const prep[4],
-                         const int32_t *const orig[4], const int32_t *const nk[4], int32_t nk_total_bound,
-                         const double eps[4], const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int,
-                         const void *const cls[4],                 // cls / box: classifier and culling records (score4_device.h) of the
-                         const float *const box[4], int64_t bstride);   // same bins and thresholds
-int rhk_gb32_build(rh_cloud *c);
+int rhk_gb32_build(rh_cloud *c);   // (score4.hip: gb32 from gb)
 int rhk_store_cls(rh_cloud *c, const rh_prep *const prep[4], const int32_t n[4], const int32_t pbase[5], const double eps[4],
                   const double cosa[4], void *d_cls, float *d_box, int64_t bstride);
-int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, const rh_prep *const prep[4], const void *const cls[4], const float *const box[4],
-                   int64_t bstride, const int32_t *const orig[4], const int32_t *const nk[4], int32_t nk_total_bound, const double eps[4],
-                   const double cosa[4], int32_t *d_counts);
-// (score4.hip: gb32 from gb)
-int rhk_prep_f32(rh_cloud *c, rh_batch_ws &w, const int32_t *d_orig, const int64_t off[4], const int32_t *d_nk,
-                 int32_t nmax);                                    // w.f32_shapes -> w.d_prep32 (f32.hip)
-// Float32 clouds (f32.hip)
+int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, rh_score_job job);   // the same over dis[first, first + cnt): fills in job.points
+// Float32 clouds (f32.hip); the brute-force pair takes bins whose sizes lie side by side (job.nk[k] = job.nk[0] + k)
 int rhk_f32_build(rh_cloud *c);
-int rhk_score_all_f32(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const int32_t *d_orig,
-                      const int64_t off[4], const int32_t *d_nk, const int32_t nk_bound[4], const double eps[4],
-                      const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int);
+int rhk_prep_f32(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t nmax);   // job.shapes -> w.d_prep32
+int rhk_score_all_f32(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job);
 int rhk_refit_mask_f32(rh_cloud *c, const rh_shape &shape, double eps, double cosa, bool apply = false);
 int rhk_cloud_aabb(rh_cloud *c, const double *d_xyz, int64_t n, double lo[3], double hi[3], bool has[3], double *mag);   // kdorder.hip
 int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const int32_t *d_idx0);   // kdorder.hip: subset 1's k-d leaf order on the device
@@ -498,6 +506,9 @@ int32_t rh_spread_multiplier(int32_t b);   // t -> (t * m) mod b: a permutation 
 // freed, `bytes` allocated, and only then the capacity published (*cap = new_cap; cap may be null); a failure leaves null / 0
 int rh_grow_buffer(rh_cloud *c, void **buf, int64_t *cap, int64_t new_cap, size_t bytes);
 int rh_ensure_batch(rh_cloud *c, rh_batch_ws &w, int64_t b);
+// rh_score_batch_dev whose prepare launch also zeroes zero_extra_n ints from zero_extra (null: nothing besides the counts)
+int rh_score_batch_dev_zeroing(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const rh_params *p, int32_t *d_counts, uint64_t *d_masks,
+                               int32_t *zero_extra, int32_t zero_extra_n);
 int rh_join_batches(rh_cloud *c);   // the cloud's stream waits for what the other batch slots have in flight ("batches_in_flight")
 int rh_cloud_join(rh_cloud *c);     // the same with the cloud's device made current first (options.cpp)
 int rh_ensure_pin(rh_cloud *c, int64_t bytes);

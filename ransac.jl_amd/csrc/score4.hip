@@ -1045,26 +1045,32 @@ static int ensure_stlists(rh_cloud *c, rh_batch_ws &w, int64_t cap)
     return RH_OK;
 }
 
-// the v4 launch: cls[k] / box[k] = the classifier / culling records of bin prep[k], slot for slot, made for eps / cosa.
-int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], const rh_prep *const prep[4], const void *const cls[4],
-                   const float *const box[4], int64_t bstride, const int32_t *const orig[4], const int32_t *const nk[4],
-                   int32_t nk_total_bound, const double eps[4], const double cosa[4], int32_t *d_counts, uint64_t *d_masks_int)
+// the v4 launch: job.bins' cls[k] / box[k] = the classifier / culling records of bin prep[k], slot for slot, made for eps / cosa.
+int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t *launch_info)
 {
-    const bool open_count = c->s4_open_count;
+    const rh_bins &B = job.bins;
+    const int32_t nk_total_bound = job.bound;
+    int32_t *const d_counts = job.d_counts;
+    uint64_t *const d_masks_int = job.d_masks_int;
+    const bool open_count = job.open_count;
     const bool f32cloud = c->f32;   // the exact tests in binary32, on float records derived from `prep`
     // the points: subset 1 in internal order, or the set rhk_score4_dis put in place (a segment of the disabled list)
-    rh_s4_points PS = { c->sub, c->s_pad, c->s, c->ngroups, c->gb32 };
-    if (c->s4_points != nullptr) PS = *c->s4_points;
+    const bool on_subset = job.points.pts == nullptr;
+    const rh_s4_points PS = on_subset ? rh_s4_points{ c->sub, c->s_pad, c->s, c->ngroups, c->gb32 } : job.points;
     const int64_t ntiles = (PS.ngroups + S4_TG - 1) / S4_TG;
     const int nchunks = cdiv4(nk_total_bound, 64) + 3;   // every bin may end in a partial chunk
     if (ntiles == 0 || nk_total_bound <= 0) return RH_OK;
+    if (B.cls[0] == nullptr || B.box[0] == nullptr || !rh_score_v4_enabled(c) || PS.gb32 == nullptr || (d_masks_int != nullptr && !w.masks4)) {
+        rh_set_error("internal: the culled score kernel without its records (classifier, culling, group boxes, mask lists)");
+        return RH_E_INTERNAL;
+    }
     const int dbg = (int)rh_opt_int(c, RH_OPT_G2_DBG, 0);   // (diag build only -- 1: no pair survives stage 1, the skeleton alone: tools/region_counters.sh)
     S4AllArgs A;
     for (int k = 0; k < 4; k++)
-        A.k[k] = { (const rh_cls *)cls[k], box[k], prep[k], orig[k], nk[k], en[k], eps[k], cosa[k] };
-    A.stop = c->s4_stop;
+        A.k[k] = { (const rh_cls *)B.cls[k], B.box[k], B.prep[k], B.orig[k], job.nk[k], job.en[k], job.eps[k], job.cosa[k] };
+    A.stop = job.stop;
     A.ntiles = ntiles;
-    A.bstride = bstride;
+    A.bstride = job.bstride;
     A.ngroups = PS.ngroups;
     A.gb32 = PS.gb32;
     A.masks = d_masks_int;
@@ -1083,7 +1089,7 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], con
     // has no inlier in any of its groups.  For launches whose candidate count the host knows, on subset 1.
     A.stlist = nullptr; A.stcount = nullptr; A.stcap = 0;
     const int64_t st_opt = rh_opt_int(c, RH_OPT_ST_CULL, 0);   // 0 = by size, 1 = whenever possible, 2 = never
-    bool use_lists = !open_count && c->s4_points == nullptr && dbg == 0 && c->st32 != nullptr && c->nst >= 2 && nk_total_bound <= 16384 && st_opt != 2;
+    bool use_lists = !open_count && on_subset && dbg == 0 && c->st32 != nullptr && c->nst >= 2 && nk_total_bound <= 16384 && st_opt != 2;
     // By size (measured, cfg3's mix on 10M / 20M / 30M / cfg5's on 50M points = 1221 / 2442 / 3662 / 6104 tiles, a batch of 4096): the
     // lists cut the launch's instructions by a fifth, but its blocks become three times fewer and heavier, and a small grid then
     // ends in a long tail (and the list launch sits between the prepare and the score launch) -- one batch at a time +17 % / +0 % /
@@ -1094,11 +1100,11 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], con
     if (use_lists) {
         RH_TRY(ensure_stlists(c, w, ((int64_t)nk_total_bound + 63) / 64 * 64));
         StCullArgs SA;
-        for (int k = 0; k < 4; k++) { SA.box[k] = box[k]; SA.nk[k] = nk[k]; }
-        SA.bstride = bstride; SA.stcap = w.stlist_cap; SA.st32 = c->st32; SA.stlist = w.d_stlist; SA.stcount = w.d_stcount;
+        for (int k = 0; k < 4; k++) { SA.box[k] = B.box[k]; SA.nk[k] = job.nk[k]; }
+        SA.bstride = job.bstride; SA.stcap = w.stlist_cap; SA.st32 = c->st32; SA.stlist = w.d_stlist; SA.stcount = w.d_stcount;
         hipLaunchKernelGGL(st_cull_kernel, dim3((unsigned)c->nst, 4), dim3(256), 0, c->stream, SA);
         A.stlist = w.d_stlist; A.stcount = w.d_stcount; A.stcap = w.stlist_cap;
-        if (c->time_cull && c->ev_cull != nullptr) RH_HIP(hipEventRecord(c->ev_cull, c->stream));
+        if (job.ev_listed != nullptr) RH_HIP(hipEventRecord(job.ev_listed, c->stream));
     }
     const int env_r = (int)rh_opt_int(c, RH_OPT_S4_ROWS, 0);   // rh_set_option(.., "s4_rows", ..), read on every launch: the fuzzers vary it from case to case
     // R = chunks of 64 candidates per block row.  A block's fixed work -- prologue, staging its tile, the four kinds' dispatch --
@@ -1117,7 +1123,7 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], con
     else if (ntiles * ((nchunks + 3) / 4) >= 4000) R = 4;
     else R = 2;
     int64_t rows = (nchunks + R - 1) / R;
-    if (!open_count) { c->last_s4[0] = R; c->last_s4[1] = use_lists ? 1 : 0; c->last_s4[2] = (int32_t)rows; c->last_s4[3] = (int32_t)ntiles; }
+    if (!open_count && launch_info != nullptr) { launch_info[0] = R; launch_info[1] = use_lists ? 1 : 0; launch_info[2] = (int32_t)rows; launch_info[3] = (int32_t)ntiles; }
     if (rows > 65535) { rh_set_error("batch of %d candidates is too large for one launch", nk_total_bound); return RH_E_INVALID; }
     // XCD-aware grid: the hardware deals consecutive block ids round-robin to the 8 XCDs, each with an L2 of its own; with grid.x
     // padded to a multiple of 8 a tile meets the same XCD in every row (only with >= 128 tiles per XCD: cfg2's 15 per XCD unbalance)
@@ -1141,8 +1147,8 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], con
     // (measured on the cfg3 octree leg, 18 chunks: 27 us against 39 + 7 for rows + tail; from ~40 chunks on the rows win:
     // sweep of the threshold 32 / 40 / 48 / 64 -> 0.0491 / 0.0498 / 0.0498 / 0.0499 s for the leg)
     const int loop_max = open_count ? 32 : 0;
-    if (loop_max > 0 && d_masks_int == nullptr && nchunks <= loop_max) {
-        dim3 gt(tiles_x, 1);
+    auto launch_tail = [&](unsigned ny) {   // the TAIL instantiations (open-ended windows: R = 4 / 8, no masks) on a (tile, ny) grid
+        const dim3 gt(tiles_x, ny);
         if (f32cloud) {
             if (R == 4) hipLaunchKernelGGL((score4_kernel<4, false, true, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
             else hipLaunchKernelGGL((score4_kernel<8, false, true, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
@@ -1150,6 +1156,9 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], con
             if (R == 4) hipLaunchKernelGGL((score4_kernel<4, false, false, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
             else hipLaunchKernelGGL((score4_kernel<8, false, false, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
         }
+    };
+    if (loop_max > 0 && d_masks_int == nullptr && nchunks <= loop_max) {
+        launch_tail(1);
         RH_HIP(hipGetLastError());
         return RH_OK;
     }
@@ -1179,14 +1188,7 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const uint64_t *const en[4], con
         // its blocks return at once when there is nothing (the usual case)
         if (d_masks_int != nullptr) { rh_set_error("rhk_score4_all: masks need an exact candidate count"); return RH_E_INTERNAL; }
         A.row0 = (int)rows;
-        dim3 gt(tiles_x, 2);
-        if (f32cloud) {
-            if (R == 4) hipLaunchKernelGGL((score4_kernel<4, false, true, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
-            else hipLaunchKernelGGL((score4_kernel<8, false, true, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
-        } else {
-            if (R == 4) hipLaunchKernelGGL((score4_kernel<4, false, false, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
-            else hipLaunchKernelGGL((score4_kernel<8, false, false, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
-        }
+        launch_tail(2);
     }
     RH_HIP(hipGetLastError());
     return RH_OK;
@@ -1224,23 +1226,17 @@ int rhk_store_cls(rh_cloud *c, const rh_prep *const prep[4], const int32_t n[4],
     return RH_OK;
 }
 
-// the v4 kernel on cnt points of the disabled list from `first` on (every one counts: no enabled words)
-int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, const rh_prep *const prep[4], const void *const cls[4], const float *const box[4],
-                   int64_t bstride, const int32_t *const orig[4], const int32_t *const nk[4], int32_t nk_total_bound, const double eps[4],
-                   const double cosa[4], int32_t *d_counts)
+// the v4 kernel on cnt points of the disabled list from `first` on (every one counts: the job comes without enabled words)
+int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, rh_score_job job)
 {
-    if (cnt <= 0 || nk_total_bound <= 0) return RH_OK;
+    if (cnt <= 0 || job.bound <= 0) return RH_OK;
     const int64_t ng = (cnt + 63) / 64;
     if (ng > c->ng_pad) { rh_set_error("rhk_score4_dis: %lld groups", (long long)ng); return RH_E_INTERNAL; }
     RH_TRY(rhk_group_bounds_of(c, c->dis + first, c->dis_stride, cnt, ng, c->dis_gb, c->ng_pad));
     hipLaunchKernelGGL(gb32_kernel, dim3(cdiv4(ng, 256)), dim3(256), 0, c->stream, c->dis_gb, c->ng_pad, ng, c->dis_gb32);
     RH_HIP(hipGetLastError());
-    const rh_s4_points PS = { c->dis + first, c->dis_stride, cnt, ng, c->dis_gb32 };
-    const uint64_t *en[4] = { nullptr, nullptr, nullptr, nullptr };
-    c->s4_points = &PS;
-    const int rc = rhk_score4_all(c, c->ws[0], en, prep, cls, box, bstride, orig, nk, nk_total_bound, eps, cosa, d_counts);   // (no lists over s4_points: w is not touched)
-    c->s4_points = nullptr;
-    return rc;
+    job.points = { c->dis + first, c->dis_stride, cnt, ng, c->dis_gb32 };
+    return rhk_score4_all(c, c->ws[0], job);   // (no lists over another set than subset 1: w is not touched)
 }
 
 #ifdef RH_DIAG
@@ -1365,17 +1361,14 @@ int rhk_unpermute_masks4(rh_cloud *c, rh_batch_ws &w, int32_t b, uint64_t *d_out
         attr_set = true;
     }
     const uint64_t *sm = nullptr;
-    if (nseg > 1 && nseg <= 16) {   // which bits of a word belong to which segment: made once per cloud and segment width
-        if (c->unp_segmask == nullptr || c->unp_seg_words != seg_words) {
-            (void)hipFree(c->unp_segmask);
-            c->unp_segmask = nullptr;
-            RH_HIP(hipMalloc((void **)&c->unp_segmask, sizeof(uint64_t) * (size_t)nseg * (size_t)c->ng_pad));
+    if (nseg > 1 && nseg <= 16) {   // which bits of a word belong to which segment: made once per workspace and segment width, on its stream
+        if (w.d_segmask == nullptr || w.segmask_words != seg_words) {
+            RH_TRY(rh_grow_buffer(c, (void **)&w.d_segmask, &w.segmask_words, seg_words, sizeof(uint64_t) * (size_t)nseg * (size_t)c->ng_pad));
             hipLaunchKernelGGL(segmask_kernel, dim3((unsigned)cdiv4(c->ngroups, 256)), dim3(256), 0, c->stream, c->sub_perm, c->s, c->ngroups,
-                               seg_words * 64, nseg, c->ng_pad, c->unp_segmask);
+                               seg_words * 64, nseg, c->ng_pad, w.d_segmask);
             RH_HIP(hipGetLastError());
-            c->unp_seg_words = seg_words;
         }
-        sm = c->unp_segmask;
+        sm = w.d_segmask;
     }
     const bool waveword = nseg == 1;
     if (waveword)

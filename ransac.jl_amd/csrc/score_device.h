@@ -1,5 +1,5 @@
-// score_device.h -- the per-point tests, the conservative group-box tests and the band prefilter of the score
-// kernels (shared by kernels.hip and score3.hip; moved here unchanged from kernels.hip).
+// score_device.h -- the per-point tests and the conservative group-box tests of the score and refit kernels (shared by
+// kernels.hip, score4.hip and korder.hip).
 //
 // Numerics contract: IEEE binary64, the reference's operation order, NO fused multiply-add (built with
 // -ffp-contract=off), correctly rounded sqrt and divide.  Each per-point test cites the reference function it

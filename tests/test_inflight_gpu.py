@@ -16,12 +16,18 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def scene():
-    import bench
+def arrays():
     prim = ["plane", "plane", "sphere", "cylinder", "cone", "cylinder"]
     n = 400_000
     xyz, nrm, truth = synth.make_cloud(n, prim, 0.25, seed=31)
     subs = synth.make_subsets(n, 8, seed=31)       # 50 000 subset points: the culled kernel
+    return xyz, nrm, truth, subs
+
+
+@pytest.fixture(scope="module")
+def scene(arrays):
+    import bench
+    xyz, nrm, truth, subs = arrays
     pc = R.RANSACCloud(xyz, nrm, subs)
     oc = orc.Cloud(xyz, nrm, subs[0])
     cp = R.params_to_c(R.ransacparameters([R.FittedPlane, R.FittedSphere, R.FittedCylinder, R.FittedCone]))
@@ -160,6 +166,58 @@ def test_mask_batches_in_flight(scene, in_flight):
             i = k % len(sizes)
             got = mk[k % in_flight].cpu().numpy().view(np.uint64)[: sizes[i] * w].reshape(sizes[i], w)
             assert np.array_equal(got, want[i][1]) and np.array_equal(cn[k % in_flight].cpu().numpy()[:sizes[i]], want[i][0])
+
+
+def test_first_mask_batch_of_a_cloud_on_another_slot_than_0(scene, arrays):
+    """a fresh cloud whose first mask batches land on slots 1, 2, 0, ... with rows of several segments ("unp_words"): every slot
+    un-permutes with a segment-mask table of its own, built on its own stream, and a change of the segment width rebuilds the
+    tables while nothing is joined.  Dense masks and counts of every batch equal those of the host-buffer call, word for word.
+    (With one table per cloud the other slots read a table another stream was still writing, or had just freed: a race, a
+    matter of timing -- this test asserts the right result on that path and is its only cover; it cannot be made to fail
+    deterministically there and must not be looped to try.)"""
+    import torch
+    _, oc, cp, arrs, _, b = scene
+    xyz, nrm, _, subs = arrays
+    lib = R.lib()
+    oc.enable_all()
+    pc = R.RANSACCloud(xyz, nrm, subs)      # no host-side mask call on it before the batches below
+    w = (len(subs[0]) + 63) // 64
+    assert len(subs[0]) == 50_000 and w == 782
+    sizes = [b, 900, b, 40, 1300, b, 700, b, 64]
+    batches = [rdist.DeviceBatch(pc, arrs[i], b) for i in range(len(sizes))]
+    cn = [torch.zeros(b, dtype=torch.int32, device="cuda") for _ in sizes]       # a buffer of its own per batch: all are read back
+    mk = [torch.zeros(b * w, dtype=torch.int64, device="cuda") for _ in sizes]
+    torch.cuda.synchronize()
+
+    def run(k, masks=True):
+        L.check(lib.rh_score_batch_dev(pc._h, batches[k].slice_ptr(0), sizes[k], C.byref(cp), C.c_void_p(cn[k].data_ptr()),
+                                       C.c_void_p(mk[k].data_ptr()) if masks else None))
+    with R.option("batches_in_flight", 3, cloud=pc):
+        with R.option("unp_words", 128, cloud=pc):      # 7 segments a row
+            run(0, masks=False)                         # slot 0
+            for k in range(1, 6):                       # slots 1, 2, 0, 1, 2: no join in between
+                run(k)
+            L.check(lib.rh_cloud_sync(pc._h))
+            R.set_option("unp_words", 64, cloud=pc)     # 13 segments a row
+            for k in range(6, 9):
+                run(k)
+            L.check(lib.rh_cloud_sync(pc._h))
+    got = [(cn[k].cpu().numpy()[:sizes[k]].copy(), mk[k].cpu().numpy().view(np.uint64)[: sizes[k] * w].reshape(sizes[k], w).copy())
+           for k in range(len(sizes))]
+    # only now the expected values: the host-buffer call (one segment a row again), and the oracle on one of the batches
+    for k, nb in enumerate(sizes):
+        want_counts, want_masks = R.score_batch(pc, (L.Shape * nb).from_buffer_copy(bytes(arrs[k])[: C.sizeof(L.Shape) * nb]), cp, want_masks=True)
+        assert want_masks.shape == (nb, w)
+        assert np.array_equal(got[k][0], want_counts), k
+        if k > 0:
+            assert np.array_equal(got[k][1], want_masks), k
+    sh = (orc.Shape * sizes[4])()
+    C.memmove(sh, arrs[4], C.sizeof(L.Shape) * sizes[4])
+    oc_counts, oc_masks = oc.score_batch(sh, orc.Params.from_buffer_copy(bytes(cp)), want_masks=True)
+    assert int(oc_counts.sum()) > 10_000
+    assert np.array_equal(got[4][0], oc_counts) and np.array_equal(got[4][1], oc_masks)
+    for bt in batches:
+        bt.free()
 
 
 def test_the_same_buffer_call_after_call_is_still_right(scene):

@@ -22,8 +22,8 @@ ring_masks = [torch.zeros(len(shapes) * words, dtype=torch.int64, device="cuda")
 
 
 def batches_in_flight(pc):
-    """every batch slot of the cloud gets its stream and its workspaces (counts only, then with masks): the cloud's
-    destruction has to free them all"""
+    """every batch slot of the cloud gets its stream and its workspaces (counts only, then with masks -- a slot whose rows
+    span several segments also holds a segment-mask table of its own): the cloud's destruction has to free them all"""
     lib = R.lib()
     bt = rdist.DeviceBatch(pc, shapes_c, len(shapes))
     R.set_option("batches_in_flight", 4, cloud=pc)
