@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 110
+#define RH_VERSION 111
 
 enum {
     RH_OK = 0,
@@ -159,6 +159,36 @@ int rh_score_batch_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const r
  * 1-based.  If more than cap are found returns RH_E_CAPACITY with *n_out = needed. */
 int rh_refit(rh_cloud *c, const rh_shape *shape, const rh_params *p,
              int64_t *idx_out_1based, int64_t cap, int64_t *n_out);
+
+/* ---- the largest connected patch of a refit set (Schnabel et al. 2007, section 4.4; no live counterpart in the reference,
+ *      whose parameterspacebitmap.jl is dead code) ----
+ * rh_refit returns every enabled compatible point of the whole cloud: two coplanar table tops come out as one plane.
+ * rh_refit_component keeps the largest connected component of that set, with connectivity on a 3-D voxel grid:
+ *  1. I = the set rh_refit returns for (cloud, shape, params).  Its points are finite (a NaN or inf fails the distance test);
+ *  2. o = the componentwise minimum of the coordinates over I (binary64; on a Float32 cloud the floats promoted exactly);
+ *  3. the cell of point i is (floor((x_i - o_x) / beta), floor((y_i - o_y) / beta), floor((z_i - o_z) / beta)): IEEE
+ *     binary64 subtraction and division, no contraction, floor, then integers.  beta must be finite and > 0, and no axis may
+ *     have more than 2^20 cells: RH_E_INVALID otherwise;
+ *  4. two occupied cells are adjacent when every coordinate differs by at most 1 (conn26 != 0), or, with conn26 = 0, when
+ *     exactly one coordinate differs by exactly 1;
+ *  5. a component is a maximal set of occupied cells joined by adjacency; its size is its number of POINTS, not of cells;
+ *     the largest wins, and among equals the one that holds the smallest point index;
+ *  6. the result is the points of I in the winning component, ascending and 1-based like rh_refit's.  An empty I gives
+ *     an empty result and RH_OK.
+ * The same list on every run and under either refit_path; the enabled bits are not changed.  *n_out = the size of the
+ * winning component (RH_E_CAPACITY when it exceeds cap, like rh_refit); optional: *n_refit_out = |I|, *n_components_out =
+ * the number of components.  Works on Float64 and Float32 clouds; RH_E_INVALID on clouds of 2^31 points or more. */
+int rh_refit_component(rh_cloud *c, const rh_shape *shape, const rh_params *p, double beta, int32_t conn26,
+                       int64_t *idx_out_1based, int64_t cap, int64_t *n_out,
+                       int64_t *n_refit_out_or_null, int32_t *n_components_out_or_null);
+/* The same filter as a step of rh_ransac / rh_ransac_f32: with beta > 0 every extraction takes only the winning component
+ * of the best candidate's refit set -- only those points reach inpoints and are invalidated; the rest of the set stays
+ * enabled, so the second table top can be found as a shape of its own.  beta <= 0: off (the default; an extraction's
+ * launches are then exactly those of a cloud that never had a filter).  The setting lives on the cloud (rh_params mirrors
+ * the reference's parameters).  rh_ransac_mp returns RH_E_INVALID while a filter is set.  A NaN or infinite beta:
+ * RH_E_INVALID.  The getter reports beta = 0 for "off". */
+int rh_cloud_set_component_filter(rh_cloud *c, double beta, int32_t conn26);   /* beta <= 0: off (the default) */
+int rh_cloud_get_component_filter(const rh_cloud *c, double *beta_out, int32_t *conn26_out);
 
 /* Least-squares refit -- the step of the paper the reference leaves out (docs/src/ransac.md:163-168;
  * its `refit` returns the shape unchanged).  NOT part of parity runs.  Selects the enabled points

@@ -170,6 +170,30 @@ function refit(s::FittedShape, h::HIPCloud, params; cparams = toC(params))
     return ExtractedShape(s, idx)
 end
 
+"""
+The largest connected patch of `refit(s, h, params)` (Schnabel et al. 2007, section 4.4): connectivity on a voxel grid of
+size `beta` over the inliers, 26-neighbourhood (`conn26`) or faces only, size counted in points, ties to the component
+with the smallest point index (include/ransac_hip.h has the definition).  Returns `(ExtractedShape, n_refit, n_components)`.
+"""
+function refit_component(s::FittedShape, h::HIPCloud, params, beta; conn26 = true, cparams = toC(params))
+    idx = Vector{Int}(undef, h.pc.size)
+    n = Ref{Int64}(0); nrefit = Ref{Int64}(0); ncomp = Ref{Int32}(0)
+    check(ccall((:rh_refit_component, LIB), Cint,
+        (Ptr{Cvoid}, Ref{RhShape}, Ref{RhParams}, Cdouble, Int32, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}),
+        h.handle, toC(s), cparams, beta, conn26 ? 1 : 0, idx, length(idx), n, nrefit, ncomp))
+    resize!(idx, n[])
+    return ExtractedShape(s, idx), nrefit[], ncomp[]
+end
+
+"With `beta > 0` every extraction of `rh_ransac` on this cloud takes only the largest connected patch of its refit set; `beta <= 0`: off."
+set_component_filter!(h::HIPCloud, beta; conn26 = true) = check(ccall((:rh_cloud_set_component_filter, LIB), Cint,
+    (Ptr{Cvoid}, Cdouble, Int32), h.handle, beta, conn26 ? 1 : 0))
+function component_filter(h::HIPCloud)
+    beta = Ref{Cdouble}(0); conn = Ref{Int32}(0)
+    check(ccall((:rh_cloud_get_component_filter, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}), h.handle, beta, conn))
+    return beta[], conn[] != 0
+end
+
 "Replacement for `invalidate_indexes!` (src/fitting.jl:197-202): host bits and device bits."
 function invalidate_indexes!(h::HIPCloud, indexlist)
     RANSAC.invalidate_indexes!(h.pc, indexlist)

@@ -91,6 +91,9 @@ SIGNATURES = {
     "rh_cloud_set_stream": (C.c_int, [_vp, _vp, C.c_int]),
     "rh_score_batch_dev_timed": (C.c_int, [_vp, _vp, C.c_int32, _pp, _vp, _vp, C.POINTER(C.c_float)]),
     "rh_refit": (C.c_int, [_vp, _sp, _pp, _i64p, C.c_int64, _i64p]),
+    "rh_refit_component": (C.c_int, [_vp, _sp, _pp, C.c_double, C.c_int32, _i64p, C.c_int64, _i64p, _i64p, _i32p]),
+    "rh_cloud_set_component_filter": (C.c_int, [_vp, C.c_double, C.c_int32]),
+    "rh_cloud_get_component_filter": (C.c_int, [_vp, _dp, _i32p]),
     "rh_refit_lsq": (C.c_int, [_vp, _sp, _pp, C.c_int32, _sp, _i64p, _dp, _i32p]),
     "rh_invalidate": (C.c_int, [_vp, _i64p, C.c_int64]),
     "rh_select_enabled": (C.c_int, [_vp, _i64p, C.c_int32, _i64p]),

@@ -534,6 +534,18 @@ class RANSACCloud:
         check(lib().rh_cloud_count_enabled(self._h, C.byref(out)))
         return out.value
 
+    def set_component_filter(self, beta, conn26=True):
+        """With beta > 0 every extraction of ransac() on this cloud takes only the largest connected component of the best
+        candidate's refit set (voxel grid of size beta; refit_component); beta <= 0 or None: off, the default."""
+        check(lib().rh_cloud_set_component_filter(self._h, float(beta or 0.0), 1 if conn26 else 0))
+
+    @property
+    def component_filter(self):
+        """(beta, conn26) of set_component_filter; beta = 0.0: off"""
+        beta, conn = C.c_double(), C.c_int32()
+        check(lib().rh_cloud_get_component_filter(self._h, C.byref(beta), C.byref(conn)))
+        return beta.value, bool(conn.value)
+
     def __repr__(self):
         return "RANSACCloud of size %d & %d subsets" % (self.size, len(self.subsets))
 
@@ -724,6 +736,20 @@ def refit(s, pc, params):
     return ExtractedShape(s if not isinstance(s, L.Shape) else shape_from_c(s), out[: n.value].copy())
 
 
+def refit_component(s, pc, params, beta, conn26=True, return_stats=False):
+    """The largest connected patch of refit(s, pc, params): connectivity on a voxel grid of size beta over the inliers,
+    26-neighbourhood (conn26) or faces only, size counted in points, ties to the component with the smallest point index
+    (include/ransac_hip.h has the definition in full).  -> ExtractedShape; with return_stats also
+    {"n_refit": the whole refit set's size, "n_components": ...}."""
+    out = np.zeros(max(1, pc.size), dtype=np.int64)
+    n, n_refit, n_comp = C.c_int64(), C.c_int64(), C.c_int32()
+    cs = s if isinstance(s, L.Shape) else (shape_f32(s) if getattr(pc, "is_f32", False) else s.to_c())
+    check(lib().rh_refit_component(pc._h, C.byref(cs), C.byref(_cparams(params)), float(beta), 1 if conn26 else 0,
+                                   _p(out, C.c_int64), pc.size, C.byref(n), C.byref(n_refit), C.byref(n_comp)))
+    es = ExtractedShape(s if not isinstance(s, L.Shape) else shape_from_c(s), out[: n.value].copy())
+    return (es, {"n_refit": n_refit.value, "n_components": n_comp.value}) if return_stats else es
+
+
 def refit_lsq(s, pc, params, max_iter=10):
     """Least-squares refit of `s` to its compatible points within 3*eps (the step the reference omits,
     docs/src/ransac.md:163-168).  Returns (shape, n_used, rms, iterations)."""
@@ -856,12 +882,23 @@ class MpGroup:
 
 def ransac(pc, params, setenabled=False, reset_rand=False, seed=1234, stream=None,
            score_mode=L.SCORE_INT64_WRAP, sphere_uses_enabled=False, sampling_streams=0, octree_sampling=False,
-           return_stats=False, mp=None):
+           return_stats=False, mp=None, component_beta=None, component_conn26=True):
     """ransac(pc, params[, setenabled]; reset_rand) -> (Vector{ExtractedShape}, seconds)
     (iterations.jl:14-21, 35-162).  `reset_rand` reseeds the generator with 1234 like
     Random.seed!(1234); `stream` injects raw 64-bit draws (rand(1:n) = 1 + floor(u*n/2^64)).
     mp: an MpGroup -- the loop is then run by all its ranks together on this one scene (rh_ransac_mp: the minimal
-    sets of every iteration dealt round-robin to the ranks); every rank gets the same result as a single process."""
+    sets of every iteration dealt round-robin to the ranks); every rank gets the same result as a single process.
+    component_beta: this call runs with pc.set_component_filter(component_beta, component_conn26) -- every extraction
+    keeps the largest connected patch of its refit set -- and the cloud's previous setting is restored afterwards
+    (None: the cloud's own setting holds)."""
+    if component_beta is not None:
+        previous = pc.component_filter
+        pc.set_component_filter(component_beta, component_conn26)
+        try:
+            return ransac(pc, params, setenabled, reset_rand, seed, stream, score_mode, sphere_uses_enabled, sampling_streams,
+                          octree_sampling, return_stats, mp)
+        finally:
+            pc.set_component_filter(*previous)
     if setenabled:
         pc.enable_all()
     cp = params if isinstance(params, L.Params) else params_to_c(params, score_mode, sphere_uses_enabled, sampling_streams, octree_sampling)

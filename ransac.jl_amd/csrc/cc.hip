@@ -170,8 +170,8 @@ extern "C" int rh_largestconncomp(const uint8_t *bitmap, int32_t xs, int32_t ys,
 }
 
 // bitmapparameters: parameterspacebitmap.jl:12-46.  Sequential "first writer wins" per pixel;
-// O(n) on the host (the live reference never produces 2-D parameters, so there is no device
-// producer to fuse with yet).
+// O(n) on the host: the live reference never produces 2-D parameters.  The device-side connected-component
+// filter of a refit set works on a 3-D voxel grid of the inliers instead: component.hip (rh_refit_component).
 extern "C" int rh_bitmapparameters(const double *prm2, const uint8_t *compat, const int64_t *idsource, int64_t n,
                                    double beta, int32_t *xs_out, int32_t *ys_out, double *betax, double *betay,
                                    uint8_t *bitmap, int64_t *idxmap)

@@ -388,6 +388,10 @@ extern "C" int rh_ransac_mp(rh_cloud *c, const double *xyz, const double *nrm, c
 {
     if (!mp) { rh_set_error("rh_ransac_mp: mp is NULL"); return RH_E_INVALID; }
     if (!c || !p) { rh_set_error("rh_ransac_mp: NULL argument"); return RH_E_INVALID; }
+    if (c->comp_beta > 0) {   // (the ranks' replay of filtered extractions has nothing to be held against yet)
+        rh_set_error("rh_ransac_mp is not available while a component filter is set (rh_cloud_set_component_filter)");
+        return RH_E_INVALID;
+    }
     if (!p->sampling_streams) { rh_set_error("rh_ransac_mp needs sampling_streams = 1 (one random stream per minimal set)"); return RH_E_INVALID; }
     if (p->minsubsetN < mp->world) {   // (a rank without a single minimal set per iteration would have nothing to launch)
         rh_set_error("rh_ransac_mp: minsubsetN = %d is below the number of ranks (%d)", p->minsubsetN, mp->world);

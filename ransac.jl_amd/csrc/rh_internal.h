@@ -266,6 +266,15 @@ struct rh_cloud {
     int64_t *idx_out = nullptr;        // [n] compacted indices
     int32_t *d_total = nullptr;        // scalar
 
+    // largest-connected-component filter of a refit set (component.hip): the setting rh_ransac's extractions read
+    // (rh_cloud_set_component_filter; 0: off) and the workspace, grown on demand and kept between calls
+    double comp_beta = 0;
+    int32_t comp_conn26 = 1;
+    void *comp_tab = nullptr;          // the cell table: per slot key (8 B), parent, point count, smallest index (4 B each)
+    int64_t comp_cap = 0;              // in slots
+    uint64_t *comp_scal = nullptr;     // the call's scalars on the device (minimum, maximum, |I|, winner, components) ...
+    uint64_t *comp_h = nullptr;        // ... and where the host reads the first seven (pinned)
+
     // the batch workspaces: ws[0] the cloud's own, ws[1 ..] the other slots of rh_score_batch_dev's pipeline (rh_batch_ws)
     rh_batch_ws ws[RH_MAX_IN_FLIGHT];
     uint32_t pipe_k = 0;               // batches since the pipeline (re)started
@@ -395,6 +404,10 @@ int rhk_oct_build_tab(rh_cloud *c);                                     // the s
 int rhk_oct_gather_enabled(rh_cloud *c);                                // oct_men = enabled in Morton order
 int rhk_compact_mask(rh_cloud *c, const uint64_t *mask, int64_t nwords, int64_t *idx_out, int64_t cap,
                      int32_t *d_total);
+// component.hip: refit_mask &= the largest connected component of its points on the voxel grid of size beta (one wait for
+// the stream: |I| sizes the table); the number of components follows in stream order
+int rhk_component_filter(rh_cloud *c, double beta, int conn26, int64_t *n_refit_out);
+int rhk_component_stats(rh_cloud *c, int64_t *h_ncomp);
 int rhk_invalidate_idx(rh_cloud *c, const int64_t *d_idx, int64_t n);
 int rhk_rebuild_sub_enabled(rh_cloud *c, bool reset_list);
 int rhk_compact_refit_apply(rh_cloud *c);
