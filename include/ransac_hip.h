@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 111
+#define RH_VERSION 112
 
 enum {
     RH_OK = 0,
@@ -190,6 +190,58 @@ int rh_refit_component(rh_cloud *c, const rh_shape *shape, const rh_params *p, d
 int rh_cloud_set_component_filter(rh_cloud *c, double beta, int32_t conn26);   /* beta <= 0: off (the default) */
 int rh_cloud_get_component_filter(const rh_cloud *c, double *beta_out, int32_t *conn26_out);
 
+/* ---- oriented extents and fit residuals of extracted shapes (no live counterpart in the reference: its findOBB_,
+ *      src/orientedbox_.jl, is unexported and unused, and toDict / exportJSON write the bare parameters) ----
+ * rh_ransac returns unbounded primitives with index lists.  These calls add, for b shapes at once, the frame each
+ * shape's points suggest, the box of the points in that frame, and how far the points sit from the shape.
+ * Shape j's points are idx[offsets[j] .. offsets[j+1]): 1-based indices into the cloud, in any order, duplicates counted
+ * as given.  The cloud's resident coordinates are read (a Float32 cloud's floats promoted exactly); every operation below
+ * is an IEEE binary64 operation, none contracted.  Nothing on the cloud changes (enabled bits, refit state, ...).
+ *  1. invalid input -- RH_E_INVALID: offsets[0] != 0, decreasing offsets, (the _dev entry: offsets[b] != total,) an index
+ *     outside 1..N, a listed point with a non-finite coordinate, a kind outside 0..3, a plane / cylinder / cone whose
+ *     axis has norm 0 or a non-finite norm.  Indices are checked on the device before anything is read through them; the
+ *     kernels raise a flag word the host entries read back with the results, and every record of such a call carries
+ *     RH_EXT_INVALID (what a caller of the _dev entry can test).  b == 0: RH_OK;
+ *  2. moments: p0 = the first listed point, q_i = p_i - p0, m = sum q_i / n, S = sum q_i q_i^T / n - m m^T,
+ *     centroid = p0 + m (sums in a fixed order that depends on the list's length alone);
+ *  3. frame (rows u, v, w).  a = the plane's normal / the cylinder's axis / the cone's axis;
+ *     w = a / sqrt((ax*ax + ay*ay) + az*az), component by component; u = the unit eigenvector of the largest eigenvalue
+ *     of (I - w w^T) S (I - w w^T), made orthogonal to w again and normalised, its component of largest magnitude
+ *     positive (the first one on a tie); v = w x u; lambda[0] >= lambda[1] the two in-plane eigenvalues, lambda[2] = 0.
+ *     Spheres: u, v = the eigenvectors of the two largest eigenvalues of S, each with that sign rule, w = u x v, lambda =
+ *     the three eigenvalues, descending.  When lambda[0] is not positive (one point, coincident points):
+ *     RH_EXT_NO_DIRECTION, and with k the index of the smallest |w_k| (the first on a tie) u = e_k - w (w . e_k),
+ *     normalised; for spheres the frame is the identity.  A nearly isotropic scatter (a full cylinder) gets whatever
+ *     orthonormal frame the solver yields: lambda tells;
+ *  4. extents: d = p_i - origin componentwise (origin: the plane's point, the sphere's or the cylinder's center, the
+ *     cone's apex); the coordinate along a frame row f is t = (dx*fx + dy*fy) + dz*fz; lo / hi = the minima / maxima of
+ *     (tu, tv, tw) over the listed points;
+ *  5. distance: plane e = tw; sphere e = sqrt((tu*tu + tv*tv) + tw*tw) - r; cylinder e = sqrt(tu*tu + tv*tv) - r; cone
+ *     e = sqrt(tu*tu + tv*tv)*v[7] + tw*v[8] (rh_shape_finalize's cos and sin of -opang/2);
+ *     dist_maxabs = max |e_i|, dist_rms = sqrt(sum e_i^2 / n);
+ *  6. an empty list: RH_EXT_EMPTY, kind and origin set, everything else zero.
+ * Steps 4 to 6 are exact given the frame (lo, hi, dist_maxabs: the very bits; dist_rms: a sum in a fixed order).  The
+ * same bits on every run, and for a shape whether it is passed alone or among others. */
+enum { RH_EXT_EMPTY = 1, RH_EXT_NO_DIRECTION = 2, RH_EXT_INVALID = 4 };
+typedef struct {
+    int64_t n;               /* listed points */
+    int32_t kind;            /* copy of the shape's kind */
+    int32_t flags;           /* RH_EXT_* */
+    double origin[3];        /* plane: point; sphere: center; cylinder: center; cone: apex */
+    double frame[9];         /* rows u, v, w: orthonormal, right-handed (w = u x v) */
+    double lo[3], hi[3];     /* min / max over the points of their coordinates along u, v, w, measured from origin */
+    double centroid[3];
+    double lambda[3];        /* scatter along u, v (and w for spheres; 0 otherwise) */
+    double dist_rms, dist_maxabs;   /* signed distance to the shape: root mean square, largest magnitude */
+} rh_extent;
+/* host arrays in and out; one wait */
+int rh_shape_extents(rh_cloud *c, const rh_shape *shapes, int32_t b,
+                     const int64_t *offsets /* b + 1 */, const int64_t *idx_1based, rh_extent *out);
+/* everything resident on the cloud's device, enqueued on the cloud's stream without synchronising: four launches.
+ * total = offsets[b] = the number of entries of d_idx_1based (the host cannot read the offsets; the grid is sized by it) */
+int rh_shape_extents_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const int64_t *d_offsets,
+                         const int64_t *d_idx_1based, int64_t total, rh_extent *d_out);
+
 /* Least-squares refit -- the step of the paper the reference leaves out (docs/src/ransac.md:163-168;
  * its `refit` returns the shape unchanged).  NOT part of parity runs.  Selects the enabled points
  * compatible with `shape` at 3*eps, then fits: plane = total least squares; sphere / cylinder / cone
@@ -297,6 +349,9 @@ int rh_ransac(rh_cloud *c, const double *xyz_aos, const double *nrm_aos, const r
 int rh_ransac_f32(rh_cloud *c, const float *xyz_aos, const float *nrm_aos, const rh_params *p,
                   rh_rng *rng, rh_result *out);
 void rh_result_free(rh_result *r);
+/* rh_shape_extents (above) of a result's own shapes and index lists, one call for all of them; the lists are uploaded
+ * from the result's pinned block */
+int rh_result_extents(rh_cloud *c, const rh_result *r, rh_extent *out /* r->n_shapes */);
 
 /* ---- one scene on several GPUs of a node (no counterpart in the reference, which is single-threaded:
  *      src/iterations.jl:35-162 run by `world` processes, one per GPU) ----

@@ -194,6 +194,39 @@ function component_filter(h::HIPCloud)
     return beta[], conn[] != 0
 end
 
+# rh_extent, field for field (include/ransac_hip.h; 224 bytes)
+struct RhExtent
+    n::Int64
+    kind::Cint
+    flags::Cint                       # 1: empty list, 2: no principal direction (fallback frame)
+    origin::NTuple{3,Cdouble}
+    frame::NTuple{9,Cdouble}          # rows u, v, w
+    lo::NTuple{3,Cdouble}
+    hi::NTuple{3,Cdouble}
+    centroid::NTuple{3,Cdouble}
+    lambda::NTuple{3,Cdouble}
+    dist_rms::Cdouble
+    dist_maxabs::Cdouble
+end
+
+"""
+Oriented extents and fit residuals of extracted shapes, all in one call on the device (`rh_shape_extents`,
+include/ransac_hip.h has the definition): for every `ExtractedShape` the frame its points suggest (rows u, v, w), their
+box `lo`..`hi` along it measured from the shape's origin, centroid, scatter, and the rms / largest distance to the shape.
+"""
+function shape_extents(h::HIPCloud, extracted::AbstractVector{<:ExtractedShape})
+    b = length(extracted)
+    out = Vector{RhExtent}(undef, b)
+    b == 0 && return out
+    shapes = RhShape[toC(e.shape) for e in extracted]
+    offsets = Int64[0; cumsum(Int64[length(e.inpoints) for e in extracted])]
+    idx = isempty(extracted) ? Int64[] : reduce(vcat, (Vector{Int64}(e.inpoints) for e in extracted))
+    check(ccall((:rh_shape_extents, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{RhShape}, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{RhExtent}),
+        h.handle, shapes, b, offsets, idx, out))
+    return out
+end
+
 "Replacement for `invalidate_indexes!` (src/fitting.jl:197-202): host bits and device bits."
 function invalidate_indexes!(h::HIPCloud, indexlist)
     RANSAC.invalidate_indexes!(h.pc, indexlist)

@@ -2,7 +2,7 @@
 cserteGT3/RANSAC.jl: FittedShape / RANSACCloud / ransac().  Import as `ransac_jl_amd`."""
 from . import _lib, synth
 from ._lib import (CONE, CYLINDER, PLANE, SPHERE, SCORE_F64, SCORE_INT64_WRAP, RansacHipError, lib)
-from .api import (DEFAULT_PARAMETERS, DEFAULT_SHAPE_DICT, ConfidenceInterval, E, ExtractedShape, FittedCone,
+from .api import (DEFAULT_PARAMETERS, DEFAULT_SHAPE_DICT, ConfidenceInterval, E, ExtractedShape, Extent, FittedCone,
                   IterationCandidates, deleteat, findhighestscore, forcefitshapes, push2candidatesandlevels, recordscore,
                   removeinvalidshapes, scorecandidates, setfloattype, findAABB, smallestdistance,
                   FittedCylinder, FittedPlane, FittedShape, FittedSphere, RANSACCloud, bitmapparameters,
@@ -10,7 +10,7 @@ from .api import (DEFAULT_PARAMETERS, DEFAULT_SHAPE_DICT, ConfidenceInterval, E,
                   defaultshapeparameters, estimatenormals, estimatescore, fit, invalidate_indexes, largestconncomp,
                   notsoconfident, params_to_c, prob, ransac, ransacparameters, MpGroup, refit, refit_component, refit_lsq, score_batch,
                   scorecandidate, select_enabled, sample_sets, fit_sets, shape_f32, shape_from_c, strt, buildoctree, octreedepth, findleaf,
-                  getnthcell, iswithinrectangle, cell_enabled_points, OctreeCell, set_option, get_option, option)
+                  getnthcell, iswithinrectangle, cell_enabled_points, shape_extents, OctreeCell, set_option, get_option, option)
 
 from .io import exportJSON, readconfig, toDict
 

@@ -58,6 +58,16 @@ class NormalsParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("orient", C.c_int32), ("radius", C.c_double), ("viewpoint", C.c_double * 3)]
 
 
+EXT_EMPTY, EXT_NO_DIRECTION, EXT_INVALID = 1, 2, 4
+
+
+class Extent(C.Structure):
+    """rh_extent: the frame, box and residuals of a shape's points (include/ransac_hip.h)"""
+    _fields_ = [("n", C.c_int64), ("kind", C.c_int32), ("flags", C.c_int32), ("origin", C.c_double * 3),
+                ("frame", C.c_double * 9), ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("centroid", C.c_double * 3),
+                ("lam", C.c_double * 3), ("dist_rms", C.c_double), ("dist_maxabs", C.c_double)]
+
+
 class RansacHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libransac_hip error %d: %s" % (code, msg))
@@ -145,6 +155,9 @@ SIGNATURES = {
     "rh_score_batch_allreduce_dev": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _pp, _vp]),
     "rh_comm_fence": (C.c_int, [_vp, _vp]),
     "rh_comm_sync": (C.c_int, [_vp]),
+    "rh_shape_extents": (C.c_int, [_vp, _sp, C.c_int32, _i64p, _i64p, C.POINTER(Extent)]),
+    "rh_shape_extents_dev": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp]),
+    "rh_result_extents": (C.c_int, [_vp, C.POINTER(Result), C.POINTER(Extent)]),
     "rh_estimate_normals": (C.c_int, [_dp, C.c_int64, C.POINTER(NormalsParams), _dp, C.c_int, _dp, _dp, _i32p]),
     "rh_estimate_normals_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(NormalsParams), C.POINTER(C.c_float),
                                           C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32p]),

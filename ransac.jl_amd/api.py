@@ -794,6 +794,52 @@ def estimatenormals(vertices, k=16, radius=0.0, viewpoint=None, hints=None, devi
     return out[0] if len(out) == 1 else out
 
 
+class Extent:
+    """Where a shape's points lie and how well they sit on it (rh_extent, include/ransac_hip.h has the definition in full):
+    n, kind, flags (EXT_EMPTY / EXT_NO_DIRECTION of _lib), origin[3], frame[3, 3] (rows u, v, w), lo[3] / hi[3] (the box
+    of the points along u, v, w, measured from origin), centroid[3], lam[3] (the scatter along u, v -- and w for spheres),
+    dist_rms, dist_maxabs.  `c` keeps the C record."""
+
+    def __init__(self, c):
+        self.c = L.Extent.from_buffer_copy(bytes(c))
+        self.n, self.kind, self.flags = int(c.n), int(c.kind), int(c.flags)
+        self.origin = np.array(c.origin, dtype=np.float64)
+        self.frame = np.array(c.frame, dtype=np.float64).reshape(3, 3)
+        self.lo, self.hi = np.array(c.lo, dtype=np.float64), np.array(c.hi, dtype=np.float64)
+        self.centroid = np.array(c.centroid, dtype=np.float64)
+        self.lam = np.array(c.lam, dtype=np.float64)
+        self.dist_rms, self.dist_maxabs = float(c.dist_rms), float(c.dist_maxabs)
+
+    @property
+    def size(self):
+        """hi - lo: the sides of the box along u, v, w"""
+        return self.hi - self.lo
+
+    def __repr__(self):
+        return "Extent(%s, %d ps, %s, rms %.3g)" % (L.KIND_NAMES.get(self.kind, "?"), self.n, self.size, self.dist_rms)
+
+
+def shape_extents(pc, extracted_shapes):
+    """Oriented extents and fit residuals of shapes with their point lists, all in ONE call on the device
+    (rh_shape_extents): for every ExtractedShape -- or (shape, 1-based index array) pair -- an Extent.  The lists may be
+    in any order and hold duplicates; Float64 and Float32 clouds.  Nothing on the cloud changes."""
+    pairs = [(x.shape, x.inpoints, getattr(x, "c_shape", None)) if isinstance(x, ExtractedShape) else (x[0], x[1], None)
+             for x in extracted_shapes]
+    b = len(pairs)
+    if b == 0:
+        return []
+    arr = (L.Shape * b)()
+    for j, (s, _, cs) in enumerate(pairs):
+        arr[j] = cs if cs is not None else (s if isinstance(s, L.Shape) else s.to_c())
+    lists = [np.ascontiguousarray(i, dtype=np.int64).reshape(-1) for _, i, _ in pairs]
+    off = np.zeros(b + 1, dtype=np.int64)
+    np.cumsum([a.size for a in lists], out=off[1:])
+    idx = np.ascontiguousarray(np.concatenate(lists)) if off[-1] else np.zeros(1, dtype=np.int64)
+    out = (L.Extent * b)()
+    check(lib().rh_shape_extents(pc._h, arr, b, _p(off, C.c_int64), _p(idx, C.c_int64), out))
+    return [Extent(e) for e in out]
+
+
 def invalidate_indexes(pc, indexlist):  # invalidate_indexes!: fitting.jl:197-202
     idx = np.ascontiguousarray(indexlist, dtype=np.int64)
     check(lib().rh_invalidate(pc._h, _p(idx, C.c_int64), idx.size))
@@ -882,7 +928,7 @@ class MpGroup:
 
 def ransac(pc, params, setenabled=False, reset_rand=False, seed=1234, stream=None,
            score_mode=L.SCORE_INT64_WRAP, sphere_uses_enabled=False, sampling_streams=0, octree_sampling=False,
-           return_stats=False, mp=None, component_beta=None, component_conn26=True):
+           return_stats=False, mp=None, component_beta=None, component_conn26=True, extents=False):
     """ransac(pc, params[, setenabled]; reset_rand) -> (Vector{ExtractedShape}, seconds)
     (iterations.jl:14-21, 35-162).  `reset_rand` reseeds the generator with 1234 like
     Random.seed!(1234); `stream` injects raw 64-bit draws (rand(1:n) = 1 + floor(u*n/2^64)).
@@ -890,13 +936,15 @@ def ransac(pc, params, setenabled=False, reset_rand=False, seed=1234, stream=Non
     sets of every iteration dealt round-robin to the ranks); every rank gets the same result as a single process.
     component_beta: this call runs with pc.set_component_filter(component_beta, component_conn26) -- every extraction
     keeps the largest connected patch of its refit set -- and the cloud's previous setting is restored afterwards
-    (None: the cloud's own setting holds)."""
+    (None: the cloud's own setting holds).
+    extents: after the loop, one rh_result_extents call for all extracted shapes; every ExtractedShape then carries an
+    Extent as `.extent` (shape_extents; off by default: the result objects are what they were)."""
     if component_beta is not None:
         previous = pc.component_filter
         pc.set_component_filter(component_beta, component_conn26)
         try:
             return ransac(pc, params, setenabled, reset_rand, seed, stream, score_mode, sphere_uses_enabled, sampling_streams,
-                          octree_sampling, return_stats, mp)
+                          octree_sampling, return_stats, mp, extents=extents)
         finally:
             pc.set_component_filter(*previous)
     if setenabled:
@@ -934,6 +982,11 @@ def ransac(pc, params, setenabled=False, reset_rand=False, seed=1234, stream=Non
         es = ExtractedShape(shape_from_c(e.shape), idx)
         es.score_E, es.iteration, es.c_shape = e.score_E, e.iteration, L.Shape.from_buffer_copy(bytes(e.shape))
         extracted.append(es)
+    if extents and res.n_shapes > 0:
+        ext = (L.Extent * res.n_shapes)()
+        check(lib().rh_result_extents(pc._h, C.byref(res), ext))
+        for es, e in zip(extracted, ext):
+            es.extent = Extent(e)
     stats = {"iterations": res.iterations, "candidates_scored": res.candidates_scored,
              "scored_left": res.scored_left, "seconds": res.seconds, "seconds_score": res.seconds_score,
              "seconds_extract": res.seconds_extract, "seconds_host": res.seconds_host,

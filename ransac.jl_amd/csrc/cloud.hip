@@ -188,6 +188,7 @@ static void cloud_free(rh_cloud *c)
     (void)hipFree(c->word_prefix); (void)hipFree(c->idx_out); (void)hipFree(c->d_total);
     (void)hipFree(c->d_nk); (void)hipFree(c->d_masks); (void)hipFree(c->d_ranks); (void)hipFree(c->d_stage);
     (void)hipFree(c->comp_tab); (void)hipFree(c->comp_scal);
+    (void)hipFree(c->ext_part); (void)hipFree(c->ext_flag); (void)hipFree(c->ext_in);
     if (c->comp_h) (void)hipHostFree(c->comp_h);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

@@ -22,6 +22,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "jacobi3.h"
 #include "rh_internal.h"
 
 namespace {
@@ -251,31 +252,6 @@ __device__ inline double wsum(double v)
     return v;
 }
 
-// one Jacobi rotation annihilating A[p][q] (Numerical Recipes' jacobi, written out for 3 x 3)
-__device__ __forceinline__ void jrot(double A[3][3], double V[3][3], int p, int q)
-{
-    const double apq = A[p][q];
-    if (apq == 0.0) return;
-    const double app = A[p][p], aqq = A[q][q], g = 100.0 * fabs(apq);
-    if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) { A[p][q] = A[q][p] = 0.0; return; }
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = fabs(theta) > 1e150 ? 0.5 / theta
-                                         : (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    A[p][p] = app - t * apq;
-    A[q][q] = aqq + t * apq;
-    A[p][q] = A[q][p] = 0.0;
-    const int r = 3 - p - q;
-    const double arp = A[r][p], arq = A[r][q];
-    A[r][p] = A[p][r] = c * arp - s * arq;
-    A[r][q] = A[q][r] = s * arp + c * arq;
-    for (int i = 0; i < 3; i++) {
-        const double vip = V[i][p], viq = V[i][q];
-        V[i][p] = c * vip - s * viq;
-        V[i][q] = s * vip + c * viq;
-    }
-}
-
 struct QueryArgs {
     int64_t nq;              // query points (waves)
     int64_t n;
@@ -383,12 +359,7 @@ __global__ __launch_bounds__(NRM_BLOCK) void nrm_query_kernel(Grid g, QueryArgs 
     if (lane != 0) return;
 
     double V[3][3] = { { 1.0, 0.0, 0.0 }, { 0.0, 1.0, 0.0 }, { 0.0, 0.0, 1.0 } };
-    for (int sweep = 0; sweep < 32; sweep++) {
-        if (A[0][1] == 0.0 && A[0][2] == 0.0 && A[1][2] == 0.0) break;
-        jrot(A, V, 0, 1);
-        jrot(A, V, 0, 2);
-        jrot(A, V, 1, 2);
-    }
+    rh_jacobi3(A, V);
     int i0 = 0, i1 = 1, i2 = 2;                                    // ascending eigenvalues
     if (A[i1][i1] < A[i0][i0]) { const int t = i0; i0 = i1; i1 = t; }
     if (A[i2][i2] < A[i1][i1]) { const int t = i1; i1 = i2; i2 = t; }

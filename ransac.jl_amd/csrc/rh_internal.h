@@ -275,6 +275,13 @@ struct rh_cloud {
     uint64_t *comp_scal = nullptr;     // the call's scalars on the device (minimum, maximum, |I|, winner, components) ...
     uint64_t *comp_h = nullptr;        // ... and where the host reads the first seven (pinned)
 
+    // oriented extents of extracted shapes (extent.hip): workspaces, grown on demand and kept between calls
+    double *ext_part = nullptr;        // one row of partial sums / minima / maxima per chunk of list entries
+    int64_t ext_part_rows = 0;
+    int32_t *ext_flag = nullptr;       // the call's error word (RH_EXT_BAD_* bits of extent.hip), raised by the kernels
+    void *ext_in = nullptr;            // the host entry's uploads: shapes, offsets, records, index lists
+    int64_t ext_in_bytes = 0;
+
     // the batch workspaces: ws[0] the cloud's own, ws[1 ..] the other slots of rh_score_batch_dev's pipeline (rh_batch_ws)
     rh_batch_ws ws[RH_MAX_IN_FLIGHT];
     uint32_t pipe_k = 0;               // batches since the pipeline (re)started

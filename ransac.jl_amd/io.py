@@ -12,13 +12,24 @@ _FIELDS = {FittedPlane: ("point", "normal"), FittedSphere: ("center", "radius", 
            FittedCylinder: ("axis", "center", "radius", "outwards"), FittedCone: ("apex", "axis", "opang", "outwards")}
 
 
-def toDict(s):
+def _extent_dict(e):
+    return {"origin": [float(x) for x in e.origin], "frame": [[float(x) for x in row] for row in e.frame],
+            "lo": [float(x) for x in e.lo], "hi": [float(x) for x in e.hi], "centroid": [float(x) for x in e.centroid],
+            "rms": float(e.dist_rms), "maxabs": float(e.dist_maxabs)}
+
+
+def toDict(s, extents=False):
     """toDict(s) (json-yaml.jl:9-30): {"type": strt(s), <field>: value ...}; a list of shapes /
-    ExtractedShapes becomes {"primitives": [...]}."""
+    ExtractedShapes becomes {"primitives": [...]}.  extents=True: an ExtractedShape that carries an `.extent`
+    (ransac(..., extents=True), shape_extents) also gets an "extent" entry -- origin, frame (rows u, v, w), lo, hi,
+    centroid, rms, maxabs; without it the output is the reference's."""
     if isinstance(s, (list, tuple)):
-        return {"primitives": [toDict(x) for x in s]}
+        return {"primitives": [toDict(x, extents) for x in s]}
     if isinstance(s, ExtractedShape):
-        return toDict(s.shape)
+        d = toDict(s.shape)
+        if extents and getattr(s, "extent", None) is not None:
+            d["extent"] = _extent_dict(s.extent)
+        return d
     if not isinstance(s, FittedShape):
         raise TypeError("toDict expects a FittedShape, an ExtractedShape or a list of them")
     d = {"type": strt(s)}
@@ -28,12 +39,12 @@ def toDict(s):
     return d
 
 
-def exportJSON(io, s, indent=None):
-    """exportJSON(io, s[, indent]) (json-yaml.jl:43-59)."""
+def exportJSON(io, s, indent=None, extents=False):
+    """exportJSON(io, s[, indent]) (json-yaml.jl:43-59); extents: see toDict."""
     if indent is None:
-        io.write(json.dumps(toDict(s), separators=(",", ":")))
+        io.write(json.dumps(toDict(s, extents), separators=(",", ":")))
     else:
-        io.write(json.dumps(toDict(s), indent=indent) + "\n")
+        io.write(json.dumps(toDict(s, extents), indent=indent) + "\n")
 
 
 def _dict2nt(v):
