@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 112
+#define RH_VERSION 113
 
 enum {
     RH_OK = 0,
@@ -489,6 +489,53 @@ int rh_estimate_normals(const double *xyz_aos, int64_t n, const rh_normals_param
 /* Julia's Vector{SVector{3,Float32}} in and out: the binary64 result on the widened coordinates, rounded once */
 int rh_estimate_normals_f32(const float *xyz_aos, int64_t n, const rh_normals_params *p, const float *hints_aos_or_null,
                             int device, float *nrm_out_aos, float *curv_out_or_null, int32_t *flags_out_or_null);
+
+/* ---- voxel-grid downsampling of a raw cloud (no counterpart in the reference, which leaves thinning to the user) ----
+ * One output row per occupied cell of a grid of width beta, and the map point -> row that carries a shape found on the
+ * thinned cloud back to the scan.  n points (binary64 array-of-structures; the _f32 entry widens exactly), optional normals.
+ *  1. dropped: a point with a coordinate that is not finite; with normals, also one with a normal component that is not
+ *     finite or exceeds 2 in magnitude.  F = the points that are left;
+ *  2. o = the componentwise minimum over F;
+ *  3. per axis a = (x - o) / beta (one binary64 subtraction, one division, no contraction), c = floor(a), t = a - c
+ *     (exact, 0 <= t < 1), f = (uint64) floor(t * 4294967296.0).  The cell is (cx, cy, cz).  beta must be finite and
+ *     positive and no axis may have more than 2^20 cells (the rule and the 21-bit key fields of rh_refit_component):
+ *     RH_E_INVALID otherwise, and for n < 1 or n >= 2^31;
+ *  4. the occupied cells are numbered 1 .. M by the smallest point index they hold, ascending (first-appearance order:
+ *     first[] is strictly increasing);
+ *  5. per row: count; first = the 1-based index of the cell's first point; the output point --
+ *     mode RH_VOX_FIRST:    the first point's coordinates (and normal) copied bit for bit;
+ *     mode RH_VOX_CENTROID: per axis S = sum of f over the cell in uint64 (exact, whatever the order), then
+ *                           num = (double)(S >> 32) * 4294967296.0 + (double)(S & 0xFFFFFFFF)   (one rounding),
+ *                           m = (num / (double)count) * 2^-32,  x = o + ((double)c + m) * beta,
+ *                           each operation rounded on its own: the centroid at a resolution of beta * 2^-32;
+ *  6. normals in centroid mode: per component g = llrint(n_c * 1048576.0) (the product is exact, ties to even),
+ *     G = sum of g in int64 (|G| <= 2^52: (double)G is exact), len = sqrt((Gx*Gx + Gy*Gy) + Gz*Gz), output G / len per
+ *     component, (0, 0, 0) when len == 0.  With flags & RH_VOX_ALIGN_NORMALS a point's g is negated before the sum when
+ *     (nx*rx + ny*ry) + nz*rz < 0, r = the normal of the cell's first point (for rh_estimate_normals with orient = 0,
+ *     whose canonical sign flips inside a cell);
+ *  7. row_of_point[i] = the 1-based row of point i, 0 for a dropped point;
+ *  8. F empty: M = 0 and RH_OK;
+ *  9. the _f32 entry: the binary64 result on the widened input, rounded once.
+ * The same bits on every run; permuting the input permutes the rows and changes nothing else (except that with
+ * RH_VOX_ALIGN_NORMALS the side the normals are turned to is that of the cell's first point, which a permutation changes).
+ * *n_out = M.  M > cap: RH_E_CAPACITY (like rh_refit) with row_of_point still written in full; cap = n always suffices.
+ * xyz_out (cap x 3) is required when cap > 0; normals out need normals in; the other outputs are optional.  Parameters
+ * and pointers are checked before the first device call. */
+enum { RH_VOX_FIRST = 0, RH_VOX_CENTROID = 1 };
+#define RH_VOX_ALIGN_NORMALS 1
+typedef struct {
+    double beta;             /* cell width */
+    int32_t mode;            /* RH_VOX_FIRST / RH_VOX_CENTROID */
+    int32_t flags;           /* RH_VOX_ALIGN_NORMALS or 0 */
+} rh_voxel_params;
+int rh_voxel_downsample(const double *xyz_aos, const double *nrm_aos_or_null, int64_t n, const rh_voxel_params *p, int device,
+                        double *xyz_out_aos, double *nrm_out_aos_or_null, int64_t *first_out_1based_or_null,
+                        int32_t *count_out_or_null, int64_t cap, int32_t *row_of_point_out_or_null,
+                        int64_t *n_out, int64_t *n_dropped_out_or_null);
+int rh_voxel_downsample_f32(const float *xyz_aos, const float *nrm_aos_or_null, int64_t n, const rh_voxel_params *p, int device,
+                            float *xyz_out_aos, float *nrm_out_aos_or_null, int64_t *first_out_1based_or_null,
+                            int32_t *count_out_or_null, int64_t cap, int32_t *row_of_point_out_or_null,
+                            int64_t *n_out, int64_t *n_dropped_out_or_null);
 
 /* ---- tuning options ----
  * The library reads NO environment variable: what a caller may tune goes through this call, for one cloud or, with

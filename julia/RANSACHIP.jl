@@ -480,4 +480,57 @@ function estimatenormals(vertices::AbstractVector{SVector{3,T}}; k::Integer = 16
     return out
 end
 
+# ---- voxel-grid downsampling of a raw cloud (rh_voxel_downsample; the reference leaves thinning to the user) ----
+# typedef struct { double beta; int32_t mode; int32_t flags; } rh_voxel_params;   (16 bytes)
+struct RhVoxelParams
+    beta::Cdouble
+    mode::Cint
+    flags::Cint
+end
+
+"""
+    voxeldownsample(vertices, beta; normals = nothing, mode = :centroid, align_normals = false)
+        -> (vertices, normals or nothing, first, count, row_of_point)
+
+One point per occupied cell of a grid of width `beta`, rows in the order in which the cells first appear.
+`mode = :centroid`: the mean of the cell's points (integer sums: the same bits whatever the order) and the normalised
+sum of their normals, each first turned to the side of the cell's first normal with `align_normals`; `mode = :first`:
+the cell's first point and normal as they are.  `first` holds the 1-based index of every cell's first point, `count` the
+points per cell, `row_of_point[i]` the row of point `i` (0: dropped, a coordinate or normal was not finite).
+"""
+function voxeldownsample(vertices::AbstractVector{SVector{3,T}}, beta::Real; normals = nothing, mode::Symbol = :centroid,
+                         align_normals::Bool = false, device::Integer = 0) where {T<:Union{Float32,Float64}}
+    mode in (:first, :centroid) || error("voxeldownsample: mode is :first or :centroid")
+    p = RhVoxelParams(beta, mode === :centroid ? 1 : 0, align_normals ? 1 : 0)
+    vs = convert(Vector{SVector{3,T}}, vertices)
+    ns = normals === nothing ? nothing : convert(Vector{SVector{3,T}}, normals)
+    n = length(vs)
+    ns === nothing || length(ns) == n || error("voxeldownsample: $(length(ns)) normals for $n points")
+    vout = Vector{SVector{3,T}}(undef, n)
+    nout = ns === nothing ? nothing : Vector{SVector{3,T}}(undef, n)
+    first = Vector{Int64}(undef, n)
+    count = Vector{Int32}(undef, n)
+    rowof = zeros(Int32, n)
+    m = Ref{Int64}(0)
+    np = ns === nothing ? Ptr{T}(C_NULL) : pointer(reinterpret(T, ns))
+    nop = nout === nothing ? Ptr{T}(C_NULL) : pointer(reinterpret(T, nout))
+    GC.@preserve vs ns vout nout first count rowof begin
+        if T == Float32
+            check(ccall((:rh_voxel_downsample_f32, LIB), Cint,
+                (Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ref{RhVoxelParams}, Cint, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Int64}, Ptr{Int32}, Int64,
+                 Ptr{Int32}, Ref{Int64}, Ptr{Int64}),
+                pointer(reinterpret(Float32, vs)), np, n, p, device, pointer(reinterpret(Float32, vout)), nop, first, count, n,
+                rowof, m, C_NULL))
+        else
+            check(ccall((:rh_voxel_downsample, LIB), Cint,
+                (Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ref{RhVoxelParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int32}, Int64,
+                 Ptr{Int32}, Ref{Int64}, Ptr{Int64}),
+                pointer(reinterpret(Float64, vs)), np, n, p, device, pointer(reinterpret(Float64, vout)), nop, first, count, n,
+                rowof, m, C_NULL))
+        end
+    end
+    k = m[]
+    return resize!(vout, k), (nout === nothing ? nothing : resize!(nout, k)), resize!(first, k), resize!(count, k), rowof
+end
+
 end # module

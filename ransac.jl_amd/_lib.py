@@ -58,6 +58,13 @@ class NormalsParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("orient", C.c_int32), ("radius", C.c_double), ("viewpoint", C.c_double * 3)]
 
 
+class VoxelParams(C.Structure):
+    """rh_voxel_params (include/ransac_hip.h)"""
+    _fields_ = [("beta", C.c_double), ("mode", C.c_int32), ("flags", C.c_int32)]
+
+
+VOX_FIRST, VOX_CENTROID = 0, 1
+VOX_ALIGN_NORMALS = 1
 EXT_EMPTY, EXT_NO_DIRECTION, EXT_INVALID = 1, 2, 4
 
 
@@ -161,6 +168,10 @@ SIGNATURES = {
     "rh_estimate_normals": (C.c_int, [_dp, C.c_int64, C.POINTER(NormalsParams), _dp, C.c_int, _dp, _dp, _i32p]),
     "rh_estimate_normals_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(NormalsParams), C.POINTER(C.c_float),
                                           C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32p]),
+    "rh_voxel_downsample": (C.c_int, [_dp, _dp, C.c_int64, C.POINTER(VoxelParams), C.c_int, _dp, _dp, _i64p, _i32p, C.c_int64,
+                                      _i32p, _i64p, _i64p]),
+    "rh_voxel_downsample_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(VoxelParams), C.c_int,
+                                          C.POINTER(C.c_float), C.POINTER(C.c_float), _i64p, _i32p, C.c_int64, _i32p, _i64p, _i64p]),
 }
 
 # include/ransac_hip_diag.h: exported by the diag build only

@@ -794,6 +794,63 @@ def estimatenormals(vertices, k=16, radius=0.0, viewpoint=None, hints=None, devi
     return out[0] if len(out) == 1 else out
 
 
+def voxeldownsample(vertices, beta, normals=None, mode="centroid", align_normals=False, device=0, return_index=False,
+                    return_counts=False, return_map=False):
+    """Thin a raw cloud on a voxel grid of width beta (rh_voxel_downsample, include/ransac_hip.h has the definition in
+    full): one point per occupied cell, rows in the order in which the cells first appear.  vertices: (n, 3) float64 or
+    float32, the result has that dtype; normals (optional, same shape) are thinned along.  mode "centroid": the mean of
+    the cell's points (exact integer sums: the same bits whatever the order of the points) and the normalised sum of
+    their normals, with align_normals each normal first turned to the side of the cell's first (for
+    estimatenormals(...) output without a viewpoint or hints, whose sign flips inside a cell); mode "first": the cell's
+    first point and its normal as they are.  Points with a non-finite coordinate (or a non-finite / larger-than-2 normal
+    component) are dropped.
+    Returns the thinned vertices, then the normals when they were given, then on request: return_index the 1-based index
+    of every cell's first point, return_counts the points per cell, return_map row_of_point (n int32: the 1-based row of
+    every point, 0 for a dropped one; expand_inpoints carries a shape's point list back through it)."""
+    modes = {"first": L.VOX_FIRST, "centroid": L.VOX_CENTROID}
+    if isinstance(mode, str) and mode not in modes:
+        raise ValueError("voxeldownsample: mode %r is neither 'first' nor 'centroid'" % (mode,))
+    f32 = np.asarray(vertices).dtype == np.float32
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    xyz = np.ascontiguousarray(vertices, dtype=t).reshape(-1, 3)
+    n = xyz.shape[0]
+    nrm = None
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, dtype=t).reshape(-1, 3)
+        if nrm.shape[0] != n:
+            raise ValueError("voxeldownsample: %d normals for %d points" % (nrm.shape[0], n))
+    prm = L.VoxelParams(beta=float(beta), mode=int(modes.get(mode, mode)), flags=L.VOX_ALIGN_NORMALS if align_normals else 0)
+    xo = np.empty((max(n, 1), 3), dtype=t)
+    no = np.empty((max(n, 1), 3), dtype=t) if nrm is not None else None
+    first = np.empty(max(n, 1), dtype=np.int64) if return_index else None
+    count = np.empty(max(n, 1), dtype=np.int32) if return_counts else None
+    rowof = np.zeros(n, dtype=np.int32) if return_map else None
+    m = C.c_int64(0)
+    fn = lib().rh_voxel_downsample_f32 if f32 else lib().rh_voxel_downsample
+    check(fn(_p(xyz, ct), None if nrm is None else _p(nrm, ct), n, C.byref(prm), device, _p(xo, ct),
+             None if no is None else _p(no, ct), None if first is None else _p(first, C.c_int64),
+             None if count is None else _p(count, C.c_int32), n, None if rowof is None else _p(rowof, C.c_int32),
+             C.byref(m), None))
+    m = int(m.value)
+    out = (xo[:m].copy(),) + ((no[:m].copy(),) if no is not None else ())
+    out += ((first[:m].copy(),) if return_index else ()) + ((count[:m].copy(),) if return_counts else ())
+    out += ((rowof,) if return_map else ())
+    return out[0] if len(out) == 1 else out
+
+
+def expand_inpoints(inpoints, row_of_point):
+    """The full-cloud 1-based indices, ascending, of the points whose row (row_of_point of voxeldownsample) is in
+    `inpoints`, a list of 1-based indices into the thinned cloud: what carries an ExtractedShape found on the thinned
+    cloud back to the raw scan."""
+    rows = np.asarray(row_of_point)
+    want = np.zeros(int(rows.max(initial=0)) + 1, dtype=bool)
+    idx = np.asarray(inpoints, dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 1 or idx.max() >= want.size):
+        raise ValueError("expand_inpoints: a row outside 1 .. %d" % (want.size - 1))
+    want[idx] = True
+    return np.flatnonzero(want[rows] & (rows > 0)).astype(np.int64) + 1
+
+
 class Extent:
     """Where a shape's points lie and how well they sit on it (rh_extent, include/ransac_hip.h has the definition in full):
     n, kind, flags (EXT_EMPTY / EXT_NO_DIRECTION of _lib), origin[3], frame[3, 3] (rows u, v, w), lo[3] / hi[3] (the box

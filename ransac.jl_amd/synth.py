@@ -184,6 +184,33 @@ def make_subsets(n, r, seed=0):
     return subs
 
 
+def median_nn_distance(xyz, samples=512, seed=0):
+    """Median distance to the nearest other point, over `samples` points drawn with default_rng(seed): the scale a
+    voxel width is chosen against.  Exact per sample (a window of the x-sorted cloud, widened until it holds the
+    neighbour)."""
+    xyz = np.asarray(xyz, dtype=np.float64)
+    n = xyz.shape[0]
+    if n < 2:
+        return 0.0
+    order = np.argsort(xyz[:, 0], kind="stable")
+    xs = xyz[order, 0]
+    pick = np.random.default_rng(seed).choice(n, size=min(samples, n), replace=False)
+    w0 = max((xs[-1] - xs[0]) / max(n, 1) ** (1.0 / 3.0), np.finfo(np.float64).tiny)
+    out = []
+    for i in pick:
+        p, w = xyz[i], w0
+        while True:
+            lo, hi = np.searchsorted(xs, p[0] - w, "left"), np.searchsorted(xs, p[0] + w, "right")
+            cand = order[lo:hi]
+            cand = cand[cand != i]
+            d = np.sqrt(((xyz[cand] - p) ** 2).sum(axis=1).min()) if cand.size else np.inf
+            if d <= w or (lo == 0 and hi == n):
+                break
+            w *= 2.0
+        out.append(d)
+    return float(np.median(out))
+
+
 # the BASELINE.json / SURVEY.md 8(d) configurations
 def config(name):
     if name == "cfg1":   # 50k plane + sphere, r = 2 (faithful-parity config, no Int64 wrap)
