@@ -627,6 +627,7 @@ def test_refit_lsq_recovers_primitives_and_matches_oracle(small_scene):
         got, n, rms, it = R.refit_lsq(cand, pc, cp, max_iter=12)
         exp, on, orms, oit = oc.refit_lsq(orc.Shape.from_buffer_copy(bytes(cand.to_c())), op, max_iter=12)
         assert n == on and n > 500, (R.strt(cand), n, on)
+        assert 1 <= it < 12 and abs(it - oit) <= 1, (R.strt(cand), it, oit)   # converged; the stop test sits at a threshold
         gv, ev = np.array(list(got.to_c().v)), np.array(list(exp.v))
         assert np.allclose(gv, ev, rtol=1e-8, atol=1e-9), (R.strt(cand), gv, ev)
         assert abs(rms - orms) <= 1e-9 + 1e-6 * orms
