@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 113
+#define RH_VERSION 114
 
 enum {
     RH_OK = 0,
@@ -241,6 +241,56 @@ int rh_shape_extents(rh_cloud *c, const rh_shape *shapes, int32_t b,
  * total = offsets[b] = the number of entries of d_idx_1based (the host cannot read the offsets; the grid is sized by it) */
 int rh_shape_extents_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const int64_t *d_offsets,
                          const int64_t *d_idx_1based, int64_t total, rh_extent *d_out);
+
+/* ---- every point labelled with its nearest compatible shape (no counterpart in the reference, whose extraction is
+ *      greedy: a point on two shapes stays with the one extracted first, src/iterations.jl:124-140) ----
+ * n points with optional normals, b shapes in the caller's order (0 <= b <= RH_ASSIGN_MAX_SHAPES) and finalised
+ * parameters, of which eps[kind] and cos_alpha[kind] are used.
+ *  1. for point i and shape j, (d_ij, t_ij) are the two compared quantities of the reference's compatibles* test
+ *     (plane.jl:114-130, sphere.jl:144-172, cylinder.jl:194-221, cone.jl:132-153): d the distance side --
+ *     |dot(o_z, p - point)|, |norm(p - o) - R|, |norm(curr_norm) - R|, |dist| of project2cone --, t the angle side.
+ *     IEEE binary64 operations in the reference's order, none contracted: the bits the score and refit kernels compare;
+ *  2. shape j claims point i when d_ij < eps[kind_j] and t_ij > cos_alpha[kind_j] -- rh_refit's predicate.  Without
+ *     normals (nrm_aos_or_null = NULL) or with RH_ASSIGN_NO_NORMALS the distance half alone decides.  A NaN fails every
+ *     comparison: a point with a non-finite coordinate, or a shape with a zero axis, claims nothing, and no validation
+ *     pass is needed for them;
+ *  3. label[i] = j + 1 for the claiming shape of smallest d_ij, among equal d the smallest j in the caller's order;
+ *     label[i] = 0 when no shape claims the point.  int32;
+ *  4. dist[i] (optional) = d_ij of the winner, -1.0 for label 0;
+ *  5. counts[0 .. b] (optional, int64): counts[0] = the unlabelled points, counts[j + 1] = the points of shape j;
+ *  6. lists (optional; offsets[b + 2] and idx[n], both or neither): the 1-based indices of the points grouped by label,
+ *     label 0 first, ascending within each group; offsets[k] .. offsets[k + 1] is label k's run and offsets[b + 1] = n:
+ *     the stable partition of 1 .. n by label.  idx[offsets[j + 1] .. offsets[j + 2]) is shape j's list as
+ *     rh_shape_extents takes it;
+ *  7. Float32 input (the _f32 entry, a Float32 cloud) is promoted exactly and tested in binary64, the shapes taken as
+ *     given.  On a Float32 cloud a point within rounding of a threshold can therefore be claimed differently than by
+ *     rh_refit, whose tests run in binary32: one definition for both element types;
+ *  8. the cloud entries with RH_ASSIGN_ENABLED_ONLY: a disabled point gets label 0 and dist -1 whatever its geometry.
+ *     Nothing on the cloud changes;
+ *  9. the same bits on every run; a point's label and dist do not depend on which other points are in the call.
+ * RH_E_INVALID, checked on the host before the first device call: b outside 0 .. 1024, a kind outside 0 .. 3 (host
+ * shapes; a device-resident shape of another kind claims nothing), n < 0 or n >= 2^31, a null required pointer, one of
+ * offsets / idx without the other, unknown flag bits, RH_ASSIGN_ENABLED_ONLY on the raw-array entries.  b == 0: every
+ * label 0, counts[0] = n, RH_OK.  n == 0: RH_OK.
+ * The raw-array entries (the scan that was thinned before detection: no rh_cloud needed) upload the arrays whole --
+ * 24 or 48 bytes per point in binary64, half that in binary32 -- and return RH_E_NOMEM when they do not fit. */
+enum { RH_ASSIGN_NO_NORMALS = 1, RH_ASSIGN_ENABLED_ONLY = 2 };
+#define RH_ASSIGN_MAX_SHAPES 1024
+int rh_assign_points(const double *xyz_aos, const double *nrm_aos_or_null, int64_t n, const rh_shape *shapes, int32_t b,
+                     const rh_params *p, int32_t flags, int device, int32_t *labels_out, double *dist_out_or_null,
+                     int64_t *counts_out_or_null, int64_t *offsets_out_or_null, int64_t *idx_out_or_null);
+int rh_assign_points_f32(const float *xyz_aos, const float *nrm_aos_or_null, int64_t n, const rh_shape *shapes, int32_t b,
+                         const rh_params *p, int32_t flags, int device, int32_t *labels_out, double *dist_out_or_null,
+                         int64_t *counts_out_or_null, int64_t *offsets_out_or_null, int64_t *idx_out_or_null);
+/* the cloud's resident coordinates (Float64 or Float32 cloud), host arrays out, one wait */
+int rh_cloud_assign(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, int32_t flags, int32_t *labels_out,
+                    double *dist_out_or_null, int64_t *counts_out_or_null, int64_t *offsets_out_or_null,
+                    int64_t *idx_out_or_null);
+/* everything resident on the cloud's device, enqueued on the cloud's stream without synchronising and without a host
+ * read-back: d_labels[n], d_dist[n], d_counts[b + 1], d_offsets[b + 2], d_idx[n] */
+int rh_cloud_assign_dev(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const rh_params *p, int32_t flags,
+                        int32_t *d_labels, double *d_dist_or_null, int64_t *d_counts_or_null, int64_t *d_offsets_or_null,
+                        int64_t *d_idx_or_null);
 
 /* Least-squares refit -- the step of the paper the reference leaves out (docs/src/ransac.md:163-168;
  * its `refit` returns the shape unchanged).  NOT part of parity runs.  Selects the enabled points

@@ -533,4 +533,66 @@ function voxeldownsample(vertices::AbstractVector{SVector{3,T}}, beta::Real; nor
     return resize!(vout, k), (nout === nothing ? nothing : resize!(nout, k)), resize!(first, k), resize!(count, k), rowof
 end
 
+_assign_shape(x::ExtractedShape) = toC(x.shape)
+_assign_shape(x::FittedShape) = toC(x)
+
+"""
+    assign_points(vertices, normals, shapes, params; use_normals = true, device = 0) -> (labels, dist, counts, offsets, idx)
+
+Every point labelled with its nearest compatible shape (`rh_assign_points`, include/ransac_hip.h has the definition):
+`labels[i] = j` for the shape `shapes[j]` (`FittedShape`s or `ExtractedShape`s, at most 1024) that claims point `i` -- the
+test of `refit`, distance < eps and angle within alpha -- at the smallest distance, ties to the earlier shape; 0 when none
+does.  `normals = nothing` or `use_normals = false`: the distance alone decides.  `dist[i]`: the winner's distance, -1 for
+label 0; `counts[1]` the unlabelled points, `counts[j + 1]` those of shape `j`; `idx[offsets[k] + 1 : offsets[k + 1]]` the
+points of label `k - 1`, ascending (label 0 first).  Float32 points are promoted exactly; no cloud is needed.
+"""
+function assign_points(vertices::AbstractVector{SVector{3,T}}, normals, shapes, params; use_normals::Bool = true,
+                       device::Integer = 0, cparams = toC(params)) where {T<:Union{Float32,Float64}}
+    vs = convert(Vector{SVector{3,T}}, vertices)
+    ns = normals === nothing ? nothing : convert(Vector{SVector{3,T}}, normals)
+    n = length(vs)
+    ns === nothing || length(ns) == n || error("assign_points: $(length(ns)) normals for $n points")
+    cs = RhShape[_assign_shape(x) for x in shapes]
+    b = length(cs)
+    b <= 1024 || error("assign_points: $b shapes, at most 1024 in one call")
+    labels = zeros(Int32, n); dist = Vector{Cdouble}(undef, n)
+    counts = zeros(Int64, b + 1); offsets = zeros(Int64, b + 2); idx = Vector{Int64}(undef, n)
+    np = ns === nothing ? Ptr{T}(C_NULL) : pointer(reinterpret(T, ns))
+    flags = use_normals ? 0 : 1
+    GC.@preserve vs ns begin
+        if T == Float32
+            check(ccall((:rh_assign_points_f32, LIB), Cint,
+                (Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ptr{RhShape}, Int32, Ref{RhParams}, Int32, Cint, Ptr{Int32}, Ptr{Cdouble},
+                 Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                pointer(reinterpret(Float32, vs)), np, n, cs, b, cparams, flags, device, labels, dist, counts, offsets, idx))
+        else
+            check(ccall((:rh_assign_points, LIB), Cint,
+                (Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{RhShape}, Int32, Ref{RhParams}, Int32, Cint, Ptr{Int32}, Ptr{Cdouble},
+                 Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                pointer(reinterpret(Float64, vs)), np, n, cs, b, cparams, flags, device, labels, dist, counts, offsets, idx))
+        end
+    end
+    return labels, dist, counts, offsets, idx
+end
+
+"""
+    assign_cloud(h, shapes, params; enabled_only = false, use_normals = true) -> (labels, dist, counts, offsets, idx)
+
+`assign_points` on the cloud's resident points (`rh_cloud_assign`; Float64 and Float32 clouds, both tested in binary64).
+`enabled_only`: a disabled point gets label 0 whatever its geometry.  Nothing on the cloud changes.
+"""
+function assign_cloud(h::HIPCloud, shapes, params; enabled_only::Bool = false, use_normals::Bool = true, cparams = toC(params))
+    n = h.pc.size
+    cs = RhShape[_assign_shape(x) for x in shapes]
+    b = length(cs)
+    b <= 1024 || error("assign_cloud: $b shapes, at most 1024 in one call")
+    labels = zeros(Int32, n); dist = Vector{Cdouble}(undef, n)
+    counts = zeros(Int64, b + 1); offsets = zeros(Int64, b + 2); idx = Vector{Int64}(undef, n)
+    flags = (use_normals ? 0 : 1) | (enabled_only ? 2 : 0)
+    check(ccall((:rh_cloud_assign, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{RhShape}, Int32, Ref{RhParams}, Int32, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        h.handle, cs, b, cparams, flags, labels, dist, counts, offsets, idx))
+    return labels, dist, counts, offsets, idx
+end
+
 end # module

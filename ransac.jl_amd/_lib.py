@@ -66,6 +66,8 @@ class VoxelParams(C.Structure):
 VOX_FIRST, VOX_CENTROID = 0, 1
 VOX_ALIGN_NORMALS = 1
 EXT_EMPTY, EXT_NO_DIRECTION, EXT_INVALID = 1, 2, 4
+ASSIGN_NO_NORMALS, ASSIGN_ENABLED_ONLY = 1, 2
+ASSIGN_MAX_SHAPES = 1024
 
 
 class Extent(C.Structure):
@@ -165,6 +167,11 @@ SIGNATURES = {
     "rh_shape_extents": (C.c_int, [_vp, _sp, C.c_int32, _i64p, _i64p, C.POINTER(Extent)]),
     "rh_shape_extents_dev": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp]),
     "rh_result_extents": (C.c_int, [_vp, C.POINTER(Result), C.POINTER(Extent)]),
+    "rh_assign_points": (C.c_int, [_dp, _dp, C.c_int64, _sp, C.c_int32, _pp, C.c_int32, C.c_int, _i32p, _dp, _i64p, _i64p, _i64p]),
+    "rh_assign_points_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, _sp, C.c_int32, _pp, C.c_int32, C.c_int,
+                                       _i32p, _dp, _i64p, _i64p, _i64p]),
+    "rh_cloud_assign": (C.c_int, [_vp, _sp, C.c_int32, _pp, C.c_int32, _i32p, _dp, _i64p, _i64p, _i64p]),
+    "rh_cloud_assign_dev": (C.c_int, [_vp, _vp, C.c_int32, _pp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "rh_estimate_normals": (C.c_int, [_dp, C.c_int64, C.POINTER(NormalsParams), _dp, C.c_int, _dp, _dp, _i32p]),
     "rh_estimate_normals_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(NormalsParams), C.POINTER(C.c_float),
                                           C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32p]),

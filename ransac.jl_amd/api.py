@@ -897,6 +897,88 @@ def shape_extents(pc, extracted_shapes):
     return [Extent(e) for e in out]
 
 
+def _assign_shapes(shapes, who):
+    """FittedShapes, ExtractedShapes (their c_shape when they carry one) or L.Shapes -> the C array, as shape_extents unpacks them"""
+    cs = []
+    for x in shapes:
+        if isinstance(x, ExtractedShape):
+            c = getattr(x, "c_shape", None)
+            x = c if c is not None else x.shape
+        cs.append(x if isinstance(x, L.Shape) else x.to_c())
+    if len(cs) > L.ASSIGN_MAX_SHAPES:
+        raise ValueError("%s: %d shapes, at most %d in one call" % (who, len(cs), L.ASSIGN_MAX_SHAPES))
+    arr = (L.Shape * max(1, len(cs)))()
+    for j, c in enumerate(cs):
+        arr[j] = c
+    return arr, len(cs)
+
+
+def _assign_outputs(n, b, return_dist, return_counts, return_lists):
+    labels = np.zeros(max(1, n), dtype=np.int32)
+    dist = np.empty(max(1, n), dtype=np.float64) if return_dist else None
+    counts = np.zeros(b + 1, dtype=np.int64) if return_counts else None
+    offsets = np.zeros(b + 2, dtype=np.int64) if return_lists else None
+    idx = np.zeros(max(1, n), dtype=np.int64) if return_lists else None
+    ptrs = (_p(labels, C.c_int32), None if dist is None else _p(dist, C.c_double), None if counts is None else _p(counts, C.c_int64),
+            None if offsets is None else _p(offsets, C.c_int64), None if idx is None else _p(idx, C.c_int64))
+
+    def result():
+        out = (labels[:n],) + ((dist[:n],) if return_dist else ()) + ((counts,) if return_counts else ())
+        out += ((offsets, idx[:n]) if return_lists else ())
+        return out[0] if len(out) == 1 else out
+    return ptrs, result
+
+
+def assign_points(vertices, normals, shapes, params, use_normals=True, device=0, return_dist=False, return_counts=False,
+                  return_lists=False):
+    """Label every point of a raw scan with its nearest compatible shape (rh_assign_points, include/ransac_hip.h has the
+    definition in full): label j + 1 for the shape j that claims the point -- rh_refit's test, distance < eps and angle
+    within alpha -- at the smallest distance, ties to the earlier shape; 0 when none does.  vertices: (n, 3) float64 or
+    float32 (promoted exactly; the tests run in binary64 either way); normals: the same shape, or None -- then, or with
+    use_normals = False, the distance alone decides.  shapes: FittedShapes, ExtractedShapes or C shape records, at most 1024.
+    No RANSACCloud is needed: this is the stage that carries shapes found on a thinned cloud back to the scan, point by
+    point.  Returns labels (int32), then on request: return_dist the winner's distance (-1 for label 0), return_counts
+    int64[b + 1] (unlabelled first), return_lists (offsets[b + 2], idx[n]): the 1-based indices grouped by label, label 0
+    first, ascending within a group (lists_from_assignment splits them)."""
+    f32 = np.asarray(vertices).dtype == np.float32
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    xyz = np.ascontiguousarray(vertices, dtype=t).reshape(-1, 3)
+    n = xyz.shape[0]
+    nrm = None
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, dtype=t).reshape(-1, 3)
+        if nrm.shape[0] != n:
+            raise ValueError("assign_points: %d normals for %d points" % (nrm.shape[0], n))
+    arr, b = _assign_shapes(shapes, "assign_points")
+    ptrs, result = _assign_outputs(n, b, return_dist, return_counts, return_lists)
+    fn = lib().rh_assign_points_f32 if f32 else lib().rh_assign_points
+    check(fn(_p(xyz, ct), None if nrm is None else _p(nrm, ct), n, arr, b, C.byref(_cparams(params)),
+             0 if use_normals else L.ASSIGN_NO_NORMALS, device, *ptrs))
+    return result()
+
+
+def assign_cloud(pc, shapes, params, enabled_only=False, use_normals=True, return_dist=False, return_counts=False,
+                 return_lists=False):
+    """assign_points on a RANSACCloud's resident points (rh_cloud_assign; Float64 and Float32 clouds, both tested in
+    binary64 with the shapes as given).  enabled_only: a disabled point gets label 0 whatever its geometry.  Nothing on the
+    cloud changes."""
+    arr, b = _assign_shapes(shapes, "assign_cloud")
+    ptrs, result = _assign_outputs(pc.size, b, return_dist, return_counts, return_lists)
+    flags = (0 if use_normals else L.ASSIGN_NO_NORMALS) | (L.ASSIGN_ENABLED_ONLY if enabled_only else 0)
+    check(lib().rh_cloud_assign(pc._h, arr, b, C.byref(_cparams(params)), flags, *ptrs))
+    return result()
+
+
+def lists_from_assignment(offsets, idx):
+    """The per-label index arrays of an assignment's lists: element 0 the unlabelled points, element j + 1 the points of
+    shape j (1-based, ascending) -- what shape_extents takes as a shape's list."""
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+    if offsets.size < 2 or offsets[0] != 0 or offsets[-1] != idx.size or (np.diff(offsets) < 0).any():
+        raise ValueError("lists_from_assignment: offsets do not partition %d indices" % idx.size)
+    return [idx[offsets[k]:offsets[k + 1]] for k in range(offsets.size - 1)]
+
+
 def invalidate_indexes(pc, indexlist):  # invalidate_indexes!: fitting.jl:197-202
     idx = np.ascontiguousarray(indexlist, dtype=np.int64)
     check(lib().rh_invalidate(pc._h, _p(idx, C.c_int64), idx.size))

@@ -189,6 +189,7 @@ static void cloud_free(rh_cloud *c)
     (void)hipFree(c->d_nk); (void)hipFree(c->d_masks); (void)hipFree(c->d_ranks); (void)hipFree(c->d_stage);
     (void)hipFree(c->comp_tab); (void)hipFree(c->comp_scal);
     (void)hipFree(c->ext_part); (void)hipFree(c->ext_flag); (void)hipFree(c->ext_in);
+    (void)hipFree(c->asg_ws); (void)hipFree(c->asg_io);
     if (c->comp_h) (void)hipHostFree(c->comp_h);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

@@ -282,6 +282,12 @@ struct rh_cloud {
     void *ext_in = nullptr;            // the host entry's uploads: shapes, offsets, records, index lists
     int64_t ext_in_bytes = 0;
 
+    // per-point labels (assign.hip): workspaces, grown on demand and kept between calls
+    void *asg_ws = nullptr;            // prepared shape records, the lists' count matrix, label totals and offsets
+    int64_t asg_ws_bytes = 0;
+    void *asg_io = nullptr;            // the host entry's shapes and its outputs on their way to the host
+    int64_t asg_io_bytes = 0;
+
     // the batch workspaces: ws[0] the cloud's own, ws[1 ..] the other slots of rh_score_batch_dev's pipeline (rh_batch_ws)
     rh_batch_ws ws[RH_MAX_IN_FLIGHT];
     uint32_t pipe_k = 0;               // batches since the pipeline (re)started
