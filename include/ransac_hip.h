@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 114
+#define RH_VERSION 115
 
 enum {
     RH_OK = 0,
@@ -586,6 +586,74 @@ int rh_voxel_downsample_f32(const float *xyz_aos, const float *nrm_aos_or_null, 
                             float *xyz_out_aos, float *nrm_out_aos_or_null, int64_t *first_out_1based_or_null,
                             int32_t *count_out_or_null, int64_t cap, int32_t *row_of_point_out_or_null,
                             int64_t *n_out, int64_t *n_dropped_out_or_null);
+
+/* ---- exact k nearest neighbours of a raw cloud, and outlier removal on them (no counterpart in the reference, which
+ *      starts from clean clouds) ----
+ * The search is that of rh_estimate_normals, step 1.  For point i (0-based) the ORDER of the other points is: ascending
+ * d^2 = (dx*dx + dy*dy) + dz*dz (binary64, dx = q.x - p.x, no contraction), ties to the smaller index; the point itself is
+ * left out by its index, not by its distance, so a duplicate of p_i (d^2 = 0) is a neighbour.
+ * rh_knn:
+ *  1. k is 1 .. RH_KNN_MAX_K; the neighbours of i are the first k of its order, with radius > 0 those with
+ *     d^2 > radius*radius dropped; count[i] = how many are left (0 <= count[i] <= min(k, n - 1));
+ *  2. idx is int32 [n x k], row i = the neighbours' 1-based indices in that order, 0 past count[i]; d2 is double [n x k],
+ *     the d^2 as computed, +inf past count[i]; count is int32 [n].  Every output is optional;
+ *  3. the _f32 entry widens the coordinates exactly and searches in binary64; d2 stays double;
+ *  4. RH_E_INVALID: k outside 1 .. 63, radius negative or not finite, n < 1, n >= 2^31 - 1, a null xyz -- decided before
+ *     the device is touched -- and a coordinate that is not finite (found on the device, nothing is written).
+ * The same bits on every run.  The array arguments of rh_knn and rh_remove_outliers may be host or device pointers (the
+ * copies are hipMemcpyDefault); scalars, parameters and stats are host memory.
+ *
+ * rh_remove_outliers: statistical / absolute / radius outlier removal, defined so that every output is one fixed sequence of
+ * IEEE binary64 operations.
+ *  T(a_0 .. a_(L-1)) is the root of the perfect binary tree over ADJACENT pairs of the values, padded with +0.0 to the next
+ *  power of two: b = a; while (len(b) > 1) b = { b_0 + b_1, b_2 + b_3, ... }.  (Adding zeros is exact, so the padding does not
+ *  show and the result does not depend on how the device cuts the tree into lanes, waves and blocks; its blocks hold
+ *  RH_OUT_BLOCK_POINTS points.)
+ *  1. count_i and d2_i1 .. d2_i,count_i: rh_knn's for (k, radius);
+ *  2. m_i = T(sqrt(d2_i1), .., sqrt(d2_i,count_i)) / count_i, the mean distance to the neighbours; +inf when count_i == 0;
+ *  3. V = { i : count_i >= 1 }, in index order; n_valid = |V|;
+ *  4. mu = T(m_i if i in V else +0.0, i = 0 .. n-1) / n_valid, 0 when V is empty;
+ *  5. sigma = sqrt(T((m_i - mu)*(m_i - mu) if i in V else +0.0, i = 0 .. n-1) / (n_valid - 1)), 0 when n_valid < 2;
+ *  6. mode RH_OUT_STATISTICAL: tau = mu + std_mul*sigma (product rounded, then the sum); keep_i = i in V and m_i <= tau;
+ *     mode RH_OUT_ABSOLUTE:    tau = threshold, the same test;
+ *     mode RH_OUT_RADIUS:      keep_i = count_i == k (at least k other points within radius; radius > 0 required);
+ *                              tau = radius in the stats;
+ *  7. nn_median = the lower median -- sorted position floor((n_valid - 1) / 2) -- of sqrt(d2_i1) over V, 0 when V is
+ *     empty: the cloud's point spacing, from which beta and eps are chosen.
+ * keep_out: uint8 [n], 1 = kept.  kept_idx_out (optional): the kept points' 1-based indices, ascending, int32;
+ * *n_kept_out = their number; more than cap: RH_E_CAPACITY (like rh_refit) with *n_kept_out set and keep_out,
+ * mean_dist_out and stats still written in full.  mean_dist_out (optional): m_i, double [n].  stats (optional).
+ * RH_E_INVALID, before the device is touched: k outside 1 .. 63, an unknown mode, radius negative or not finite (or not
+ * positive in mode RH_OUT_RADIUS), std_mul not finite (statistical), threshold NaN (absolute), n < 1, n >= 2^31 - 1, a
+ * null xyz / params / keep_out / n_kept_out, cap < 0, cap > 0 without kept_idx_out; on the device: a coordinate that is
+ * not finite.  The same bits on every run; a permutation of the input permutes m_i and keep_i and can change mu, sigma and
+ * tau in their last bits (the tree runs over the index order). */
+#define RH_KNN_MAX_K 63
+#define RH_OUT_BLOCK_POINTS 1024
+enum { RH_OUT_STATISTICAL = 0, RH_OUT_ABSOLUTE = 1, RH_OUT_RADIUS = 2 };
+typedef struct {
+    int32_t k;               /* 1 .. RH_KNN_MAX_K */
+    int32_t mode;            /* RH_OUT_* */
+    double std_mul;          /* RH_OUT_STATISTICAL */
+    double radius;           /* 0 = no limit (RH_OUT_RADIUS: > 0) */
+    double threshold;        /* RH_OUT_ABSOLUTE */
+} rh_outlier_params;
+typedef struct {
+    int64_t n_valid;         /* |V| */
+    int64_t n_kept;
+    double mu, sigma, tau;
+    double nn_median;
+} rh_outlier_stats;
+int rh_knn(const double *xyz_aos, int64_t n, int32_t k, double radius, int device, int32_t *idx_out_or_null,
+           double *d2_out_or_null, int32_t *count_out_or_null);
+int rh_knn_f32(const float *xyz_aos, int64_t n, int32_t k, double radius, int device, int32_t *idx_out_or_null,
+               double *d2_out_or_null, int32_t *count_out_or_null);
+int rh_remove_outliers(const double *xyz_aos, int64_t n, const rh_outlier_params *p, int device, uint8_t *keep_out,
+                       int32_t *kept_idx_out_or_null, int64_t cap, int64_t *n_kept_out, double *mean_dist_out_or_null,
+                       rh_outlier_stats *stats_or_null);
+int rh_remove_outliers_f32(const float *xyz_aos, int64_t n, const rh_outlier_params *p, int device, uint8_t *keep_out,
+                           int32_t *kept_idx_out_or_null, int64_t cap, int64_t *n_kept_out, double *mean_dist_out_or_null,
+                           rh_outlier_stats *stats_or_null);
 
 /* ---- tuning options ----
  * The library reads NO environment variable: what a caller may tune goes through this call, for one cloud or, with

@@ -533,6 +533,92 @@ function voxeldownsample(vertices::AbstractVector{SVector{3,T}}, beta::Real; nor
     return resize!(vout, k), (nout === nothing ? nothing : resize!(nout, k)), resize!(first, k), resize!(count, k), rowof
 end
 
+# ---- exact k nearest neighbours and outlier removal of a raw cloud (rh_knn, rh_remove_outliers) ----
+# typedef struct { int32_t k; int32_t mode; double std_mul; double radius; double threshold; } rh_outlier_params;   (32 bytes)
+struct RhOutlierParams
+    k::Cint
+    mode::Cint
+    std_mul::Cdouble
+    radius::Cdouble
+    threshold::Cdouble
+end
+# typedef struct { int64_t n_valid, n_kept; double mu, sigma, tau, nn_median; } rh_outlier_stats;   (48 bytes)
+struct RhOutlierStats
+    n_valid::Int64
+    n_kept::Int64
+    mu::Cdouble
+    sigma::Cdouble
+    tau::Cdouble
+    nn_median::Cdouble
+end
+
+"""
+    knn(vertices, k; radius = 0.0) -> (idx, d2, count)
+
+The `k` (1 to 63) nearest neighbours of every point among the other points, exact: ascending
+`d2 = (dx*dx + dy*dy) + dz*dz` in Float64, ties to the smaller index; a duplicate of the point is a neighbour at
+distance 0.  `idx` is `k x n` Int32 (column `i` = the neighbours of point `i`, 1-based, 0 past `count[i]`), `d2` the
+squared distances (`Inf` there), `count[i]` the neighbours left after `radius > 0` dropped the farther ones.
+"""
+function knn(vertices::AbstractVector{SVector{3,T}}, k::Integer; radius::Real = 0.0,
+             device::Integer = 0) where {T<:Union{Float32,Float64}}
+    vs = convert(Vector{SVector{3,T}}, vertices)
+    n = length(vs)
+    kk = 1 <= k <= 63 ? Int(k) : 1
+    idx = zeros(Int32, kk, n)
+    d2 = fill(Inf, kk, n)
+    count = zeros(Int32, n)
+    GC.@preserve vs idx d2 count begin
+        if T == Float32
+            check(ccall((:rh_knn_f32, LIB), Cint, (Ptr{Cfloat}, Int64, Int32, Cdouble, Cint, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}),
+                pointer(reinterpret(Float32, vs)), n, k, radius, device, idx, d2, count))
+        else
+            check(ccall((:rh_knn, LIB), Cint, (Ptr{Cdouble}, Int64, Int32, Cdouble, Cint, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}),
+                pointer(reinterpret(Float64, vs)), n, k, radius, device, idx, d2, count))
+        end
+    end
+    return idx, d2, count
+end
+
+"""
+    removeoutliers(vertices; k = 16, std_mul = 2.0, mode = :statistical, radius = 0.0, threshold = nothing, normals = nothing)
+        -> (vertices, normals or nothing, kept_idx, stats)
+
+Drops the stray points of a raw cloud (`rh_remove_outliers`, include/ransac_hip.h has the definition in full).  With
+`m[i]` the mean distance of point `i` to its `k` nearest neighbours (within `radius` when it is positive):
+`:statistical` keeps `m[i] <= mu + std_mul * sigma`, `:absolute` keeps `m[i] <= threshold`, `:radius` keeps the points
+with at least `k` other points within `radius`.  `kept_idx`: the kept points' indices, ascending; `stats`: an
+`RhOutlierStats` (`nn_median` is the cloud's median nearest-neighbour distance).
+"""
+function removeoutliers(vertices::AbstractVector{SVector{3,T}}; k::Integer = 16, std_mul::Real = 2.0, mode::Symbol = :statistical,
+                        radius::Real = 0.0, threshold = nothing, normals = nothing,
+                        device::Integer = 0) where {T<:Union{Float32,Float64}}
+    mode in (:statistical, :absolute, :radius) || error("removeoutliers: mode is :statistical, :absolute or :radius")
+    mode === :absolute && threshold === nothing && error("removeoutliers: mode :absolute needs a threshold")
+    m = mode === :statistical ? 0 : (mode === :absolute ? 1 : 2)
+    p = RhOutlierParams(k, m, std_mul, radius, threshold === nothing ? 0.0 : threshold)
+    vs = convert(Vector{SVector{3,T}}, vertices)
+    n = length(vs)
+    normals === nothing || length(normals) == n || error("removeoutliers: $(length(normals)) normals for $n points")
+    keep = zeros(UInt8, n)
+    idx = zeros(Int32, max(n, 1))
+    nk = Ref{Int64}(0)
+    st = Ref(RhOutlierStats(0, 0, 0.0, 0.0, 0.0, 0.0))
+    GC.@preserve vs keep idx begin
+        if T == Float32
+            check(ccall((:rh_remove_outliers_f32, LIB), Cint,
+                (Ptr{Cfloat}, Int64, Ref{RhOutlierParams}, Cint, Ptr{UInt8}, Ptr{Int32}, Int64, Ref{Int64}, Ptr{Cdouble}, Ref{RhOutlierStats}),
+                pointer(reinterpret(Float32, vs)), n, p, device, keep, idx, n, nk, C_NULL, st))
+        else
+            check(ccall((:rh_remove_outliers, LIB), Cint,
+                (Ptr{Cdouble}, Int64, Ref{RhOutlierParams}, Cint, Ptr{UInt8}, Ptr{Int32}, Int64, Ref{Int64}, Ptr{Cdouble}, Ref{RhOutlierStats}),
+                pointer(reinterpret(Float64, vs)), n, p, device, keep, idx, n, nk, C_NULL, st))
+        end
+    end
+    resize!(idx, nk[])
+    return vs[idx], (normals === nothing ? nothing : normals[idx]), idx, st[]
+end
+
 _assign_shape(x::ExtractedShape) = toC(x.shape)
 _assign_shape(x::FittedShape) = toC(x)
 

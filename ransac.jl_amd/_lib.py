@@ -63,6 +63,21 @@ class VoxelParams(C.Structure):
     _fields_ = [("beta", C.c_double), ("mode", C.c_int32), ("flags", C.c_int32)]
 
 
+class OutlierParams(C.Structure):
+    """rh_outlier_params (include/ransac_hip.h)"""
+    _fields_ = [("k", C.c_int32), ("mode", C.c_int32), ("std_mul", C.c_double), ("radius", C.c_double),
+                ("threshold", C.c_double)]
+
+
+class OutlierStats(C.Structure):
+    """rh_outlier_stats (include/ransac_hip.h)"""
+    _fields_ = [("n_valid", C.c_int64), ("n_kept", C.c_int64), ("mu", C.c_double), ("sigma", C.c_double),
+                ("tau", C.c_double), ("nn_median", C.c_double)]
+
+
+KNN_MAX_K = 63
+OUT_BLOCK_POINTS = 1024
+OUT_STATISTICAL, OUT_ABSOLUTE, OUT_RADIUS = 0, 1, 2
 VOX_FIRST, VOX_CENTROID = 0, 1
 VOX_ALIGN_NORMALS = 1
 EXT_EMPTY, EXT_NO_DIRECTION, EXT_INVALID = 1, 2, 4
@@ -179,6 +194,12 @@ SIGNATURES = {
                                       _i32p, _i64p, _i64p]),
     "rh_voxel_downsample_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(VoxelParams), C.c_int,
                                           C.POINTER(C.c_float), C.POINTER(C.c_float), _i64p, _i32p, C.c_int64, _i32p, _i64p, _i64p]),
+    "rh_knn": (C.c_int, [_dp, C.c_int64, C.c_int32, C.c_double, C.c_int, _i32p, _dp, _i32p]),
+    "rh_knn_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_double, C.c_int, _i32p, _dp, _i32p]),
+    "rh_remove_outliers": (C.c_int, [_dp, C.c_int64, C.POINTER(OutlierParams), C.c_int, _u8p, _i32p, C.c_int64, _i64p, _dp,
+                                     C.POINTER(OutlierStats)]),
+    "rh_remove_outliers_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(OutlierParams), C.c_int, _u8p, _i32p,
+                                         C.c_int64, _i64p, _dp, C.POINTER(OutlierStats)]),
 }
 
 # include/ransac_hip_diag.h: exported by the diag build only

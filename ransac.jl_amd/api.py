@@ -794,6 +794,70 @@ def estimatenormals(vertices, k=16, radius=0.0, viewpoint=None, hints=None, devi
     return out[0] if len(out) == 1 else out
 
 
+def knn(vertices, k, radius=0.0, return_dist=True, return_count=False, device=0):
+    """The k nearest neighbours of every point among the other points (rh_knn: exact, d^2 = (dx*dx + dy*dy) + dz*dz in
+    binary64, ties to the smaller index; a duplicate of the point is a neighbour at distance 0).  vertices: (n, 3) float64
+    or float32 (widened exactly).  k: 1 .. 63; radius > 0 drops neighbours farther than it.
+    Returns idx (n, k) int32, 1-based, 0 where a point has fewer neighbours; then with return_dist the squared distances
+    (n, k) float64, +inf there; then with return_count the neighbours per point (n,) int32."""
+    f32 = np.asarray(vertices).dtype == np.float32
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    xyz = np.ascontiguousarray(vertices, dtype=t).reshape(-1, 3)
+    n, k = xyz.shape[0], int(k)
+    kk = k if 1 <= k <= L.KNN_MAX_K else 1            # (the library refuses the call; nothing is written)
+    idx = np.zeros((n, kk), dtype=np.int32)
+    d2 = np.full((n, kk), np.inf) if return_dist else None
+    cnt = np.zeros(n, dtype=np.int32) if return_count else None
+    fn = lib().rh_knn_f32 if f32 else lib().rh_knn
+    check(fn(_p(xyz, ct), n, k, float(radius), device, _p(idx, C.c_int32), None if d2 is None else _p(d2, C.c_double),
+             None if cnt is None else _p(cnt, C.c_int32)))
+    out = (idx,) + ((d2,) if return_dist else ()) + ((cnt,) if return_count else ())
+    return out[0] if len(out) == 1 else out
+
+
+def removeoutliers(vertices, k=16, std_mul=2.0, mode="statistical", radius=0.0, threshold=None, normals=None, device=0,
+                   return_index=False, return_stats=False, return_mean_dist=False):
+    """Drop the stray points of a raw cloud (rh_remove_outliers; include/ransac_hip.h has the definition in full).  With
+    m_i the mean distance of point i to its k nearest neighbours (within radius, when radius > 0):
+    mode "statistical" keeps m_i <= mu + std_mul * sigma (mean and standard deviation of the m_i), "absolute" keeps
+    m_i <= threshold, "radius" keeps the points with at least k other points within radius.  A point without a neighbour
+    is dropped.  vertices: (n, 3) float64 or float32; normals (optional, same shape) are thinned along.
+    Returns the kept vertices, then the kept normals when they were given, then on request: return_index the kept points'
+    1-based indices (ascending, int32), return_stats a dict n_valid, n_kept, mu, sigma, tau, nn_median (the median
+    nearest-neighbour distance: the cloud's point spacing), return_mean_dist the m_i of every point (+inf: no
+    neighbour)."""
+    modes = {"statistical": L.OUT_STATISTICAL, "absolute": L.OUT_ABSOLUTE, "radius": L.OUT_RADIUS}
+    if isinstance(mode, str) and mode not in modes:
+        raise ValueError("removeoutliers: mode %r is none of %s" % (mode, sorted(modes)))
+    mode = int(modes.get(mode, mode))
+    if mode == L.OUT_ABSOLUTE and threshold is None:
+        raise ValueError("removeoutliers: mode 'absolute' needs a threshold")
+    f32 = np.asarray(vertices).dtype == np.float32
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    xyz = np.ascontiguousarray(vertices, dtype=t).reshape(-1, 3)
+    n = xyz.shape[0]
+    nrm = None
+    if normals is not None:
+        nrm = np.asarray(normals).reshape(-1, 3)
+        if nrm.shape[0] != n:
+            raise ValueError("removeoutliers: %d normals for %d points" % (nrm.shape[0], n))
+    prm = L.OutlierParams(k=int(k), mode=mode, std_mul=float(std_mul), radius=float(radius),
+                          threshold=0.0 if threshold is None else float(threshold))
+    keep = np.zeros(n, dtype=np.uint8)
+    idx = np.zeros(max(n, 1), dtype=np.int32)
+    mean = np.zeros(n) if return_mean_dist else None
+    st, nk = L.OutlierStats(), C.c_int64(0)
+    fn = lib().rh_remove_outliers_f32 if f32 else lib().rh_remove_outliers
+    check(fn(_p(xyz, ct), n, C.byref(prm), device, _p(keep, C.c_uint8), _p(idx, C.c_int32), n, C.byref(nk),
+             None if mean is None else _p(mean, C.c_double), C.byref(st)))
+    idx = idx[:nk.value].copy()
+    out = (xyz[idx - 1],) + ((nrm[idx - 1],) if nrm is not None else ())
+    out += ((idx,) if return_index else ())
+    out += (({f: getattr(st, f) for f, _ in L.OutlierStats._fields_},) if return_stats else ())
+    out += ((mean,) if return_mean_dist else ())
+    return out[0] if len(out) == 1 else out
+
+
 def voxeldownsample(vertices, beta, normals=None, mode="centroid", align_normals=False, device=0, return_index=False,
                     return_counts=False, return_map=False):
     """Thin a raw cloud on a voxel grid of width beta (rh_voxel_downsample, include/ransac_hip.h has the definition in
