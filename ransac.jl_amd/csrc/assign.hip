@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "assign_device.h"
+#include "call_scope.h"
 #include "rh_internal.h"
 
 namespace {
@@ -257,7 +258,6 @@ __global__ void __launch_bounds__(ASG_BLOCK) asg_scatter_kernel(const asg_job J)
 
 enum { SRC_AOS64 = 0, SRC_AOS32 = 1, SRC_PLANES64 = 2, SRC_PLANES32 = 3 };
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline int64_t runs_of(int64_t n) { return (n + ASG_RUN - 1) / ASG_RUN; }
 
 // where the workspace's parts lie (prep, mat, tot, off) and how large it is
@@ -332,29 +332,6 @@ void fill_thresholds(asg_job &J, const rh_params *p)
     for (int k = 0; k < 4; k++) { J.eps[k] = p->eps[k]; J.cosa[k] = p->cos_alpha[k]; }
 }
 
-// device buffers and the stream of one raw-array call, released on every way out
-struct Scratch {
-    std::vector<void *> ptrs;
-    hipStream_t st = nullptr;
-    ~Scratch()
-    {
-        for (void *q : ptrs) (void)hipFree(q);
-        if (st) (void)hipStreamDestroy(st);
-    }
-    int alloc(const char *who, void **q, size_t bytes)
-    {
-        *q = nullptr;
-        const hipError_t e = hipMalloc(q, bytes > 0 ? bytes : 16);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            rh_set_error("%s: hipMalloc(%zu bytes) failed: %s", who, bytes, hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? RH_E_NOMEM : RH_E_NODEVICE;
-        }
-        ptrs.push_back(*q);
-        return RH_OK;
-    }
-};
-
 // b == 0 or n == 0 on host arrays: nothing to compute
 void trivial_result(int64_t n, int32_t b, int32_t *labels, double *dist, int64_t *counts, int64_t *offsets, int64_t *idx)
 {
@@ -371,54 +348,49 @@ int assign_raw(const char *who, const T *xyz, const T *nrm, int64_t n, const rh_
 {
     RH_TRY(asg_check(who, xyz != nullptr, n, shapes, shapes != nullptr, b, p, flags, RH_ASSIGN_NO_NORMALS, labels, offsets, idx));
     if (n == 0 || b == 0) { trivial_result(n, b, labels, dist, counts, offsets, idx); return RH_OK; }
-    int ndev = 0;
-    RH_TRY(rh_device_count(&ndev));
-    if (ndev <= 0) { rh_set_error("no HIP device is visible; libransac_hip has no CPU fallback"); return RH_E_NODEVICE; }
-    if (device < 0 || device >= ndev) { rh_set_error("device %d out of range (%d visible)", device, ndev); return RH_E_INVALID; }
-    RH_HIP(hipSetDevice(device));
-    Scratch S;
-    RH_HIP(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
+    CallScope S;
+    RH_TRY(S.open(who, device));
     const bool use_nrm = nrm != nullptr && !(flags & RH_ASSIGN_NO_NORMALS);
     const bool tally = counts != nullptr || idx != nullptr;
     asg_job J;
     memset(&J, 0, sizeof J);
     J.n = n; J.b = b; J.nruns = runs_of(n);
     fill_thresholds(J, p);
-    const size_t pts = sizeof(T) * 3 * (size_t)n;
-    void *d_xyz = nullptr, *d_nrm = nullptr, *d_shapes = nullptr, *d_ws = nullptr;
-    RH_TRY(S.alloc(who, &d_xyz, pts));
-    RH_HIP(hipMemcpyAsync(d_xyz, xyz, pts, hipMemcpyHostToDevice, S.st));
+    T *d_xyz = nullptr, *d_nrm = nullptr;
+    RH_TRY(S.alloc(&d_xyz, 3 * n));
+    SCOPE_HIP(S, hipMemcpyAsync(d_xyz, xyz, sizeof(T) * 3 * (size_t)n, hipMemcpyHostToDevice, S.st));
     if (use_nrm) {
-        RH_TRY(S.alloc(who, &d_nrm, pts));
-        RH_HIP(hipMemcpyAsync(d_nrm, nrm, pts, hipMemcpyHostToDevice, S.st));
+        RH_TRY(S.alloc(&d_nrm, 3 * n));
+        SCOPE_HIP(S, hipMemcpyAsync(d_nrm, nrm, sizeof(T) * 3 * (size_t)n, hipMemcpyHostToDevice, S.st));
     }
     J.xyz = d_xyz; J.nrm = d_nrm;
     const asg_ws_layout W = ws_layout(n, b, tally);
-    RH_TRY(S.alloc(who, &d_ws, W.bytes));
+    char *d_ws = nullptr;
+    RH_TRY(S.alloc(&d_ws, (int64_t)W.bytes));
     ws_bind(J, d_ws, W);
     std::vector<rh_prep> prep((size_t)b);
     for (int32_t j = 0; j < b; j++) rh_prep_host(shapes[j], &prep[(size_t)j]);
-    RH_TRY(S.alloc(who, &d_shapes, sizeof(rh_shape) * (size_t)b));
-    RH_HIP(hipMemcpyAsync(d_shapes, shapes, sizeof(rh_shape) * (size_t)b, hipMemcpyHostToDevice, S.st));
-    RH_HIP(hipMemcpyAsync((void *)J.prep, prep.data(), sizeof(rh_prep) * (size_t)b, hipMemcpyHostToDevice, S.st));
-    J.shapes = (const rh_shape *)d_shapes;
-    void *q = nullptr;
-    RH_TRY(S.alloc(who, &q, sizeof(int32_t) * (size_t)n)); J.labels = (int32_t *)q;
-    if (dist) { RH_TRY(S.alloc(who, &q, sizeof(double) * (size_t)n)); J.dist = (double *)q; }
-    if (counts) { RH_TRY(S.alloc(who, &q, sizeof(int64_t) * (size_t)(b + 1))); J.counts = (int64_t *)q; }
+    rh_shape *d_shapes = nullptr;
+    RH_TRY(S.alloc(&d_shapes, b));
+    SCOPE_HIP(S, hipMemcpyAsync(d_shapes, shapes, sizeof(rh_shape) * (size_t)b, hipMemcpyHostToDevice, S.st));
+    SCOPE_HIP(S, hipMemcpyAsync((void *)J.prep, prep.data(), sizeof(rh_prep) * (size_t)b, hipMemcpyHostToDevice, S.st));
+    J.shapes = d_shapes;
+    RH_TRY(S.alloc(&J.labels, n));
+    if (dist) RH_TRY(S.alloc(&J.dist, n));
+    if (counts) RH_TRY(S.alloc(&J.counts, b + 1));
     if (idx) {
-        RH_TRY(S.alloc(who, &q, sizeof(int64_t) * (size_t)(b + 2))); J.offsets = (int64_t *)q;
-        RH_TRY(S.alloc(who, &q, sizeof(int64_t) * (size_t)n)); J.idx = (int64_t *)q;
+        RH_TRY(S.alloc(&J.offsets, b + 2));
+        RH_TRY(S.alloc(&J.idx, n));
     }
     RH_TRY(asg_enqueue(S.st, J, sizeof(T) == sizeof(double) ? SRC_AOS64 : SRC_AOS32));
-    RH_HIP(hipMemcpyAsync(labels, J.labels, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, S.st));
-    if (dist) RH_HIP(hipMemcpyAsync(dist, J.dist, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, S.st));
-    if (counts) RH_HIP(hipMemcpyAsync(counts, J.counts, sizeof(int64_t) * (size_t)(b + 1), hipMemcpyDeviceToHost, S.st));
+    SCOPE_HIP(S, hipMemcpyAsync(labels, J.labels, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, S.st));
+    if (dist) SCOPE_HIP(S, hipMemcpyAsync(dist, J.dist, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, S.st));
+    if (counts) SCOPE_HIP(S, hipMemcpyAsync(counts, J.counts, sizeof(int64_t) * (size_t)(b + 1), hipMemcpyDeviceToHost, S.st));
     if (idx) {
-        RH_HIP(hipMemcpyAsync(offsets, J.offsets, sizeof(int64_t) * (size_t)(b + 2), hipMemcpyDeviceToHost, S.st));
-        RH_HIP(hipMemcpyAsync(idx, J.idx, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, S.st));
+        SCOPE_HIP(S, hipMemcpyAsync(offsets, J.offsets, sizeof(int64_t) * (size_t)(b + 2), hipMemcpyDeviceToHost, S.st));
+        SCOPE_HIP(S, hipMemcpyAsync(idx, J.idx, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, S.st));
     }
-    RH_HIP(hipStreamSynchronize(S.st));
+    SCOPE_HIP(S, hipStreamSynchronize(S.st));
     return RH_OK;
 }
 

@@ -1,0 +1,95 @@
+// call_scope.h -- what an entry point on raw host arrays (rh_voxel_downsample, rh_knn, rh_remove_outliers,
+// rh_estimate_normals, rh_assign_points, rh_largestconncomp) owns for the length of the call: the device, a stream of its
+// own and its device buffers, released on every way out.  Host code only.  The cloud-bound paths do not come here: a
+// cloud has its stream and its grown buffers (rh_grow_buffer, RH_HIP).
+// Everything lives in an anonymous namespace: each translation unit that includes the header gets its own widen kernel.
+#pragma once
+
+#include <vector>
+
+#include "rh_internal.h"
+
+namespace {
+
+inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+template <typename T>
+__global__ void scope_widen_kernel(const T *__restrict__ in, double *__restrict__ out, int64_t cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cnt) out[i] = (double)in[i];
+}
+
+// a HIP call of scope S_ that must succeed
+#define SCOPE_HIP(S_, x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { rh_set_error("%s: %s", (S_).who, hipGetErrorString(e_)); return RH_E_NODEVICE; } } while (0)
+
+struct CallScope {
+    const char *who = "";    // the entry point, for error texts
+    hipStream_t st = nullptr;
+    std::vector<void *> ptrs;
+    CallScope() = default;
+    CallScope(const CallScope &) = delete;
+    CallScope &operator=(const CallScope &) = delete;
+    // the buffers first (hipFree waits for the device: copies still in flight at an early return end there), then the stream
+    ~CallScope()
+    {
+        for (void *p : ptrs) (void)hipFree(p);
+        if (st) (void)hipStreamDestroy(st);
+    }
+
+    // the usable device and a non-blocking stream of the call's own
+    int open(const char *who_, int device)
+    {
+        who = who_;
+        int ndev = 0;
+        RH_TRY(rh_device_count(&ndev));
+        if (ndev <= 0) { rh_set_error("no HIP device is visible; libransac_hip has no CPU fallback"); return RH_E_NODEVICE; }
+        if (device < 0 || device >= ndev) { rh_set_error("device %d out of range (%d visible)", device, ndev); return RH_E_INVALID; }
+        SCOPE_HIP(*this, hipSetDevice(device));
+        SCOPE_HIP(*this, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        return RH_OK;
+    }
+
+    template <typename T>
+    int alloc(T **p, int64_t count)
+    {
+        *p = nullptr;
+        const size_t bytes = sizeof(T) * (size_t)(count > 0 ? count : 1);
+        const hipError_t e = hipMalloc((void **)p, bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            rh_set_error("%s: hipMalloc(%zu bytes) failed: %s", who, bytes, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? RH_E_NOMEM : RH_E_NODEVICE;
+        }
+        ptrs.push_back(*p);
+        return RH_OK;
+    }
+
+    // before the call ends (null and foreign pointers are ignored)
+    void release(void *p)
+    {
+        for (auto &q : ptrs)
+            if (q == p) { (void)hipFree(q); q = nullptr; }
+    }
+
+    // cnt values of T from the caller's array into doubles on the device, widened exactly
+    template <typename T>
+    int upload(const T *src, double *dst, int64_t cnt, hipMemcpyKind kind)
+    {
+        if (sizeof(T) == sizeof(double)) {
+            SCOPE_HIP(*this, hipMemcpyAsync(dst, src, sizeof(double) * (size_t)cnt, kind, st));
+            return RH_OK;
+        }
+        T *d_in = nullptr;
+        RH_TRY(alloc(&d_in, cnt));
+        SCOPE_HIP(*this, hipMemcpyAsync(d_in, src, sizeof(T) * (size_t)cnt, kind, st));
+        hipLaunchKernelGGL(scope_widen_kernel<T>, dim3(blocks_for(cnt)), dim3(256), 0, st, d_in, dst, cnt);
+        SCOPE_HIP(*this, hipGetLastError());
+        SCOPE_HIP(*this, hipStreamSynchronize(st));
+        release(d_in);
+        return RH_OK;
+    }
+};
+
+}  // namespace

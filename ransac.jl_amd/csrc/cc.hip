@@ -1,7 +1,7 @@
 // cc.hip -- parameter-space bitmap + largest connected component
 // (src/parameterspacebitmap.jl:12-60, 69-109; dead code in the reference, pinned by
 // test/parameterspacebitmap.jl).  The labelling replaces Images.label_components with a
-// lock-free union-find on the pixel grid: every set pixel is united with its forward
+// lock-free union-find (union_find.h) on the pixel grid: every set pixel is united with its forward
 // neighbours, the root of a component is its smallest column-major linear index (= the pixel
 // label_components meets first, so "first largest component" ties break the same way).
 #include <math.h>
@@ -9,34 +9,11 @@
 
 #include <vector>
 
+#include "call_scope.h"
 #include "rh_internal.h"
+#include "union_find.h"
 
 namespace {
-
-__device__ __forceinline__ int32_t ld(const int32_t *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ int32_t uf_find(const int32_t *L, int32_t i)
-{
-    int32_t p = ld(&L[i]);
-    while (p != i) { i = p; p = ld(&L[i]); }
-    return i;
-}
-
-__device__ void uf_unite(int32_t *L, int32_t a, int32_t b)
-{
-    for (;;) {
-        a = uf_find(L, a);
-        b = uf_find(L, b);
-        if (a == b) return;
-        if (a > b) { const int32_t t = a; a = b; b = t; }
-        const int32_t old = atomicMin(&L[b], a);   // hang the larger root under the smaller
-        if (old == b) return;
-        b = old;                                    // somebody re-parented b meanwhile: retry from there
-    }
-}
 
 __global__ void cc_init_kernel(const uint8_t *__restrict__ bm, int32_t npx, int32_t *__restrict__ L,
                                int32_t *__restrict__ size)
@@ -66,7 +43,7 @@ __global__ void cc_flatten_kernel(int32_t npx, int32_t *L, int32_t *__restrict__
     if (i >= npx) return;
     if (ld(&L[i]) < 0) return;
     const int32_t r = uf_find(L, i);
-    L[i] = r;                        // safe: r is a root, roots never change in this launch
+    atomicMin(&L[i], r);             // (r is a root, roots never change in this launch, and no ancestor is smaller)
     atomicAdd(&size[r], 1);
 }
 
@@ -105,11 +82,8 @@ extern "C" int rh_largestconncomp(const uint8_t *bitmap, int32_t xs, int32_t ys,
     const int64_t npx64 = (int64_t)xs * ys;
     if (npx64 == 0) return RH_OK;
     if (npx64 > 0x7FFFFFF0) { rh_set_error("rh_largestconncomp: bitmap too large"); return RH_E_INVALID; }
-    int ndev = 0;
-    RH_TRY(rh_device_count(&ndev));
-    if (ndev <= 0) { rh_set_error("no HIP device is visible; libransac_hip has no CPU fallback"); return RH_E_NODEVICE; }
-    if (device < 0 || device >= ndev) { rh_set_error("device %d out of range", device); return RH_E_INVALID; }
-    RH_HIP(hipSetDevice(device));
+    CallScope S;
+    RH_TRY(S.open("rh_largestconncomp", device));
     const int32_t npx = (int32_t)npx64;
     const int64_t nwords = (npx64 + 63) / 64;
     const int64_t nb = (nwords + RH_WORDS_PER_BLOCK - 1) / RH_WORDS_PER_BLOCK;
@@ -118,54 +92,42 @@ extern "C" int rh_largestconncomp(const uint8_t *bitmap, int32_t xs, int32_t ys,
     unsigned long long *d_best = nullptr;
     uint64_t *d_mask = nullptr;
     int64_t *d_idx = nullptr;
-    hipStream_t stream = nullptr;
-    int rc = RH_OK;
-    auto cleanup = [&]() {
-        (void)hipFree(d_bm); (void)hipFree(d_L); (void)hipFree(d_size); (void)hipFree(d_bs); (void)hipFree(d_total);
-        (void)hipFree(d_best); (void)hipFree(d_mask); (void)hipFree(d_idx);
-        if (stream) (void)hipStreamDestroy(stream);
-    };
-#define CKH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rh_set_error("%s: %s", #x, hipGetErrorString(e_)); cleanup(); return RH_E_NODEVICE; } } while (0)
-    CKH(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    CKH(hipMalloc((void **)&d_bm, (size_t)npx));
-    CKH(hipMalloc((void **)&d_L, sizeof(int32_t) * (size_t)npx));
-    CKH(hipMalloc((void **)&d_size, sizeof(int32_t) * (size_t)npx));
-    CKH(hipMalloc((void **)&d_bs, sizeof(int32_t) * (size_t)(nb + 2)));
-    CKH(hipMalloc((void **)&d_total, sizeof(int32_t)));
-    CKH(hipMalloc((void **)&d_best, sizeof(unsigned long long)));
-    CKH(hipMalloc((void **)&d_mask, sizeof(uint64_t) * (size_t)nwords));
-    CKH(hipMalloc((void **)&d_idx, sizeof(int64_t) * (size_t)npx));
-    CKH(hipMemcpyAsync(d_bm, bitmap, (size_t)npx, hipMemcpyHostToDevice, stream));
-    CKH(hipMemsetAsync(d_best, 0, sizeof(unsigned long long), stream));
+    // (this entry has always answered a failed allocation, out of memory included, with RH_E_NODEVICE)
+    auto alloc = [&S](auto **p, int64_t count) { return S.alloc(p, count) == RH_OK ? RH_OK : RH_E_NODEVICE; };
+    RH_TRY(alloc(&d_bm, npx));
+    RH_TRY(alloc(&d_L, npx));
+    RH_TRY(alloc(&d_size, npx));
+    RH_TRY(alloc(&d_bs, nb + 2));
+    RH_TRY(alloc(&d_total, 1));
+    RH_TRY(alloc(&d_best, 1));
+    RH_TRY(alloc(&d_mask, nwords));
+    RH_TRY(alloc(&d_idx, npx));
+    SCOPE_HIP(S, hipMemcpyAsync(d_bm, bitmap, (size_t)npx, hipMemcpyHostToDevice, S.st));
+    SCOPE_HIP(S, hipMemsetAsync(d_best, 0, sizeof(unsigned long long), S.st));
     {
-        const dim3 grid((unsigned)((npx + 255) / 256)), blk(256);
-        hipLaunchKernelGGL(cc_init_kernel, grid, blk, 0, stream, d_bm, npx, d_L, d_size);
-        hipLaunchKernelGGL(cc_union_kernel, grid, blk, 0, stream, d_bm, xs, ys, conn8 ? 1 : 0, d_L);
-        hipLaunchKernelGGL(cc_flatten_kernel, grid, blk, 0, stream, npx, d_L, d_size);
-        hipLaunchKernelGGL(cc_best_kernel, grid, blk, 0, stream, npx, d_size, d_best);
-        const dim3 gridm((unsigned)((nwords * 64 + 255) / 256));
-        hipLaunchKernelGGL(cc_mask_kernel, gridm, blk, 0, stream, npx, d_L, d_best, d_mask);
-        CKH(hipGetLastError());
+        const dim3 grid(blocks_for(npx)), blk(256);
+        hipLaunchKernelGGL(cc_init_kernel, grid, blk, 0, S.st, d_bm, npx, d_L, d_size);
+        hipLaunchKernelGGL(cc_union_kernel, grid, blk, 0, S.st, d_bm, xs, ys, conn8 ? 1 : 0, d_L);
+        hipLaunchKernelGGL(cc_flatten_kernel, grid, blk, 0, S.st, npx, d_L, d_size);
+        hipLaunchKernelGGL(cc_best_kernel, grid, blk, 0, S.st, npx, d_size, d_best);
+        hipLaunchKernelGGL(cc_mask_kernel, dim3(blocks_for(nwords * 64)), blk, 0, S.st, npx, d_L, d_best, d_mask);
+        SCOPE_HIP(S, hipGetLastError());
     }
-    rc = rhk_compact_generic(stream, d_mask, nwords, d_bs, d_idx, npx, d_total);
-    if (rc != RH_OK) { cleanup(); return rc; }
+    RH_TRY(rhk_compact_generic(S.st, d_mask, nwords, d_bs, d_idx, npx, d_total));
     int32_t total = 0;
-    CKH(hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, stream));
-    CKH(hipStreamSynchronize(stream));
+    SCOPE_HIP(S, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, S.st));
+    SCOPE_HIP(S, hipStreamSynchronize(S.st));
     *n_out = total;
     if (total > cap) {
         rh_set_error("rh_largestconncomp: component has %d pixels, capacity %lld", total, (long long)cap);
-        cleanup();
         return RH_E_CAPACITY;
     }
     if (total > 0) {
         std::vector<int64_t> tmp((size_t)total);
-        CKH(hipMemcpyAsync(tmp.data(), d_idx, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, stream));
-        CKH(hipStreamSynchronize(stream));
+        SCOPE_HIP(S, hipMemcpyAsync(tmp.data(), d_idx, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, S.st));
+        SCOPE_HIP(S, hipStreamSynchronize(S.st));
         for (int32_t i = 0; i < total; i++) out[i] = tmp[(size_t)i] - 1;   // compaction is 1-based
     }
-#undef CKH
-    cleanup();
     return RH_OK;
 }
 

@@ -3,76 +3,45 @@
 // kinds, no seam, no pole, no atan2 (include/ransac_hip.h states it in full).  Input and output are the cloud's
 // refit_mask (original order): rhk_component_filter clears the bits of every inlier outside the winning component.
 //   1. minimum:    o = componentwise minimum of the inliers (+ maximum for the extent check, + |I|) -- one read-back
-//   2. cell table: open addressing, 2 |I| slots or more; per slot the cell key, a parent (union-find), the cell's point
-//                  count and its smallest point index
+//   2. cell table: open addressing (cell_grid.h), 2 |I| slots or more; per slot the cell key, a parent (union-find), the
+//                  cell's point count and its smallest point index
 //   3. union:      every occupied slot looks up its forward neighbours (13, or 3 without diagonals) and unites lock-free
-//                  (cc.hip's idiom, with path halving); flatten; counts and minimum indices summed into the roots
+//                  (union_find.h); flatten; counts and minimum indices summed into the roots
 //   4. winner:     one 64-bit maximum over size << 32 | ~min_index
 //   5. mask:       an inlier keeps its bit when its cell's root is the winner
 // Slot numbers depend on who inserted first; nothing that leaves this file does: components are sets of cells, a
 // component is named by its smallest point index, and sizes / minima are sums / minima of integers.
 #include <math.h>
 
+#include "call_scope.h"
+#include "cell_grid.h"
 #include "rh_internal.h"
+#include "union_find.h"
 
 namespace {
 
-constexpr uint64_t CK_EMPTY = ~0ULL;
 // scalars of a call (rh_cloud::comp_scal, 8-byte words)
-enum { CS_MIN = 0, CS_MAX = 3, CS_COUNT = 6, CS_BEST = 7, CS_NCOMP = 8, CS_WORDS = 16 };
-constexpr int MM_BLOCKS = 4096;   // blocks of the minimum pass at most; each leaves 8 words of partial results behind the scalars
+enum { CS_MIN = MM_MIN, CS_MAX = MM_MAX, CS_COUNT = MM_COUNT, CS_BEST = 7, CS_NCOMP = 8, CS_WORDS = 16 };   // (the partial results of the minimum pass lie behind them)
 
 struct comp_table {
-    uint64_t *key;       // [cap] cell key, CK_EMPTY: free
+    uint64_t *key;       // [cap] cell key, GRID_EMPTY: free
     int32_t *parent;     // [cap] union-find over slots: parent <= self, a root points at itself
     int32_t *count;      // [cap] points in the cell; after the flatten pass a root holds its component's
     int32_t *minidx;     // [cap] smallest 0-based point index, likewise
     uint32_t mask;       // cap - 1 (cap is a power of two)
 };
 
-// doubles as unsigned integers in the same order (finite values; -0.0 sorts below +0.0, which the cell formula cannot tell apart)
-__host__ __device__ inline uint64_t ord_of(double x)
-{
-    uint64_t u;
-    __builtin_memcpy(&u, &x, 8);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
-}
-__host__ __device__ inline double ord_back(uint64_t u)
-{
-    u = (u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFULL) : ~u;
-    double x;
-    __builtin_memcpy(&x, &u, 8);
-    return x;
-}
-
-__device__ __forceinline__ uint32_t slot_hash(uint64_t k)
-{
-    k ^= k >> 33; k *= 0xFF51AFD7ED558CCDULL; k ^= k >> 33; k *= 0xC4CEB9FE1A85EC53ULL; k ^= k >> 33;
-    return (uint32_t)k;
-}
-
 // the cell of a point: floor((x - o) / beta) per axis (binary64 division, no contraction), each + 1 in a 21-bit field,
 // so that the -1 / +1 neighbours of cells 0 .. 2^20 - 1 stay inside their fields
 __device__ __forceinline__ uint64_t cell_key(double x, double y, double z, double ox, double oy, double oz, double beta)
 {
     const long long cx = (long long)floor((x - ox) / beta), cy = (long long)floor((y - oy) / beta), cz = (long long)floor((z - oz) / beta);
-    return ((uint64_t)(cx + 1) << 42) | ((uint64_t)(cy + 1) << 21) | (uint64_t)(cz + 1);
-}
-
-__device__ __forceinline__ int32_t table_find(const comp_table &T, uint64_t key)
-{
-    uint32_t h = slot_hash(key) & T.mask;
-    for (;;) {   // (the table is at most half full: an empty slot ends every probe sequence)
-        const uint64_t k = T.key[h];
-        if (k == key) return (int32_t)h;
-        if (k == CK_EMPTY) return -1;
-        h = (h + 1) & T.mask;
-    }
+    return grid_pack(cx, cy, cz, 1);
 }
 
 // ---- 1. minimum, maximum and number of the inliers.  A wave owns whole mask words (lane = bit), so the three planes
-// are read 64 points in a row.  Every block (256 threads: the LDS reduction below counts on it) leaves its partial result in
-// `part`, a one-block pass folds them: 4096 blocks x 7 atomics on one cache line took 0.34 ms, ten times the rest of the pass
+// are read 64 points in a row.  Every block (256 threads) leaves its partial result in `part`; the fold of cell_grid.h
+// also zeroes the winner and the component count of the call
 template <typename T>
 __global__ void __launch_bounds__(256)
 comp_minmax_kernel(const T *__restrict__ pts, int64_t stride, int64_t nwords, const uint64_t *__restrict__ mask,
@@ -80,87 +49,14 @@ comp_minmax_kernel(const T *__restrict__ pts, int64_t stride, int64_t nwords, co
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    long long cnt = 0;
+    MinMaxCount acc;
     for (int64_t w = wave; w < nwords; w += nwaves) {
         const uint64_t m = mask[w];
-        if (m == 0) continue;
-        if (lane == 0) cnt += __popcll(m);
         if (!((m >> lane) & 1ULL)) continue;
         const int64_t i = (w << 6) + lane;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const double v = (double)pts[a * stride + i];
-            lo[a] = v < lo[a] ? v : lo[a];
-            hi[a] = v > hi[a] ? v : hi[a];
-        }
+        acc.add((double)pts[i], (double)pts[stride + i], (double)pts[2 * stride + i]);
     }
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-        for (int off = 32; off > 0; off >>= 1) {
-            const double l = __shfl_down(lo[a], off), h = __shfl_down(hi[a], off);
-            lo[a] = l < lo[a] ? l : lo[a];
-            hi[a] = h > hi[a] ? h : hi[a];
-        }
-    // the block's four waves meet in LDS: one partial result per block
-    __shared__ double s_lo[4][3], s_hi[4][3];
-    __shared__ long long s_cnt[4];
-    if (lane == 0) {
-        const int wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int a = 0; a < 3; a++) { s_lo[wv][a] = lo[a]; s_hi[wv][a] = hi[a]; }
-        s_cnt[wv] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int wv = 1; wv < 4; wv++) {
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                lo[a] = s_lo[wv][a] < lo[a] ? s_lo[wv][a] : lo[a];
-                hi[a] = s_hi[wv][a] > hi[a] ? s_hi[wv][a] : hi[a];
-            }
-            cnt += s_cnt[wv];
-        }
-        unsigned long long *o = part + 8 * (size_t)blockIdx.x;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            o[CS_MIN + a] = cnt > 0 ? (unsigned long long)ord_of(lo[a]) : ~0ULL;
-            o[CS_MAX + a] = cnt > 0 ? (unsigned long long)ord_of(hi[a]) : 0ULL;
-        }
-        o[CS_COUNT] = (unsigned long long)cnt;
-    }
-}
-
-// ... folded by one block, which also zeroes the winner and the component count of the call
-__global__ void __launch_bounds__(256) comp_minmax_fold_kernel(const unsigned long long *__restrict__ part, int nparts, unsigned long long *__restrict__ scal)
-{
-    __shared__ unsigned long long sh[256][7];
-    unsigned long long v[7] = { ~0ULL, ~0ULL, ~0ULL, 0ULL, 0ULL, 0ULL, 0ULL };
-    for (int b = threadIdx.x; b < nparts; b += 256) {
-        const unsigned long long *o = part + 8 * (size_t)b;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            v[CS_MIN + a] = o[CS_MIN + a] < v[CS_MIN + a] ? o[CS_MIN + a] : v[CS_MIN + a];
-            v[CS_MAX + a] = o[CS_MAX + a] > v[CS_MAX + a] ? o[CS_MAX + a] : v[CS_MAX + a];
-        }
-        v[CS_COUNT] += o[CS_COUNT];
-    }
-#pragma unroll
-    for (int k = 0; k < 7; k++) sh[threadIdx.x][k] = v[k];
-    __syncthreads();
-    for (int step = 128; step > 0; step >>= 1) {
-        if ((int)threadIdx.x < step) {
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                const unsigned long long l = sh[threadIdx.x + step][CS_MIN + a], h = sh[threadIdx.x + step][CS_MAX + a];
-                if (l < sh[threadIdx.x][CS_MIN + a]) sh[threadIdx.x][CS_MIN + a] = l;
-                if (h > sh[threadIdx.x][CS_MAX + a]) sh[threadIdx.x][CS_MAX + a] = h;
-            }
-            sh[threadIdx.x][CS_COUNT] += sh[threadIdx.x + step][CS_COUNT];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < CS_WORDS) scal[threadIdx.x] = threadIdx.x < 7 ? sh[0][threadIdx.x] : 0ULL;
+    acc.store(part);
 }
 
 // ---- 2. the cell table
@@ -168,7 +64,7 @@ __global__ void __launch_bounds__(256) comp_init_kernel(comp_table T)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s > T.mask) return;
-    T.key[s] = CK_EMPTY;
+    T.key[s] = GRID_EMPTY;
     T.parent[s] = (int32_t)s;
     T.count[s] = 0;
     T.minidx[s] = 0x7FFFFFFF;
@@ -185,62 +81,30 @@ comp_insert_kernel(const T *__restrict__ pts, int64_t stride, int64_t nwords, co
     if (!((mask[w] >> (g & 63)) & 1ULL)) return;
     const uint64_t key = cell_key((double)pts[g], (double)pts[stride + g], (double)pts[2 * stride + g], ord_back(scal[CS_MIN]),
                                   ord_back(scal[CS_MIN + 1]), ord_back(scal[CS_MIN + 2]), beta);
-    uint32_t h = slot_hash(key) & tab.mask;
-    for (;;) {
-        const unsigned long long old = atomicCAS((unsigned long long *)&tab.key[h], (unsigned long long)CK_EMPTY, (unsigned long long)key);
-        if (old == CK_EMPTY || old == key) break;
-        h = (h + 1) & tab.mask;
-    }
+    const uint32_t h = table_insert(tab.key, tab.mask, key);
     atomicAdd(&tab.count[h], 1);
     atomicMin(&tab.minidx[h], (int32_t)g);
 }
 
-// ---- 3. union-find over the slots (parents only ever go down, so a link to any ancestor is a valid link)
-__device__ __forceinline__ int32_t ld(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ int32_t uf_find(int32_t *L, int32_t i)
-{
-    int32_t p = ld(&L[i]);
-    while (p != i) {
-        const int32_t gp = ld(&L[p]);
-        if (gp != p) atomicMin(&L[i], gp);   // path halving: i is no root and never becomes one again
-        i = p;
-        p = gp;
-    }
-    return i;
-}
-
-__device__ void uf_unite(int32_t *L, int32_t a, int32_t b)
-{
-    for (;;) {
-        a = uf_find(L, a);
-        b = uf_find(L, b);
-        if (a == b) return;
-        if (a > b) { const int32_t t = a; a = b; b = t; }
-        const int32_t old = atomicMin(&L[b], a);   // hang the larger root under the smaller
-        if (old == b) return;
-        b = old;                                    // somebody re-parented b meanwhile: retry from there
-    }
-}
-
+// ---- 3. union-find over the slots (union_find.h)
 __global__ void __launch_bounds__(256) comp_union_kernel(comp_table T, int conn26)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s > T.mask) return;
     const uint64_t key = T.key[s];
-    if (key == CK_EMPTY) return;
+    if (key == GRID_EMPTY) return;
     if (conn26) {
         // the 13 neighbours that follow the cell in (x, y, z) order; the other 13 unite from their side
         for (int dx = 0; dx <= 1; dx++)
             for (int dy = -1; dy <= 1; dy++)
                 for (int dz = -1; dz <= 1; dz++) {
                     if (!(dx > 0 || dy > 0 || (dy == 0 && dz > 0))) continue;
-                    const int32_t t = table_find(T, key + (uint64_t)(((long long)dx << 42) + ((long long)dy << 21) + dz));
+                    const int32_t t = (int32_t)table_find(T.key, T.mask, key + (uint64_t)(((long long)dx << 42) + ((long long)dy << 21) + dz));
                     if (t >= 0) uf_unite(T.parent, (int32_t)s, t);
                 }
     } else {
         for (int a = 0; a < 3; a++) {
-            const int32_t t = table_find(T, key + (1ULL << (21 * a)));
+            const int32_t t = (int32_t)table_find(T.key, T.mask, key + (1ULL << (21 * a)));
             if (t >= 0) uf_unite(T.parent, (int32_t)s, t);
         }
     }
@@ -253,7 +117,7 @@ __global__ void __launch_bounds__(256) comp_flatten_kernel(comp_table T)
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     int32_t r = -1, cnt = 0, mi = 0x7FFFFFFF;
-    if (s <= T.mask && T.key[s] != CK_EMPTY) {
+    if (s <= T.mask && T.key[s] != GRID_EMPTY) {
         const int32_t root = uf_find(T.parent, (int32_t)s);
         if (root != (int32_t)s) {
             atomicMin(&T.parent[s], root);   // (root is a root, roots never change in this launch, and no ancestor is smaller)
@@ -287,7 +151,7 @@ __global__ void __launch_bounds__(256) comp_flatten_kernel(comp_table T)
 __global__ void __launch_bounds__(256) comp_best_kernel(comp_table T, unsigned long long *__restrict__ scal)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool root = s <= T.mask && T.key[s] != CK_EMPTY && T.parent[s] == (int32_t)s;
+    const bool root = s <= T.mask && T.key[s] != GRID_EMPTY && T.parent[s] == (int32_t)s;
     const uint64_t roots = __builtin_amdgcn_ballot_w64(root);
     if (roots == 0) return;
     if ((threadIdx.x & 63) == 0) atomicAdd(&scal[CS_NCOMP], (unsigned long long)__popcll(roots));
@@ -309,15 +173,13 @@ comp_mask_kernel(const T *__restrict__ pts, int64_t stride, int64_t nwords, uint
     if ((m >> (g & 63)) & 1ULL) {
         const uint64_t key = cell_key((double)pts[g], (double)pts[stride + g], (double)pts[2 * stride + g], ord_back(scal[CS_MIN]),
                                       ord_back(scal[CS_MIN + 1]), ord_back(scal[CS_MIN + 2]), beta);
-        const int32_t s = table_find(tab, key);
+        const int32_t s = (int32_t)table_find(tab.key, tab.mask, key);
         const int32_t win_min = (int32_t)(0xFFFFFFFFu - (uint32_t)(scal[CS_BEST] & 0xFFFFFFFFu));
         keep = s >= 0 && tab.minidx[tab.parent[s]] == win_min;
     }
     const uint64_t b = __builtin_amdgcn_ballot_w64(keep);
     if ((g & 63) == 0) mask[w] = b;
 }
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
@@ -336,7 +198,7 @@ int rhk_component_filter(rh_cloud *c, double beta, int conn26, int64_t *n_refit_
     RH_TRY(rh_component_check_beta("component filter", beta));
     if (c->n >= ((int64_t)1 << 31)) { rh_set_error("component filter: clouds of 2^31 points or more are not supported"); return RH_E_INVALID; }
     if (!c->comp_scal) {
-        RH_HIP(hipMalloc((void **)&c->comp_scal, sizeof(uint64_t) * (CS_WORDS + 8 * MM_BLOCKS)));
+        RH_HIP(hipMalloc((void **)&c->comp_scal, sizeof(uint64_t) * (CS_WORDS + MM_WORDS * GRID_MM_BLOCKS)));
         RH_HIP(hipHostMalloc((void **)&c->comp_h, sizeof(uint64_t) * CS_WORDS, hipHostMallocDefault));
     }
     unsigned long long *scal = (unsigned long long *)c->comp_scal;
@@ -344,11 +206,11 @@ int rhk_component_filter(rh_cloud *c, double beta, int conn26, int64_t *n_refit_
     const int64_t stride = c->n_pad;
     {
         int64_t b = (c->nwords + 3) / 4;
-        if (b > MM_BLOCKS) b = MM_BLOCKS;
+        if (b > GRID_MM_BLOCKS) b = GRID_MM_BLOCKS;
         unsigned long long *part = scal + CS_WORDS;
         if (c->f32) hipLaunchKernelGGL((comp_minmax_kernel<float>), dim3((unsigned)b), dim3(256), 0, c->stream, c->full32, stride, c->nwords, c->refit_mask, part);
         else hipLaunchKernelGGL((comp_minmax_kernel<double>), dim3((unsigned)b), dim3(256), 0, c->stream, c->full, stride, c->nwords, c->refit_mask, part);
-        hipLaunchKernelGGL(comp_minmax_fold_kernel, dim3(1), dim3(256), 0, c->stream, part, (int)b, scal);
+        hipLaunchKernelGGL(grid_minmax_fold_kernel, dim3(1), dim3(256), 0, c->stream, part, (int)b, scal, (int)CS_WORDS);
     }
     RH_HIP(hipGetLastError());
     RH_HIP(hipMemcpyAsync(c->comp_h, scal, sizeof(uint64_t) * (CS_COUNT + 1), hipMemcpyDeviceToHost, c->stream));
@@ -357,8 +219,8 @@ int rhk_component_filter(rh_cloud *c, double beta, int conn26, int64_t *n_refit_
     if (n_refit_out) *n_refit_out = ni;
     if (ni == 0) return RH_OK;
     for (int a = 0; a < 3; a++) {
-        const double cells = floor((ord_back(c->comp_h[CS_MAX + a]) - ord_back(c->comp_h[CS_MIN + a])) / beta);
-        if (!(cells < 1048576.0)) {
+        double cells;
+        if (!grid_axis_fits(ord_back(c->comp_h[CS_MIN + a]), ord_back(c->comp_h[CS_MAX + a]), beta, &cells)) {
             rh_set_error("component filter: the inliers span more than 2^20 cells of size %g along axis %d", beta, a);
             return RH_E_INVALID;
         }

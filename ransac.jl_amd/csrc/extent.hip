@@ -21,6 +21,7 @@
 
 #include <vector>
 
+#include "call_scope.h"
 #include "jacobi3.h"
 #include "rh_internal.h"
 
@@ -407,8 +408,6 @@ int extents_enqueue(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const int6
 }
 
 struct ext_run { const int64_t *src; int64_t at, count; };   // a stretch of list entries that is contiguous on the host
-
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // the host entries: shapes + offsets through the pinned block, the lists straight from where they are, one wait
 int extents_host(rh_cloud *c, const char *who, const rh_shape *shapes, size_t shape_stride, int32_t b, const int64_t *offsets,

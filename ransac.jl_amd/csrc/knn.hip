@@ -10,7 +10,7 @@
 //      floating-point atomics;
 //   3. the flag pass and a stable compaction of the kept indices (hipcub's scan-based DeviceSelect);
 //   4. the lower median of the nearest-neighbour distances: a radix sort of the bit patterns of the non-negative doubles.
-// Scratch is allocated per call and freed on every way out (Buffers).
+// Scratch is allocated per call and freed on every way out (call_scope.h).
 #include "knn_device.h"
 
 namespace {
@@ -154,12 +154,12 @@ int check_common(const char *who, const void *xyz, int64_t n, int k, double radi
 
 // upload, bounding box, grid for lists of k + 1 entries
 template <typename T>
-int open_search(Buffers &B, hipStream_t st, const T *xyz_aos, int64_t n, int k, double radius, KnnIndex &ix, KnnQuery &kq)
+int open_search(CallScope &S, const T *xyz_aos, int64_t n, int k, double radius, KnnIndex &ix, KnnQuery &kq)
 {
     double *d_xyz = nullptr;
-    RH_TRY(B.alloc(&d_xyz, 3 * n));
-    RH_TRY(knn_upload(B, st, xyz_aos, d_xyz, 3 * n, hipMemcpyDefault));
-    RH_TRY(ix.init(B, st, d_xyz, n));
+    RH_TRY(S.alloc(&d_xyz, 3 * n));
+    RH_TRY(S.upload(xyz_aos, d_xyz, 3 * n, hipMemcpyDefault));   // (the caller's array may be on the device already)
+    RH_TRY(ix.init(S, d_xyz, n));
     return knn_index_for_k(ix, k + 1, radius, kq);
 }
 
@@ -168,41 +168,40 @@ int knn(const T *xyz_aos, int64_t n, int32_t k, double radius, int device, int32
 {
     static const char who[] = "rh_knn";
     RH_TRY(check_common(who, xyz_aos, n, k, radius));
-    StreamHolder sh;
-    RH_TRY(knn_open_device(who, device, sh));
-    const hipStream_t st = sh.s;
-    Buffers B(who);
+    CallScope S;
+    RH_TRY(S.open(who, device));
+    const hipStream_t st = S.st;
     KnnIndex ix;
     KnnQuery kq;
-    RH_TRY(open_search(B, st, xyz_aos, n, k, radius, ix, kq));
+    RH_TRY(open_search(S, xyz_aos, n, k, radius, ix, kq));
     KnnOut o;
     memset(&o, 0, sizeof o);
-    if (idx_out) RH_TRY(B.alloc(&o.idx, n * k));
-    if (d2_out) RH_TRY(B.alloc(&o.d2, n * k));
-    if (count_out) RH_TRY(B.alloc(&o.count, n));
-    hipLaunchKernelGGL(knn_query_kernel, dim3(nblk(n, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, st, ix.g, kq, o);
-    KNN_HIP(who, hipGetLastError());
-    if (idx_out) KNN_HIP(who, hipMemcpyAsync(idx_out, o.idx, sizeof(int32_t) * (size_t)n * k, hipMemcpyDefault, st));
-    if (d2_out) KNN_HIP(who, hipMemcpyAsync(d2_out, o.d2, sizeof(double) * (size_t)n * k, hipMemcpyDefault, st));
-    if (count_out) KNN_HIP(who, hipMemcpyAsync(count_out, o.count, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, st));
-    KNN_HIP(who, hipStreamSynchronize(st));
+    if (idx_out) RH_TRY(S.alloc(&o.idx, n * k));
+    if (d2_out) RH_TRY(S.alloc(&o.d2, n * k));
+    if (count_out) RH_TRY(S.alloc(&o.count, n));
+    hipLaunchKernelGGL(knn_query_kernel, dim3(blocks_for(n, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, st, ix.g, kq, o);
+    SCOPE_HIP(S, hipGetLastError());
+    if (idx_out) SCOPE_HIP(S, hipMemcpyAsync(idx_out, o.idx, sizeof(int32_t) * (size_t)n * k, hipMemcpyDefault, st));
+    if (d2_out) SCOPE_HIP(S, hipMemcpyAsync(d2_out, o.d2, sizeof(double) * (size_t)n * k, hipMemcpyDefault, st));
+    if (count_out) SCOPE_HIP(S, hipMemcpyAsync(count_out, o.count, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, st));
+    SCOPE_HIP(S, hipStreamSynchronize(st));
     return RH_OK;
 }
 
 // T() over the leaves of MODE (0 / 1) of the n points: level after level until one value is left; *root_out points at it
 template <int MODE>
-int tree_root(const char *who, hipStream_t st, const double *d_mean, const int32_t *d_count, int64_t n, OutScal *d_sc,
+int tree_root(CallScope &S, const double *d_mean, const int32_t *d_count, int64_t n, OutScal *d_sc,
               double *d_part[2], const double **root_out)
 {
     int64_t len = (n + OUT_BLOCK_POINTS - 1) / OUT_BLOCK_POINTS;
-    hipLaunchKernelGGL(out_tree_kernel<MODE>, dim3((unsigned)len), dim3(OUT_THREADS), 0, st, d_mean, d_count, n, d_sc, d_part[0]);
-    KNN_HIP(who, hipGetLastError());
+    hipLaunchKernelGGL(out_tree_kernel<MODE>, dim3((unsigned)len), dim3(OUT_THREADS), 0, S.st, d_mean, d_count, n, d_sc, d_part[0]);
+    SCOPE_HIP(S, hipGetLastError());
     int cur = 0;
     while (len > 1) {
         const int64_t nb = (len + OUT_BLOCK_POINTS - 1) / OUT_BLOCK_POINTS;
-        hipLaunchKernelGGL(out_tree_kernel<2>, dim3((unsigned)nb), dim3(OUT_THREADS), 0, st, d_part[cur], (const int32_t *)nullptr, len,
+        hipLaunchKernelGGL(out_tree_kernel<2>, dim3((unsigned)nb), dim3(OUT_THREADS), 0, S.st, d_part[cur], (const int32_t *)nullptr, len,
                            d_sc, d_part[cur ^ 1]);
-        KNN_HIP(who, hipGetLastError());
+        SCOPE_HIP(S, hipGetLastError());
         cur ^= 1;
         len = nb;
     }
@@ -225,66 +224,65 @@ int remove_outliers(const T *xyz_aos, int64_t n, const rh_outlier_params *p, int
     if (p->mode == RH_OUT_STATISTICAL && !isfinite(p->std_mul)) { rh_set_error("%s: std_mul is not finite", who); return RH_E_INVALID; }
     if (p->mode == RH_OUT_ABSOLUTE && p->threshold != p->threshold) { rh_set_error("%s: threshold is NaN", who); return RH_E_INVALID; }
     if (cap < 0 || (cap > 0 && !kept_idx_out)) { rh_set_error("%s: cap = %lld without a list to fill", who, (long long)cap); return RH_E_INVALID; }
-    StreamHolder sh;
-    RH_TRY(knn_open_device(who, device, sh));
-    const hipStream_t st = sh.s;
-    Buffers B(who);
+    CallScope S;
+    RH_TRY(S.open(who, device));
+    const hipStream_t st = S.st;
     KnnIndex ix;
     KnnQuery kq;
-    RH_TRY(open_search(B, st, xyz_aos, n, p->k, p->radius, ix, kq));
+    RH_TRY(open_search(S, xyz_aos, n, p->k, p->radius, ix, kq));
 
     // 1. m_i, count_i, sqrt(d2_i1)
     KnnOut o;
     memset(&o, 0, sizeof o);
-    RH_TRY(B.alloc(&o.mean, n));
-    RH_TRY(B.alloc(&o.nn1, n));
-    RH_TRY(B.alloc(&o.count, n));
-    hipLaunchKernelGGL(knn_query_kernel, dim3(nblk(n, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, st, ix.g, kq, o);
-    KNN_HIP(who, hipGetLastError());
+    RH_TRY(S.alloc(&o.mean, n));
+    RH_TRY(S.alloc(&o.nn1, n));
+    RH_TRY(S.alloc(&o.count, n));
+    hipLaunchKernelGGL(knn_query_kernel, dim3(blocks_for(n, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, st, ix.g, kq, o);
+    SCOPE_HIP(S, hipGetLastError());
 
     // 2. mu, then sigma and tau
     OutScal *d_sc = nullptr;
     double *d_part[2] = { nullptr, nullptr };
     const int64_t len1 = (n + OUT_BLOCK_POINTS - 1) / OUT_BLOCK_POINTS;
-    RH_TRY(B.alloc(&d_sc, 1));
-    RH_TRY(B.alloc(&d_part[0], len1));
-    RH_TRY(B.alloc(&d_part[1], (len1 + OUT_BLOCK_POINTS - 1) / OUT_BLOCK_POINTS));
-    KNN_HIP(who, hipMemsetAsync(d_sc, 0, sizeof(OutScal), st));
+    RH_TRY(S.alloc(&d_sc, 1));
+    RH_TRY(S.alloc(&d_part[0], len1));
+    RH_TRY(S.alloc(&d_part[1], (len1 + OUT_BLOCK_POINTS - 1) / OUT_BLOCK_POINTS));
+    SCOPE_HIP(S, hipMemsetAsync(d_sc, 0, sizeof(OutScal), st));
     const double *d_root = nullptr;
-    RH_TRY(tree_root<0>(who, st, o.mean, o.count, n, d_sc, d_part, &d_root));
+    RH_TRY(tree_root<0>(S, o.mean, o.count, n, d_sc, d_part, &d_root));
     hipLaunchKernelGGL(out_scalars_kernel, dim3(1), dim3(64), 0, st, d_sc, d_root, 0, *p);
-    RH_TRY(tree_root<1>(who, st, o.mean, o.count, n, d_sc, d_part, &d_root));
+    RH_TRY(tree_root<1>(S, o.mean, o.count, n, d_sc, d_part, &d_root));
     hipLaunchKernelGGL(out_scalars_kernel, dim3(1), dim3(64), 0, st, d_sc, d_root, 1, *p);
-    KNN_HIP(who, hipGetLastError());
+    SCOPE_HIP(S, hipGetLastError());
 
     // 3. flags and the kept indices; 4. the median.  The grid's key buffers are free again: the sort's keys go there.
     uint8_t *d_keep = nullptr;
     int32_t *d_kept = nullptr;
-    RH_TRY(B.alloc(&d_keep, n));
-    RH_TRY(B.alloc(&d_kept, n));
+    RH_TRY(S.alloc(&d_keep, n));
+    RH_TRY(S.alloc(&d_kept, n));
     uint64_t *d_key = ix.d_key[0], *d_sorted = ix.d_key[1];
-    hipLaunchKernelGGL(out_flag_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, o.mean, o.nn1, o.count, n, d_sc, (int)p->mode, (int)p->k,
+    hipLaunchKernelGGL(out_flag_kernel, dim3(blocks_for(n)), dim3(256), 0, st, o.mean, o.nn1, o.count, n, d_sc, (int)p->mode, (int)p->k,
                        d_keep, d_key);
-    KNN_HIP(who, hipGetLastError());
+    SCOPE_HIP(S, hipGetLastError());
     hipcub::CountingInputIterator<int32_t> one_based(1);
     size_t sel_bytes = 0, sort_bytes = 0;
-    KNN_HIP(who, hipcub::DeviceSelect::Flagged(nullptr, sel_bytes, one_based, d_keep, d_kept, &d_sc->nkept, (int)n, st));
-    KNN_HIP(who, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, d_key, d_sorted, (int)n, 0, 64, st));
+    SCOPE_HIP(S, hipcub::DeviceSelect::Flagged(nullptr, sel_bytes, one_based, d_keep, d_kept, &d_sc->nkept, (int)n, st));
+    SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, d_key, d_sorted, (int)n, 0, 64, st));
     uint8_t *d_tmp = nullptr;
     const size_t tmp_bytes = std::max(sel_bytes, sort_bytes);
-    RH_TRY(B.alloc(&d_tmp, (int64_t)tmp_bytes));
+    RH_TRY(S.alloc(&d_tmp, (int64_t)tmp_bytes));
     size_t tb = tmp_bytes;
-    KNN_HIP(who, hipcub::DeviceSelect::Flagged(d_tmp, tb, one_based, d_keep, d_kept, &d_sc->nkept, (int)n, st));
+    SCOPE_HIP(S, hipcub::DeviceSelect::Flagged(d_tmp, tb, one_based, d_keep, d_kept, &d_sc->nkept, (int)n, st));
     tb = tmp_bytes;
-    KNN_HIP(who, hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_key, d_sorted, (int)n, 0, 64, st));
+    SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_key, d_sorted, (int)n, 0, 64, st));
     hipLaunchKernelGGL(out_median_kernel, dim3(1), dim3(64), 0, st, d_sc, d_sorted, n);
-    KNN_HIP(who, hipGetLastError());
+    SCOPE_HIP(S, hipGetLastError());
 
     OutScal h;
-    KNN_HIP(who, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
-    KNN_HIP(who, hipMemcpyAsync(keep_out, d_keep, (size_t)n, hipMemcpyDefault, st));
-    if (mean_dist_out) KNN_HIP(who, hipMemcpyAsync(mean_dist_out, o.mean, sizeof(double) * (size_t)n, hipMemcpyDefault, st));
-    KNN_HIP(who, hipStreamSynchronize(st));
+    SCOPE_HIP(S, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
+    SCOPE_HIP(S, hipMemcpyAsync(keep_out, d_keep, (size_t)n, hipMemcpyDefault, st));
+    if (mean_dist_out) SCOPE_HIP(S, hipMemcpyAsync(mean_dist_out, o.mean, sizeof(double) * (size_t)n, hipMemcpyDefault, st));
+    SCOPE_HIP(S, hipStreamSynchronize(st));
     *n_kept_out = h.nkept;
     if (stats) {
         stats->n_valid = (int64_t)h.nvalid;
@@ -297,8 +295,8 @@ int remove_outliers(const T *xyz_aos, int64_t n, const rh_outlier_params *p, int
         return RH_E_CAPACITY;
     }
     if (h.nkept > 0) {
-        KNN_HIP(who, hipMemcpyAsync(kept_idx_out, d_kept, sizeof(int32_t) * (size_t)h.nkept, hipMemcpyDefault, st));
-        KNN_HIP(who, hipStreamSynchronize(st));
+        SCOPE_HIP(S, hipMemcpyAsync(kept_idx_out, d_kept, sizeof(int32_t) * (size_t)h.nkept, hipMemcpyDefault, st));
+        SCOPE_HIP(S, hipStreamSynchronize(st));
     }
     return RH_OK;
 }

@@ -78,13 +78,10 @@ __device__ void stream_cells(const Grid &g, int lane, int k, int32_t st, int32_t
 
 __device__ inline void hash_find(const Grid &g, uint64_t key, int32_t &st, int32_t &cnt)
 {
-    uint64_t sl = mix64(key) & g.mask;
-    for (;;) {
-        const uint64_t kk = g.hkey[sl];
-        if (kk == key) { st = g.hrange[2 * sl]; cnt = g.hrange[2 * sl + 1] - st; return; }
-        if (kk == NRM_EMPTY) { st = 0; cnt = 0; return; }
-        sl = (sl + 1) & g.mask;
-    }
+    const int64_t sl = table_find(g.hkey, (uint32_t)g.mask, key);
+    if (sl < 0) { st = 0; cnt = 0; return; }
+    st = g.hrange[2 * sl];
+    cnt = g.hrange[2 * sl + 1] - st;
 }
 
 // lower bound of the distance from p to the box of cell (cx, cy, cz), lowered by the margin
@@ -136,7 +133,7 @@ __device__ inline void knn_search(const Grid &g, const KnnQuery &a, int lane, in
                 const uint64_t sl = base + lane;
                 int32_t st = 0, cnt = 0;
                 const uint64_t key = g.hkey[sl];
-                if (key != NRM_EMPTY) {
+                if (key != GRID_EMPTY) {
                     const int64_t q[3] = { (int64_t)(key % (uint64_t)g.dim[0]), (int64_t)((key / (uint64_t)g.dim[0]) % (uint64_t)g.dim[1]),
                                            (int64_t)(key / (uint64_t)(g.dim[0] * g.dim[1])) };
                     int64_t cheb = 0;
@@ -202,7 +199,6 @@ __global__ __launch_bounds__(NRM_BLOCK) void knn_sample_kernel(Grid g, KnnQuery 
 //  3. the grid of that width.
 inline int knn_index_for_k(KnnIndex &ix, int k, double radius, KnnQuery &q)
 {
-    const char *who = ix.B->who;
     const int64_t n = ix.n;
     memset(&q, 0, sizeof q);
     q.n = n;
@@ -214,15 +210,15 @@ inline int knn_index_for_k(KnnIndex &ix, int k, double radius, KnnQuery &q)
     const double h0 = ix.g.h;
     const int64_t ns = std::min<int64_t>(n, NRM_SAMPLE);
     double *d_kth = nullptr;
-    RH_TRY(ix.B->alloc(&d_kth, ns));
+    RH_TRY(ix.S->alloc(&d_kth, ns));
     q.nq = ns;
     q.sample = 1;
     q.smax = ix.smax();
-    hipLaunchKernelGGL(knn_sample_kernel, dim3(nblk(ns, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, ix.st, ix.g, q, d_kth);
-    KNN_HIP(who, hipGetLastError());
+    hipLaunchKernelGGL(knn_sample_kernel, dim3(blocks_for(ns, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, ix.S->st, ix.g, q, d_kth);
+    SCOPE_HIP(*ix.S, hipGetLastError());
     std::vector<double> kth((size_t)ns);
-    KNN_HIP(who, hipMemcpyAsync(kth.data(), d_kth, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, ix.st));
-    KNN_HIP(who, hipStreamSynchronize(ix.st));
+    SCOPE_HIP(*ix.S, hipMemcpyAsync(kth.data(), d_kth, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, ix.S->st));
+    SCOPE_HIP(*ix.S, hipStreamSynchronize(ix.S->st));
     std::nth_element(kth.begin(), kth.begin() + ns / 2, kth.end());
     const double med = kth[(size_t)(ns / 2)];
     const double h = (med > 0.0 && isfinite(med)) ? 2.0 * sqrt(med) : h0;

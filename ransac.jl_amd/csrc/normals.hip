@@ -116,20 +116,19 @@ int estimate(const T *xyz_aos, int64_t n, const rh_normals_params *p, const T *h
         rh_set_error("rh_estimate_normals: the viewpoint is not finite");
         return RH_E_INVALID;
     }
-    StreamHolder sh;
-    RH_TRY(knn_open_device(who, device, sh));
-    const hipStream_t st = sh.s;
-    Buffers B(who);
+    CallScope S;
+    RH_TRY(S.open(who, device));
+    const hipStream_t st = S.st;
 
     double *d_xyz = nullptr, *d_hints = nullptr;
-    RH_TRY(B.alloc(&d_xyz, 3 * n));
-    RH_TRY(knn_upload(B, st, xyz_aos, d_xyz, 3 * n, hipMemcpyHostToDevice));
+    RH_TRY(S.alloc(&d_xyz, 3 * n));
+    RH_TRY(S.upload(xyz_aos, d_xyz, 3 * n, hipMemcpyHostToDevice));
     if (p->orient == 2) {
-        RH_TRY(B.alloc(&d_hints, 3 * n));
-        RH_TRY(knn_upload(B, st, hints, d_hints, 3 * n, hipMemcpyHostToDevice));
+        RH_TRY(S.alloc(&d_hints, 3 * n));
+        RH_TRY(S.upload(hints, d_hints, 3 * n, hipMemcpyHostToDevice));
     }
     KnnIndex ix;
-    RH_TRY(ix.init(B, st, d_xyz, n));
+    RH_TRY(ix.init(S, d_xyz, n));
     KnnQuery kq;
     RH_TRY(knn_index_for_k(ix, p->k, p->radius, kq));
 
@@ -141,15 +140,15 @@ int estimate(const T *xyz_aos, int64_t n, const rh_normals_params *p, const T *h
     // every point's neighbours and normal
     T *d_nrm = nullptr, *d_curv = nullptr;
     int32_t *d_flags = nullptr;
-    RH_TRY(B.alloc(&d_nrm, 3 * n));
-    if (curv_out) RH_TRY(B.alloc(&d_curv, n));
-    if (flags_out) RH_TRY(B.alloc(&d_flags, n));
-    hipLaunchKernelGGL(nrm_query_kernel<T>, dim3(nblk(n, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, st, ix.g, kq, na, d_nrm, d_curv, d_flags);
-    KNN_HIP(who, hipGetLastError());
-    KNN_HIP(who, hipMemcpyAsync(nrm_out, d_nrm, sizeof(T) * 3 * (size_t)n, hipMemcpyDeviceToHost, st));
-    if (curv_out) KNN_HIP(who, hipMemcpyAsync(curv_out, d_curv, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, st));
-    if (flags_out) KNN_HIP(who, hipMemcpyAsync(flags_out, d_flags, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-    KNN_HIP(who, hipStreamSynchronize(st));
+    RH_TRY(S.alloc(&d_nrm, 3 * n));
+    if (curv_out) RH_TRY(S.alloc(&d_curv, n));
+    if (flags_out) RH_TRY(S.alloc(&d_flags, n));
+    hipLaunchKernelGGL(nrm_query_kernel<T>, dim3(blocks_for(n, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, st, ix.g, kq, na, d_nrm, d_curv, d_flags);
+    SCOPE_HIP(S, hipGetLastError());
+    SCOPE_HIP(S, hipMemcpyAsync(nrm_out, d_nrm, sizeof(T) * 3 * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (curv_out) SCOPE_HIP(S, hipMemcpyAsync(curv_out, d_curv, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (flags_out) SCOPE_HIP(S, hipMemcpyAsync(flags_out, d_flags, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    SCOPE_HIP(S, hipStreamSynchronize(st));
     return RH_OK;
 }
 

@@ -1,12 +1,12 @@
 // voxel.hip -- voxel-grid downsampling of a raw cloud (rh_voxel_downsample, include/ransac_hip.h states the definition in
 // full): one output point per occupied cell of a grid of width beta, rows in first-appearance order, and the map
 // point -> row that carries a shape found on the thinned cloud back to the scan.  The reference leaves thinning to the
-// user.  Everything order-dependent is an integer: cells live in an open-addressing table (component.hip's), counts,
+// user.  Everything order-dependent is an integer: cells live in an open-addressing table (cell_grid.h), counts,
 // first indices and the 32-bit fixed-point offsets of the centroid are integer atomics, so the same bits come out
 // whatever order the points arrive in.
 //   1. minimum:    o = componentwise minimum of the points that are kept (+ maximum for the extent check, + |F|); every
 //                  point leaves 1 / 0 (kept / dropped) in its row_of_point word -- one read-back
-//   2. insert:     key loaded first, CAS only into an empty slot; count += 1, first = min(first, i); the slot of every
+//   2. insert:     table_insert; count += 1, first = min(first, i); the slot of every
 //                  point is kept (4 bytes) so that no later pass probes again.  A wave whose points all share a cell
 //                  sends one probe and one pair of atomics
 //   3. ranks:      a point flags itself when it is its cell's first; exclusive scan; second read-back (M)
@@ -22,18 +22,17 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "call_scope.h"
+#include "cell_grid.h"
 #include "rh_internal.h"
 
 namespace {
 
-constexpr uint64_t VK_EMPTY = ~0ULL;   // (no key: cells are below 2^20 per axis, bit 63 of a key is never set)
-constexpr int VOX_BLOCKS = 4096;       // blocks of the minimum pass at most, 8 words of partial results each
-enum { VS_MIN = 0, VS_MAX = 3, VS_COUNT = 6, VS_WORDS = 8 };
 constexpr int VOX_COMBINE_ROUNDS = 4;  // distinct rows per wave that are looked at for lanes to combine
 constexpr int VOX_COMBINE_MIN = 8;     // lanes that share a row before a wave reduction beats their own atomics
 
 struct vox_table {
-    uint64_t *key;      // [cap] cell key, VK_EMPTY: free
+    uint64_t *key;      // [cap] cell key, GRID_EMPTY: free
     int32_t *count;     // [cap] points in the cell
     int32_t *first;     // [cap] smallest 0-based point index
     int32_t *row;       // [cap] 1-based output row (written by the rows pass)
@@ -44,27 +43,6 @@ struct vox_grid {
     double o[3];
     double beta;
 };
-
-// doubles as unsigned integers in the same order (finite values; -0.0 sorts below +0.0, which the cell formula cannot tell apart)
-__host__ __device__ inline uint64_t ord_of(double x)
-{
-    uint64_t u;
-    __builtin_memcpy(&u, &x, 8);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
-}
-__host__ __device__ inline double ord_back(uint64_t u)
-{
-    u = (u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFULL) : ~u;
-    double x;
-    __builtin_memcpy(&x, &u, 8);
-    return x;
-}
-
-__device__ __forceinline__ uint32_t slot_hash(uint64_t k)
-{
-    k ^= k >> 33; k *= 0xFF51AFD7ED558CCDULL; k ^= k >> 33; k *= 0xC4CEB9FE1A85EC53ULL; k ^= k >> 33;
-    return (uint32_t)k;
-}
 
 // cell and 32-bit fixed-point offset inside it along one axis: a = (x - o) / beta, c = floor(a), t = a - c (exact),
 // f = floor(t * 2^32)
@@ -81,24 +59,16 @@ __device__ __forceinline__ uint64_t cell_key(const double *__restrict__ p, const
     uint64_t c[3], f;
 #pragma unroll
     for (int a = 0; a < 3; a++) cell_axis(p[a], g.o[a], g.beta, &c[a], &f);
-    return ((c[0] & 0x1FFFFFULL) << 42) | ((c[1] & 0x1FFFFFULL) << 21) | (c[2] & 0x1FFFFFULL);
-}
-
-template <typename T>
-__global__ void vox_widen_kernel(const T *__restrict__ in, double *__restrict__ out, int64_t cnt)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cnt) out[i] = (double)in[i];
+    return grid_pack((long long)c[0], (long long)c[1], (long long)c[2], 0);
 }
 
 // ---- 1. minimum, maximum and number of the points that are kept; valid[i] = 1 / 0.  Every block (256 threads) leaves
-// its partial result in `part`, one block folds them (component.hip measured the atomics form: 0.34 ms)
+// its partial result in `part`, the fold of cell_grid.h follows
 __global__ void __launch_bounds__(256)
 vox_minmax_kernel(const double *__restrict__ xyz, const double *__restrict__ nrm, int64_t n, int32_t *__restrict__ valid,
                   unsigned long long *__restrict__ part)
 {
-    double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    long long cnt = 0;
+    MinMaxCount acc;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const double p[3] = { xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2] };
         bool ok = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
@@ -107,79 +77,9 @@ vox_minmax_kernel(const double *__restrict__ xyz, const double *__restrict__ nrm
             for (int a = 0; a < 3; a++) ok = ok && fabs(nrm[3 * i + a]) <= 2.0;   // (false for NaN and infinities)
         }
         valid[i] = ok ? 1 : 0;
-        if (!ok) continue;
-        cnt++;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            lo[a] = p[a] < lo[a] ? p[a] : lo[a];
-            hi[a] = p[a] > hi[a] ? p[a] : hi[a];
-        }
+        if (ok) acc.add(p[0], p[1], p[2]);
     }
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-        for (int off = 32; off > 0; off >>= 1) {
-            const double l = __shfl_down(lo[a], off), h = __shfl_down(hi[a], off);
-            lo[a] = l < lo[a] ? l : lo[a];
-            hi[a] = h > hi[a] ? h : hi[a];
-        }
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-    __shared__ double s_lo[4][3], s_hi[4][3];
-    __shared__ long long s_cnt[4];
-    if ((threadIdx.x & 63) == 0) {
-        const int wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int a = 0; a < 3; a++) { s_lo[wv][a] = lo[a]; s_hi[wv][a] = hi[a]; }
-        s_cnt[wv] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int wv = 1; wv < 4; wv++) {
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                lo[a] = s_lo[wv][a] < lo[a] ? s_lo[wv][a] : lo[a];
-                hi[a] = s_hi[wv][a] > hi[a] ? s_hi[wv][a] : hi[a];
-            }
-            cnt += s_cnt[wv];
-        }
-        unsigned long long *o = part + VS_WORDS * (size_t)blockIdx.x;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            o[VS_MIN + a] = cnt > 0 ? (unsigned long long)ord_of(lo[a]) : ~0ULL;
-            o[VS_MAX + a] = cnt > 0 ? (unsigned long long)ord_of(hi[a]) : 0ULL;
-        }
-        o[VS_COUNT] = (unsigned long long)cnt;
-    }
-}
-
-__global__ void __launch_bounds__(256) vox_minmax_fold_kernel(const unsigned long long *__restrict__ part, int nparts, unsigned long long *__restrict__ scal)
-{
-    __shared__ unsigned long long sh[256][7];
-    unsigned long long v[7] = { ~0ULL, ~0ULL, ~0ULL, 0ULL, 0ULL, 0ULL, 0ULL };
-    for (int b = threadIdx.x; b < nparts; b += 256) {
-        const unsigned long long *o = part + VS_WORDS * (size_t)b;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            v[VS_MIN + a] = o[VS_MIN + a] < v[VS_MIN + a] ? o[VS_MIN + a] : v[VS_MIN + a];
-            v[VS_MAX + a] = o[VS_MAX + a] > v[VS_MAX + a] ? o[VS_MAX + a] : v[VS_MAX + a];
-        }
-        v[VS_COUNT] += o[VS_COUNT];
-    }
-#pragma unroll
-    for (int k = 0; k < 7; k++) sh[threadIdx.x][k] = v[k];
-    __syncthreads();
-    for (int step = 128; step > 0; step >>= 1) {
-        if ((int)threadIdx.x < step) {
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                const unsigned long long l = sh[threadIdx.x + step][VS_MIN + a], h = sh[threadIdx.x + step][VS_MAX + a];
-                if (l < sh[threadIdx.x][VS_MIN + a]) sh[threadIdx.x][VS_MIN + a] = l;
-                if (h > sh[threadIdx.x][VS_MAX + a]) sh[threadIdx.x][VS_MAX + a] = h;
-            }
-            sh[threadIdx.x][VS_COUNT] += sh[threadIdx.x + step][VS_COUNT];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < VS_WORDS) scal[threadIdx.x] = threadIdx.x < 7 ? sh[0][threadIdx.x] : 0ULL;
+    acc.store(part);
 }
 
 // ---- 2. the cell table
@@ -187,24 +87,10 @@ __global__ void __launch_bounds__(256) vox_init_kernel(vox_table T)
 {
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s > T.mask) return;
-    T.key[s] = VK_EMPTY;
+    T.key[s] = GRID_EMPTY;
     T.count[s] = 0;
     T.first[s] = 0x7FFFFFFF;
     T.row[s] = 0;
-}
-
-__device__ __forceinline__ uint32_t table_insert(const vox_table &T, uint64_t key)
-{
-    uint32_t h = slot_hash(key) & T.mask;
-    for (;;) {   // (the table is at most half full: an empty slot ends every probe sequence)
-        const unsigned long long k = __hip_atomic_load((const unsigned long long *)&T.key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == key) return h;
-        if (k == VK_EMPTY) {   // a dense cell sends its CAS only until the key stands there
-            const unsigned long long old = atomicCAS((unsigned long long *)&T.key[h], (unsigned long long)VK_EMPTY, (unsigned long long)key);
-            if (old == VK_EMPTY || old == key) return h;
-        }
-        h = (h + 1) & T.mask;
-    }
 }
 
 // (no thread leaves before the end: the ballots and shuffles count on whole waves; the grid covers n rounded up to 256)
@@ -215,7 +101,7 @@ vox_insert_kernel(const double *__restrict__ xyz, int64_t n, const int32_t *__re
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const bool v = i < n && valid[i] != 0;
-    uint64_t key = VK_EMPTY;
+    uint64_t key = GRID_EMPTY;
     if (v) key = cell_key(xyz + 3 * i, g);
     const uint64_t act = __builtin_amdgcn_ballot_w64(v);
     if (act == 0) return;   // (the whole wave)
@@ -225,7 +111,7 @@ vox_insert_kernel(const double *__restrict__ xyz, int64_t n, const int32_t *__re
         // one cell for the whole wave: its lowest lane holds the smallest index
         uint32_t h = 0;
         if (lane == lead) {
-            h = table_insert(T, key);
+            h = table_insert(T.key, T.mask, key);
             atomicAdd(&T.count[h], (int32_t)__popcll(act));
             atomicMin(&T.first[h], (int32_t)i);
         }
@@ -234,7 +120,7 @@ vox_insert_kernel(const double *__restrict__ xyz, int64_t n, const int32_t *__re
         return;
     }
     if (v) {
-        const uint32_t h = table_insert(T, key);
+        const uint32_t h = table_insert(T.key, T.mask, key);
         atomicAdd(&T.count[h], 1);
         atomicMin(&T.first[h], (int32_t)i);
         slot[i] = h;
@@ -367,7 +253,7 @@ vox_finish_kernel(const double *__restrict__ xyz, const double *__restrict__ nrm
 #pragma unroll
     for (int a = 0; a < 3; a++) {
         const unsigned long long S = sums[6 * (size_t)r + a];
-        const double c = (double)((key >> (21 * (2 - a))) & 0x1FFFFFULL);
+        const double c = (double)grid_field(key, a);
         const double num = (double)(S >> 32) * 4294967296.0 + (double)(S & 0xFFFFFFFFULL);
         const double m = (num / cnt) * (1.0 / 4294967296.0);
         xyz_out[3 * r + a] = (OutT)(g.o[a] + (c + m) * g.beta);
@@ -382,38 +268,6 @@ vox_finish_kernel(const double *__restrict__ xyz, const double *__restrict__ nrm
     }
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// device buffers of one call, freed on every way out
-struct Buffers {
-    std::vector<void *> ptrs;
-    ~Buffers() { for (void *p : ptrs) (void)hipFree(p); }
-    template <typename T>
-    int alloc(T **p, int64_t count)
-    {
-        *p = nullptr;
-        const size_t bytes = sizeof(T) * (size_t)(count > 0 ? count : 1);
-        const hipError_t e = hipMalloc((void **)p, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            rh_set_error("rh_voxel_downsample: hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? RH_E_NOMEM : RH_E_NODEVICE;
-        }
-        ptrs.push_back(*p);
-        return RH_OK;
-    }
-    void release(void *p)
-    {
-        for (auto &q : ptrs)
-            if (q == p) { (void)hipFree(q); q = nullptr; }
-    }
-};
-
-struct StreamHolder {
-    hipStream_t s = nullptr;
-    ~StreamHolder() { if (s) (void)hipStreamDestroy(s); }
-};
-
 template <typename T>
 int downsample(const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_voxel_params *p, int device, T *xyz_out, T *nrm_out,
                int64_t *first_out, int32_t *count_out, int64_t cap, int32_t *rowof_out, int64_t *n_out, int64_t *n_dropped_out)
@@ -427,57 +281,39 @@ int downsample(const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_voxel_par
     if (p->flags & ~RH_VOX_ALIGN_NORMALS) { rh_set_error("rh_voxel_downsample: unknown flags %d", p->flags); return RH_E_INVALID; }
     if (cap < 0 || (cap > 0 && !xyz_out)) { rh_set_error("rh_voxel_downsample: no output for %lld rows", (long long)cap); return RH_E_INVALID; }
     if (nrm_out && !nrm_aos) { rh_set_error("rh_voxel_downsample: normals out without normals in"); return RH_E_INVALID; }
-    int ndev = 0;
-    RH_TRY(rh_device_count(&ndev));
-    if (ndev <= 0) { rh_set_error("no HIP device is visible; libransac_hip has no CPU fallback"); return RH_E_NODEVICE; }
-    if (device < 0 || device >= ndev) { rh_set_error("device %d out of range (%d visible)", device, ndev); return RH_E_INVALID; }
-#define VH(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { rh_set_error("rh_voxel_downsample: %s", hipGetErrorString(e_)); return RH_E_NODEVICE; } } while (0)
-    VH(hipSetDevice(device));
-    StreamHolder sh;
-    VH(hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking));
-    const hipStream_t st = sh.s;
-    Buffers B;
+    CallScope S;
+    RH_TRY(S.open("rh_voxel_downsample", device));
+    const hipStream_t st = S.st;
     const int centroid = p->mode == RH_VOX_CENTROID;
     const dim3 blk(256), gp(blocks_for(n));
 
     double *d_xyz = nullptr, *d_nrm = nullptr;
-    auto upload = [&](const T *src, double **dst) -> int {
-        RH_TRY(B.alloc(dst, 3 * n));
-        if (sizeof(T) == sizeof(double)) {
-            VH(hipMemcpyAsync(*dst, src, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-            return RH_OK;
-        }
-        T *d_in = nullptr;
-        RH_TRY(B.alloc(&d_in, 3 * n));
-        VH(hipMemcpyAsync(d_in, src, sizeof(T) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(vox_widen_kernel<T>, dim3(blocks_for(3 * n)), blk, 0, st, d_in, *dst, 3 * n);
-        VH(hipGetLastError());
-        VH(hipStreamSynchronize(st));
-        B.release(d_in);
-        return RH_OK;
-    };
-    RH_TRY(upload(xyz_aos, &d_xyz));
-    if (nrm_aos) RH_TRY(upload(nrm_aos, &d_nrm));
+    RH_TRY(S.alloc(&d_xyz, 3 * n));
+    RH_TRY(S.upload(xyz_aos, d_xyz, 3 * n, hipMemcpyHostToDevice));
+    if (nrm_aos) {
+        RH_TRY(S.alloc(&d_nrm, 3 * n));
+        RH_TRY(S.upload(nrm_aos, d_nrm, 3 * n, hipMemcpyHostToDevice));
+    }
 
     // 1. o, the extent and |F|
     int32_t *d_rowof = nullptr;
     unsigned long long *d_scal = nullptr;
-    RH_TRY(B.alloc(&d_rowof, n));
-    RH_TRY(B.alloc(&d_scal, VS_WORDS * (1 + VOX_BLOCKS)));
+    RH_TRY(S.alloc(&d_rowof, n));
+    RH_TRY(S.alloc(&d_scal, MM_WORDS * (1 + GRID_MM_BLOCKS)));
     {
-        const int64_t b = std::min<int64_t>((n + 255) / 256, VOX_BLOCKS);
-        hipLaunchKernelGGL(vox_minmax_kernel, dim3((unsigned)b), blk, 0, st, d_xyz, d_nrm, n, d_rowof, d_scal + VS_WORDS);
-        hipLaunchKernelGGL(vox_minmax_fold_kernel, dim3(1), blk, 0, st, d_scal + VS_WORDS, (int)b, d_scal);
-        VH(hipGetLastError());
+        const int64_t b = std::min<int64_t>((n + 255) / 256, GRID_MM_BLOCKS);
+        hipLaunchKernelGGL(vox_minmax_kernel, dim3((unsigned)b), blk, 0, st, d_xyz, d_nrm, n, d_rowof, d_scal + MM_WORDS);
+        hipLaunchKernelGGL(grid_minmax_fold_kernel, dim3(1), blk, 0, st, d_scal + MM_WORDS, (int)b, d_scal, (int)MM_WORDS);
+        SCOPE_HIP(S, hipGetLastError());
     }
-    unsigned long long h_scal[VS_WORDS];
-    VH(hipMemcpyAsync(h_scal, d_scal, sizeof h_scal, hipMemcpyDeviceToHost, st));
-    VH(hipStreamSynchronize(st));
-    const int64_t nf = (int64_t)h_scal[VS_COUNT];
+    unsigned long long h_scal[MM_WORDS];
+    SCOPE_HIP(S, hipMemcpyAsync(h_scal, d_scal, sizeof h_scal, hipMemcpyDeviceToHost, st));
+    SCOPE_HIP(S, hipStreamSynchronize(st));
+    const int64_t nf = (int64_t)h_scal[MM_COUNT];
     if (n_dropped_out) *n_dropped_out = n - nf;
     auto download_map = [&]() -> int {
-        if (rowof_out) VH(hipMemcpyAsync(rowof_out, d_rowof, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-        VH(hipStreamSynchronize(st));
+        if (rowof_out) SCOPE_HIP(S, hipMemcpyAsync(rowof_out, d_rowof, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+        SCOPE_HIP(S, hipStreamSynchronize(st));
         return RH_OK;
     };
     if (nf == 0) return download_map();   // (every word of the map is 0)
@@ -485,9 +321,9 @@ int downsample(const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_voxel_par
     g.beta = p->beta;
     double box_cells = 1.0;
     for (int a = 0; a < 3; a++) {
-        g.o[a] = ord_back(h_scal[VS_MIN + a]);
-        const double cells = floor((ord_back(h_scal[VS_MAX + a]) - g.o[a]) / g.beta);
-        if (!(cells < 1048576.0)) {
+        g.o[a] = ord_back(h_scal[MM_MIN + a]);
+        double cells;
+        if (!grid_axis_fits(g.o[a], ord_back(h_scal[MM_MAX + a]), g.beta, &cells)) {
             rh_set_error("rh_voxel_downsample: the points span more than 2^20 cells of size %g along axis %d", g.beta, a);
             return RH_E_INVALID;
         }
@@ -498,7 +334,7 @@ int downsample(const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_voxel_par
     uint64_t tcap = 64;
     while ((double)tcap < 2.0 * std::min((double)nf, box_cells)) tcap <<= 1;
     uint8_t *d_tab = nullptr;
-    RH_TRY(B.alloc(&d_tab, (int64_t)(tcap * 20)));
+    RH_TRY(S.alloc(&d_tab, (int64_t)(tcap * 20)));
     vox_table tab;
     tab.key = (uint64_t *)d_tab;
     tab.count = (int32_t *)(tab.key + tcap);
@@ -507,23 +343,23 @@ int downsample(const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_voxel_par
     tab.mask = (uint32_t)(tcap - 1);
     uint32_t *d_slot = nullptr;
     int32_t *d_flag = nullptr, *d_rank = nullptr;
-    RH_TRY(B.alloc(&d_slot, n));
-    RH_TRY(B.alloc(&d_flag, n));
-    RH_TRY(B.alloc(&d_rank, n));
+    RH_TRY(S.alloc(&d_slot, n));
+    RH_TRY(S.alloc(&d_flag, n));
+    RH_TRY(S.alloc(&d_rank, n));
     size_t tmp_bytes = 0;
-    VH(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_flag, d_rank, (int)n, st));
+    SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_flag, d_rank, (int)n, st));
     uint8_t *d_tmp = nullptr;
-    RH_TRY(B.alloc(&d_tmp, (int64_t)tmp_bytes));
+    RH_TRY(S.alloc(&d_tmp, (int64_t)tmp_bytes));
     hipLaunchKernelGGL(vox_init_kernel, dim3(blocks_for((int64_t)tcap)), blk, 0, st, tab);
     hipLaunchKernelGGL(vox_insert_kernel, gp, blk, 0, st, d_xyz, n, d_rowof, g, tab, d_slot);
     // 3. ranks of the first points
     hipLaunchKernelGGL(vox_flag_kernel, gp, blk, 0, st, n, d_rowof, d_slot, tab, d_flag);
-    VH(hipGetLastError());
-    VH(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flag, d_rank, (int)n, st));
+    SCOPE_HIP(S, hipGetLastError());
+    SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flag, d_rank, (int)n, st));
     int32_t last[2] = { 0, 0 };
-    VH(hipMemcpyAsync(&last[0], d_rank + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    VH(hipMemcpyAsync(&last[1], d_flag + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    VH(hipStreamSynchronize(st));
+    SCOPE_HIP(S, hipMemcpyAsync(&last[0], d_rank + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    SCOPE_HIP(S, hipMemcpyAsync(&last[1], d_flag + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    SCOPE_HIP(S, hipStreamSynchronize(st));
     const int64_t M = (int64_t)last[0] + last[1];
     if (M < 1 || M > nf) { rh_set_error("rh_voxel_downsample: %lld rows from %lld points", (long long)M, (long long)nf); return RH_E_INTERNAL; }
     *n_out = M;
@@ -535,18 +371,18 @@ int downsample(const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_voxel_par
     int32_t *d_count = nullptr;
     uint64_t *d_rkey = nullptr;
     unsigned long long *d_sums = nullptr;
-    RH_TRY(B.alloc(&d_first, M));
-    RH_TRY(B.alloc(&d_count, M));
-    RH_TRY(B.alloc(&d_rkey, M));
+    RH_TRY(S.alloc(&d_first, M));
+    RH_TRY(S.alloc(&d_count, M));
+    RH_TRY(S.alloc(&d_rkey, M));
     if (sum_mode) {
-        RH_TRY(B.alloc(&d_sums, 6 * M));
-        VH(hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 6 * (size_t)M, st));
+        RH_TRY(S.alloc(&d_sums, 6 * M));
+        SCOPE_HIP(S, hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 6 * (size_t)M, st));
     }
     hipLaunchKernelGGL(vox_rows_kernel, gp, blk, 0, st, n, d_flag, d_rank, d_slot, tab, M, d_first, d_count, d_rkey);
     const int align = (p->flags & RH_VOX_ALIGN_NORMALS) ? 1 : 0;
     if (d_nrm) hipLaunchKernelGGL(vox_accum_kernel<6>, gp, blk, 0, st, d_xyz, d_nrm, n, d_rowof, d_slot, g, tab, M, sum_mode, align, d_sums);
     else hipLaunchKernelGGL(vox_accum_kernel<3>, gp, blk, 0, st, d_xyz, d_nrm, n, d_rowof, d_slot, g, tab, M, sum_mode, align, d_sums);
-    VH(hipGetLastError());
+    SCOPE_HIP(S, hipGetLastError());
     if (!fits) {
         RH_TRY(download_map());
         rh_set_error("rh_voxel_downsample: %lld occupied cells, capacity %lld", (long long)M, (long long)cap);
@@ -555,17 +391,16 @@ int downsample(const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_voxel_par
 
     // 6. the output rows
     T *d_xout = nullptr, *d_nout = nullptr;
-    RH_TRY(B.alloc(&d_xout, 3 * M));
-    if (nrm_out) RH_TRY(B.alloc(&d_nout, 3 * M));
+    RH_TRY(S.alloc(&d_xout, 3 * M));
+    if (nrm_out) RH_TRY(S.alloc(&d_nout, 3 * M));
     hipLaunchKernelGGL(vox_finish_kernel<T>, dim3(blocks_for(M)), blk, 0, st, d_xyz, d_nrm, n, M, g, centroid, d_first, d_count, d_rkey,
                        d_sums, d_xout, d_nout);
-    VH(hipGetLastError());
-    VH(hipMemcpyAsync(xyz_out, d_xout, sizeof(T) * 3 * (size_t)M, hipMemcpyDeviceToHost, st));
-    if (nrm_out) VH(hipMemcpyAsync(nrm_out, d_nout, sizeof(T) * 3 * (size_t)M, hipMemcpyDeviceToHost, st));
-    if (first_out) VH(hipMemcpyAsync(first_out, d_first, sizeof(int64_t) * (size_t)M, hipMemcpyDeviceToHost, st));
-    if (count_out) VH(hipMemcpyAsync(count_out, d_count, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, st));
+    SCOPE_HIP(S, hipGetLastError());
+    SCOPE_HIP(S, hipMemcpyAsync(xyz_out, d_xout, sizeof(T) * 3 * (size_t)M, hipMemcpyDeviceToHost, st));
+    if (nrm_out) SCOPE_HIP(S, hipMemcpyAsync(nrm_out, d_nout, sizeof(T) * 3 * (size_t)M, hipMemcpyDeviceToHost, st));
+    if (first_out) SCOPE_HIP(S, hipMemcpyAsync(first_out, d_first, sizeof(int64_t) * (size_t)M, hipMemcpyDeviceToHost, st));
+    if (count_out) SCOPE_HIP(S, hipMemcpyAsync(count_out, d_count, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, st));
     RH_TRY(download_map());
-#undef VH
     return RH_OK;
 }
 

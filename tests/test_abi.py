@@ -312,6 +312,22 @@ def test_octview_searches_match_std(tmp_path):
     assert out.stdout.strip().endswith("0 bad")
 
 
+def test_cell_grid_integers(tmp_path):
+    """The integer part of csrc/cell_grid.h, shared by the component filter, the voxel downsampler and the kNN grid: doubles
+    as order-preserving integers (round trip, strict order from -DBL_MAX over the denormals and -0.0 < +0.0 to DBL_MAX),
+    cell keys packed and extracted at cells 0, 1 and 2^20 - 1 with bias 0 and 1, and the 13 forward-neighbour offsets of
+    the component filter staying inside their fields."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "cell_grid_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(root, "include"),
+                           "-I", os.path.join(root, "ransac.jl_amd", "csrc"),
+                           os.path.join(root, "tests", "native", "cell_grid_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout[-2000:]
+    assert out.stdout.strip().endswith(" 0 bad")
+
+
 def test_product_library_reads_no_environment_and_ships_no_diagnostics():
     """libransac_hip.so sits under someone else's process: it must not change what it computes because of a variable in
     that process's environment.  The A/B switches of the experiments (RH_NO_PIPELINE, ...), the skeleton-only launch

@@ -380,3 +380,16 @@ def test_ransac_mp_refuses_a_filter():
         assert len(got) >= 2
     finally:
         grp.close()
+
+
+@pytest.mark.parametrize("conn26", [True, False])
+def test_minimum_pass_of_258_blocks_folds_past_its_first_trip(conn26):
+    """64 * 4 * 257 + 1 inliers of one plane: 258 blocks of the masked minimum pass, so the one folding block
+    (cell_grid.h) goes round its loop a second, partial time; the box's corner is the last block's single point."""
+    n = 64 * 4 * 257 + 1
+    rng = np.random.default_rng(258)
+    xyz = np.concatenate([rng.uniform(0, 3, size=(n, 2)), np.zeros((n, 1))], axis=1)
+    xyz[n // 2:, 0] += 5.0                             # two slabs two cells apart
+    xyz[-1] = [-0.5, -0.5, 0.0]
+    got, st = _check(_cloud(xyz), 1.0, conn26, np.ones(n, dtype=bool))
+    assert st["n_refit"] == n and st["n_components"] == 2 and got.size >= n // 2

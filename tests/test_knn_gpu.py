@@ -192,3 +192,30 @@ def test_errors_and_capacity():
     got = R.knn(far, 8)
     e = ref_knn(far, 8)
     assert np.array_equal(got[0], e[0]) and _same_bytes(got[1], e[1])
+
+
+@pytest.mark.parametrize("offset", [0.0, -3.0])
+def test_bounding_box_minimum_reached_by_both_zeros(offset):
+    """The box comes from the order-preserving integers of cell_grid.h, where -0.0 sorts below +0.0: the minimum of x is
+    reached by both (with the offset, by two equal negative numbers), either first."""
+    rng = np.random.default_rng(31)
+    xyz = rng.uniform(0.0, 2.0, size=(200, 3))
+    for zeros in ([0.0, -0.0], [-0.0, 0.0]):
+        pts = xyz.copy()
+        pts[[17, 150], 0] = zeros
+        if offset != 0.0:
+            pts[:, 0] += offset                                # (adding 0.0 would turn -0.0 into +0.0)
+        else:
+            assert (pts[[17, 150], 0] == 0.0).all() and np.signbit(pts[17, 0]) != np.signbit(pts[150, 0])
+        idx, d2, count = R.knn(pts, 8, return_count=True)
+        eidx, ed2, ecount = ref_knn(pts, 8)
+        assert np.array_equal(count, ecount) and np.array_equal(idx, eidx) and _same_bytes(d2, ed2)
+
+
+def test_a_nan_in_the_last_row_of_the_second_block_is_seen():
+    bad = np.random.default_rng(32).uniform(0, 1, size=(257, 3))
+    bad[256, 2] = np.nan
+    for call in (lambda: R.knn(bad, 8), lambda: R.removeoutliers(bad, k=8), lambda: R.estimatenormals(bad, k=8)):
+        with pytest.raises(R.RansacHipError) as e:
+            call()
+        assert e.value.code == L.RH_E_INVALID

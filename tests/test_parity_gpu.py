@@ -674,6 +674,30 @@ def test_largestconncomp_random_bitmaps(shape, density, seed):
         assert np.array_equal(got, orc.largestconncomp(bm, conn8=conn8))
 
 
+def _serpentine():
+    """64 x 64, one path: every other column full, joined to the next at alternating ends -- 2079 pixels in a chain"""
+    bm = np.zeros((64, 64), dtype=bool)
+    bm[0::2, :] = True
+    for k, x in enumerate(range(1, 63, 2)):
+        bm[x, 63 if k % 2 == 0 else 0] = True
+    return bm
+
+
+@pytest.mark.parametrize("cut", [False, True])
+def test_largestconncomp_serpentine(cut):
+    """one long chain: finds that walk far and halve their paths on the way (union_find.h); cut in two by one cleared
+    pixel in the middle, the halves differ by a few pixels"""
+    bm = _serpentine()
+    assert bm.sum() == 32 * 64 + 31
+    if cut:
+        bm[32, 30] = False
+    for conn8 in (False, True):
+        got = R.largestconncomp(bm, None, "eight" if conn8 else "default")
+        exp = orc.largestconncomp(bm, conn8=conn8)
+        assert np.array_equal(got, exp)
+        assert len(got) == (bm.sum() if not cut else max(16 * 64 + 16 + 30, 15 * 64 + 15 + 33))
+
+
 @pytest.mark.diag
 def test_full_size_octree_leg_is_the_same_run_under_every_switch(monkeypatch):
     """The bench's octree-sampling leg at full size (cfg3: 10M points, minsubsetN = 4096, ~1000 candidates per iteration,

@@ -265,3 +265,16 @@ def test_thinned_cloud_through_ransac_and_back():
         assert d.max() <= eps + beta, (R.strt(g.shape), d.max(), eps + beta)
         total += len(full)
     assert total > 0.8 * len(xyz)
+
+
+@pytest.mark.parametrize("mode", ["first", "centroid"])
+def test_minimum_pass_of_258_blocks_folds_past_its_first_trip(mode):
+    """256 * 257 + 1 points: 258 partial results, so the one folding block (cell_grid.h) goes round its loop a second,
+    partial time; the minimum and the maximum sit in the last block's single point."""
+    n = 256 * 257 + 1
+    rng = np.random.default_rng(258)
+    xyz = rng.uniform(0, 6, size=(n, 3))
+    xyz[-1] = [-1.25, -0.5, -3.0]
+    xyz[256 * 256 + 5] = [7.5, 8.25, 6.125]           # the maximum: block 256, the first of the second trip
+    nrm = unit(rng.normal(size=(n, 3)))
+    check_against_twin(xyz, nrm, 0.75, mode)
