@@ -103,7 +103,6 @@ int rh_ensure_batch(rh_cloud *c, rh_batch_ws &w, int64_t b)
     RH_TRY(rh_grow_buffer(c, (void **)&w.d_box, nullptr, 0, sizeof(float) * (size_t)rh4::RH_BOX_FIELDS * (size_t)(4 * cap)));
     RH_TRY(rh_grow_buffer(c, (void **)&w.d_orig, nullptr, 0, sizeof(int32_t) * (size_t)(4 * cap)));
     RH_TRY(rh_grow_buffer(c, (void **)&w.d_counts, nullptr, 0, sizeof(int32_t) * (size_t)cap));
-    if (c->f32) RH_TRY(rh_grow_buffer(c, &w.d_prep32, nullptr, 0, (size_t)(4 * cap) * 12 * sizeof(float)));
     w.batch_cap = cap;
     return RH_OK;
 }
@@ -158,7 +157,7 @@ static void batch_ws_free(rh_batch_ws &w)
 {
     if (w.stream) (void)hipStreamSynchronize(w.stream);
     (void)hipFree(w.d_shapes); (void)hipFree(w.d_prep); (void)hipFree(w.d_orig); (void)hipFree(w.d_counts); (void)hipFree(w.d_nk2);
-    (void)hipFree(w.d_qpre); (void)hipFree(w.d_prep32); (void)hipFree(w.d_box); (void)hipFree(w.d_masks_int); (void)hipFree(w.d_occ);
+    (void)hipFree(w.d_qpre); (void)hipFree(w.d_box); (void)hipFree(w.d_masks_int); (void)hipFree(w.d_occ);
     (void)hipFree(w.d_stlist); (void)hipFree(w.d_stcount); (void)hipFree(w.d_segmask);
     if (w.done) (void)hipEventDestroy(w.done);
     if (w.start) (void)hipEventDestroy(w.start);
@@ -628,9 +627,15 @@ extern "C" int rh_cloud_destroy(rh_cloud *c)
 }
 
 // RANSACCloud(vertices, normals, subsets; force_eltype = Float32) (src/octree.jl:102-109): xyz / nrm are Julia's
-// Vector{SVector{3,Float32}} memory as is.  The cloud is built like a Float64 cloud from the exactly converted values
-// (k-d leaf order, boxes, enabled bits, index plumbing) and gets float copies of its two point sets on top; scoring and
-// refit then compute in binary32 (f32.hip).
+// Vector{SVector{3,Float32}} memory as is.  Such a cloud makes every operation of the four compatibles* a binary32
+// operation -- points, normals and the shapes fitted to them are Float32 -- while eps and cos(alpha) stay what the caller
+// made them: the kernels run the tests of score_device.h with T = float and compare with the double thresholds after
+// exact promotion.  On the device it has everything a Float64 cloud has, built from the exactly converted values (k-d
+// leaf order, boxes, enabled bits, masks, index lists, binary64 candidate records), plus float copies of its point sets:
+// full32 / fullk32 (what the refit scans stream, half the bytes) and sub32 (what the brute-force batch score reads;
+// subsets of 8192 points and more take the culled kernel of score4.hip, whose margins bracket the binary32 chain).
+// The float record of a candidate is derived from its binary64 record where a test needs it (prepf_of, rh_internal.h).
+// rh_ransac runs on such a cloud too (binary32 fits: fit_shared.h); rh_refit_lsq stays Float64-only.
 extern "C" int rh_cloud_create_f32(const float *xyz, const float *nrm, int64_t n, const int64_t *subset1, int64_t s, int device,
                                    rh_cloud **out)
 {
@@ -647,7 +652,6 @@ extern "C" int rh_cloud_create_f32(const float *xyz, const float *nrm, int64_t n
     int rc = dev_alloc(&c->full32, 6 * std::max<int64_t>(c->n_pad, 1));
     if (rc == RH_OK) rc = dev_alloc(&c->sub32, 6 * std::max<int64_t>(c->s_pad, 1));
     if (rc == RH_OK) rc = rhk_f32_build(c);
-    if (rc == RH_OK) rc = rhk_korder_build_f32(c);
     if (rc == RH_OK && hipStreamSynchronize(c->stream) != hipSuccess) { rh_set_error("rh_cloud_create_f32: device error"); rc = RH_E_NODEVICE; }
     if (rc != RH_OK) { cloud_free(c); return rc; }
     *out = c;
@@ -772,12 +776,14 @@ static int score_bins_subset(rh_cloud *c, rh_batch_ws &w, const rh_score_job &jo
     }
     for (int k = 0; k < 4; k++) {
         if (ms_kind) RH_HIP(hipEventRecord(c->evk[k], c->stream));
-        if (c->f32 || job.kind_bound[k] == 0) continue;
-        RH_TRY(rhk_score_kind(c, k, c->sub, c->s_pad, c->s, job.en[k], job.bins.prep[k], job.bins.orig[k], job.nk[k], job.kind_bound[k],
-                              job.eps[k], job.cosa[k], job.d_counts, job.d_masks_int, c->swords));
+        if (job.kind_bound[k] == 0) continue;
+        auto score = [&](auto *pts) {   // (a Float32 cloud: over the float copy of the subset)
+            return rhk_score_kind(c, k, pts, c->s_pad, c->s, job.en[k], job.bins.prep[k], job.bins.orig[k], job.nk[k], job.kind_bound[k],
+                                  job.eps[k], job.cosa[k], job.d_counts, job.d_masks_int, c->swords);
+        };
+        RH_TRY(c->f32 ? score(c->sub32) : score(c->sub));
     }
-    // Float32 cloud, small subset: float records from the batch's shapes, brute-force float kernel (f32.hip)
-    return c->f32 ? rhk_score_all_f32(c, w, job) : RH_OK;
+    return RH_OK;
 }
 
 extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, int32_t *counts_out,
@@ -874,7 +880,6 @@ extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, co
     for (int k = 0; k < 4; k++) job.kind_bound[k] = nk[k];
     job.d_counts = d_counts_use;
     job.d_masks_int = d_masks_int;
-    job.shapes = w.d_shapes;   // sorted like the bins
     RH_TRY(score_bins_subset(c, w, job, nullptr));
     if (d_masks_int) RH_TRY(rh_masks_finish(c, w, b, d_masks));
     RH_HIP(hipMemcpyAsync(h_counts, d_counts_use, sizeof(int32_t) * (size_t)b, hipMemcpyDeviceToHost, c->stream));
@@ -994,8 +999,6 @@ static int score_batch_dev_impl(rh_cloud *c, int slot, const rh_shape *d_shapes,
     for (int k = 0; k < 4; k++) job.kind_bound[k] = b;
     job.d_counts = d_counts;
     job.d_masks_int = d_masks_int;
-    job.shapes = d_shapes;     // the caller's order: the float records go through d_orig
-    job.shapes_via_orig = 1;
     int32_t s4[4] = { 0, 0, 0, 0 };   // what the last sized launch below chose
     if (ms_kind) {   // the product launch (all kinds in one kernel) first, then the per-kind launches
         ms_kind[4] = 0.f;
@@ -1111,8 +1114,7 @@ extern "C" int rh_refit(rh_cloud *c, const rh_shape *shape, const rh_params *p, 
     rh_prep_host(*shape, &P);
     c->select_valid = false;   // block_sums / d_total are shared with the select directory
     RH_HIP(hipEventRecord(c->evk[0], c->stream));
-    if (c->f32) RH_TRY(rhk_refit_mask_f32(c, *shape, p->eps[shape->kind], p->cos_alpha[shape->kind]));
-    else RH_TRY(rhk_refit_mask(c, P, shape->kind, p->eps[shape->kind], p->cos_alpha[shape->kind]));
+    RH_TRY(rhk_refit_mask(c, P, shape->kind, p->eps[shape->kind], p->cos_alpha[shape->kind]));
     RH_HIP(hipEventRecord(c->evk[1], c->stream));
     RH_TRY(rhk_compact_mask(c, c->refit_mask, c->nwords, c->idx_out, c->n, c->d_total));
     RH_HIP(hipEventRecord(c->evk[2], c->stream));

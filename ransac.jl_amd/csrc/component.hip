@@ -270,8 +270,7 @@ extern "C" int rh_refit_component(rh_cloud *c, const rh_shape *shape, const rh_p
     rh_prep P;
     rh_prep_host(*shape, &P);
     c->select_valid = false;   // block_sums / d_total are shared with the select directory
-    if (c->f32) RH_TRY(rhk_refit_mask_f32(c, *shape, p->eps[shape->kind], p->cos_alpha[shape->kind]));
-    else RH_TRY(rhk_refit_mask(c, P, shape->kind, p->eps[shape->kind], p->cos_alpha[shape->kind]));
+    RH_TRY(rhk_refit_mask(c, P, shape->kind, p->eps[shape->kind], p->cos_alpha[shape->kind]));
     int64_t n_refit = 0, ncomp = 0;
     RH_TRY(rhk_component_filter(c, beta, conn26, &n_refit));
     if (n_refit_out) *n_refit_out = n_refit;

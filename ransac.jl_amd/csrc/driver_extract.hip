@@ -186,8 +186,7 @@ int Driver::maybe_extract(int64_t k, bool *did)
     // bits cleared on the way, no block sums left behind -- rhk_compact_refit_apply then regathers / recounts as after a plain
     // scan), the mask shrinks to its largest connected component, and everything below extracts just that
     const bool filtered = c->comp_beta > 0;
-    if (c->f32) RUN(rhk_refit_mask_f32(c, bestshape, p->eps[bestshape.kind], p->cos_alpha[bestshape.kind], !filtered));
-    else RUN(rhk_refit_mask(c, P, bestshape.kind, p->eps[bestshape.kind], p->cos_alpha[bestshape.kind], !filtered));
+    RUN(rhk_refit_mask(c, P, bestshape.kind, p->eps[bestshape.kind], p->cos_alpha[bestshape.kind], !filtered));
     if (filtered) RUN(rhk_component_filter(c, c->comp_beta, c->comp_conn26, nullptr));
     if (list_copy_pending) {   // the previous list must have left idx_out before it is written again
         RUNH(hipStreamWaitEvent(c->stream, c->ev_copied, 0));

@@ -71,6 +71,19 @@ extern "C" void rh_shape_finalize(rh_shape *s)
     if (s->kind == RH_CONE) rhfit::cone_finalize(s);   // deterministic cos / sin (det_math.h)
 }
 
+// a Float32 shape: fields rounded to binary32, the cone's cos / sin of -opang/2 as binary32 (cos / sin of a Float32 are
+// Float32 in Julia); the deterministic kernels of det_math.h evaluated on the binary32 angle, rounded once
+extern "C" void rh_shape_finalize_f32(rh_shape *s)
+{
+    if (!s) return;
+    for (int i = 0; i < 7; i++) s->v[i] = (double)(float)s->v[i];
+    if (s->kind == RH_CONE) {
+        const float th = -(float)s->v[6] / 2.0f;
+        s->v[7] = (double)(float)rh_cos((double)th);
+        s->v[8] = (double)(float)rh_sin((double)th);
+    }
+}
+
 extern "C" int rh_fit(int kind, const double *p, const double *n, int32_t lp, const rh_params *prm, rh_shape *out,
                       int32_t *fitted)
 {

@@ -14,63 +14,18 @@
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "rh_internal.h"
 #include "score_device.h"
-#include "score_device32.h"
 #include "score4_device.h"
 
 namespace {
 
 using namespace rhdev;
-using namespace rhdev32;
 
 // -------------------------------------------------------------- prep ------
-// Per-candidate constants of the CONSERVATIVE stages (box tests, band prefilter), in the record's free slots so that
-// stage 1 does not recompute them per (chunk, tile): f[11] = sum |f[0..6]| (the magnitude behind box_slack); cylinder:
-// f[8] = 1 + |c0|_1, f[9] = k = 2 - |a|^2, f[10] = 1 + |k| |a|^2 (closed-form rho^2 of the prefilter, score_device.h).
-__host__ __device__ inline void prep_derived(rh_prep &o, int kind)
-{
-    o.f[11] = (((((fabs(o.f[0]) + fabs(o.f[1])) + fabs(o.f[2])) + fabs(o.f[3])) + fabs(o.f[4])) + fabs(o.f[5])) + fabs(o.f[6]);
-    if (kind == RH_CYLINDER) {
-        const double a2 = (o.f[0] * o.f[0] + o.f[1] * o.f[1]) + o.f[2] * o.f[2];
-        const double k = 2.0 - a2;
-        o.f[8] = (1.0 + fabs(o.f[3])) + (fabs(o.f[4]) + fabs(o.f[5]));
-        o.f[9] = k;
-        o.f[10] = 1.0 + fabs(k) * a2;
-    }
-}
-
-__device__ __forceinline__ void prep_one(const rh_shape &s, rh_prep &o)
-{
-#pragma unroll
-    for (int i = 0; i < 12; i++) o.f[i] = 0.0;
-    const double sgn = s.outwards ? 1.0 : -1.0;
-    switch (s.kind) {
-    case RH_PLANE: {
-        for (int i = 0; i < 6; i++) o.f[i] = s.v[i];
-        const double a = s.v[3], b = s.v[4], c = s.v[5];
-        const double inv = 1.0 / sqrt((a * a + b * b) + c * c);   // o_z = normalize(plane.normal)
-        o.f[6] = inv * a; o.f[7] = inv * b; o.f[8] = inv * c;
-        break;
-    }
-    case RH_SPHERE:
-        for (int i = 0; i < 4; i++) o.f[i] = s.v[i];
-        o.f[4] = sgn;
-        break;
-    case RH_CYLINDER:
-        for (int i = 0; i < 7; i++) o.f[i] = s.v[i];
-        o.f[7] = sgn;
-        break;
-    default:
-        for (int i = 0; i < 6; i++) o.f[i] = s.v[i];
-        o.f[6] = s.v[7];   // cos(-opang/2)
-        o.f[7] = s.v[8];   // sin(-opang/2)
-        o.f[8] = sgn;
-        break;
-    }
-    prep_derived(o, s.kind);
-}
-
+// (the record makers themselves: prep_one / prep_derived, rh_internal.h)
 // thresholds and magnitudes behind the classifier / culling records (rh4::cls_make) the prep kernels leave beside the bins
 struct PreArgs { double eps[4]; double cosa[4]; double coord_mag, nrm_mag; int f32; float *box; int64_t bstride; };
 
@@ -193,10 +148,11 @@ __global__ void prep_entries_kernel(const rh_cand_entry *__restrict__ entries, c
 // registers) and walks the block's candidates; per candidate it issues PPT tests per
 // lane, PPT ballots, and one LDS atomic with the wave's popcount.
 // F32: the points are a Float32 cloud's (exactly converted), the test is the binary32 one on the float record that follows
-// from the candidate's binary64 record (prepf_of, score_device32.h) -- rh_ransac's liveness passes and small subsets
-template <int KIND, bool MASK, bool F32 = false>
+// from the candidate's binary64 record (prepf_of, rh_internal.h) -- every brute-force score of such a cloud.  T: how the
+// points are stored -- doubles (the disabled list, rh_ransac's subsets), or the float copy of subset 1 (batches)
+template <int KIND, bool MASK, bool F32 = false, typename T = double>
 __global__ void __launch_bounds__(RH_SC_THREADS)
-score_kernel(const double *__restrict__ pts, int64_t stride, int64_t s,
+score_kernel(const T *__restrict__ pts, int64_t stride, int64_t s,
              const uint64_t *__restrict__ enabled_words, const rh_prep *__restrict__ prep,
              const int32_t *__restrict__ orig, const int32_t *__restrict__ nk_ptr, double eps, double cosa,
              int32_t *__restrict__ counts, uint64_t *__restrict__ masks, int64_t mask_stride)
@@ -213,17 +169,17 @@ score_kernel(const double *__restrict__ pts, int64_t stride, int64_t s,
     if (tid < RH_SC_CT) lcnt[tid] = 0;
     __syncthreads();
 
-    const double *__restrict__ X = pts, *__restrict__ Y = pts + stride, *__restrict__ Z = pts + 2 * stride;
-    const double *__restrict__ NX = pts + 3 * stride, *__restrict__ NY = pts + 4 * stride,
-                 *__restrict__ NZ = pts + 5 * stride;
+    const T *__restrict__ X = pts, *__restrict__ Y = pts + stride, *__restrict__ Z = pts + 2 * stride;
+    const T *__restrict__ NX = pts + 3 * stride, *__restrict__ NY = pts + 4 * stride, *__restrict__ NZ = pts + 5 * stride;
     const int64_t ntiles = (s + RH_SC_TILE - 1) / RH_SC_TILE;
     const int64_t swords = (s + 63) >> 6;
     static_assert(RH_SC_CT == 64, "one lane per candidate of the tile");
+    static_assert(F32 || sizeof(T) == sizeof(double), "float points are a Float32 cloud's");
     int acc = 0;
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t wbase = tile * RH_SC_TILE + (int64_t)wave * RH_SC_WAVE_PTS;
-        double px[RH_SC_PPT], py[RH_SC_PPT], pz[RH_SC_PPT], qx[RH_SC_PPT], qy[RH_SC_PPT], qz[RH_SC_PPT];
+        T px[RH_SC_PPT], py[RH_SC_PPT], pz[RH_SC_PPT], qx[RH_SC_PPT], qy[RH_SC_PPT], qz[RH_SC_PPT];
         uint64_t en[RH_SC_PPT];
 #pragma unroll
         for (int p = 0; p < RH_SC_PPT; p++) {
@@ -243,8 +199,8 @@ score_kernel(const double *__restrict__ pts, int64_t stride, int64_t s,
             int n = 0;
 #pragma unroll
             for (int p = 0; p < RH_SC_PPT; p++) {
-                if (F32) bw[p] = test_point32<KIND>(prepf_of<KIND>(P), (float)px[p], (float)py[p], (float)pz[p], (float)qx[p], (float)qy[p],
-                                                    (float)qz[p], eps, cosa) & en[p];
+                if (F32) bw[p] = test_point<KIND>(prepf_of<KIND>(P), (float)px[p], (float)py[p], (float)pz[p], (float)qx[p], (float)qy[p],
+                                                  (float)qz[p], eps, cosa) & en[p];
                 else bw[p] = test_point<KIND>(P, px[p], py[p], pz[p], qx[p], qy[p], qz[p], eps, cosa) & en[p];
                 n += __popcll(bw[p]);
             }
@@ -363,39 +319,40 @@ __global__ void unpermute_masks_atomic_kernel(const uint64_t *__restrict__ in, c
 // wave mean more waves in flight, and with one word the compiler sinks the second half of the loads below the
 // wave-level early-out of the exact test (a word whose 64 points all fail the first half never fetches the other
 // three planes: 0.048 ms on a cloud of random normals).
-constexpr int RH_RF_WPW = 2;
+// The float scan of a Float32 cloud (24 B per point) keeps 4 words per wave: 24 loads in flight per lane.
+template <typename T> constexpr int RH_RF_WPW = 2;
+template <> constexpr int RH_RF_WPW<float> = 4;
 
-template <int KIND>
+template <int KIND, typename T, typename REC, int WPW>
 __global__ void __launch_bounds__(256)
-refit_mask_kernel(const double *__restrict__ pts, int64_t stride, int64_t n, int64_t nwords,
-                  const uint64_t *__restrict__ enabled, const rh_prep P, double eps, double cosa,
+refit_mask_kernel(const T *__restrict__ pts, int64_t stride, int64_t n, int64_t nwords,
+                  const uint64_t *__restrict__ enabled, const REC P, double eps, double cosa,
                   uint64_t *__restrict__ mask_out)
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    const double *__restrict__ X = pts, *__restrict__ Y = pts + stride, *__restrict__ Z = pts + 2 * stride;
-    const double *__restrict__ NX = pts + 3 * stride, *__restrict__ NY = pts + 4 * stride,
-                 *__restrict__ NZ = pts + 5 * stride;
-    const int64_t ngroups = (nwords + RH_RF_WPW - 1) / RH_RF_WPW;
+    const T *__restrict__ X = pts, *__restrict__ Y = pts + stride, *__restrict__ Z = pts + 2 * stride;
+    const T *__restrict__ NX = pts + 3 * stride, *__restrict__ NY = pts + 4 * stride, *__restrict__ NZ = pts + 5 * stride;
+    const int64_t ngroups = (nwords + WPW - 1) / WPW;
     for (int64_t g = wave0; g < ngroups; g += nwaves) {
-        const int64_t w0 = g * RH_RF_WPW;
-        uint64_t en[RH_RF_WPW];
-        double px[RH_RF_WPW], py[RH_RF_WPW], pz[RH_RF_WPW], qx[RH_RF_WPW], qy[RH_RF_WPW], qz[RH_RF_WPW];
+        const int64_t w0 = g * WPW;
+        uint64_t en[WPW];
+        T px[WPW], py[WPW], pz[WPW], qx[WPW], qy[WPW], qz[WPW];
 #pragma unroll
-        for (int k = 0; k < RH_RF_WPW; k++) {
+        for (int k = 0; k < WPW; k++) {
             const int64_t w = w0 + k;
             en[k] = w < nwords ? (enabled[w] & valid_mask(w << 6, n)) : 0ULL;
         }
 #pragma unroll
-        for (int k = 0; k < RH_RF_WPW; k++) {
+        for (int k = 0; k < WPW; k++) {
             // an all-disabled word re-reads the (L2-hot) first line of the planes instead of streaming its 3 KB
             const int64_t i = (en[k] != 0 ? ((w0 + k) << 6) : (int64_t)0) + lane;
             px[k] = X[i]; py[k] = Y[i]; pz[k] = Z[i];
             qx[k] = NX[i]; qy[k] = NY[i]; qz[k] = NZ[i];
         }
 #pragma unroll
-        for (int k = 0; k < RH_RF_WPW; k++) {
+        for (int k = 0; k < WPW; k++) {
             const uint64_t b = test_point<KIND>(P, px[k], py[k], pz[k], qx[k], qy[k], qz[k], eps, cosa) & en[k];
             if (lane == 0 && w0 + k < nwords) mask_out[w0 + k] = b;
         }
@@ -647,7 +604,7 @@ __device__ __forceinline__ void live_kind(const rh_live_args &A, const double (&
             const rh_prepf Pf = prepf_of<KIND>(P);
 #pragma unroll
             for (int p = 0; p < RH_SC_PPT; p++)
-                hit |= test_point32<KIND>(Pf, (float)px[p], (float)py[p], (float)pz[p], (float)qx[p], (float)qy[p], (float)qz[p], eps, cosa) & vm[p];
+                hit |= test_point<KIND>(Pf, (float)px[p], (float)py[p], (float)pz[p], (float)qx[p], (float)qy[p], (float)qz[p], eps, cosa) & vm[p];
         } else {
 #pragma unroll
             for (int p = 0; p < RH_SC_PPT; p++)
@@ -831,10 +788,22 @@ __global__ void gather_prep_kernel(const rh_prep *__restrict__ src, const int32_
     if (i < n) dst[i] = src[idx[i]];
 }
 
-inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// the one spelling of "which kind": f is a generic lambda that gets the kind as an integral constant
+template <typename F>
+int with_kind(int kind, F &&f)
+{
+    switch (kind) {
+    case RH_PLANE: return f(std::integral_constant<int, RH_PLANE>());
+    case RH_SPHERE: return f(std::integral_constant<int, RH_SPHERE>());
+    case RH_CYLINDER: return f(std::integral_constant<int, RH_CYLINDER>());
+    case RH_CONE: return f(std::integral_constant<int, RH_CONE>());
+    }
+    rh_set_error("unknown shape kind %d", kind);
+    return RH_E_INVALID;
+}
 
-template <int KIND>
-int launch_score(rh_cloud *c, const double *pts, int64_t stride, int64_t s, const uint64_t *en,
+template <int KIND, typename T>
+int launch_score(rh_cloud *c, const T *pts, int64_t stride, int64_t s, const uint64_t *en,
                  const rh_prep *prep, const int32_t *orig, const int32_t *nk, int32_t nk_bound, double eps,
                  double cosa, int32_t *counts, uint64_t *masks, int64_t mask_stride)
 {
@@ -852,58 +821,34 @@ int launch_score(rh_cloud *c, const double *pts, int64_t stride, int64_t s, cons
     if (splits < 1) splits = 1;
     if (splits > ntiles) splits = ntiles;
     dim3 grid((unsigned)splits, (unsigned)ctiles);
-    if (c->f32) {
+    constexpr bool FLT = sizeof(T) == sizeof(float);
+    if (FLT || c->f32) {
         if (masks)
-            hipLaunchKernelGGL((score_kernel<KIND, true, true>), grid, dim3(RH_SC_THREADS), 0, c->stream, pts, stride, s, en,
+            hipLaunchKernelGGL((score_kernel<KIND, true, true, T>), grid, dim3(RH_SC_THREADS), 0, c->stream, pts, stride, s, en,
                                prep, orig, nk, eps, cosa, counts, masks, mask_stride);
         else
-            hipLaunchKernelGGL((score_kernel<KIND, false, true>), grid, dim3(RH_SC_THREADS), 0, c->stream, pts, stride, s, en,
+            hipLaunchKernelGGL((score_kernel<KIND, false, true, T>), grid, dim3(RH_SC_THREADS), 0, c->stream, pts, stride, s, en,
                                prep, orig, nk, eps, cosa, counts, masks, mask_stride);
     } else if (masks)
-        hipLaunchKernelGGL((score_kernel<KIND, true>), grid, dim3(RH_SC_THREADS), 0, c->stream, pts, stride, s, en,
+        hipLaunchKernelGGL((score_kernel<KIND, true, FLT, T>), grid, dim3(RH_SC_THREADS), 0, c->stream, pts, stride, s, en,
                            prep, orig, nk, eps, cosa, counts, masks, mask_stride);
     else
-        hipLaunchKernelGGL((score_kernel<KIND, false>), grid, dim3(RH_SC_THREADS), 0, c->stream, pts, stride, s, en,
+        hipLaunchKernelGGL((score_kernel<KIND, false, FLT, T>), grid, dim3(RH_SC_THREADS), 0, c->stream, pts, stride, s, en,
                            prep, orig, nk, eps, cosa, counts, masks, mask_stride);
     RH_HIP(hipGetLastError());
     return RH_OK;
+}
+
+template <typename T, typename... A>
+int score_kind(rh_cloud *c, int kind, const T *pts, A... a)
+{
+    return with_kind(kind, [&](auto K) { return launch_score<K.value>(c, pts, a...); });
 }
 
 }  // namespace
 
 int rhk_compact_generic(hipStream_t stream, const uint64_t *mask, int64_t nwords, int32_t *ws_block_sums,
                         int64_t *idx_out, int64_t cap, int32_t *d_total);
-
-// host twin of prep_one (used when the candidate is passed by value as a kernel argument)
-void rh_prep_host(const rh_shape &s, rh_prep *o)
-{
-    for (int i = 0; i < 12; i++) o->f[i] = 0.0;
-    const double sgn = s.outwards ? 1.0 : -1.0;
-    switch (s.kind) {
-    case RH_PLANE: {
-        for (int i = 0; i < 6; i++) o->f[i] = s.v[i];
-        const double a = s.v[3], b = s.v[4], c = s.v[5];
-        const double inv = 1.0 / __builtin_sqrt((a * a + b * b) + c * c);
-        o->f[6] = inv * a; o->f[7] = inv * b; o->f[8] = inv * c;
-        break;
-    }
-    case RH_SPHERE:
-        for (int i = 0; i < 4; i++) o->f[i] = s.v[i];
-        o->f[4] = sgn;
-        break;
-    case RH_CYLINDER:
-        for (int i = 0; i < 7; i++) o->f[i] = s.v[i];
-        o->f[7] = sgn;
-        break;
-    default:
-        for (int i = 0; i < 6; i++) o->f[i] = s.v[i];
-        o->f[6] = s.v[7];
-        o->f[7] = s.v[8];
-        o->f[8] = sgn;
-        break;
-    }
-    prep_derived(*o, s.kind);
-}
 
 int rhk_transpose_aos(rh_cloud *c, const double *d_xyz, const double *d_nrm, int64_t n, const int32_t *d_gather,
                       int64_t count, double *dst, int64_t dst_stride)
@@ -1041,14 +986,34 @@ int rhk_score_kind(rh_cloud *c, int kind, const double *pts, int64_t stride, int
                    const rh_prep *d_prep, const int32_t *d_orig, const int32_t *d_nk, int32_t nk_bound, double eps,
                    double cosa, int32_t *d_counts, uint64_t *d_masks, int64_t mask_stride)
 {
-    switch (kind) {
-    case RH_PLANE: return launch_score<RH_PLANE>(c, pts, stride, s, en, d_prep, d_orig, d_nk, nk_bound, eps, cosa, d_counts, d_masks, mask_stride);
-    case RH_SPHERE: return launch_score<RH_SPHERE>(c, pts, stride, s, en, d_prep, d_orig, d_nk, nk_bound, eps, cosa, d_counts, d_masks, mask_stride);
-    case RH_CYLINDER: return launch_score<RH_CYLINDER>(c, pts, stride, s, en, d_prep, d_orig, d_nk, nk_bound, eps, cosa, d_counts, d_masks, mask_stride);
-    case RH_CONE: return launch_score<RH_CONE>(c, pts, stride, s, en, d_prep, d_orig, d_nk, nk_bound, eps, cosa, d_counts, d_masks, mask_stride);
-    }
-    rh_set_error("unknown shape kind %d", kind);
-    return RH_E_INVALID;
+    return score_kind(c, kind, pts, stride, s, en, d_prep, d_orig, d_nk, nk_bound, eps, cosa, d_counts, d_masks, mask_stride);
+}
+
+int rhk_score_kind(rh_cloud *c, int kind, const float *pts, int64_t stride, int64_t s, const uint64_t *en,
+                   const rh_prep *d_prep, const int32_t *d_orig, const int32_t *d_nk, int32_t nk_bound, double eps,
+                   double cosa, int32_t *d_counts, uint64_t *d_masks, int64_t mask_stride)
+{
+    return score_kind(c, kind, pts, stride, s, en, d_prep, d_orig, d_nk, nk_bound, eps, cosa, d_counts, d_masks, mask_stride);
+}
+
+// the streaming scan over the planes of the cloud's element type, with the candidate's record in that type
+template <typename T, typename REC>
+static int launch_refit(rh_cloud *c, const T *pts, const REC &P, int kind, double eps, double cosa)
+{
+    constexpr int WPW = RH_RF_WPW<T>;
+    const int env_blocks = (int)rh_opt_int(c, RH_OPT_REFIT_BLOCKS, 0);
+    int64_t blocks = cdiv(c->nwords, 4 * WPW);
+    // one group of words per wave up to 32768 blocks, a grid-stride loop beyond (measured with 4-word groups, plane
+    // scan: 10M points 0.0771 ms at 2048 blocks, 0.0743 at 4096-9766; 50M points 0.364 ms at 2048, 0.350 at 32768+)
+    const int64_t cap = env_blocks > 0 ? env_blocks : 32768;
+    if (blocks > cap) blocks = cap;
+    RH_TRY(with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((refit_mask_kernel<K.value, T, REC, WPW>), dim3((unsigned)blocks), dim3(256), 0, c->stream, pts, c->n_pad, c->n,
+                           c->nwords, c->enabled, P, eps, cosa, c->refit_mask);
+        return RH_OK;
+    }));
+    RH_HIP(hipGetLastError());
+    return RH_OK;
 }
 
 int rhk_refit_mask(rh_cloud *c, const rh_prep &P, int kind, double eps, double cosa, bool apply)
@@ -1062,26 +1027,7 @@ int rhk_refit_mask(rh_cloud *c, const rh_prep &P, int kind, double eps, double c
         c->k_sums_ready = apply;
         return RH_OK;
     }
-    const int env_blocks = (int)rh_opt_int(c, RH_OPT_REFIT_BLOCKS, 0);
-    int64_t blocks = cdiv(c->nwords, 4 * RH_RF_WPW);
-    // one group of words per wave up to 32768 blocks, a grid-stride loop beyond (measured with 4-word groups, plane
-    // scan: 10M points 0.0771 ms at 2048 blocks, 0.0743 at 4096-9766; 50M points 0.364 ms at 2048, 0.350 at 32768+)
-    const int64_t cap = env_blocks > 0 ? env_blocks : 32768;
-    if (blocks > cap) blocks = cap;
-    dim3 grid((unsigned)blocks), blk(256);
-#define RH_LAUNCH_REFIT(K)                                                                                        \
-    hipLaunchKernelGGL((refit_mask_kernel<K>), grid, blk, 0, c->stream, c->full, c->n_pad, c->n, c->nwords,       \
-                       c->enabled, P, eps, cosa, c->refit_mask)
-    switch (kind) {
-    case RH_PLANE: RH_LAUNCH_REFIT(RH_PLANE); break;
-    case RH_SPHERE: RH_LAUNCH_REFIT(RH_SPHERE); break;
-    case RH_CYLINDER: RH_LAUNCH_REFIT(RH_CYLINDER); break;
-    case RH_CONE: RH_LAUNCH_REFIT(RH_CONE); break;
-    default: rh_set_error("unknown shape kind %d", kind); return RH_E_INVALID;
-    }
-#undef RH_LAUNCH_REFIT
-    RH_HIP(hipGetLastError());
-    return RH_OK;
+    return c->f32 ? launch_refit(c, c->full32, prepf_of_kind(P, kind), kind, eps, cosa) : launch_refit(c, c->full, P, kind, eps, cosa);
 }
 
 int rhk_compact_mask(rh_cloud *c, const uint64_t *mask, int64_t nwords, int64_t *idx_out, int64_t cap,

@@ -24,15 +24,10 @@
 
 #include "rh_internal.h"
 #include "score_device.h"
-#include "score_device32.h"
 
 namespace {
 
 using namespace rhdev;
-using rhdev32::rh_prepf;
-
-inline unsigned cdivk(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
-
 __device__ __forceinline__ uint64_t spread21_dev(uint64_t v)
 {
     v &= 0x1FFFFFULL;
@@ -72,7 +67,7 @@ invert_perm_kernel(const int32_t *__restrict__ perm, int64_t n, int32_t *__restr
 }
 
 __global__ void __launch_bounds__(256)
-to_float_k(const double *__restrict__ src, int64_t count, float *__restrict__ dst)
+to_float_kernel(const double *__restrict__ src, int64_t count, float *__restrict__ dst)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) dst[i] = (float)src[i];
@@ -115,21 +110,7 @@ refitk_boxes_kernel(const double *__restrict__ gb, int64_t gstride, int64_t ng, 
 }
 
 // ---- pass 2: one wave per listed group --------------------------------------------------------------------------
-template <int KIND>
-__device__ __forceinline__ uint64_t exact64(const rh_prep &P, double px, double py, double pz, double qx, double qy, double qz,
-                                            double eps, double cosa)
-{
-    return test_point<KIND>(P, px, py, pz, qx, qy, qz, eps, cosa);
-}
-
-template <int KIND>
-__device__ __forceinline__ uint64_t exact32(const rh_prepf &P, float px, float py, float pz, float qx, float qy, float qz,
-                                            double eps, double cosa)
-{
-    return rhdev32::test_point32<KIND>(P, px, py, pz, qx, qy, qz, eps, cosa);
-}
-
-template <int KIND, bool F32, typename T, typename PREP>
+template <int KIND, typename T, typename PREP>
 __global__ void __launch_bounds__(256)
 refitk_groups_kernel(const T *__restrict__ pts, int64_t stride, int64_t n, const int32_t *__restrict__ perm,
                      uint64_t *__restrict__ men, int apply, const PREP P, double eps, double cosa,
@@ -147,10 +128,7 @@ refitk_groups_kernel(const T *__restrict__ pts, int64_t stride, int64_t n, const
         const T px = X[i], py = Y[i], pz = Z[i], qx = NX[i], qy = NY[i], qz = NZ[i];
         const int32_t o = perm[i < n ? i : g << 6];
         const uint64_t en = men[g] & valid_mask(g << 6, n);
-        uint64_t b;
-        if constexpr (F32) b = exact32<KIND>(P, px, py, pz, qx, qy, qz, eps, cosa);
-        else b = exact64<KIND>(P, px, py, pz, qx, qy, qz, eps, cosa);
-        b &= en;
+        const uint64_t b = test_point<KIND>(P, px, py, pz, qx, qy, qz, eps, cosa) & en;
         if (b == 0) continue;
         // one byte per inlier at its ORIGINAL index -- a plain store: bit atomics on the mask words serialise (a shape's
         // points are often neighbours in the original order as well: 64 atomics per word, 50 us at 175 000 inliers)
@@ -233,13 +211,13 @@ int rhk_korder_build(rh_cloud *c, const double *d_xyz, const double *d_nrm, cons
     KH(hipMemsetAsync(c->kflag, 0, (size_t)c->n_pad, c->stream));
     KH(hipMemsetAsync(c->fullk, 0, sizeof(double) * 6 * (size_t)c->n_pad, c->stream));
     KH(hipMemsetAsync(c->kgb, 0, sizeof(double) * 7 * (size_t)c->kg_pad, c->stream));
-    hipLaunchKernelGGL(morton_kernel, dim3(cdivk(n, 256)), dim3(256), 0, c->stream, d_xyz, n, lo[0], lo[1], lo[2], size, code_in,
+    hipLaunchKernelGGL(morton_kernel, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, d_xyz, n, lo[0], lo[1], lo[2], size, code_in,
                        idx_in);
     // stable LSD radix sort of (code, index) pairs by code: equal codes keep ascending indices = sort by (code, index)
     KH(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, code_in, c->oct_code, idx_in, c->oct_perm, (int)n, 0, 63, c->stream));
     KH(hipMalloc(&tmp, tmp_bytes > 0 ? tmp_bytes : 1));
     KH(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, code_in, c->oct_code, idx_in, c->oct_perm, (int)n, 0, 63, c->stream));
-    hipLaunchKernelGGL(invert_perm_kernel, dim3(cdivk(n, 256)), dim3(256), 0, c->stream, c->oct_perm, n, c->oct_pos);
+    hipLaunchKernelGGL(invert_perm_kernel, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, c->oct_perm, n, c->oct_pos);
     KH(hipGetLastError());
     int rc = rhk_transpose_aos(c, d_xyz, d_nrm, n, c->oct_perm, n, c->fullk, c->n_pad);
     if (rc == RH_OK) rc = rhk_group_bounds_of(c, c->fullk, c->n_pad, n, c->nwords, c->kgb, c->kg_pad);
@@ -251,11 +229,19 @@ int rhk_korder_build(rh_cloud *c, const double *d_xyz, const double *d_nrm, cons
     return RH_OK;
 }
 
-int rhk_korder_build_f32(rh_cloud *c)
+// Float32 cloud: the float copies of the cloud in original order and of subset 1 (full32, sub32: the caller's
+// allocations) and of the Morton order (the values are binary32 numbers: the conversion is exact)
+int rhk_f32_build(rh_cloud *c)
 {
-    if (!c->k_built) return RH_OK;
-    RH_HIP(hipMalloc((void **)&c->fullk32, sizeof(float) * 6 * (size_t)c->n_pad));
-    hipLaunchKernelGGL(to_float_k, dim3(cdivk(6 * c->n_pad, 256)), dim3(256), 0, c->stream, c->fullk, 6 * c->n_pad, c->fullk32);
+    auto to_float = [&](const double *src, int64_t count, float *dst) {
+        if (count > 0) hipLaunchKernelGGL(to_float_kernel, dim3(cdiv(count, 256)), dim3(256), 0, c->stream, src, count, dst);
+    };
+    to_float(c->full, 6 * c->n_pad, c->full32);
+    to_float(c->sub, 6 * c->s_pad, c->sub32);
+    if (c->k_built) {
+        RH_HIP(hipMalloc((void **)&c->fullk32, sizeof(float) * 6 * (size_t)c->n_pad));
+        to_float(c->fullk, 6 * c->n_pad, c->fullk32);
+    }
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
@@ -280,18 +266,19 @@ bool rhk_refit_is_culled(const rh_cloud *c)
     return c->n >= RH_KREFIT_MIN;
 }
 
-template <bool F32, typename T, typename PREP>
+template <typename T, typename PREP>
 static int launch_refitk(rh_cloud *c, const T *pts, const PREP &PX, const rh_prep &P, int kind, double eps, double cosa, bool apply)
 {
     RH_TRY(rhk_korder_sync_enabled(c));
     const int64_t ng = c->nwords;
-    const dim3 g1(cdivk(ng, 256)), blk(256);
+    const dim3 g1(cdiv(ng, 256)), blk(256);
     // pass 2 learns the list length on the device: a grid that covers a long list with a few groups per wave
     int64_t b2 = (ng + 3) / 4;
     if (b2 > 2048) b2 = 2048;
     const dim3 g2((unsigned)b2);
     const int ap = apply ? 1 : 0;
     const int dbg = rh_opt_on(c, RH_OPT_KREFIT_DBG) ? 1 : 0;
+    constexpr bool F32 = sizeof(T) == sizeof(float);   // (the box tests' slack follows the exact test's precision)
 #define RH_K(K)                                                                                                              \
     do {                                                                                                                     \
         hipLaunchKernelGGL((refitk_boxes_kernel<K, F32>), g1, blk, 0, c->stream, c->kgb, c->kg_pad, ng, c->n, c->oct_men, P, eps, \
@@ -302,7 +289,7 @@ static int launch_refitk(rh_cloud *c, const T *pts, const PREP &PX, const rh_pre
             (void)hipStreamSynchronize(c->stream);                                                                           \
             fprintf(stderr, "[refitk] kind %d: %d of %lld groups survive the box test\n", kind, cnt, (long long)ng);         \
         }                                                                                                                    \
-        hipLaunchKernelGGL((refitk_groups_kernel<K, F32, T, PREP>), g2, blk, 0, c->stream, pts, c->n_pad, c->n, c->oct_perm,  \
+        hipLaunchKernelGGL((refitk_groups_kernel<K, T, PREP>), g2, blk, 0, c->stream, pts, c->n_pad, c->n, c->oct_perm,  \
                            c->oct_men, ap, PX, eps, cosa, c->klist, c->kctr, c->kflag);                                      \
         hipLaunchKernelGGL(refitk_flags_kernel, dim3((unsigned)c->nblocks), blk, 0, c->stream, c->kflag, ng, c->refit_mask,  \
                            c->kctr, c->block_sums);                                                                          \
@@ -319,15 +306,11 @@ static int launch_refitk(rh_cloud *c, const T *pts, const PREP &PX, const rh_pre
     return RH_OK;
 }
 
+// P: the shape's binary64 record (the box tests run on it whatever the cloud); a Float32 cloud's exact test runs on its
+// float planes with the float record that follows from P
 int rhk_refitk_mask(rh_cloud *c, const rh_prep &P, int kind, double eps, double cosa, bool apply)
 {
     if (c->nwords == 0) return RH_OK;
-    return launch_refitk<false, double, rh_prep>(c, c->fullk, P, P, kind, eps, cosa, apply);
-}
-
-// Float32 cloud: `prepf` is the float record of the shape (rhdev32::rh_prepf), P its binary64 record for the box tests
-int rhk_refitk_mask_f32(rh_cloud *c, const void *prepf, const rh_prep &P, int kind, double eps, double cosa, bool apply)
-{
-    if (c->nwords == 0) return RH_OK;
-    return launch_refitk<true, float, rh_prepf>(c, c->fullk32, *(const rh_prepf *)prepf, P, kind, eps, cosa, apply);
+    if (c->f32) return launch_refitk(c, c->fullk32, prepf_of_kind(P, kind), P, kind, eps, cosa, apply);
+    return launch_refitk(c, c->fullk, P, P, kind, eps, cosa, apply);
 }

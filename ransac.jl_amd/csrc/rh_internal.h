@@ -27,6 +27,8 @@ void rh_set_error(const char *fmt, ...);
         if (rc_ != RH_OK) return rc_; \
     } while (0)
 
+static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }   // blocks of b that cover a
+
 // ---- options (options.cpp): what rh_set_option stores; the diag build also reads the RH_* environment ---------
 enum rh_opt_id {
     RH_OPT_SCORE_PATH = 0,      // product keys (rh_set_option, include/ransac_hip.h)
@@ -69,6 +71,87 @@ struct rh_prep {
     double f[12];
 };
 
+// Per-candidate constants of the CONSERVATIVE stages (box tests, band prefilter), in the record's free slots so that
+// stage 1 does not recompute them per (chunk, tile): f[11] = sum |f[0..6]| (the magnitude behind box_slack); cylinder:
+// f[8] = 1 + |c0|_1, f[9] = k = 2 - |a|^2, f[10] = 1 + |k| |a|^2 (closed-form rho^2 of the prefilter, score_device.h).
+__host__ __device__ inline void prep_derived(rh_prep &o, int kind)
+{
+    o.f[11] = (((((fabs(o.f[0]) + fabs(o.f[1])) + fabs(o.f[2])) + fabs(o.f[3])) + fabs(o.f[4])) + fabs(o.f[5])) + fabs(o.f[6]);
+    if (kind == RH_CYLINDER) {
+        const double a2 = (o.f[0] * o.f[0] + o.f[1] * o.f[1]) + o.f[2] * o.f[2];
+        const double k = 2.0 - a2;
+        o.f[8] = (1.0 + fabs(o.f[3])) + (fabs(o.f[4]) + fabs(o.f[5]));
+        o.f[9] = k;
+        o.f[10] = 1.0 + fabs(k) * a2;
+    }
+}
+
+// the record of a shape: on the device in the prep kernels, on the host where a candidate is passed by value as a kernel
+// argument (both builds: no contraction, IEEE sqrt and divide -- the same bits)
+__host__ __device__ __forceinline__ void prep_one(const rh_shape &s, rh_prep &o)
+{
+#pragma unroll
+    for (int i = 0; i < 12; i++) o.f[i] = 0.0;
+    const double sgn = s.outwards ? 1.0 : -1.0;
+    switch (s.kind) {
+    case RH_PLANE: {
+        for (int i = 0; i < 6; i++) o.f[i] = s.v[i];
+        const double a = s.v[3], b = s.v[4], c = s.v[5];
+        const double inv = 1.0 / sqrt((a * a + b * b) + c * c);   // o_z = normalize(plane.normal)
+        o.f[6] = inv * a; o.f[7] = inv * b; o.f[8] = inv * c;
+        break;
+    }
+    case RH_SPHERE:
+        for (int i = 0; i < 4; i++) o.f[i] = s.v[i];
+        o.f[4] = sgn;
+        break;
+    case RH_CYLINDER:
+        for (int i = 0; i < 7; i++) o.f[i] = s.v[i];
+        o.f[7] = sgn;
+        break;
+    default:
+        for (int i = 0; i < 6; i++) o.f[i] = s.v[i];
+        o.f[6] = s.v[7];   // cos(-opang/2)
+        o.f[7] = s.v[8];   // sin(-opang/2)
+        o.f[8] = sgn;
+        break;
+    }
+    prep_derived(o, s.kind);
+}
+inline void rh_prep_host(const rh_shape &s, rh_prep *out) { prep_one(s, *out); }
+
+// The float record of a candidate on a Float32 cloud, from its binary64 record: the record's leading fields are the
+// shape's own numbers (+ sgn), so the casts are exact for a Float32 shape, whose fields are binary32 numbers, and one
+// rounding for any other; a plane's normalised normal (f[6..8]) is recomputed in binary32 (plane.jl:85 on a Float32
+// plane).  Every kernel holds rh_prep records only and derives this one where it runs the binary32 test.
+struct rh_prepf {
+    float f[12];
+};
+template <int KIND>
+__host__ __device__ inline rh_prepf prepf_of(const rh_prep &P)
+{
+    rh_prepf o;
+    for (int i = 0; i < 9; i++) o.f[i] = (float)P.f[i];
+    for (int i = 9; i < 12; i++) o.f[i] = 0.0f;
+    if (KIND == RH_PLANE) {
+        const float a = o.f[3], b = o.f[4], c = o.f[5];
+        const float inv = 1.0f / sqrtf((a * a + b * b) + c * c);
+        o.f[6] = inv * a; o.f[7] = inv * b; o.f[8] = inv * c;
+    }
+    if (KIND == RH_SPHERE) { o.f[5] = o.f[6] = o.f[7] = o.f[8] = 0.0f; }
+    if (KIND == RH_CYLINDER) { o.f[8] = 0.0f; }
+    return o;
+}
+__host__ __device__ inline rh_prepf prepf_of_kind(const rh_prep &P, int kind)
+{
+    switch (kind) {
+    case RH_PLANE: return prepf_of<RH_PLANE>(P);
+    case RH_SPHERE: return prepf_of<RH_SPHERE>(P);
+    case RH_CYLINDER: return prepf_of<RH_CYLINDER>(P);
+    default: return prepf_of<RH_CONE>(P);
+    }
+}
+
 // score kernel geometry (kernels.hip)
 constexpr int RH_SC_THREADS = 256;
 constexpr int RH_SC_PPT = 4;                             // points per lane
@@ -107,7 +190,6 @@ struct rh_batch_ws {
     rh_shape *d_shapes = nullptr;      // [batch_cap]
     rh_prep *d_prep = nullptr;         // [4 * batch_cap], kind-major
     int32_t *d_orig = nullptr, *d_counts = nullptr;   // [4 * batch_cap], [batch_cap]
-    void *d_prep32 = nullptr;          // [4 * batch_cap] float records (rh_prepf) of a Float32 cloud's bins (f32.hip)
     void *d_qpre = nullptr;            // [4 * batch_cap] classifier records (rh4::rh_cls, 64 B) of the bins in d_prep; culling records: d_box
     float *d_box = nullptr;            // [RH_BOX_FIELDS][4 * batch_cap] culling records of the same bins (v4 score kernel), structure of arrays
     bool qpre_v4 = false;              // ... made by the last prep kernel (for the thresholds it was given)
@@ -169,8 +251,6 @@ struct rh_score_job {
     const int32_t *stop = nullptr;     // chained octree windows: the window's stop flag as the score kernel sees it
     bool open_count = false;           // `bound` is a guess (windows of the candidate loop): a tail launch covers a longer list
     hipEvent_t ev_listed = nullptr;    // timed launches: recorded behind the list launch, in front of the score launch
-    const rh_shape *shapes = nullptr;  // Float32 clouds, brute-force kernel: the batch's shapes on the device ...
-    int shapes_via_orig = 0;           // ... indexed through the bins' orig (caller's order) or directly (sorted like the bins)
 };
 struct rh_cloud {
     int64_t opt[RH_OPT_COUNT];         // rh_set_option on this cloud (RH_OPTION_UNSET: the process-wide value holds); rh_opt_init_cloud
@@ -309,11 +389,11 @@ struct rh_cloud {
     int64_t *d_ranks = nullptr;        // select in/out
     int64_t ranks_cap = 0;
 
-    // Float32 clouds (rh_cloud_create_f32; f32.hip): float copies of the two point sets (the float candidate records: rh_batch_ws)
+    // Float32 clouds (rh_cloud_create_f32): float copies of the two point sets (fullk32: the Morton-order twin of full32)
     bool f32 = false;
-    bool f32_groups = false;           // scored by the culled kernel (exact test in binary32); else by the brute-force float kernel
+    bool f32_groups = false;           // scored by the culled kernel; else by the brute-force kernel (both: exact test in binary32)
     float *full32 = nullptr;           // 6 planes x n_pad, original order (the refit scan streams these: 24 B per point)
-    float *sub32 = nullptr;            // 6 planes x s_pad, subset 1 in k-d leaf order
+    float *sub32 = nullptr;            // 6 planes x s_pad, subset 1 in k-d leaf order (the brute-force batch score reads these)
 
     // rh_ransac_mp: this process's share of every iteration's minimal sets (set j belongs to rank j % world)
     int32_t mp_rank = 0, mp_world = 1;
@@ -387,31 +467,29 @@ int rhk_score_kind(rh_cloud *c, int kind, const double *pts, int64_t stride, int
                    const uint64_t *enabled_words_or_null, const rh_prep *d_prep, const int32_t *d_orig,
                    const int32_t *d_nk, int32_t nk_bound, double eps, double cosa, int32_t *d_counts,
                    uint64_t *d_masks_or_null, int64_t mask_stride);
+int rhk_score_kind(rh_cloud *c, int kind, const float *pts, int64_t stride, int64_t s,   // ... over float planes (Float32 cloud: sub32)
+                   const uint64_t *enabled_words_or_null, const rh_prep *d_prep, const int32_t *d_orig,
+                   const int32_t *d_nk, int32_t nk_bound, double eps, double cosa, int32_t *d_counts,
+                   uint64_t *d_masks_or_null, int64_t mask_stride);
 int rhk_gb32_build(rh_cloud *c);   // (score4.hip: gb32 from gb)
 int rhk_store_cls(rh_cloud *c, const rh_prep *const prep[4], const int32_t n[4], const int32_t pbase[5], const double eps[4],
                   const double cosa[4], void *d_cls, float *d_box, int64_t bstride);
 int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, rh_score_job job);   // the same over dis[first, first + cnt): fills in job.points
-// Float32 clouds (f32.hip); the brute-force pair takes bins whose sizes lie side by side (job.nk[k] = job.nk[0] + k)
-int rhk_f32_build(rh_cloud *c);
-int rhk_prep_f32(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t nmax);   // job.shapes -> w.d_prep32
-int rhk_score_all_f32(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job);
-int rhk_refit_mask_f32(rh_cloud *c, const rh_shape &shape, double eps, double cosa, bool apply = false);
 int rhk_cloud_aabb(rh_cloud *c, const double *d_xyz, int64_t n, double lo[3], double hi[3], bool has[3], double *mag);   // kdorder.hip
 int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const int32_t *d_idx0);   // kdorder.hip: subset 1's k-d leaf order on the device
 int rhk_score_kind_dis(rh_cloud *c, int kind, int64_t first, int64_t cnt, const rh_prep *d_prep, const int32_t *d_orig,
                        const int32_t *d_nk, int32_t nk_bound, double eps, double cosa, int32_t *d_counts);
 int rhk_group_bounds(rh_cloud *c);
 int rhk_unpermute_masks(rh_cloud *c, const uint64_t *d_in, int32_t b, uint64_t *d_out);
-// refit_mask = the shape's inliers among the enabled points (original order); `apply`: the caller follows up with
-// rhk_compact_refit_apply, so a culled scan may clear the Morton-order enabled bits on the way
+// refit_mask = the shape's inliers among the enabled points (original order), by the cloud's element type; `apply`: the
+// caller follows up with rhk_compact_refit_apply, so a culled scan may clear the Morton-order enabled bits on the way
 int rhk_refit_mask(rh_cloud *c, const rh_prep &P, int kind, double eps, double cosa, bool apply = false);
 // korder.hip
 int rhk_korder_build(rh_cloud *c, const double *d_xyz, const double *d_nrm, const double lo[3], double size, double mag);
-int rhk_korder_build_f32(rh_cloud *c);
+int rhk_f32_build(rh_cloud *c);   // full32, sub32 (the caller's allocations) and fullk32 of a Float32 cloud
 int rhk_korder_sync_enabled(rh_cloud *c);
 bool rhk_refit_is_culled(const rh_cloud *c);
 int rhk_refitk_mask(rh_cloud *c, const rh_prep &P, int kind, double eps, double cosa, bool apply);
-int rhk_refitk_mask_f32(rh_cloud *c, const void *prepf, const rh_prep &P, int kind, double eps, double cosa, bool apply);
 int rhk_group_bounds_of(rh_cloud *c, const double *pts, int64_t stride, int64_t count, int64_t ngroups, double *gb, int64_t gstride);
 int rhk_oct_build_tab(rh_cloud *c);                                     // the sampler's cell directory (needs oct_depth)
 int rhk_oct_gather_enabled(rh_cloud *c);                                // oct_men = enabled in Morton order
@@ -524,7 +602,6 @@ int rhk_oct_sync_enabled(rh_cloud *c);                                  // men =
 int rhk_oct_clear_mask(rh_cloud *c, const uint64_t *mask);             // clear the bits of an original-order mask
 int rhk_word_prefix(rh_cloud *c, const uint64_t *words, int64_t nwords, int32_t *prefix_out);
 
-void rh_prep_host(const rh_shape &s, rh_prep *out);
 int32_t rh_spread_multiplier(int32_t b);   // t -> (t * m) mod b: a permutation of the batch that separates neighbours
 
 // ---- host helpers (cloud.hip) -----------------------------------------------

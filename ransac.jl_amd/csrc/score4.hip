@@ -34,13 +34,11 @@
 #endif
 #include "score_device.h"
 #include "score4_device.h"
-#include "score_device32.h"
 
 namespace {
 
 using namespace rhdev;
 using namespace rh4;
-using namespace rhdev32;
 
 typedef float rh_f32x4 __attribute__((ext_vector_type(4)));
 typedef float rh_f32x2 __attribute__((ext_vector_type(2)));
@@ -180,7 +178,7 @@ score4_batch(S4Shared<R, MASK, LIST> &sh, const int wv, const int lane, const in
             const rh_prepf Pv = prepf_of<KIND>(prep[LIST ? (int)sh.ctab[pe >> S4_GB] : cbase + (int)(pe >> S4_GB)]);
             const rh_f32x4 a = sh.pa[pe & S4_GM][e2 & 63u];
             const rh_f32x2 b = sh.pb[pe & S4_GM][e2 & 63u];
-            r = test_point32<KIND>(Pv, a.x, a.y, a.z, a.w, b.x, b.y, eps, cosa);
+            r = test_point<KIND>(Pv, a.x, a.y, a.z, a.w, b.x, b.y, eps, cosa);
         } else {
             const rh_prep Pv = prep[LIST ? (int)sh.ctab[pe >> S4_GB] : cbase + (int)(pe >> S4_GB)];
             r = test_point<KIND>(Pv, pts[gi], pts[stride + gi], pts[2 * stride + gi], pts[3 * stride + gi], pts[4 * stride + gi],
@@ -702,7 +700,7 @@ static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4S
 {
     const double eps = A.eps[KIND], cosa = A.cosa[KIND];
     uint64_t ex;
-    if (A.f32) ex = test_point32<KIND>(Q.Pf, (float)x, (float)y, (float)z, (float)nx, (float)ny, (float)nz, eps, cosa);
+    if (A.f32) ex = test_point<KIND>(Q.Pf, (float)x, (float)y, (float)z, (float)nx, (float)ny, (float)nz, eps, cosa);
     else ex = test_point<KIND>(Q.P, x, y, z, nx, ny, nz, eps, cosa);
     ex &= valid;
     const bool skip = box_skip32<KIND>(Q.box, G);
@@ -1296,7 +1294,7 @@ extern "C" int rh_dbg_cls_soundness(rh_cloud *c, const rh_shape *shapes, int32_t
         Q.pad = 0;
         if (Q.kind < 0 || Q.kind > 3) { Q.kind = -1; continue; }
         rh_prep_host(shapes[i], &Q.P);
-        prep_one32(shapes[i], Q.Pf);
+        Q.Pf = prepf_of_kind(Q.P, Q.kind);
         cls_make(Q.P, Q.kind, p->eps[Q.kind], p->cos_alpha[Q.kind], c->coord_mag, c->nrm_mag, Q.C, Q.box, 1, nullptr, c->f32);
     }
     S4SoundArgs A;

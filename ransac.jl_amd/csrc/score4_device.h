@@ -93,7 +93,7 @@ __host__ __device__ inline void cls_make(const rh_prep &P, int kind, double eps,
                                          float *box, int64_t bstride, double *dbg4 = nullptr, bool f32cloud = false)
 {
     // f32cloud: the EXACT test of this cloud is itself a binary32 chain without fused operations (Float32 cloud,
-    // score_device32.h: 1.3 - 2 x the rounding steps of the classifier's chain on the same magnitudes).  Every margin
+    // score_device.h with T = float: 1.3 - 2 x the rounding steps of the classifier's chain on the same magnitudes).  Every margin
     // is tripled: one part for the classifier's own error, two for the exact chain's.
     const double u = RH_CLS_U, S = f32cloud ? 3.0 * RH_CLS_SAFETY : RH_CLS_SAFETY;
     const float fnan = __builtin_nanf("");

@@ -1,9 +1,9 @@
 // score_device.h -- the per-point tests and the conservative group-box tests of the score and refit kernels (shared by
 // kernels.hip, score4.hip and korder.hip).
 //
-// Numerics contract: IEEE binary64, the reference's operation order, NO fused multiply-add (built with
-// -ffp-contract=off), correctly rounded sqrt and divide.  Each per-point test cites the reference function it
-// restates (paths under /root/reference/src).
+// Numerics contract: IEEE binary64 (binary32 for the points of a Float32 cloud), the reference's operation order, NO
+// fused multiply-add (built with -ffp-contract=off), correctly rounded sqrt and divide.  Each per-point test cites the
+// reference function it restates (paths under /root/reference/src).
 #pragma once
 
 #include "rh_internal.h"
@@ -30,90 +30,95 @@ static __device__ __forceinline__ rh_prep rh_ld_prep_const(const rh_prep *p)
 #define WB(cond) __builtin_amdgcn_ballot_w64(cond)
 
 // ------------------------------------------------------------------ tests ----
+// One statement of each test for both element types: T is the cloud's (double, or float on a Float32 cloud:
+// RANSACCloud(...; force_eltype = Float32), src/octree.jl:102-109) and is deduced from the point, REC is the candidate's
+// record in that type (rh_prep / rh_prepf, rh_internal.h).  Every operation is an operation of T in the reference's
+// order; eps and cos(alpha) stay doubles, and a float result is compared with them after exact promotion, like Julia
+// compares a Float32 with a Float64.  The oracle's binary32 twin is oracle/orc_f32.c.
 // plane: compatiblesPlane shapes/plane.jl:114-130 (+ project2plane :82-95), isparallel utilities.jl:115-117
-static __device__ __forceinline__ uint64_t test_plane(const rh_prep &P, double px, double py, double pz, double nx,
-                                           double ny, double nz, double eps, double cosa)
+template <typename REC, typename T>
+static __device__ __forceinline__ uint64_t test_plane(const REC &P, T px, T py, T pz, T nx, T ny, T nz, double eps, double cosa)
 {
     // The normal half first: a point whose normal is not within alpha of the plane's fails whatever its
     // distance, and in most groups that is every point of the wave (outliers and other primitives' points),
     // so the distance half is skipped with one scalar branch.  Same bits as evaluating both.
-    const double dn = (P.f[3] * nx + P.f[4] * ny) + P.f[5] * nz;
+    const T dn = (P.f[3] * nx + P.f[4] * ny) + P.f[5] * nz;
     const uint64_t mn = WB(dn > cosa);
     if (mn == 0) return 0;
-    const double vx = px - P.f[0], vy = py - P.f[1], vz = pz - P.f[2];
-    const double d = (P.f[6] * vx + P.f[7] * vy) + P.f[8] * vz;
+    const T vx = px - P.f[0], vy = py - P.f[1], vz = pz - P.f[2];
+    const T d = (P.f[6] * vx + P.f[7] * vy) + P.f[8] * vz;
     return mn & WB(fabs(d) < eps);
 }
 
 // sphere: compatiblesSphere shapes/sphere.jl:144-172.  Inward case: normalize(o-p) = -normalize(p-o)
 // and dot(-u, n) = -dot(u, n) exactly (round-to-nearest is odd-symmetric), hence sgn * dot.
-static __device__ __forceinline__ uint64_t test_sphere(const rh_prep &P, double px, double py, double pz, double nx,
-                                            double ny, double nz, double eps, double cosa)
+template <typename REC, typename T>
+static __device__ __forceinline__ uint64_t test_sphere(const REC &P, T px, T py, T pz, T nx, T ny, T nz, double eps, double cosa)
 {
-    const double dx = px - P.f[0], dy = py - P.f[1], dz = pz - P.f[2];
-    const double nr = sqrt((dx * dx + dy * dy) + dz * dz);
+    const T dx = px - P.f[0], dy = py - P.f[1], dz = pz - P.f[2];
+    const T nr = sqrt((dx * dx + dy * dy) + dz * dz);
     const uint64_t md = WB(fabs(nr - P.f[3]) < eps);
     if (md == 0) return 0;     // no lane of the wave inside the band: the normal half cannot change that
-    const double inv = 1.0 / nr;
-    const double ux = inv * dx, uy = inv * dy, uz = inv * dz;
-    const double dt = (ux * nx + uy * ny) + uz * nz;
+    const T inv = T(1) / nr;
+    const T ux = inv * dx, uy = inv * dy, uz = inv * dz;
+    const T dt = (ux * nx + uy * ny) + uz * nz;
     return WB(P.f[4] * dt > cosa) & md;
 }
 
 // cylinder: compatiblesCylinder shapes/cylinder.jl:194-221
-static __device__ __forceinline__ uint64_t test_cylinder(const rh_prep &P, double px, double py, double pz, double nx,
-                                              double ny, double nz, double eps, double cosa)
+template <typename REC, typename T>
+static __device__ __forceinline__ uint64_t test_cylinder(const REC &P, T px, T py, T pz, T nx, T ny, T nz, double eps, double cosa)
 {
-    const double ax = P.f[0], ay = P.f[1], az = P.f[2];
-    const double cx = P.f[3], cy = P.f[4], cz = P.f[5];
-    const double tx = px - cx, ty = py - cy, tz = pz - cz;
-    const double sd = (ax * tx + ay * ty) + az * tz;
+    const T ax = P.f[0], ay = P.f[1], az = P.f[2];
+    const T cx = P.f[3], cy = P.f[4], cz = P.f[5];
+    const T tx = px - cx, ty = py - cy, tz = pz - cz;
+    const T sd = (ax * tx + ay * ty) + az * tz;
     // curr_norm = p - a*dot(a, p-c) - c
-    const double qx = (px - ax * sd) - cx, qy = (py - ay * sd) - cy, qz = (pz - az * sd) - cz;
-    const double nr = sqrt((qx * qx + qy * qy) + qz * qz);
+    const T qx = (px - ax * sd) - cx, qy = (py - ay * sd) - cy, qz = (pz - az * sd) - cz;
+    const T nr = sqrt((qx * qx + qy * qy) + qz * qz);
     // the reference nests the two tests (cylinder.jl:209-214); their conjunction is the same bit
     const uint64_t md = WB(fabs(nr - P.f[6]) < eps);
     if (md == 0) return 0;
-    const double inv = 1.0 / nr;
-    const double ux = inv * qx, uy = inv * qy, uz = inv * qz;
-    const double dt = (ux * nx + uy * ny) + uz * nz;
+    const T inv = T(1) / nr;
+    const T ux = inv * qx, uy = inv * qy, uz = inv * qz;
+    const T dt = (ux * nx + uy * ny) + uz * nz;
     return md & WB(P.f[7] * dt > cosa);
 }
 
 // cone: compatiblesCone shapes/cone.jl:132-153, project2cone :68-85,
 // rodriguesrad/rodrigues/pluscrossprod! utilities.jl:61-64,19-24,32-43
 // (the frame: dist = dot(-current_normal, -to_point), dt = dot(current_normal, n); the audit kernels read them too)
-static __device__ __forceinline__ void cone_frame(const rh_prep &P, double px, double py, double pz, double nx,
-                                           double ny, double nz, double &dist_out, double &dt_out)
+template <typename REC, typename T>
+static __device__ __forceinline__ void cone_frame(const REC &P, T px, T py, T pz, T nx, T ny, T nz, T &dist_out, T &dt_out)
 {
-    const double ax = P.f[3], ay = P.f[4], az = P.f[5];
-    const double c = P.f[6], s = P.f[7];
+    const T ax = P.f[3], ay = P.f[4], az = P.f[5];
+    const T c = P.f[6], s = P.f[7];
     // to_point = apex - p; to_pointn = normalize(to_point)
-    const double tx = P.f[0] - px, ty = P.f[1] - py, tz = P.f[2] - pz;
-    double inv = 1.0 / sqrt((tx * tx + ty * ty) + tz * tz);
-    const double tnx = inv * tx, tny = inv * ty, tnz = inv * tz;
+    const T tx = P.f[0] - px, ty = P.f[1] - py, tz = P.f[2] - pz;
+    T inv = T(1) / sqrt((tx * tx + ty * ty) + tz * tz);
+    const T tnx = inv * tx, tny = inv * ty, tnz = inv * tz;
     // rot_ax = normalize(cross(axis, to_pointn))
-    double kx = ay * tnz - az * tny, ky = az * tnx - ax * tnz, kz = ax * tny - ay * tnx;
-    inv = 1.0 / sqrt((kx * kx + ky * ky) + kz * kz);
-    const double rx = inv * kx, ry = inv * ky, rz = inv * kz;
+    T kx = ay * tnz - az * tny, ky = az * tnx - ax * tnz, kz = ax * tny - ay * tnx;
+    inv = T(1) / sqrt((kx * kx + ky * ky) + kz * kz);
+    const T rx = inv * kx, ry = inv * ky, rz = inv * kz;
     // comp_n = normalize(cross(axis, rot_ax))
     kx = ay * rz - az * ry; ky = az * rx - ax * rz; kz = ax * ry - ay * rx;
-    inv = 1.0 / sqrt((kx * kx + ky * ky) + kz * kz);
-    const double mx = inv * kx, my = inv * ky, mz = inv * kz;
+    inv = T(1) / sqrt((kx * kx + ky * ky) + kz * kz);
+    const T mx = inv * kx, my = inv * ky, mz = inv * kz;
     // rodriguesrad re-normalizes the axis
-    inv = 1.0 / sqrt((rx * rx + ry * ry) + rz * rz);
-    const double vx = inv * rx, vy = inv * ry, vz = inv * rz;
+    inv = T(1) / sqrt((rx * rx + ry * ry) + rz * rz);
+    const T vx = inv * rx, vy = inv * ry, vz = inv * rz;
     // R = v v' + cos .* (I - v v'), then pluscrossprod!(R, sin, v)
-    const double nxx = vx * vx, nxy = vx * vy, nxz = vx * vz, nyy = vy * vy, nyz = vy * vz, nzz = vz * vz;
-    const double R00 = nxx + c * (1.0 - nxx);
-    double R01 = nxy + c * (0.0 - nxy);
-    double R02 = nxz + c * (0.0 - nxz);
-    double R10 = R01;
-    const double R11 = nyy + c * (1.0 - nyy);
-    double R12 = nyz + c * (0.0 - nyz);
-    double R20 = R02;
-    double R21 = R12;
-    const double R22 = nzz + c * (1.0 - nzz);
+    const T nxx = vx * vx, nxy = vx * vy, nxz = vx * vz, nyy = vy * vy, nyz = vy * vz, nzz = vz * vz;
+    const T R00 = nxx + c * (T(1) - nxx);
+    T R01 = nxy + c * (T(0) - nxy);
+    T R02 = nxz + c * (T(0) - nxz);
+    T R10 = R01;
+    const T R11 = nyy + c * (T(1) - nyy);
+    T R12 = nyz + c * (T(0) - nyz);
+    T R20 = R02;
+    T R21 = R12;
+    const T R22 = nzz + c * (T(1) - nzz);
     R01 -= s * vz; R02 += s * vy;
     R10 += s * vz; R12 -= s * vx;
     R20 -= s * vy; R21 += s * vx;
@@ -121,24 +126,23 @@ static __device__ __forceinline__ void cone_frame(const rh_prep &P, double px, d
     kx = (R00 * mx + R01 * my) + R02 * mz;
     ky = (R10 * mx + R11 * my) + R12 * mz;
     kz = (R20 * mx + R21 * my) + R22 * mz;
-    inv = 1.0 / sqrt((kx * kx + ky * ky) + kz * kz);
-    const double gx = inv * kx, gy = inv * ky, gz = inv * kz;
+    inv = T(1) / sqrt((kx * kx + ky * ky) + kz * kz);
+    const T gx = inv * kx, gy = inv * ky, gz = inv * kz;
     // dist = dot(-current_normal, -to_point)
     dist_out = ((-gx) * (-tx) + (-gy) * (-ty)) + (-gz) * (-tz);
     dt_out = (gx * nx + gy * ny) + gz * nz;
 }
 
-static __device__ __forceinline__ uint64_t test_cone(const rh_prep &P, double px, double py, double pz, double nx,
-                                          double ny, double nz, double eps, double cosa)
+template <typename REC, typename T>
+static __device__ __forceinline__ uint64_t test_cone(const REC &P, T px, T py, T pz, T nx, T ny, T nz, double eps, double cosa)
 {
-    double dist, dt;
+    T dist, dt;
     cone_frame(P, px, py, pz, nx, ny, nz, dist, dt);
     return WB(P.f[8] * dt > cosa) & WB(fabs(dist) < eps);
 }
 
-template <int KIND>
-static __device__ __forceinline__ uint64_t test_point(const rh_prep &P, double px, double py, double pz, double nx,
-                                           double ny, double nz, double eps, double cosa)
+template <int KIND, typename REC, typename T>
+static __device__ __forceinline__ uint64_t test_point(const REC &P, T px, T py, T pz, T nx, T ny, T nz, double eps, double cosa)
 {
     if (KIND == RH_PLANE) return test_plane(P, px, py, pz, nx, ny, nz, eps, cosa);
     if (KIND == RH_SPHERE) return test_sphere(P, px, py, pz, nx, ny, nz, eps, cosa);
@@ -168,7 +172,7 @@ static __device__ __forceinline__ double box_slack(const rh_prep &P, double coor
 }
 
 // Float32 clouds: the conservative stages still run in binary64 on the exactly converted values (they bound the
-// REAL-valued distance), the exact test runs in binary32 (score_device32.h).  Its result differs from the real value by
+// REAL-valued distance), the exact test runs in binary32 (the tests above with T = float).  Its result differs from the real value by
 // the binary32 rounding of ~10-30 operations on terms of the size of the coordinates and parameters -- and, for a
 // cylinder, of |a|^2 (p - c) (the axis is used as stored, cylinder.jl:207) -- so the slack is 2^-16 of that magnitude:
 // 256 binary32 ulps, ~10x the worst chain (the Float64 slack is 1e-9 of it: 4.5e6 ulps).

@@ -328,6 +328,25 @@ def test_cell_grid_integers(tmp_path):
     assert out.stdout.strip().endswith(" 0 bad")
 
 
+def test_prep_records(tmp_path):
+    """The candidate records of csrc/rh_internal.h on the host: for every kind, both signs and fields that are binary32
+    numbers, that round (0.1, 1/3) and that are around 1e6, the float record derived from the binary64 one
+    (prepf_of_kind of prep_one) is byte for byte the record written out from the shape alone, and rh_prep_host gives
+    the bytes of prep_one.  rh_internal.h includes the HIP runtime's header: g++ finds it beside hipcc."""
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = os.path.realpath(shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "prep_record_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
+                           "-I", os.path.join(os.path.dirname(os.path.dirname(hipcc)), "include"),
+                           "-I", os.path.join(root, "include"), "-I", os.path.join(root, "ransac.jl_amd", "csrc"),
+                           os.path.join(root, "tests", "native", "prep_record_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout[-2000:]
+    assert out.stdout.strip().endswith("48 checks, 0 bad")
+
+
 def test_product_library_reads_no_environment_and_ships_no_diagnostics():
     """libransac_hip.so sits under someone else's process: it must not change what it computes because of a variable in
     that process's environment.  The A/B switches of the experiments (RH_NO_PIPELINE, ...), the skeleton-only launch

@@ -35,7 +35,7 @@ def to_orc(arr, b):
 
 @pytest.fixture(scope="module", params=["groups", "brute"])
 def scene32(request):
-    """both scorers: the culled kernel with the exact test in binary32, and the brute-force float kernel"""
+    """both scorers: the culled kernel and the brute-force kernel, each with the exact test in binary32"""
     with R.option("score_path", request.param):
         yield _scene32()
 
@@ -202,6 +202,82 @@ def test_f32_device_batch_and_unsupported_calls(scene32):
     batch.free()
     with pytest.raises(R.RansacHipError):
         R.refit_lsq(arr[0], pc, cp)      # (the least-squares refit stays Float64-only)
+
+
+def _sc_tile():
+    """points per block and tile of the brute-force score kernel (RH_SC_TILE, csrc/rh_internal.h)"""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ransac.jl_amd", "csrc", "rh_internal.h")).read()
+    return int(re.search(r"RH_SC_THREADS = (\d+);", src).group(1)) * int(re.search(r"RH_SC_PPT = (\d+);", src).group(1))
+
+
+@pytest.fixture(scope="module")
+def small32():
+    """one Float32 scene and its candidates for the small-subset test: half of them Float32 shapes, the other half
+    left with binary64 fields that round when the binary32 test reads them"""
+    prim = ["plane", "plane", "sphere", "sphere", "cylinder", "cylinder", "cone", "cone"]
+    xyz, nrm, truth = synth.make_cloud(4000, prim, 0.2, seed=43)
+    cands = synth.jittered_candidates(truth, 400, seed=6)
+
+    def batch(pick, b):
+        arr = (L.Shape * b)()
+        for i, (name, outw, v) in enumerate([c for c in cands if pick(c[0])][:b]):
+            arr[i].kind = KMAP[name]
+            arr[i].outwards = int(outw)
+            for j, x in enumerate(v):
+                arr[i].v[j] = float(x)
+            (R.lib().rh_shape_finalize_f32 if i % 2 == 0 else R.lib().rh_shape_finalize)(C.byref(arr[i]))
+        assert b == 1 or any(float(np.float32(arr[i].v[0])) != arr[i].v[0] for i in range(b))   # some fields do round
+        return arr
+    batches = [(batch(lambda k: True, b), b) for b in (1, 64, 65, 130)]
+    batches.append((batch(lambda k: k != "cone", 65), 65))      # a kind absent
+    batches.append((batch(lambda k: k == "plane", 64), 64))     # all one kind
+    return xyz.astype(np.float32), nrm.astype(np.float32), batches
+
+
+@pytest.mark.parametrize("s", [1, 63, 64, 65, _sc_tile() + 1])
+def test_f32_small_subsets_take_the_brute_kernel(small32, s):
+    """Float32 clouds whose subset 1 is below 8192 points: the library picks the brute-force kernel on its own, and that
+    kernel reads the subset's doubles and the binary64 records and runs the binary32 test on their casts.  Subsets of 1,
+    63, 64, 65 and tile + 1 points (one wave word, one short of it, one past it, one past the block's tile), batches of 1,
+    64, 65 and 130 candidates (one candidate tile, one past it, three), one batch without cones and one of planes only,
+    some points disabled; counts and masks through rh_score_batch and through rh_score_batch_dev in the caller's
+    order, bit for bit against the oracle's binary32 twin."""
+    import torch
+    from ransac_jl_amd import dist as rdist
+    x32, n32, batches = small32
+    n = len(x32)
+    perm = np.random.default_rng(s).permutation(n).astype(np.int64) + 1
+    subs = [perm[:s], perm[s:]]
+    pc = R.RANSACCloud(x32, n32, subs, force_eltype=np.float32)
+    oc = orc.Cloud32(x32, n32, subs[0])
+    gone = np.sort(np.concatenate([perm[0:s:3], perm[s:s + 50]]))   # a third of the subset (its first point included) and some others
+    R.invalidate_indexes(pc, gone)
+    oc.invalidate(gone)
+    cp = R.params_to_c(R.ransacparameters())
+    op = orc.Params.from_buffer_copy(bytes(cp))
+    sw = (s + 63) // 64
+    total = 0
+    for arr, b in batches:
+        ocounts, omasks = oc.score_batch(to_orc(arr, b), op, want_masks=True)
+        counts, masks = R.score_batch(pc, arr, cp, want_masks=True)
+        assert np.array_equal(counts, ocounts) and np.array_equal(masks, omasks)
+        assert np.array_equal(R.score_batch(pc, arr, cp), ocounts)                 # counts-only instantiation
+        batch = rdist.DeviceBatch(pc, arr, b)
+        for want_masks in (False, True):
+            dc = torch.full((b,), -1, dtype=torch.int32, device="cuda")
+            dm = torch.zeros((b, sw), dtype=torch.int64, device="cuda") if want_masks else None
+            torch.cuda.synchronize()   # (torch fills on its own stream, the library scores on the cloud's)
+            L.check(R.lib().rh_score_batch_dev(pc._h, batch.slice_ptr(0), b, C.byref(cp), C.c_void_p(dc.data_ptr()),
+                                               C.c_void_p(dm.data_ptr()) if want_masks else None))
+            L.check(R.lib().rh_cloud_sync(pc._h))
+            assert np.array_equal(dc.cpu().numpy(), ocounts)
+            if want_masks:
+                assert np.array_equal(dm.cpu().numpy().view(np.uint64), np.asarray(omasks).reshape(b, sw))
+        batch.free()
+        total += int(ocounts.sum())
+    assert s < 1000 or total > 1000   # (the candidates do hit the larger subset)
 
 
 def test_f32_full_size_refit_halves_the_bytes():
