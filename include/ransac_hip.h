@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 115
+#define RH_VERSION 116
 
 enum {
     RH_OK = 0,
@@ -654,6 +654,62 @@ int rh_remove_outliers(const double *xyz_aos, int64_t n, const rh_outlier_params
 int rh_remove_outliers_f32(const float *xyz_aos, int64_t n, const rh_outlier_params *p, int device, uint8_t *keep_out,
                            int32_t *kept_idx_out_or_null, int64_t cap, int64_t *n_kept_out, double *mean_dist_out_or_null,
                            rh_outlier_stats *stats_or_null);
+
+/* ---- density-based clustering of a raw cloud: DBSCAN, and Euclidean cluster extraction at min_pts = 1 (no counterpart in
+ *      the reference, whose clouds hold one object) ----
+ * Splits a cloud into its spatially connected parts: a scan into objects before rh_ransac, the points that rh_assign_points
+ * left without a label into the next objects or clutter, the inpoints of one shape into its patches.
+ * Points p_1 .. p_n (binary64 array-of-structures; the _f32 entry widens exactly), eps > 0, min_pts >= 1, min_size >= 1.
+ *  1. d2(i, j) = (dx*dx + dy*dy) + dz*dz in binary64, no contraction: rh_knn's expression.  eps2 = eps*eps, rounded once;
+ *  2. j is a neighbour of i when j != i and d2(i, j) <= eps2.  The boundary is included; i is left out by its index, so a
+ *     duplicate of p_i is a neighbour at distance 0;
+ *  3. i is a CORE point when 1 + (the number of its neighbours) >= min_pts: the point counts itself, as in scikit-learn and
+ *     Open3D.  With min_pts = 1 every point is a core point and the result is plain Euclidean cluster extraction;
+ *  4. a cluster is a connected component of the graph on the core points whose edges are the neighbour relation.  Two
+ *     clusters are never joined through a point that is no core point;
+ *  5. a BORDER point is no core point and has at least one core neighbour; it belongs to the cluster of its NEAREST core
+ *     neighbour: smallest d2, ties to the smaller index.  Textbook DBSCAN gives a border point to whichever cluster reaches
+ *     it first, which depends on the order of processing; this rule does not, and differs from it only for border points
+ *     within eps of two clusters;
+ *  6. every other point is NOISE, and so are, in the labels, all points of a cluster with fewer than min_size members (core
+ *     and border points counted);
+ *  7. order = RH_CLUSTER_BY_INDEX: the clusters that are left are numbered 1 .. M by ascending index of their smallest core
+ *     point; RH_CLUSTER_BY_SIZE: by descending size, ties by the smallest core point's index.  Noise has label 0.
+ * Every decision is a comparison of binary64 values of fixed expressions or integer arithmetic: the same bits on every run,
+ * and a permutation of the input permutes the result (with the numbering following the indices).
+ * labels_out: int32 [n].  kind_out (optional): uint8 [n], RH_PT_*; the kind of a point of a cluster dropped in step 6 is what
+ * it was before the drop, core or border.  *n_clusters_out = M.
+ * counts (optional): int64 [cap + 1], the points per label, label 0 first; offsets (optional): int64 [cap + 2] and idx
+ * (optional): int64 [n]: the 1-based indices grouped by label, label 0 first, ascending within a label, label l at
+ * idx[offsets[l] .. offsets[l + 1]) -- the lists of rh_assign_points.  The entries of the labels M + 1 .. min(cap, n) are
+ * counts 0 and offsets n; nothing is written beyond min(cap, n).  M > cap with counts or offsets asked for: RH_E_CAPACITY
+ * (like rh_refit) with *n_clusters_out = M and labels_out, kind_out and stats still written in full; cap = n always suffices.
+ * stats (optional): n_clusters = M; n_core + n_border + n_noise = n by the kinds; n_small = the core and border points of the
+ * clusters dropped in step 6 (label 0 holds n_noise + n_small points); largest = the size of the largest cluster left, 0
+ * when M = 0.
+ * The array arguments may be host or device pointers (the copies are hipMemcpyDefault); parameters, scalars and stats are
+ * host memory.  RH_E_INVALID, before the device is touched: a null xyz / params / labels_out / n_clusters_out, n < 1,
+ * n >= 2^31, eps not finite or <= 0, min_pts < 1, min_size < 1, an unknown order, cap < 0; on the device: a coordinate that
+ * is not finite (nothing is written). */
+enum { RH_CLUSTER_BY_INDEX = 0, RH_CLUSTER_BY_SIZE = 1 };
+enum { RH_PT_NOISE = 0, RH_PT_BORDER = 1, RH_PT_CORE = 2 };
+typedef struct {
+    double eps;
+    int32_t min_pts, min_size;
+    int32_t order;           /* RH_CLUSTER_BY_* */
+    int32_t reserved;        /* 0 */
+} rh_cluster_params;
+typedef struct {
+    int64_t n_clusters, n_core, n_border, n_noise;
+    int64_t n_small;         /* points of clusters below min_size */
+    int64_t largest;
+} rh_cluster_stats;
+int rh_cluster(const double *xyz_aos, int64_t n, const rh_cluster_params *p, int device, int32_t *labels_out,
+               uint8_t *kind_out_or_null, int64_t cap, int64_t *counts_out_or_null, int64_t *offsets_out_or_null,
+               int64_t *idx_out_or_null, int64_t *n_clusters_out, rh_cluster_stats *stats_or_null);
+int rh_cluster_f32(const float *xyz_aos, int64_t n, const rh_cluster_params *p, int device, int32_t *labels_out,
+                   uint8_t *kind_out_or_null, int64_t cap, int64_t *counts_out_or_null, int64_t *offsets_out_or_null,
+                   int64_t *idx_out_or_null, int64_t *n_clusters_out, rh_cluster_stats *stats_or_null);
 
 /* ---- tuning options ----
  * The library reads NO environment variable: what a caller may tune goes through this call, for one cloud or, with

@@ -619,6 +619,66 @@ function removeoutliers(vertices::AbstractVector{SVector{3,T}}; k::Integer = 16,
     return vs[idx], (normals === nothing ? nothing : normals[idx]), idx, st[]
 end
 
+# ---- density-based clustering of a raw cloud (rh_cluster) ----
+# typedef struct { double eps; int32_t min_pts, min_size, order, reserved; } rh_cluster_params;   (24 bytes)
+struct RhClusterParams
+    eps::Cdouble
+    min_pts::Cint
+    min_size::Cint
+    order::Cint
+    reserved::Cint
+end
+# typedef struct { int64_t n_clusters, n_core, n_border, n_noise, n_small, largest; } rh_cluster_stats;   (48 bytes)
+struct RhClusterStats
+    n_clusters::Int64
+    n_core::Int64
+    n_border::Int64
+    n_noise::Int64
+    n_small::Int64
+    largest::Int64
+end
+
+"""
+    cluster(vertices, eps; min_pts = 8, min_size = 1, order = :index) -> (labels, kind, counts, offsets, idx, stats)
+
+Splits a raw cloud into its spatially connected parts (`rh_cluster`: DBSCAN, include/ransac_hip.h has the definition in
+full).  Points are neighbours when `d2 <= eps*eps`; a point with at least `min_pts` points within `eps`, itself included,
+is a core point; clusters are the connected components of the core points, any other point joins the cluster of its
+nearest core neighbour (ties to the smaller index) or is noise, and clusters below `min_size` points become noise.
+`min_pts = 1` is Euclidean cluster extraction.  `labels[i]`: 0 for noise, else 1 to M, numbered by the smallest core
+point's index (`:index`) or by descending size (`:size`); `kind[i]`: 0 noise, 1 border, 2 core; `counts[1]` the noise
+points, `counts[l + 1]` those of cluster `l`; `idx[offsets[l + 1] + 1 : offsets[l + 2]]` the points of label `l`,
+ascending; `stats`: an `RhClusterStats`.
+"""
+function cluster(vertices::AbstractVector{SVector{3,T}}, eps::Real; min_pts::Integer = 8, min_size::Integer = 1,
+                 order::Symbol = :index, device::Integer = 0) where {T<:Union{Float32,Float64}}
+    order in (:index, :size) || error("cluster: order is :index or :size")
+    p = RhClusterParams(eps, min_pts, min_size, order === :index ? 0 : 1, 0)
+    vs = convert(Vector{SVector{3,T}}, vertices)
+    n = length(vs)
+    labels = zeros(Int32, max(n, 1))
+    kind = zeros(UInt8, max(n, 1))
+    counts = zeros(Int64, n + 1)
+    offsets = zeros(Int64, n + 2)
+    idx = zeros(Int64, max(n, 1))
+    m = Ref{Int64}(0)
+    st = Ref(RhClusterStats(0, 0, 0, 0, 0, 0))
+    GC.@preserve vs labels kind counts offsets idx begin
+        if T == Float32
+            check(ccall((:rh_cluster_f32, LIB), Cint,
+                (Ptr{Cfloat}, Int64, Ref{RhClusterParams}, Cint, Ptr{Int32}, Ptr{UInt8}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
+                 Ref{Int64}, Ref{RhClusterStats}),
+                pointer(reinterpret(Float32, vs)), n, p, device, labels, kind, n, counts, offsets, idx, m, st))
+        else
+            check(ccall((:rh_cluster, LIB), Cint,
+                (Ptr{Cdouble}, Int64, Ref{RhClusterParams}, Cint, Ptr{Int32}, Ptr{UInt8}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
+                 Ref{Int64}, Ref{RhClusterStats}),
+                pointer(reinterpret(Float64, vs)), n, p, device, labels, kind, n, counts, offsets, idx, m, st))
+        end
+    end
+    return resize!(labels, n), resize!(kind, n), resize!(counts, m[] + 1), resize!(offsets, m[] + 2), resize!(idx, n), st[]
+end
+
 _assign_shape(x::ExtractedShape) = toC(x.shape)
 _assign_shape(x::FittedShape) = toC(x)
 

@@ -75,9 +75,23 @@ class OutlierStats(C.Structure):
                 ("tau", C.c_double), ("nn_median", C.c_double)]
 
 
+class ClusterParams(C.Structure):
+    """rh_cluster_params (include/ransac_hip.h)"""
+    _fields_ = [("eps", C.c_double), ("min_pts", C.c_int32), ("min_size", C.c_int32), ("order", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class ClusterStats(C.Structure):
+    """rh_cluster_stats (include/ransac_hip.h)"""
+    _fields_ = [("n_clusters", C.c_int64), ("n_core", C.c_int64), ("n_border", C.c_int64), ("n_noise", C.c_int64),
+                ("n_small", C.c_int64), ("largest", C.c_int64)]
+
+
 KNN_MAX_K = 63
 OUT_BLOCK_POINTS = 1024
 OUT_STATISTICAL, OUT_ABSOLUTE, OUT_RADIUS = 0, 1, 2
+CLUSTER_BY_INDEX, CLUSTER_BY_SIZE = 0, 1
+PT_NOISE, PT_BORDER, PT_CORE = 0, 1, 2
 VOX_FIRST, VOX_CENTROID = 0, 1
 VOX_ALIGN_NORMALS = 1
 EXT_EMPTY, EXT_NO_DIRECTION, EXT_INVALID = 1, 2, 4
@@ -190,6 +204,10 @@ SIGNATURES = {
     "rh_estimate_normals": (C.c_int, [_dp, C.c_int64, C.POINTER(NormalsParams), _dp, C.c_int, _dp, _dp, _i32p]),
     "rh_estimate_normals_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(NormalsParams), C.POINTER(C.c_float),
                                           C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32p]),
+    "rh_cluster": (C.c_int, [_dp, C.c_int64, C.POINTER(ClusterParams), C.c_int, _i32p, _u8p, C.c_int64, _i64p, _i64p, _i64p, _i64p,
+                             C.POINTER(ClusterStats)]),
+    "rh_cluster_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(ClusterParams), C.c_int, _i32p, _u8p, C.c_int64, _i64p,
+                                 _i64p, _i64p, _i64p, C.POINTER(ClusterStats)]),
     "rh_voxel_downsample": (C.c_int, [_dp, _dp, C.c_int64, C.POINTER(VoxelParams), C.c_int, _dp, _dp, _i64p, _i32p, C.c_int64,
                                       _i32p, _i64p, _i64p]),
     "rh_voxel_downsample_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(VoxelParams), C.c_int,

@@ -858,6 +858,64 @@ def removeoutliers(vertices, k=16, std_mul=2.0, mode="statistical", radius=0.0, 
     return out[0] if len(out) == 1 else out
 
 
+def cluster(vertices, eps, min_pts=8, min_size=1, order="index", device=0, return_kind=False, return_counts=False,
+            return_lists=False, return_stats=False):
+    """Split a raw cloud into its spatially connected parts (rh_cluster: DBSCAN, include/ransac_hip.h has the definition in
+    full).  Two points are neighbours when d^2 <= eps*eps (the boundary counts); a point with at least min_pts points
+    within eps, itself included, is a core point; the clusters are the connected components of the core points, a point
+    that is no core point joins the cluster of its nearest core neighbour (ties to the smaller index), the rest is noise,
+    and so are clusters of fewer than min_size points.  min_pts = 1 is plain Euclidean cluster extraction.  order "index"
+    numbers the clusters by their smallest core point's index, "size" by descending size.  eps is usually a small multiple
+    of the point spacing (removeoutliers(..., return_stats=True)["nn_median"]).  vertices: (n, 3) float64 or float32
+    (widened exactly).
+    Returns labels (int32, 0 = noise, 1 .. M), then on request: return_kind uint8 per point (_lib.PT_NOISE / PT_BORDER /
+    PT_CORE), return_counts int64[M + 1] (noise first), return_lists (offsets[M + 2], idx[n]): the 1-based indices grouped
+    by label, noise first, ascending within a label (lists_from_assignment splits them), return_stats a dict n_clusters,
+    n_core, n_border, n_noise, n_small, largest."""
+    orders = {"index": L.CLUSTER_BY_INDEX, "size": L.CLUSTER_BY_SIZE}
+    if isinstance(order, str) and order not in orders:
+        raise ValueError("cluster: order %r is neither 'index' nor 'size'" % (order,))
+    f32 = np.asarray(vertices).dtype == np.float32
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    xyz = np.ascontiguousarray(vertices, dtype=t).reshape(-1, 3)
+    n = xyz.shape[0]
+    prm = L.ClusterParams(eps=float(eps), min_pts=int(min_pts), min_size=int(min_size), order=int(orders.get(order, order)))
+    labels = np.zeros(max(n, 1), dtype=np.int32)
+    kind = np.zeros(max(n, 1), dtype=np.uint8) if return_kind else None
+    counts = np.zeros(n + 1, dtype=np.int64) if return_counts else None
+    offsets = np.zeros(n + 2, dtype=np.int64) if return_lists else None
+    idx = np.zeros(max(n, 1), dtype=np.int64) if return_lists else None
+    st, m = L.ClusterStats(), C.c_int64(0)
+    fn = lib().rh_cluster_f32 if f32 else lib().rh_cluster
+    check(fn(_p(xyz, ct), n, C.byref(prm), device, _p(labels, C.c_int32), None if kind is None else _p(kind, C.c_uint8), n,
+             None if counts is None else _p(counts, C.c_int64), None if offsets is None else _p(offsets, C.c_int64),
+             None if idx is None else _p(idx, C.c_int64), C.byref(m), C.byref(st)))
+    m = int(m.value)
+    out = (labels[:n],) + ((kind[:n],) if return_kind else ()) + ((counts[:m + 1].copy(),) if return_counts else ())
+    out += ((offsets[:m + 2].copy(), idx[:n]) if return_lists else ())
+    out += (({f: int(getattr(st, f)) for f, _ in L.ClusterStats._fields_},) if return_stats else ())
+    return out[0] if len(out) == 1 else out
+
+
+def cluster_inpoints(vertices, inpoints, eps, **kw):
+    """The clusters of the points vertices[inpoints - 1] (inpoints: 1-based indices, e.g. an ExtractedShape's, or the
+    unlabelled list of assign_points): a list of int64 arrays, one per cluster in the order of cluster(...), each holding
+    that cluster's members as 1-based indices into `vertices` -- the caller's indexing -- in the order in which inpoints
+    lists them.  Noise is left out.  kw: min_pts, min_size, order, device of cluster()."""
+    bad = [k for k in kw if k not in ("min_pts", "min_size", "order", "device")]
+    if bad:
+        raise TypeError("cluster_inpoints: unexpected argument %s" % bad[0])
+    v = np.asarray(vertices)
+    v = v.reshape(-1, 3)
+    sel = np.asarray(inpoints, dtype=np.int64).reshape(-1)
+    if sel.size == 0:
+        return []
+    if sel.min() < 1 or sel.max() > v.shape[0]:
+        raise ValueError("cluster_inpoints: an index outside 1 .. %d" % v.shape[0])
+    _, offsets, idx = cluster(v[sel - 1], eps, return_lists=True, **kw)
+    return [sel[part - 1] for part in lists_from_assignment(offsets, idx)[1:]]
+
+
 def voxeldownsample(vertices, beta, normals=None, mode="centroid", align_normals=False, device=0, return_index=False,
                     return_counts=False, return_map=False):
     """Thin a raw cloud on a voxel grid of width beta (rh_voxel_downsample, include/ransac_hip.h has the definition in

@@ -1,5 +1,6 @@
 // knn_grid.h -- the uniform grid of the exact k-nearest-neighbour search (knn_device.h has the query), shared by
-// normals.hip (rh_estimate_normals) and knn.hip (rh_knn, rh_remove_outliers):
+// normals.hip (rh_estimate_normals), knn.hip (rh_knn, rh_remove_outliers) and cluster.hip (rh_cluster, which walks the
+// cells itself):
 //   points radix-sorted by cell key, an open-addressing hash table key -> [start, end) of the occupied cells only (empty
 //   space costs nothing; table and bounding box are cell_grid.h's), the coordinates gathered into cell order.  KnnIndex
 //   holds the grid's buffers in the call's scope (call_scope.h) and rebuilds the grid for any cell width.
