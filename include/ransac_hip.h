@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 116
+#define RH_VERSION 117
 
 enum {
     RH_OK = 0,
@@ -710,6 +710,71 @@ int rh_cluster(const double *xyz_aos, int64_t n, const rh_cluster_params *p, int
 int rh_cluster_f32(const float *xyz_aos, int64_t n, const rh_cluster_params *p, int device, int32_t *labels_out,
                    uint8_t *kind_out_or_null, int64_t cap, int64_t *counts_out_or_null, int64_t *offsets_out_or_null,
                    int64_t *idx_out_or_null, int64_t *n_clusters_out, rh_cluster_stats *stats_or_null);
+
+/* ---- nearest neighbours of query points in ANOTHER cloud, and cloud-to-cloud distances on them (no counterpart in the
+ *      reference, which works on one cloud) ----
+ * Carries labels, shapes and normals from one cloud to another (a thinned cloud to the full scan, one scan to the next),
+ * and measures how far a scan lies from a reference cloud.  Reference points r_1 .. r_n, query points q_1 .. q_m (binary64
+ * array-of-structures; the _f32 entries widen both arrays exactly and search in binary64).
+ * rh_knn_query: for query j (0-based) the ORDER of the n reference points is: ascending d^2 = (dx*dx + dy*dy) + dz*dz
+ * (binary64, dx = r.x - q.x, no contraction: rh_knn's expression), ties to the smaller reference index.  NO point is left
+ * out: a reference point equal to the query is its first neighbour at d^2 = 0.
+ *  1. k is 1 .. RH_KNN_MAX_K; the neighbours of j are the first k of its order, with radius > 0 those with
+ *     d^2 > radius*radius dropped (the boundary is included); count[j] = how many are left (0 <= count[j] <= min(k, n));
+ *  2. idx is int32 [m x k], row j = the neighbours' 1-based reference indices in that order, 0 past count[j]; d2 is double
+ *     [m x k], the d^2 as computed, +inf past count[j]; count is int32 [m].  Rows are in the caller's query order, whatever
+ *     order the device serves them in.  Every output is optional;
+ *  3. d2 stays double in the _f32 entry;
+ *  4. RH_E_INVALID: a null array, n < 1, n >= 2^31 - 1, m < 1, m >= 2^31, k outside 1 .. 63, radius negative or not finite
+ *     -- decided before the device is touched -- and a coordinate of either cloud that is not finite (found on the device,
+ *     nothing is written).
+ * The same bits on every run.  The array arguments may be host or device pointers (the copies are hipMemcpyDefault);
+ * parameters and stats are host memory.
+ *
+ * rh_cloud_distance: the distance of every query to the reference cloud and its summary, every output one fixed sequence of
+ * IEEE binary64 operations.  nn_j is the first entry of the order above (k = 1, the params' radius); query j is VALID when
+ * there is such an entry.  With e = q_j - r_nn componentwise:
+ *  RH_DIST_POINT: d_j = sqrt(d^2), the d^2 of the order;
+ *  RH_DIST_PLANE: d_j = fabs((e.x*n.x + e.y*n.y) + e.z*n.z), n the normal stored for r_nn, used as given: it is neither
+ *                 normalised nor checked (the distance to the tangent plane at the nearest point when n is a unit normal).
+ * dist_out: double [m], d_j, +inf when query j is not valid.  nn_idx_out (optional): int32 [m], the 1-based reference index,
+ * 0 when query j is not valid.  stats (optional), with T() the tree of rh_remove_outliers over the query index order
+ * j = 0 .. m-1 (blocks of RH_OUT_BLOCK_POINTS):
+ *  n_valid  = the number of valid queries;
+ *  mean     = T(d_j if valid else +0.0) / n_valid;
+ *  rms      = sqrt(T(d_j*d_j if valid else +0.0) / n_valid);
+ *  max      = the largest d_j over the valid queries: the one-sided Hausdorff distance from the queries to the reference;
+ *  argmax   = the smallest 1-based j reaching max, 0 when there is none;
+ *  n_within = the number of valid j with d_j <= threshold (threshold may be +inf);
+ *  median   = the lower median of d_j over the valid queries -- sorted position floor((n_valid - 1) / 2), as nn_median.
+ * All four doubles are 0 when n_valid == 0.  No floating-point atomics: the same bits on every run; a permutation of the
+ * queries permutes d_j and can change mean and rms in their last bits.  The measures are ONE-SIDED, queries -> reference.
+ * The symmetric ones are two calls composed by the caller: Hausdorff = the larger of the two max, Chamfer = the sum (or
+ * mean) of the two mean (or of the two rms squared), with the roles of the clouds exchanged in the second call.
+ * RH_E_INVALID, before the device is touched: a null ref / qry / params / dist_out, n and m as above, radius negative or not
+ * finite, threshold NaN, an unknown metric, RH_DIST_PLANE without normals; on the device: a coordinate that is not finite. */
+enum { RH_DIST_POINT = 0, RH_DIST_PLANE = 1 };
+typedef struct {
+    double radius;           /* 0 = no limit */
+    double threshold;        /* for n_within */
+    int32_t metric;          /* RH_DIST_* */
+    int32_t reserved;        /* 0 */
+} rh_distance_params;
+typedef struct {
+    int64_t n_valid, n_within;
+    int64_t argmax;          /* 1-based query index, 0 = none */
+    double mean, rms, max, median;
+} rh_distance_stats;
+int rh_knn_query(const double *ref_xyz_aos, int64_t n, const double *qry_xyz_aos, int64_t m, int32_t k, double radius,
+                 int device, int32_t *idx_out_or_null, double *d2_out_or_null, int32_t *count_out_or_null);
+int rh_knn_query_f32(const float *ref_xyz_aos, int64_t n, const float *qry_xyz_aos, int64_t m, int32_t k, double radius,
+                     int device, int32_t *idx_out_or_null, double *d2_out_or_null, int32_t *count_out_or_null);
+int rh_cloud_distance(const double *ref_xyz_aos, const double *ref_nrm_aos_or_null, int64_t n, const double *qry_xyz_aos,
+                      int64_t m, const rh_distance_params *p, int device, double *dist_out, int32_t *nn_idx_out_or_null,
+                      rh_distance_stats *stats_or_null);
+int rh_cloud_distance_f32(const float *ref_xyz_aos, const float *ref_nrm_aos_or_null, int64_t n, const float *qry_xyz_aos,
+                          int64_t m, const rh_distance_params *p, int device, double *dist_out, int32_t *nn_idx_out_or_null,
+                          rh_distance_stats *stats_or_null);
 
 /* ---- tuning options ----
  * The library reads NO environment variable: what a caller may tune goes through this call, for one cloud or, with

@@ -679,6 +679,98 @@ function cluster(vertices::AbstractVector{SVector{3,T}}, eps::Real; min_pts::Int
     return resize!(labels, n), resize!(kind, n), resize!(counts, m[] + 1), resize!(offsets, m[] + 2), resize!(idx, n), st[]
 end
 
+# ---- nearest neighbours of query points in another cloud, and cloud distances (rh_knn_query, rh_cloud_distance) ----
+# typedef struct { double radius; double threshold; int32_t metric; int32_t reserved; } rh_distance_params;   (24 bytes)
+struct RhDistanceParams
+    radius::Cdouble
+    threshold::Cdouble
+    metric::Cint
+    reserved::Cint
+end
+# typedef struct { int64_t n_valid, n_within, argmax; double mean, rms, max, median; } rh_distance_stats;   (56 bytes)
+struct RhDistanceStats
+    n_valid::Int64
+    n_within::Int64
+    argmax::Int64
+    mean::Cdouble
+    rms::Cdouble
+    max::Cdouble
+    median::Cdouble
+end
+
+"""
+    knn_query(reference, queries, k; radius = 0.0) -> (idx, d2, count)
+
+The `k` (1 to 63) nearest points of `reference` for every point of `queries`, exact: ascending
+`d2 = (dx*dx + dy*dy) + dz*dz` in Float64, ties to the smaller reference index; no point is left out, so a reference
+point equal to the query is its first neighbour at 0 (`knn` is the call for a cloud's own points).  `idx` is `k x m`
+Int32 (column `j` = the neighbours of query `j`, 1-based rows of `reference`, 0 past `count[j]`), `d2` the squared
+distances (`Inf` there), `count[j]` the neighbours left after `radius > 0` dropped the farther ones.
+"""
+function knn_query(reference::AbstractVector{SVector{3,T}}, queries::AbstractVector{SVector{3,T}}, k::Integer;
+                   radius::Real = 0.0, device::Integer = 0) where {T<:Union{Float32,Float64}}
+    rs = convert(Vector{SVector{3,T}}, reference)
+    qs = convert(Vector{SVector{3,T}}, queries)
+    n, m = length(rs), length(qs)
+    kk = 1 <= k <= 63 ? Int(k) : 1
+    idx = zeros(Int32, kk, m)
+    d2 = fill(Inf, kk, m)
+    count = zeros(Int32, m)
+    GC.@preserve rs qs idx d2 count begin
+        if T == Float32
+            check(ccall((:rh_knn_query_f32, LIB), Cint,
+                (Ptr{Cfloat}, Int64, Ptr{Cfloat}, Int64, Int32, Cdouble, Cint, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}),
+                pointer(reinterpret(Float32, rs)), n, pointer(reinterpret(Float32, qs)), m, k, radius, device, idx, d2, count))
+        else
+            check(ccall((:rh_knn_query, LIB), Cint,
+                (Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Int32, Cdouble, Cint, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}),
+                pointer(reinterpret(Float64, rs)), n, pointer(reinterpret(Float64, qs)), m, k, radius, device, idx, d2, count))
+        end
+    end
+    return idx, d2, count
+end
+
+"""
+    cloud_distance(reference, queries; normals = nothing, radius = 0.0, threshold = Inf, metric = nothing)
+        -> (dist, nn_idx, stats)
+
+How far every point of `queries` lies from the cloud `reference` (`rh_cloud_distance`, include/ransac_hip.h has the
+definition in full).  `metric = :point`: the distance to the nearest reference point; `:plane`: `|(q - r) . n|` with `r`
+that point and `n` its entry of `normals` (the reference's, used as given); the default is `:plane` when normals are
+given.  `radius > 0`: a query without a reference point within it is not valid, `dist[j] = Inf`, `nn_idx[j] = 0`.
+`stats`: an `RhDistanceStats` over the valid queries (`max` is the one-sided Hausdorff distance; the symmetric measures
+are two calls with the clouds exchanged).
+"""
+function cloud_distance(reference::AbstractVector{SVector{3,T}}, queries::AbstractVector{SVector{3,T}}; normals = nothing,
+                        radius::Real = 0.0, threshold::Real = Inf, metric = nothing,
+                        device::Integer = 0) where {T<:Union{Float32,Float64}}
+    metric === nothing && (metric = normals === nothing ? :point : :plane)
+    metric in (:point, :plane) || error("cloud_distance: metric is :point or :plane")
+    rs = convert(Vector{SVector{3,T}}, reference)
+    qs = convert(Vector{SVector{3,T}}, queries)
+    ns = normals === nothing ? nothing : convert(Vector{SVector{3,T}}, normals)
+    n, m = length(rs), length(qs)
+    ns === nothing || length(ns) == n || error("cloud_distance: $(length(ns)) normals for $n reference points")
+    p = RhDistanceParams(radius, threshold, metric === :point ? 0 : 1, 0)
+    dist = fill(Inf, m)
+    nn = zeros(Int32, m)
+    st = Ref(RhDistanceStats(0, 0, 0, 0.0, 0.0, 0.0, 0.0))
+    GC.@preserve rs qs ns dist nn begin
+        if T == Float32
+            check(ccall((:rh_cloud_distance_f32, LIB), Cint,
+                (Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ptr{Cfloat}, Int64, Ref{RhDistanceParams}, Cint, Ptr{Cdouble}, Ptr{Int32}, Ref{RhDistanceStats}),
+                pointer(reinterpret(Float32, rs)), ns === nothing ? C_NULL : pointer(reinterpret(Float32, ns)), n,
+                pointer(reinterpret(Float32, qs)), m, p, device, dist, nn, st))
+        else
+            check(ccall((:rh_cloud_distance, LIB), Cint,
+                (Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ref{RhDistanceParams}, Cint, Ptr{Cdouble}, Ptr{Int32}, Ref{RhDistanceStats}),
+                pointer(reinterpret(Float64, rs)), ns === nothing ? C_NULL : pointer(reinterpret(Float64, ns)), n,
+                pointer(reinterpret(Float64, qs)), m, p, device, dist, nn, st))
+        end
+    end
+    return dist, nn, st[]
+end
+
 _assign_shape(x::ExtractedShape) = toC(x.shape)
 _assign_shape(x::FittedShape) = toC(x)
 

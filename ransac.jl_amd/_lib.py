@@ -87,7 +87,19 @@ class ClusterStats(C.Structure):
                 ("n_small", C.c_int64), ("largest", C.c_int64)]
 
 
+class DistanceParams(C.Structure):
+    """rh_distance_params (include/ransac_hip.h)"""
+    _fields_ = [("radius", C.c_double), ("threshold", C.c_double), ("metric", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DistanceStats(C.Structure):
+    """rh_distance_stats (include/ransac_hip.h)"""
+    _fields_ = [("n_valid", C.c_int64), ("n_within", C.c_int64), ("argmax", C.c_int64), ("mean", C.c_double),
+                ("rms", C.c_double), ("max", C.c_double), ("median", C.c_double)]
+
+
 KNN_MAX_K = 63
+DIST_POINT, DIST_PLANE = 0, 1
 OUT_BLOCK_POINTS = 1024
 OUT_STATISTICAL, OUT_ABSOLUTE, OUT_RADIUS = 0, 1, 2
 CLUSTER_BY_INDEX, CLUSTER_BY_SIZE = 0, 1
@@ -214,6 +226,13 @@ SIGNATURES = {
                                           C.POINTER(C.c_float), C.POINTER(C.c_float), _i64p, _i32p, C.c_int64, _i32p, _i64p, _i64p]),
     "rh_knn": (C.c_int, [_dp, C.c_int64, C.c_int32, C.c_double, C.c_int, _i32p, _dp, _i32p]),
     "rh_knn_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_double, C.c_int, _i32p, _dp, _i32p]),
+    "rh_knn_query": (C.c_int, [_dp, C.c_int64, _dp, C.c_int64, C.c_int32, C.c_double, C.c_int, _i32p, _dp, _i32p]),
+    "rh_knn_query_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_double, C.c_int,
+                                   _i32p, _dp, _i32p]),
+    "rh_cloud_distance": (C.c_int, [_dp, _dp, C.c_int64, _dp, C.c_int64, C.POINTER(DistanceParams), C.c_int, _dp, _i32p,
+                                    C.POINTER(DistanceStats)]),
+    "rh_cloud_distance_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float), C.c_int64,
+                                        C.POINTER(DistanceParams), C.c_int, _dp, _i32p, C.POINTER(DistanceStats)]),
     "rh_remove_outliers": (C.c_int, [_dp, C.c_int64, C.POINTER(OutlierParams), C.c_int, _u8p, _i32p, C.c_int64, _i64p, _dp,
                                      C.POINTER(OutlierStats)]),
     "rh_remove_outliers_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(OutlierParams), C.c_int, _u8p, _i32p,

@@ -815,6 +815,86 @@ def knn(vertices, k, radius=0.0, return_dist=True, return_count=False, device=0)
     return out[0] if len(out) == 1 else out
 
 
+def _cloud_pair(who, reference, queries, extra=None):
+    """The two clouds (and the reference's `extra` rows) as (n, 3) / (m, 3) arrays of one dtype: float32 when all are,
+    float64 otherwise (a mixed pair is widened, exactly)."""
+    arrs = [np.asarray(a) for a in (reference, queries) + ((extra,) if extra is not None else ())]
+    f32 = all(a.dtype == np.float32 for a in arrs)
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    arrs = [np.ascontiguousarray(a, dtype=t).reshape(-1, 3) for a in arrs]
+    if extra is not None and arrs[2].shape[0] != arrs[0].shape[0]:
+        raise ValueError("%s: %d normals for %d reference points" % (who, arrs[2].shape[0], arrs[0].shape[0]))
+    return f32, ct, arrs
+
+
+def knn_query(reference, queries, k, radius=0.0, return_dist=True, return_count=False, device=0):
+    """The k nearest points of `reference` for every point of `queries` (rh_knn_query: exact, d^2 = (dx*dx + dy*dy) + dz*dz
+    in binary64, ties to the smaller reference index; no point is left out, so a reference point equal to the query is its
+    first neighbour at 0 -- knn() is the call for a cloud's own points).  reference (n, 3), queries (m, 3): both float32
+    take the float32 entry (widened exactly on the device), a mixed pair is widened to float64 here.  k: 1 .. 63;
+    radius > 0 drops neighbours farther than it.
+    Returns idx (m, k) int32, 1-based rows of `reference` in the order of `queries`, 0 where a query has fewer neighbours;
+    then with return_dist the squared distances (m, k) float64, +inf there; then with return_count the neighbours per
+    query (m,) int32."""
+    f32, ct, (ref, qry) = _cloud_pair("knn_query", reference, queries)
+    n, m, k = ref.shape[0], qry.shape[0], int(k)
+    kk = k if 1 <= k <= L.KNN_MAX_K else 1            # (the library refuses the call; nothing is written)
+    idx = np.zeros((m, kk), dtype=np.int32)
+    d2 = np.full((m, kk), np.inf) if return_dist else None
+    cnt = np.zeros(m, dtype=np.int32) if return_count else None
+    fn = lib().rh_knn_query_f32 if f32 else lib().rh_knn_query
+    check(fn(_p(ref, ct), n, _p(qry, ct), m, k, float(radius), device, _p(idx, C.c_int32),
+             None if d2 is None else _p(d2, C.c_double), None if cnt is None else _p(cnt, C.c_int32)))
+    out = (idx,) + ((d2,) if return_dist else ()) + ((cnt,) if return_count else ())
+    return out[0] if len(out) == 1 else out
+
+
+def cloud_distance(reference, queries, normals=None, radius=0.0, threshold=math.inf, metric=None, return_index=False,
+                   return_stats=False, device=0):
+    """How far every point of `queries` lies from the cloud `reference` (rh_cloud_distance; include/ransac_hip.h has the
+    definition in full).  metric "point": the distance to the nearest reference point; "plane": |(q - r) . n| with r that
+    point and n its row of `normals` (the reference's, used as given); the default is "plane" when normals are given and
+    "point" otherwise.  radius > 0: a query without a reference point within it is not valid and gets +inf.
+    Returns dist (m,) float64, then on request: return_index the nearest reference point of every query (1-based int32, 0:
+    none), return_stats a dict n_valid, n_within (valid queries with dist <= threshold), argmax (1-based, 0: none), mean,
+    rms, max, median over the valid queries.  The measures are one-sided, queries -> reference: the symmetric Hausdorff
+    distance is the larger `max` of the two calls with the clouds exchanged, the Chamfer distance the sum of their `mean`."""
+    metrics = {"point": L.DIST_POINT, "plane": L.DIST_PLANE}
+    if metric is None:
+        metric = "point" if normals is None else "plane"
+    if isinstance(metric, str) and metric not in metrics:
+        raise ValueError("cloud_distance: metric %r is neither 'point' nor 'plane'" % (metric,))
+    f32, ct, arrs = _cloud_pair("cloud_distance", reference, queries, normals)
+    ref, qry, nrm = arrs[0], arrs[1], (arrs[2] if normals is not None else None)
+    n, m = ref.shape[0], qry.shape[0]
+    prm = L.DistanceParams(radius=float(radius), threshold=float(threshold), metric=int(metrics.get(metric, metric)))
+    dist = np.full(m, np.inf)
+    nn = np.zeros(m, dtype=np.int32) if return_index else None
+    st = L.DistanceStats()
+    fn = lib().rh_cloud_distance_f32 if f32 else lib().rh_cloud_distance
+    check(fn(_p(ref, ct), None if nrm is None else _p(nrm, ct), n, _p(qry, ct), m, C.byref(prm), device, _p(dist, C.c_double),
+             None if nn is None else _p(nn, C.c_int32), C.byref(st) if return_stats else None))
+    out = (dist,) + ((nn,) if return_index else ())
+    out += (({f: getattr(st, f) for f, _ in L.DistanceStats._fields_},) if return_stats else ())
+    return out[0] if len(out) == 1 else out
+
+
+def transfer_labels(reference, labels, queries, radius=0.0, fill=0, device=0):
+    """Carry a per-point attribute from one cloud to another: row j of the result is labels[i] for the point i of
+    `reference` nearest to queries[j] (knn_query with k = 1), or `fill` when radius > 0 and no reference point lies within
+    it.  labels: (n,) or (n, ...), any dtype -- labels of assign_points or cluster found on a thinned or cleaned cloud,
+    normals, colours.  Returns an array of shape (m, ...) and the dtype of labels."""
+    lab = np.asarray(labels)
+    n = np.asarray(reference).reshape(-1, 3).shape[0]
+    if lab.shape[:1] != (n,):
+        raise ValueError("transfer_labels: %d labels for %d reference points" % (lab.shape[0] if lab.ndim else 0, n))
+    idx = knn_query(reference, queries, 1, radius=radius, return_dist=False, device=device)[:, 0]
+    out = np.full((idx.shape[0],) + lab.shape[1:], fill, dtype=lab.dtype)
+    hit = idx > 0
+    out[hit] = lab[idx[hit] - 1]
+    return out
+
+
 def removeoutliers(vertices, k=16, std_mul=2.0, mode="statistical", radius=0.0, threshold=None, normals=None, device=0,
                    return_index=False, return_stats=False, return_mean_dist=False):
     """Drop the stray points of a raw cloud (rh_remove_outliers; include/ransac_hip.h has the definition in full).  With

@@ -4,22 +4,14 @@
 //   1. the query epilogue: lanes 1 .. k of the wave's sorted list written as idx / d2 / count in original point order, or,
 //      for outlier removal, only m_i (the mean neighbour distance), count_i and sqrt(d2_i1) -- 20 bytes per point, the
 //      n x k lists never exist;
-//   2. the tree reductions of mu and sigma: T() of the header is a perfect binary tree over adjacent pairs, and a lane's
-//      four values, a butterfly over lanes with xor 1, 2, .. 32, adjacent pairs of the four wave sums and then the same
-//      kernel over the block partials are that very tree, so the bits do not depend on the launch geometry.  No
-//      floating-point atomics;
+//   2. the tree reductions of mu and sigma: T() of the header, stated once in tree_sum.h.  No floating-point atomics;
 //   3. the flag pass and a stable compaction of the kept indices (hipcub's scan-based DeviceSelect);
 //   4. the lower median of the nearest-neighbour distances: a radix sort of the bit patterns of the non-negative doubles.
 // Scratch is allocated per call and freed on every way out (call_scope.h).
 #include "knn_device.h"
+#include "tree_sum.h"
 
 namespace {
-
-constexpr int OUT_THREADS = 256;
-constexpr int OUT_PER_THREAD = 4;
-constexpr int OUT_BLOCK_POINTS = OUT_THREADS * OUT_PER_THREAD;
-static_assert(OUT_BLOCK_POINTS == RH_OUT_BLOCK_POINTS, "the header names the block size of the reduction tree");
-static_assert(OUT_THREADS == 4 * 64, "the block's last two tree levels are written out for four waves");
 
 struct KnnOut {
     int32_t *idx;            // [n x kk] or null
@@ -28,13 +20,6 @@ struct KnnOut {
     double *mean;            // [n] or null: outlier mode, with nn1
     double *nn1;             // [n]
 };
-
-// the sum of the 64 lanes' values as the tree over adjacent pairs; every lane ends with the same bits
-__device__ inline double tree64(double v)
-{
-    for (int j = 1; j < 64; j <<= 1) v += __shfl_xor(v, j);
-    return v;
-}
 
 __global__ __launch_bounds__(NRM_BLOCK) void knn_query_kernel(Grid g, KnnQuery kq, KnnOut o)
 {
@@ -76,38 +61,6 @@ struct OutScal {
     int32_t nkept;
     int32_t pad;
 };
-
-// One level of the tree: block b leaves T() of its OUT_BLOCK_POINTS leaves (+0.0 past n) in part[b].
-// MODE 0: leaf i = m_i for i in V (count_i >= 1), and V is counted; 1: (m_i - mu)*(m_i - mu) for i in V; 2: v_i as it is.
-template <int MODE>
-__global__ __launch_bounds__(OUT_THREADS) void out_tree_kernel(const double *__restrict__ v, const int32_t *__restrict__ count,
-                                                              int64_t n, OutScal *sc, double *__restrict__ part)
-{
-    const int64_t base = ((int64_t)blockIdx.x * OUT_THREADS + threadIdx.x) * OUT_PER_THREAD;
-    double a[OUT_PER_THREAD];
-    int nv = 0;
-    const double mu = MODE == 1 ? sc->mu : 0.0;
-    for (int j = 0; j < OUT_PER_THREAD; j++) {
-        const int64_t i = base + j;
-        a[j] = 0.0;
-        if (i >= n) continue;
-        if (MODE == 2) { a[j] = v[i]; continue; }
-        if (count[i] < 1) continue;
-        nv++;
-        const double x = v[i];
-        if (MODE == 0) a[j] = x;
-        else { const double d = x - mu; a[j] = d * d; }
-    }
-    const double s = tree64((a[0] + a[1]) + (a[2] + a[3]));
-    __shared__ double ws[OUT_THREADS / 64];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    if (MODE == 0) {
-        for (int j = 1; j < 64; j <<= 1) nv += __shfl_xor(nv, j);
-        if ((threadIdx.x & 63) == 0 && nv) atomicAdd(&sc->nvalid, (unsigned long long)nv);   // an integer count
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
-}
 
 // step 0: mu from the root of the first tree; step 1: sigma from the second's, and tau
 __global__ void out_scalars_kernel(OutScal *sc, const double *root, int step, rh_outlier_params p)
@@ -188,27 +141,6 @@ int knn(const T *xyz_aos, int64_t n, int32_t k, double radius, int device, int32
     return RH_OK;
 }
 
-// T() over the leaves of MODE (0 / 1) of the n points: level after level until one value is left; *root_out points at it
-template <int MODE>
-int tree_root(CallScope &S, const double *d_mean, const int32_t *d_count, int64_t n, OutScal *d_sc,
-              double *d_part[2], const double **root_out)
-{
-    int64_t len = (n + OUT_BLOCK_POINTS - 1) / OUT_BLOCK_POINTS;
-    hipLaunchKernelGGL(out_tree_kernel<MODE>, dim3((unsigned)len), dim3(OUT_THREADS), 0, S.st, d_mean, d_count, n, d_sc, d_part[0]);
-    SCOPE_HIP(S, hipGetLastError());
-    int cur = 0;
-    while (len > 1) {
-        const int64_t nb = (len + OUT_BLOCK_POINTS - 1) / OUT_BLOCK_POINTS;
-        hipLaunchKernelGGL(out_tree_kernel<2>, dim3((unsigned)nb), dim3(OUT_THREADS), 0, S.st, d_part[cur], (const int32_t *)nullptr, len,
-                           d_sc, d_part[cur ^ 1]);
-        SCOPE_HIP(S, hipGetLastError());
-        cur ^= 1;
-        len = nb;
-    }
-    *root_out = d_part[cur];
-    return RH_OK;
-}
-
 template <typename T>
 int remove_outliers(const T *xyz_aos, int64_t n, const rh_outlier_params *p, int device, uint8_t *keep_out, int32_t *kept_idx_out,
                     int64_t cap, int64_t *n_kept_out, double *mean_dist_out, rh_outlier_stats *stats)
@@ -243,15 +175,13 @@ int remove_outliers(const T *xyz_aos, int64_t n, const rh_outlier_params *p, int
     // 2. mu, then sigma and tau
     OutScal *d_sc = nullptr;
     double *d_part[2] = { nullptr, nullptr };
-    const int64_t len1 = (n + OUT_BLOCK_POINTS - 1) / OUT_BLOCK_POINTS;
     RH_TRY(S.alloc(&d_sc, 1));
-    RH_TRY(S.alloc(&d_part[0], len1));
-    RH_TRY(S.alloc(&d_part[1], (len1 + OUT_BLOCK_POINTS - 1) / OUT_BLOCK_POINTS));
+    RH_TRY(tree_alloc(S, n, d_part));
     SCOPE_HIP(S, hipMemsetAsync(d_sc, 0, sizeof(OutScal), st));
     const double *d_root = nullptr;
-    RH_TRY(tree_root<0>(S, o.mean, o.count, n, d_sc, d_part, &d_root));
+    RH_TRY(tree_root<0>(S, o.mean, o.count, n, &d_sc->mu, &d_sc->nvalid, d_part, &d_root));
     hipLaunchKernelGGL(out_scalars_kernel, dim3(1), dim3(64), 0, st, d_sc, d_root, 0, *p);
-    RH_TRY(tree_root<1>(S, o.mean, o.count, n, d_sc, d_part, &d_root));
+    RH_TRY(tree_root<1>(S, o.mean, o.count, n, &d_sc->mu, &d_sc->nvalid, d_part, &d_root));
     hipLaunchKernelGGL(out_scalars_kernel, dim3(1), dim3(64), 0, st, d_sc, d_root, 1, *p);
     SCOPE_HIP(S, hipGetLastError());
 

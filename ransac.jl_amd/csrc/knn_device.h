@@ -1,13 +1,15 @@
 // knn_device.h -- the exact k-nearest-neighbour query over the grid of knn_grid.h, one wave per query point:
-//   lane j holds the j-th best (d^2, rank) pair, rank 0 = the point itself, rank i + 1 = point i (so ties go to the smaller
-//   index), d^2 = (dx*dx + dy*dy) + dz*dz in binary64.  The cells of shell s (Chebyshev distance s from the query's cell)
+//   lane j holds the j-th best (d^2, rank) pair, rank 0 = the point itself (a self query), rank i + 1 = point i (so ties
+//   go to the smaller index), d^2 = (dx*dx + dy*dy) + dz*dz in binary64.  The cells of shell s (Chebyshev distance s from the query's cell)
 //   stream their points in 64 at a time; a batch with a candidate below the k-th best is sorted (bitonic, __shfl_xor) and
 //   merged with the best list.  The search stops when the k-th best d^2 is below the squared distance to the faces of the
 //   cube searched so far (or beyond the radius), so the result is exact.  A point whose next shell would enumerate more
 //   cells than the hash table has slots scans the table instead (every occupied cell not yet visited, pruned by its box
 //   distance): isolated points end, and end exact.
-// knn_search() is that loop; a kernel calls it and goes on with its own epilogue over the wave's sorted list (the PCA of
-// normals.hip, the lists and mean distances of knn.hip).  knn_index_for_k() chooses the cell width for a list length.
+// knn_search_point() is that loop, for any query point; knn_search() runs it for a point of the cloud itself.  A kernel
+// calls one of them and goes on with its own epilogue over the wave's sorted list (the PCA of normals.hip, the lists and
+// mean distances of knn.hip, the cross-cloud lists and distances of knn_query.hip).  knn_index_for_k() chooses the cell
+// width for a list length.
 #pragma once
 
 #include "knn_grid.h"
@@ -111,14 +113,19 @@ struct KnnQuery {
     int smax;                // last shell enumerated cell by cell; beyond it the hash table is scanned
 };
 
-// The search of query wave w (wave-uniform; the caller has checked w < a.nq): on return lane j holds the j-th entry of the
-// point's order in (bd, br) -- br = NRM_NORANK where the cloud has fewer points -- p the point and self its original index.
-__device__ inline void knn_search(const Grid &g, const KnnQuery &a, int lane, int64_t w, double p[3], int32_t &self,
-                                  double &bd, uint32_t &br)
+// The search for query point p (wave-uniform): on return lane j holds the j-th entry of p's order in (bd, br) -- br =
+// NRM_NORANK where the cloud has fewer points.  self is the index of the reference point that is p itself and ranks first
+// (rank 0) whatever its d^2; self = -1: p is no point of the grid's cloud (a cross query, knn_query.hip), nothing is
+// excluded and rank = index + 1 throughout.
+// p need not lie inside the grid's box: cell_of clamps, so c is the cell nearest to p along every axis.  cell_lb is the
+// distance to a cell's box wherever p is.  The bound `inner` below stays a lower bound for a clamped cell: along an axis
+// where p lies below the box, c = 0, so the cube's lower face is the grid's boundary and is not used (no point lies beyond
+// it), and its upper face o + (s + 1) h lies above p, so every unseen point beyond that face is at least face - p away;
+// above the box the same holds with the sides exchanged.  g.margin must cover the rounding of p - face at p's magnitude:
+// a cross query enlarges it by the query box (enlarging the margin never changes a result, it only prunes less).
+__device__ inline void knn_search_point(const Grid &g, const KnnQuery &a, int lane, const double p[3], int32_t self,
+                                        double &bd, uint32_t &br)
 {
-    const int64_t sp = a.sample ? w * a.n / a.nq : w;
-    p[0] = g.sx[sp]; p[1] = g.sy[sp]; p[2] = g.sz[sp];
-    self = g.sidx[sp];
     int64_t c[3];
     for (int ax = 0; ax < 3; ax++) c[ax] = cell_of(p[ax], g.o[ax], g.h, g.dim[ax]);
     const int k = a.k;
@@ -177,6 +184,17 @@ __device__ inline void knn_search(const Grid &g, const KnnQuery &a, int lane, in
         inner -= g.margin;
         if (inner > 0.0 && (inner * inner > kd || (radius > 0.0 && inner > radius))) break;
     }
+}
+
+// The self query of wave w (wave-uniform; the caller has checked w < a.nq): the query point is a point of the sorted
+// arrays; on return p is the point and self its original index, (bd, br) as above.
+__device__ inline void knn_search(const Grid &g, const KnnQuery &a, int lane, int64_t w, double p[3], int32_t &self,
+                                  double &bd, uint32_t &br)
+{
+    const int64_t sp = a.sample ? w * a.n / a.nq : w;
+    p[0] = g.sx[sp]; p[1] = g.sy[sp]; p[2] = g.sz[sp];
+    self = g.sidx[sp];
+    knn_search_point(g, a, lane, p, self, bd, br);
 }
 
 // the cell-width sample: only the k-th best d^2 of every query

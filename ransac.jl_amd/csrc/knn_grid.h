@@ -1,6 +1,6 @@
 // knn_grid.h -- the uniform grid of the exact k-nearest-neighbour search (knn_device.h has the query), shared by
-// normals.hip (rh_estimate_normals), knn.hip (rh_knn, rh_remove_outliers) and cluster.hip (rh_cluster, which walks the
-// cells itself):
+// normals.hip (rh_estimate_normals), knn.hip (rh_knn, rh_remove_outliers), knn_query.hip (rh_knn_query,
+// rh_cloud_distance: the grid holds the reference cloud) and cluster.hip (rh_cluster, which walks the cells itself):
 //   points radix-sorted by cell key, an open-addressing hash table key -> [start, end) of the occupied cells only (empty
 //   space costs nothing; table and bounding box are cell_grid.h's), the coordinates gathered into cell order.  KnnIndex
 //   holds the grid's buffers in the call's scope (call_scope.h) and rebuilds the grid for any cell width.
@@ -100,6 +100,23 @@ __global__ void nrm_hash_kernel(const uint64_t *__restrict__ key, int64_t n, uin
     if (end) hrange[2 * (size_t)sl + 1] = (int32_t)(i + 1);
 }
 
+// the bounding box of the n points of d_xyz; RH_E_INVALID on a coordinate that is not finite (one round trip to the host)
+inline int cloud_box(CallScope &S, const double *d_xyz, int64_t n, double lo[3], double hi[3])
+{
+    const hipStream_t st = S.st;
+    const int64_t nb = std::min<int64_t>(blocks_for(n), GRID_MM_BLOCKS);
+    unsigned long long *d_scal = nullptr, h_scal[MM_COUNT + 1];
+    RH_TRY(S.alloc(&d_scal, MM_WORDS * (1 + nb)));
+    hipLaunchKernelGGL(nrm_minmax_kernel, dim3((unsigned)nb), dim3(256), 0, st, d_xyz, n, d_scal + MM_WORDS);
+    hipLaunchKernelGGL(grid_minmax_fold_kernel, dim3(1), dim3(256), 0, st, d_scal + MM_WORDS, (int)nb, d_scal, (int)MM_WORDS);
+    SCOPE_HIP(S, hipGetLastError());
+    SCOPE_HIP(S, hipMemcpyAsync(h_scal, d_scal, sizeof h_scal, hipMemcpyDeviceToHost, st));
+    SCOPE_HIP(S, hipStreamSynchronize(st));
+    if ((int64_t)h_scal[MM_COUNT] != n) { rh_set_error("%s: a coordinate is not finite", S.who); return RH_E_INVALID; }
+    for (int ax = 0; ax < 3; ax++) { lo[ax] = ord_back(h_scal[MM_MIN + ax]); hi[ax] = ord_back(h_scal[MM_MAX + ax]); }
+    return RH_OK;
+}
+
 // The grid over the n points of one call: init() finds the bounding box (RH_E_INVALID on a coordinate that is not finite)
 // and allocates, build(h) makes the grid of cell width h (again and again: the buffers are re-used).
 struct KnnIndex {
@@ -121,24 +138,14 @@ struct KnnIndex {
     int init(CallScope &S_, double *d_xyz_, int64_t n_)
     {
         S = &S_; d_xyz = d_xyz_; n = n_;
-        const hipStream_t st = S->st;
-        // bounding box and the finiteness of every coordinate
-        const int64_t nb = std::min<int64_t>(blocks_for(n), GRID_MM_BLOCKS);
-        unsigned long long *d_scal = nullptr, h_scal[MM_COUNT + 1];
-        RH_TRY(S->alloc(&d_scal, MM_WORDS * (1 + nb)));
-        hipLaunchKernelGGL(nrm_minmax_kernel, dim3((unsigned)nb), dim3(256), 0, st, d_xyz, n, d_scal + MM_WORDS);
-        hipLaunchKernelGGL(grid_minmax_fold_kernel, dim3(1), dim3(256), 0, st, d_scal + MM_WORDS, (int)nb, d_scal, (int)MM_WORDS);
-        SCOPE_HIP(*S, hipGetLastError());
-        SCOPE_HIP(*S, hipMemcpyAsync(h_scal, d_scal, sizeof h_scal, hipMemcpyDeviceToHost, st));
-        SCOPE_HIP(*S, hipStreamSynchronize(st));
-        if ((int64_t)h_scal[MM_COUNT] != n) { rh_set_error("%s: a coordinate is not finite", S->who); return RH_E_INVALID; }
-        for (int ax = 0; ax < 3; ax++) { lo[ax] = ord_back(h_scal[MM_MIN + ax]); hi[ax] = ord_back(h_scal[MM_MAX + ax]); }
+        RH_TRY(cloud_box(*S, d_xyz, n, lo, hi));
         L = 0.0; omax = 0.0;
         for (int ax = 0; ax < 3; ax++) {
             ext[ax] = hi[ax] - lo[ax];
             L = std::max(L, ext[ax]);
             omax = std::max(omax, std::max(fabs(lo[ax]), fabs(hi[ax])));
         }
+        const hipStream_t st = S->st;
         RH_TRY(S->alloc(&d_key[0], n)); RH_TRY(S->alloc(&d_key[1], n));
         RH_TRY(S->alloc(&d_idx[0], n)); RH_TRY(S->alloc(&d_idx[1], n));
         for (int ax = 0; ax < 3; ax++) RH_TRY(S->alloc(&d_s[ax], n));
