@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 117
+#define RH_VERSION 118
 
 enum {
     RH_OK = 0,
@@ -792,6 +792,9 @@ int rh_cloud_distance_f32(const float *ref_xyz_aos, const float *ref_nrm_aos_or_
  *                 culled score kernel tests every candidate against the boxes of the SUPER-TILES (16 groups of 64 points)
  *                 and leaves per super-tile the list of candidates that may meet it; the score kernel's blocks then walk
  *                 those lists instead of every candidate of the batch.  Read on every launch.
+ *   "st_list_mb"  0 (default: 512) or the most MiB the candidate lists of one batch slot may take (8 bytes per super-tile of
+ *                 1024 subset points and candidate); a launch that would need more, or whose allocation fails, takes no lists.
+ *                 Read on every launch.
  *   "batches_in_flight"  1 (default) .. 4 -- with F > 1, rh_score_batch_dev calls take turns on the cloud's
  *                 stream and F - 1 more with workspaces of their own, so one batch's prepare + score launches start while
  *                 the previous batches' launches drain.  The caller keeps F count (and mask) buffers and gives call k of a

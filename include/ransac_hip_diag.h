@@ -31,6 +31,10 @@ int rh_dbg_cls_audit(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_pa
  * out[48 + k]: pairs whose SUPER-TILE's box (16 groups: the lists of st_cull) rules the candidate out, out[52 + k]: VIOLATION: such
  * a pair with an exact inlier (must be 0). */
 int rh_dbg_cls_soundness(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out /* [56] */);
+/* the same census at the level of the TILES (4 groups: what candidate lists per tile would skip): out[k] = pairs
+ * (candidate, group) whose tile's box rules the candidate out, out[4 + k] = VIOLATION: such a pair with an exact inlier
+ * (must be 0). */
+int rh_dbg_cls_soundness_tiles(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out /* [8] */);
 /* The device's octree sampler finds a point's cell and the r-th enabled point of a cell with a cell directory and
  * bracketed 8-ary searches (csrc/fit_shared.h: cell_bounds_code, lower_bound_in, select_in, select_in_many, select_bit)
  * where the host form uses plain binary searches.  Host-only self-check of those routines against the plain ones on a

@@ -243,6 +243,7 @@ SIGNATURES = {
 DIAG_SIGNATURES = {
     "rh_dbg_cls_audit": (C.c_int, [_vp, _sp, C.c_int32, _pp, _dp]),
     "rh_dbg_cls_soundness": (C.c_int, [_vp, _sp, C.c_int32, _pp, C.POINTER(C.c_uint64)]),
+    "rh_dbg_cls_soundness_tiles": (C.c_int, [_vp, _sp, C.c_int32, _pp, C.POINTER(C.c_uint64)]),
     "rh_dbg_oct_search_selftest": (C.c_int, [C.c_int64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]),
     "rh_dbg_s4_stats": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64)]),
 }

@@ -177,7 +177,7 @@ static void cloud_free(rh_cloud *c)
     (void)hipFree(c->sub_idx0); (void)hipFree(c->enabled); (void)hipFree(c->sub_enabled);
     (void)hipFree(c->sub_perm); (void)hipFree(c->gb);
     (void)hipFree(c->full32); (void)hipFree(c->sub32); (void)hipFree(c->d_zero);
-    (void)hipFree(c->s4_stats); (void)hipFree(c->gb32); (void)hipFree(c->st32);
+    (void)hipFree(c->s4_stats); (void)hipFree(c->gb32); (void)hipFree(c->st32); (void)hipFree(c->tile32);
     (void)hipFree(c->oct_code); (void)hipFree(c->oct_perm); (void)hipFree(c->oct_pos); (void)hipFree(c->oct_men);
     (void)hipFree(c->oct_prefix); (void)hipFree(c->oct_P); (void)hipFree(c->oct_tab); (void)hipFree(c->oct_code_o);
     (void)hipFree(c->oct_state); (void)hipFree(c->oct_adv_tab); (void)hipFree(c->oct_adv_bits); (void)hipFree(c->oct_adv_E);
@@ -400,6 +400,8 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
     CK(dev_alloc(&c->gb32, 8 * c->ng_pad));
     c->nst = (c->ngroups + 15) / 16;
     CK(dev_alloc(&c->st32, 8 * std::max<int64_t>(1, c->nst)));
+    c->ntile = (c->ngroups + 3) / 4;
+    CK(dev_alloc(&c->tile32, 8 * std::max<int64_t>(1, c->ntile)));
     CK(dev_alloc(&c->dis_gb, 7 * c->ng_pad));
     CK(dev_alloc(&c->dis_gb32, 8 * c->ng_pad));
     CKH(hipMemsetAsync(c->dis_gb, 0, sizeof(double) * 7 * (size_t)c->ng_pad, c->stream));

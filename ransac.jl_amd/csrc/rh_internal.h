@@ -37,6 +37,7 @@ enum rh_opt_id {
     RH_OPT_ST_CULL,
     RH_OPT_REFIT_PATH,
     RH_OPT_BATCHES_IN_FLIGHT,
+    RH_OPT_ST_LIST_MB,
     RH_OPT_N_PRODUCT,
     // A/B switches and diagnostics: alive in the diag build only (in the product build they read as unset)
     RH_OPT_CREATE_PROF = RH_OPT_N_PRODUCT, RH_OPT_AABB_HOST, RH_OPT_SUB_ORDER, RH_OPT_KD_HOST, RH_OPT_NO_SPREAD, RH_OPT_OCT_CHAIN_W,
@@ -207,6 +208,7 @@ struct rh_batch_ws {
     uint16_t *d_stlist = nullptr;
     int32_t *d_stcount = nullptr;
     int64_t stlist_cap = 0, stlist_nst = 0;
+    int64_t stlist_nomem = 0;          // bytes of the list allocation that failed last (0: none did): not tried again at that size or above
     // mask un-permutation of rows that span 2..16 segments (rhk_unpermute_masks4): per output segment and internal word, the bits
     // that land in the segment.  Built on the slot's own stream, so stream order alone puts it in front of the slot's readers.
     uint64_t *d_segmask = nullptr;
@@ -295,6 +297,8 @@ struct rh_cloud {
     float *gb32 = nullptr;             // the same boxes in binary32, 8 floats per group (v4 score kernel: scalar loads)
     float *st32 = nullptr;             // boxes of the super-tiles (16 consecutive groups = 4 tiles of the k-d leaf order), 8 floats each
     int64_t nst = 0;
+    float *tile32 = nullptr;           // boxes of the tiles (4 consecutive groups: what a block of the culled score kernel stages; the diag build's pair census reads them), 8 floats each
+    int64_t ntile = 0;
     double *dis_gb = nullptr;          // boxes of the dis segment in use (7 x ng_pad)
     int32_t *d_ndis = nullptr;         // device counter: entries in dis
     int64_t n_dis = 0;                 // host mirror

@@ -696,7 +696,7 @@ struct S4SoundArgs { double eps[4], cosa[4]; int f32; };
 
 template <int KIND>
 static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4SoundArgs &A, double x, double y, double z, double nx, double ny,
-                                                 double nz, const uint64_t valid, const rh_box32 &G, const rh_box32 &GS, const int lane, unsigned long long *__restrict__ out)
+                                                 double nz, const uint64_t valid, const rh_box32 &G, const rh_box32 &GS, const rh_box32 &GT, const int lane, unsigned long long *__restrict__ out)
 {
     const double eps = A.eps[KIND], cosa = A.cosa[KIND];
     uint64_t ex;
@@ -705,6 +705,7 @@ static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4S
     ex &= valid;
     const bool skip = box_skip32<KIND>(Q.box, G);
     const bool stskip = box_skip32<KIND>(Q.box, GS);   // the super-tile's box (st_cull_kernel): out[48 + k] such pairs, out[52 + k] VIOLATION: with an exact inlier
+    const bool tlskip = box_skip32<KIND>(Q.box, GT);   // the tile's box (the lists the score launch walks): out[56 + k] such pairs, out[60 + k] VIOLATION: with an exact inlier
     const bool exact_only = is_nan_bits(Q.C.f[RH_CLS_FLAG]);
     const float fx = (float)x, fy = (float)y, fz = (float)z, fnx = (float)nx, fny = (float)ny, fnz = (float)nz;
     float t, t0;   // (the u of score4_device.h: sign bit = surely in, 0 <= u <= 1 undecided)
@@ -732,6 +733,8 @@ static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4S
         if (ex != 0) atomicAdd(&out[44 + KIND], 1ULL);
         if (stskip) atomicAdd(&out[48 + KIND], 1ULL);
         if (stskip && ex != 0) atomicAdd(&out[52 + KIND], 1ULL);
+        if (tlskip) atomicAdd(&out[56 + KIND], 1ULL);
+        if (tlskip && ex != 0) atomicAdd(&out[60 + KIND], 1ULL);
         unsigned long long *o = out + KIND * 10;
         atomicAdd(&o[0], 1ULL);
         if (skip) atomicAdd(&o[1], 1ULL);
@@ -747,7 +750,7 @@ static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4S
 }
 
 __global__ void __launch_bounds__(64)
-cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const float *__restrict__ gb32, const float *__restrict__ st32, const S4SoundCand *__restrict__ cands,
+cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const float *__restrict__ gb32, const float *__restrict__ st32, const float *__restrict__ tile32, const S4SoundCand *__restrict__ cands,
                  int ncand, const S4SoundArgs A, unsigned long long *__restrict__ out)
 {
     const int lane = threadIdx.x;
@@ -765,13 +768,18 @@ cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, cons
         const float *b = st32 + (g / S4_STG) * 8;
         GS.cx = b[0]; GS.cy = b[1]; GS.cz = b[2]; GS.hx = b[3]; GS.hy = b[4]; GS.hz = b[5]; GS.hr = b[6];
     }
+    rh_box32 GT;
+    {
+        const float *b = tile32 + (g / S4_TG) * 8;
+        GT.cx = b[0]; GT.cy = b[1]; GT.cz = b[2]; GT.hx = b[3]; GT.hy = b[4]; GT.hz = b[5]; GT.hr = b[6];
+    }
     for (int c = blockIdx.y; c < ncand; c += gridDim.y) {
         const S4SoundCand &Q = cands[c];
         switch (Q.kind) {
-        case RH_PLANE: sound_one<RH_PLANE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, lane, out); break;
-        case RH_SPHERE: sound_one<RH_SPHERE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, lane, out); break;
-        case RH_CYLINDER: sound_one<RH_CYLINDER>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, lane, out); break;
-        case RH_CONE: sound_one<RH_CONE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, lane, out); break;
+        case RH_PLANE: sound_one<RH_PLANE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, lane, out); break;
+        case RH_SPHERE: sound_one<RH_SPHERE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, lane, out); break;
+        case RH_CYLINDER: sound_one<RH_CYLINDER>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, lane, out); break;
+        case RH_CONE: sound_one<RH_CONE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, lane, out); break;
         default: break;
         }
     }
@@ -915,15 +923,16 @@ __global__ void gb32_kernel(const double *__restrict__ gb, int64_t gstride, int6
     for (int k = 0; k < 8; k++) out[g * 8 + k] = o[k];
 }
 
-// boxes of the super-tiles: the union of S4_STG consecutive groups' boxes, widened by what the unions' own arithmetic can
-// lose, then made binary32 like a group's.  A group box that is not finite makes the super-tile's NaN: never skipped.
-__global__ void st32_kernel(const double *__restrict__ gb, int64_t gstride, int64_t ngroups, int64_t nst, float *__restrict__ out)
+// boxes of runs of k consecutive groups (k = S4_STG: the super-tiles, k = S4_TG: the tiles): the union of the groups' boxes,
+// widened by what the unions' own arithmetic can lose, then made binary32 like a group's.  A group box that is not finite
+// makes the union's NaN: never skipped.
+__global__ void st32_kernel(const double *__restrict__ gb, int64_t gstride, int64_t ngroups, int k_groups, int64_t nst, float *__restrict__ out)
 {
     const int64_t st = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (st >= nst) return;
     double lo[3] = { __builtin_inf(), __builtin_inf(), __builtin_inf() }, hi[3] = { -__builtin_inf(), -__builtin_inf(), -__builtin_inf() };
     bool bad = false;
-    for (int64_t g = st * S4_STG; g < (st + 1) * S4_STG && g < ngroups; g++)
+    for (int64_t g = st * k_groups; g < (st + 1) * k_groups && g < ngroups; g++)
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const double cc = gb[k * gstride + g], hh = gb[(3 + k) * gstride + g];
@@ -1026,19 +1035,22 @@ int rhk_gb32_build(rh_cloud *c)
     if (c->ngroups == 0 || c->gb32 == nullptr) return RH_OK;
     hipLaunchKernelGGL(gb32_kernel, dim3(cdiv4(c->ngroups, 256)), dim3(256), 0, c->stream, c->gb, c->ng_pad, c->ngroups, c->gb32);
     if (c->st32 != nullptr && c->nst > 0)
-        hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->nst, 64)), dim3(64), 0, c->stream, c->gb, c->ng_pad, c->ngroups, c->nst, c->st32);
+        hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->nst, 64)), dim3(64), 0, c->stream, c->gb, c->ng_pad, c->ngroups, S4_STG, c->nst, c->st32);
+    if (c->tile32 != nullptr && c->ntile > 0)
+        hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->ntile, 64)), dim3(64), 0, c->stream, c->gb, c->ng_pad, c->ngroups, S4_TG, c->ntile, c->tile32);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
 
 // the super-tile lists of the workspace's batch: [nst][4][cap] bin slots + [nst][4] counts
+static inline int64_t stlist_bytes(const rh_cloud *c, int64_t cap) { return (int64_t)sizeof(uint16_t) * c->nst * 4 * cap; }
 static int ensure_stlists(rh_cloud *c, rh_batch_ws &w, int64_t cap)
 {
     if (w.d_stlist != nullptr && cap <= w.stlist_cap && w.stlist_nst == c->nst) return RH_OK;
     const int64_t ncap = std::max<int64_t>(cap, 1024);
     w.stlist_cap = 0;
     RH_TRY(rh_grow_buffer(c, (void **)&w.d_stcount, nullptr, 0, sizeof(int32_t) * (size_t)c->nst * 4));
-    RH_TRY(rh_grow_buffer(c, (void **)&w.d_stlist, &w.stlist_cap, ncap, sizeof(uint16_t) * (size_t)c->nst * 4 * (size_t)ncap));
+    RH_TRY(rh_grow_buffer(c, (void **)&w.d_stlist, &w.stlist_cap, ncap, (size_t)stlist_bytes(c, ncap)));
     w.stlist_nst = c->nst;
     return RH_OK;
 }
@@ -1095,8 +1107,28 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
     // tiles +50 % either way.
     if (use_lists && st_opt == 0)
         use_lists = nk_total_bound >= 1024 && ntiles >= (rh_opt_int(c, RH_OPT_BATCHES_IN_FLIGHT, 1) > 1 ? 1000 : 3000);
+    // The lists are a workspace of 8 bytes per (super-tile, candidate of the batch's capacity) and batch slot: 10 MB at cfg3,
+    // 50 MB at cfg5, but 3.2 GB for 16384 candidates on a subset of 25M points.  Budget: 512 MiB per slot ("st_list_mb" changes
+    // it) -- it holds the largest batch (16384) on subsets up to 4M points and cfg5's cloud four times over, and the four slots
+    // of the most batches in flight together stay below 1 % of the card's HBM.  Beyond the budget, or when the allocation
+    // fails, the launch takes no lists: the plain instantiation computes the same counts (it ran every such launch before there
+    // were lists), and a size that failed is not tried again.
+    const int64_t lcap = std::max<int64_t>(((int64_t)nk_total_bound + 63) / 64 * 64, 1024);
     if (use_lists) {
-        RH_TRY(ensure_stlists(c, w, ((int64_t)nk_total_bound + 63) / 64 * 64));
+        const int64_t mb = rh_opt_int(c, RH_OPT_ST_LIST_MB, 0);
+        const int64_t need = stlist_bytes(c, lcap);
+        if (need > ((mb > 0 ? mb : 512) << 20) || (w.stlist_nomem > 0 && need >= w.stlist_nomem)) use_lists = false;
+    }
+    if (use_lists) {
+        const int rc = ensure_stlists(c, w, lcap);
+        if (rc == RH_E_NOMEM) {
+            (void)hipGetLastError();
+            rh_set_error("%s", "");
+            w.stlist_nomem = stlist_bytes(c, lcap);
+            use_lists = false;
+        } else if (rc != RH_OK) return rc;
+    }
+    if (use_lists) {
         StCullArgs SA;
         for (int k = 0; k < 4; k++) { SA.box[k] = B.box[k]; SA.nk[k] = job.nk[k]; }
         SA.bstride = job.bstride; SA.stcap = w.stlist_cap; SA.st32 = c->st32; SA.stlist = w.d_stlist; SA.stcount = w.d_stcount;
@@ -1117,7 +1149,7 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
     if (env_r == 4 || env_r == 8 || ((env_r == 1 || env_r == 2 || env_r == 12 || env_r == 16) && !open_count)) R = env_r;
     else if (open_count) R = ntiles * ((nchunks + 7) / 8) < 3000 ? 4 : 8;
     else if (ntiles * ((nchunks + 15) / 16) >= 16384) R = 16;
-    else if (ntiles * ((nchunks + 11) / 12) >= 3000) R = 12;
+    else if (ntiles * ((nchunks + 11) / 12) >= 3000) R = use_lists ? 16 : 12;   // (round 6, cfg3 with lists, three in flight, R = 8 / 12 / 16 -> 0.0668 / 0.0641 / 0.0629 ms)
     else if (ntiles * ((nchunks + 3) / 4) >= 4000) R = 4;
     else R = 2;
     int64_t rows = (nchunks + R - 1) / R;
@@ -1280,12 +1312,14 @@ extern "C" int rh_dbg_cls_audit(rh_cloud *c, const rh_shape *shapes, int32_t b, 
 }
 
 // diagnostics (tests, tools/fuzz_score.py): the decisions of the box test and of the classifier against the exact test
-// on every (candidate, point) of a batch x subset 1 (all points taken as enabled): out[56], layout at sound_one
-extern "C" int rh_dbg_cls_soundness(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out)
+// on every (candidate, point) of a batch x subset 1 (all points taken as enabled): 64 counters, layout at sound_one.
+// rh_dbg_cls_soundness hands out the first 56 (its callers' buffers hold that many), rh_dbg_cls_soundness_tiles the 8 of the
+// tile level.
+static int cls_soundness_run(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out, const int first, const int nout)
 {
     if (c == nullptr || out == nullptr || p == nullptr || b < 0 || (b > 0 && shapes == nullptr)) { rh_set_error("rh_dbg_cls_soundness: bad arguments"); return RH_E_INVALID; }
-    for (int i = 0; i < 56; i++) out[i] = 0;
-    if (b == 0 || c->s == 0 || c->ngroups == 0 || c->gb32 == nullptr || c->st32 == nullptr) return RH_OK;
+    for (int i = 0; i < nout; i++) out[i] = 0;
+    if (b == 0 || c->s == 0 || c->ngroups == 0 || c->gb32 == nullptr || c->st32 == nullptr || c->tile32 == nullptr) return RH_OK;
     RH_HIP(hipSetDevice(c->device));
     std::vector<S4SoundCand> h((size_t)b);
     for (int32_t i = 0; i < b; i++) {
@@ -1303,18 +1337,30 @@ extern "C" int rh_dbg_cls_soundness(rh_cloud *c, const rh_shape *shapes, int32_t
     S4SoundCand *d_c = nullptr;
     unsigned long long *d_o = nullptr;
     RH_HIP(hipMalloc((void **)&d_c, sizeof(S4SoundCand) * (size_t)b));
-    RH_HIP(hipMalloc((void **)&d_o, sizeof(unsigned long long) * 56));
+    RH_HIP(hipMalloc((void **)&d_o, sizeof(unsigned long long) * 64));
     RH_HIP(hipMemcpyAsync(d_c, h.data(), sizeof(S4SoundCand) * (size_t)b, hipMemcpyHostToDevice, c->stream));
-    RH_HIP(hipMemsetAsync(d_o, 0, sizeof(unsigned long long) * 56, c->stream));
+    RH_HIP(hipMemsetAsync(d_o, 0, sizeof(unsigned long long) * 64, c->stream));
     hipLaunchKernelGGL(cls_sound_kernel, dim3((unsigned)c->ngroups, (unsigned)std::min<int32_t>(b, 64)), dim3(64), 0, c->stream, c->sub, c->s_pad, c->s,
-                       c->gb32, c->st32, d_c, b, A, d_o);
-    unsigned long long ho[56];
+                       c->gb32, c->st32, c->tile32, d_c, b, A, d_o);
+    unsigned long long ho[64];
     RH_HIP(hipMemcpyAsync(ho, d_o, sizeof ho, hipMemcpyDeviceToHost, c->stream));
     RH_HIP(hipStreamSynchronize(c->stream));
     (void)hipFree(d_c);
     (void)hipFree(d_o);
-    for (int i = 0; i < 56; i++) out[i] = (uint64_t)ho[i];
+    for (int i = 0; i < nout; i++) out[i] = (uint64_t)ho[first + i];
     return RH_OK;
+}
+
+extern "C" int rh_dbg_cls_soundness(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out)
+{
+    return cls_soundness_run(c, shapes, b, p, out, 0, 56);
+}
+
+// the tile level of the same census: out[k] = pairs (candidate, group) whose TILE's box rules the candidate out -- the pairs the
+// tile lists keep from the score launch --, out[4 + k] = VIOLATION: such a pair with an exact inlier
+extern "C" int rh_dbg_cls_soundness_tiles(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out)
+{
+    return cls_soundness_run(c, shapes, b, p, out, 56, 8);
 }
 
 #endif   // RH_DIAG

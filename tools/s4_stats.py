@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Event counts of ONE launch of the culled score kernel on a bench workload (WL=cfg2|cfg3|cfg5), from the diag build's
 counters (rh_dbg_s4_stats: chunk visits, box-tested candidates, surviving pairs, batches, second-pass pairs, undecided
-points, ring drains per kind), plus the pair census of rh_dbg_cls_soundness (pairs the box test skips, pairs whose group
-holds a band point = the floor of the necessary pair work, pairs with an exact inlier).  tools/isa_account.py multiplies
+points, ring drains per kind), plus the pair census of rh_dbg_cls_soundness / _tiles (pairs the box test skips, pairs whose group
+holds a band point = the floor of the necessary pair work, pairs with an exact inlier; pairs a super-tile's / a tile's box skips).  tools/isa_account.py multiplies
 these with the static instruction histogram of the kernel's regions; bench.py's `frac_necessary` uses the band pairs.
     python tools/s4_stats.py            -> gpurun_out/s4_stats_<WL>.json (and a table on stdout)"""
 import ctypes as C, json, os, sys
@@ -55,6 +55,8 @@ def main():
     assert np.array_equal(counts.cpu().numpy(), ref)
     snd = np.zeros(56, dtype=np.uint64)
     L.check(lib.rh_dbg_cls_soundness(pc._h, arr, 4096, C.byref(cp), snd.ctypes.data_as(C.POINTER(C.c_uint64))))
+    snt = np.zeros(8, dtype=np.uint64)   # the tile level: pairs a tile list keeps from the score launch, and of those the ones with an exact inlier
+    L.check(lib.rh_dbg_cls_soundness_tiles(pc._h, arr, 4096, C.byref(cp), snt.ctypes.data_as(C.POINTER(C.c_uint64))))
     S = int(subs[0].size)
     linfo = (C.c_int32 * 4)()
     L.check(lib.rh_score_launch_info(pc._h, linfo))
@@ -64,7 +66,7 @@ def main():
     for k, name in enumerate(KN):
         out["per_kind"][name] = {f: int(st[24 * k + i]) for i, f in enumerate(FIELDS)}
         s10 = snd[10 * k:10 * k + 10]
-        out["census"][name] = {"pairs_supertile_skips": int(snd[48 + k]), "supertile_violations": int(snd[52 + k]),"pairs": int(s10[0]), "pairs_box_skips": int(s10[1]), "violations": int(s10[2] + s10[6] + s10[7] + s10[9]),
+        out["census"][name] = {"pairs_supertile_skips": int(snd[48 + k]), "supertile_violations": int(snd[52 + k]), "pairs_tile_skips": int(snt[k]), "tile_violations": int(snt[4 + k]), "pairs": int(s10[0]), "pairs_box_skips": int(s10[1]), "violations": int(s10[2] + s10[6] + s10[7] + s10[9]),
                                "points": int(s10[3]), "surely_in": int(s10[4]), "surely_out": int(s10[5]), "exact_inliers": int(s10[8]),
                                "pairs_with_band_point": int(snd[40 + k]), "pairs_with_exact_inlier": int(snd[44 + k])}
     os.makedirs("gpurun_out", exist_ok=True)
