@@ -330,7 +330,9 @@ int rh_fit_f32(int kind, const double *p, const double *n, int32_t lp, const rh_
  * fit(T, ...) for every type of p->shape_types, in that order, on every set with ok[j] != 0 (ok = NULL: every set); the shapes
  * that fit are appended to shapes_out in (set, type) order -- the reference's candidate order -- with set_out[i] = the set a
  * shape came from.  xyz_aos / nrm_aos: the cloud's host arrays (n x 3 doubles; for f32 != 0 they hold a Float32 cloud's values
- * and the fits run in binary32, rh_fit_f32).  Host-side, O(1) per set.  RH_E_CAPACITY with *n_out = the needed size. */
+ * and the fits run in binary32, rh_fit_f32).  drawN: 3 .. 16, else RH_E_INVALID: every type's fit is given all drawN points
+ * and fit_plane reads three of them (rh_sample_sets also draws sets of two).  Host-side, O(1) per set.  RH_E_CAPACITY with
+ * *n_out = the needed size. */
 int rh_fit_sets(const double *xyz_aos, const double *nrm_aos, const int64_t *idx_1based, const int32_t *ok_or_null, int32_t k,
                 int32_t drawN, const rh_params *p, int32_t f32, rh_shape *shapes_out, int32_t *set_out_or_null, int32_t cap,
                 int32_t *n_out);
@@ -359,8 +361,12 @@ int64_t rh_rng_range(rh_rng *r, int64_t n);
  * calls would consume them -- same number, same order -- so a loop that samples a whole iteration's sets through this call
  * takes the same decisions as one that calls rh_rng_range / rh_select_enabled per point (the device evaluates the call
  * for every start position of a window of draws, the host follows the chain).  idx_out: k x drawN points (1-based);
- * ok_out[j]: the reference's first return value; level_out (optional): its second (1: every set comes from the root cell,
- * SURVEY.md 0.5; 0 with ok = 0).  RH_E_INVALID without an enabled point (the reference would draw for ever). */
+ * ok_out[j]: the reference's first return value; level_out (optional): its second where a set was drawn (1: every set comes
+ * from the root cell), and 0 with ok = 0.  One DEVIATION: for a set rejected because its points are not all
+ * different the reference returns (false, 1) (fitting.jl:427), and (false, 0) only where fewer than drawN points are
+ * enabled (:408); here level_out is 0 in both cases.  Nothing reads the level of a rejected set (iterations.jl:82 skips
+ * it).  drawN: 2 .. 16 -- the draws need two points; rh_fit_sets, which fits what this call drew, takes 3 .. 16 (a plane is
+ * fitted to three points).  RH_E_INVALID without an enabled point (the reference would draw for ever). */
 int rh_sample_sets(rh_cloud *c, int32_t drawN, rh_rng *rng, int32_t k, int64_t *idx_out_1based, int32_t *ok_out,
                    int32_t *level_out_or_null);
 

@@ -1,8 +1,9 @@
 /*
  * ransac_hip_diag.h -- entry points that exist in the DIAG build only (libransac_hip_diag.so, -DRH_DIAG): audits of the
- * score kernel's binary32 classifier and box tests against the exact test, and a host-side self-check of the octree
- * sampler's search routines.  Test infrastructure: the product library (libransac_hip.so) does not export them, reads
- * no environment variable and knows none of the A/B switches (ransac.jl_amd/csrc/options.cpp lists them).
+ * score kernel's binary32 classifier and box tests against the exact test, a host-side self-check of the octree
+ * sampler's search routines, and one window of the device sampler with everything it made.  Test infrastructure: the
+ * product library (libransac_hip.so) does not export them, reads no environment variable and knows none of the A/B
+ * switches (ransac.jl_amd/csrc/options.cpp lists them).
  */
 #ifndef RANSAC_HIP_DIAG_H
 #define RANSAC_HIP_DIAG_H
@@ -47,6 +48,25 @@ int rh_dbg_oct_search_selftest(int64_t n, uint64_t seed, int64_t queries, int64_
  * stagings): what tools/isa_account.py multiplies with the static instruction histogram of the kernel's regions.
  * mode 1: switch on + zero, 0: read into out[128], 2: switch off. */
 int rh_dbg_s4_stats(rh_cloud *c, int mode, uint64_t *out /* [128] or NULL */);
+
+/* One window of the device sampler (csrc/sampler.hip, rhk_sample_fit: the call rh_ransac's windows make) on cloud c as it
+ * is -- the enabled count, the select structures and, with P, the linear octree prepared the way the driver prepares them
+ * before its first window, the status block zeroed, no chained-window state -- and everything it made: the minimal sets of
+ * the iterations k0 .. k0 + n_iters - 1 of a run whose generator state starts with `seed`, fitted to every type of
+ * p->shape_types.  P = NULL: root-cell sampling; else n_iters x depth level distributions (host) for octree sampling
+ * (depth: info_out[0] of an earlier call, or the oracle's).  rank / world: the share of every iteration's sets this call draws
+ * (set j belongs to rank j % world, rh_ransac_mp); 0, 1 = all of them; the cloud's own share is put back afterwards.
+ * out[cap]: the fitted candidates sorted by slot = ((it * minsubsetN) + set) * n_shape_types + type position, it = 0 for
+ * iteration k0; *n_out: how many were fitted -- when that exceeds cap only cap of them come back, which ones is not
+ * determined.  draws_out[n_iters]: rand() calls per iteration; *gave_up_out: a set ran into the limit of rejected draws.
+ * info_out[8]: 0 octree depth, 1 level of the cell directory (both 0 without P), 2 the kernels that ran (1 fused rank-space,
+ * 2 fused octree, 3 sampler + fit kernels), 3 their drawN instantiation (3, or 0 = generic), 4 fit kernel with cones,
+ * 5 the flat select list was handed over, 6 the compact records, 7 the cell directory.  RH_E_INVALID for a cloud with no
+ * enabled point.  Synchronous. */
+typedef struct { int64_t slot; int32_t level; int32_t pad; rh_shape shape; } rh_dbg_cand;
+int rh_dbg_sample_fit(rh_cloud *c, const rh_params *p, uint64_t seed, int64_t k0, int32_t n_iters, const double *P_or_null,
+                      int32_t rank, int32_t world, rh_dbg_cand *out, int32_t cap, int32_t *n_out, uint64_t *draws_out,
+                      int32_t *gave_up_out, int32_t *info_out /* [8] */);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,21 @@ class Result(C.Structure):
     ]
 
 
+class SetRec(C.Structure):
+    """orc_set_rec: what happened to one minimal set (ransac_oracle.h)"""
+    _fields_ = [("ok", C.c_int32), ("level", C.c_int32), ("draws", C.c_int32), ("first_draws", C.c_int32),
+                ("redraw", C.c_int32), ("reject", C.c_int32), ("last_cell", C.c_int32), ("pad", C.c_int32)]
+
+
+class CandRec(C.Structure):
+    """orc_cand_rec: a fitted candidate with the set, the position in shape_types and the level it came from"""
+    _fields_ = [("set", C.c_int32), ("type", C.c_int32), ("level", C.c_int32), ("pad", C.c_int32), ("shape", Shape)]
+
+
+REJ_NONE, REJ_CLOUD, REJ_CELL, REJ_SAME = 0, 1, 2, 3
+SET_DTYPE = np.dtype([(n, np.int32) for n in ("ok", "level", "draws", "first_draws", "redraw", "reject", "last_cell", "pad")])
+
+
 def build(force=False):
     """Compile liboracle.so with gcc (Makefile in this directory)."""
     return _build_target(_SO, force)
@@ -192,6 +207,11 @@ def _bind(L):
         "orc_rng_next": (C.c_uint64, [C.POINTER(Rng)]),
         "orc_rng_range": (C.c_int64, [C.POINTER(Rng), C.c_int64]),
         "orc_ransac": (C.c_int, [C.c_void_p, dp, dp, pp, C.POINTER(Rng), C.c_int, C.POINTER(Result)]),
+        "orc_linoctree_build": (C.c_void_p, [C.c_void_p, C.c_int]),
+        "orc_linoctree_destroy": (None, [C.c_void_p]),
+        "orc_linoctree_depth": (C.c_int, [C.c_void_p]),
+        "orc_sample_fit_iteration": (C.c_int64, [C.c_void_p, pp, C.POINTER(Rng), C.c_int64, C.c_void_p, dp, C.c_void_p, i64p,
+                                                 C.c_void_p, C.c_int64, i64p]),
         "orc_result_free": (None, [C.POINTER(Result)]),
         "orc_largestconncomp": (C.c_int64, [u8p, C.c_int32, C.c_int32, C.c_int, i64p, C.c_int64]),
         "orc_bitmapparameters": (C.c_int, [dp, u8p, i64p, C.c_int64, C.c_double, i32p, i32p, dp, dp, u8p, i64p]),
@@ -254,7 +274,8 @@ class Cloud:
     def __init__(self, xyz, nrm, subset1_1based, L=None, f32=False):
         self.L = L if L is not None else lib()
         if f32:
-            xyz, nrm = np.asarray(xyz, dtype=np.float32), np.asarray(nrm, dtype=np.float32)
+            with np.errstate(over="ignore"):   # (a value beyond binary32's range becomes an infinity, as in the cloud under test)
+                xyz, nrm = np.asarray(xyz, dtype=np.float32), np.asarray(nrm, dtype=np.float32)
         self.xyz = _f64(xyz).reshape(-1, 3)
         self.nrm = _f64(nrm).reshape(-1, 3)
         self.subset1 = np.ascontiguousarray(subset1_1based, dtype=np.int64)
@@ -358,6 +379,42 @@ class Cloud:
 
     def select_enabled(self, k):
         return self.L.orc_select_enabled(self.h, int(k))
+
+    def linoctree_depth(self, max_depth):
+        """depth of the linear octree of octree_sampling = 1 on this cloud"""
+        o = self.L.orc_linoctree_build(self.h, int(max_depth))
+        try:
+            return self.L.orc_linoctree_depth(o)
+        finally:
+            self.L.orc_linoctree_destroy(o)
+
+    def sample_fit_iteration(self, params, s0, k, P=None):
+        """orc_sample_fit_iteration with per-set streams (params.sampling_streams must be 1): the minimal sets of iteration
+        k of a run whose generator state starts with s0, and what was fitted to them.  P: the level distribution (octree
+        sampling on the cloud's enabled bits as they are now) or None (root cell).  Returns a dict: sets (structured array,
+        SET_DTYPE), idx (minsubsetN x drawN, 1-based), cands (list of CandRec in (set, type) order), depth (octree; else 0)."""
+        assert params.sampling_streams == 1, "per-set streams only: the sets are a function of (s0, k, set)"
+        rng = Rng()
+        rng.s[0] = int(s0) & 0xFFFFFFFFFFFFFFFF
+        m, dn, nt = params.minsubsetN, params.drawN, params.n_shape_types
+        sets = np.zeros(max(1, m), dtype=SET_DTYPE)
+        idx = np.zeros((max(1, m), dn), dtype=np.int64)
+        cap = max(1, m * nt)
+        cands = (CandRec * cap)()
+        oct, depth, Pa = None, 0, None
+        if P is not None:
+            oct = self.L.orc_linoctree_build(self.h, params.octree_max_depth)
+            depth = self.L.orc_linoctree_depth(oct)
+            Pa = _f64(P).reshape(-1)
+            assert Pa.size == depth, "P has %d levels, the octree %d" % (Pa.size, depth)
+        try:
+            n = self.L.orc_sample_fit_iteration(self.h, C.byref(params), C.byref(rng), int(k), oct, None if Pa is None else _dp(Pa),
+                                                sets.ctypes.data, idx.ctypes.data_as(C.POINTER(C.c_int64)), C.addressof(cands), cap, None)
+        finally:
+            if oct is not None:
+                self.L.orc_linoctree_destroy(oct)
+        assert 0 <= n <= cap, n
+        return {"sets": sets[:m], "idx": idx[:m], "cands": [cands[i] for i in range(n)], "depth": depth}
 
     def ransac(self, params, seed=1234, stream=None, octree_depth=1):
         rng = Rng()

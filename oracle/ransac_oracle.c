@@ -1468,13 +1468,15 @@ static uint64_t draw_raw(draw_src *d)
     return mix64(d->x);
 }
 
-/* one minimal set, level-weighted; returns 1 and the level, or 0 */
+/* one minimal set, level-weighted; returns 1 and the level, or 0.  rec (optional): what happened on the way */
 static int sample_octree(const orc_cloud *c, const lin_octree *o, const double *P, const orc_params *p,
-                         draw_src *rng, int64_t n_enabled, int64_t *sd, int *level_out)
+                         draw_src *rng, int64_t n_enabled, int64_t *sd, int *level_out, orc_set_rec *rec)
 {
-    if (n_enabled <= 0) return 0;
+    if (n_enabled <= 0) { if (rec) rec->reject = ORC_REJ_CLOUD; return 0; }
+    const int64_t d0 = rng->seq->draws;
     int64_t r1 = draw_range(rng, c->n);
     while (!is_enabled(c, r1 - 1)) r1 = draw_range(rng, c->n);
+    if (rec) rec->first_draws = (int32_t)(rng->seq->draws - d0);
     double u = (double)(draw_raw(rng) >> 11) * (1.0 / 9007199254740992.0);
     int level = o->depth;
     double acc = 0;
@@ -1485,24 +1487,30 @@ static int sample_octree(const orc_cloud *c, const lin_octree *o, const double *
     *level_out = level;
     int shift = 3 * (21 - (level - 1));
     int64_t lo, hi;
+    int last = 0;
     if (shift >= 63) { lo = 0; hi = o->n; }
     else {
         uint64_t key = o->code[o->pos[r1 - 1]] >> shift;
         lo = lo_lower_bound(o, key << shift);
         hi = (key + 1) << shift == 0 ? o->n : lo_lower_bound(o, (key + 1) << shift);
         if (((key + 1) << shift) >> shift != key + 1) hi = o->n; /* top cell: no overflow */
+        last = key + 1 == 1ULL << (63 - shift); /* the last cell of its level: it ends where the 63-bit code space ends */
     }
+    if (rec) { rec->level = level; rec->last_cell = last; }
     int64_t base = lo_rank(o, lo), ne = lo_rank(o, hi) - base;
-    if (ne < p->drawN) return 0;
+    if (ne < p->drawN) { if (rec) rec->reject = ORC_REJ_CELL; return 0; }
     sd[0] = r1;
     for (int q = 1; q < p->drawN; q++) {
         int64_t pick = (int64_t)o->perm[lo_select(o, base + draw_range(rng, ne))] + 1;
-        if (pick == sd[0]) pick = (int64_t)o->perm[lo_select(o, base + draw_range(rng, ne))] + 1;
+        if (pick == sd[0]) {
+            pick = (int64_t)o->perm[lo_select(o, base + draw_range(rng, ne))] + 1;
+            if (rec) rec->redraw++;
+        }
         sd[q] = pick;
     }
     for (int i = 1; i < p->drawN; i++)
         for (int j = 0; j < i; j++)
-            if (sd[i] == sd[j]) return 0;
+            if (sd[i] == sd[j]) { if (rec) rec->reject = ORC_REJ_SAME; return 0; }
     return 1;
 }
 
@@ -1533,12 +1541,14 @@ static int jl_argmax(const double *a, int n)
 }
 
 /* samplepointcloud4!: fitting.jl:383-430 with the root cell (the
- * argmax at :401 is always 1, asserted by the caller).  sd: 1-based indices. */
-static int sample4(const orc_cloud *c, const orc_params *p, draw_src *rng, int64_t n_enabled, int64_t *sd)
+ * argmax at :401 is always 1, asserted by the caller).  sd: 1-based indices.  rec (optional): what happened on the way */
+static int sample4(const orc_cloud *c, const orc_params *p, draw_src *rng, int64_t n_enabled, int64_t *sd, orc_set_rec *rec)
 {
+    const int64_t d0 = rng->seq->draws;
     int64_t r1 = draw_range(rng, c->n);
     while (!is_enabled(c, r1 - 1)) r1 = draw_range(rng, c->n);
-    if (n_enabled < p->drawN) return 0; /* (false, 0) */
+    if (rec) rec->first_draws = (int32_t)(rng->seq->draws - d0);
+    if (n_enabled < p->drawN) { if (rec) rec->reject = ORC_REJ_CLOUD; return 0; } /* (false, 0) */
     sd[0] = r1;
     for (int k = 1; k < p->drawN; k++) {
         int64_t nexti = draw_range(rng, n_enabled);
@@ -1546,14 +1556,74 @@ static int sample4(const orc_cloud *c, const orc_params *p, draw_src *rng, int64
         if (sd[0] == cand) {
             nexti = draw_range(rng, n_enabled); /* try oncemore: fitting.jl:416-419 */
             cand = orc_select_enabled(c, nexti);
+            if (rec) rec->redraw++;
         }
         sd[k] = cand;
     }
     for (int i = 1; i < p->drawN; i++) /* allisdifferent: utilities.jl:285-295 */
         for (int j = 0; j < i; j++)
-            if (sd[i] == sd[j]) return 0; /* (false, 1) */
+            if (sd[i] == sd[j]) { if (rec) rec->reject = ORC_REJ_SAME; return 0; } /* (false, 1) */
     return 1;
 }
+
+/* The minimal sets of iteration k and the candidates fitted to them: the loop over minsubsetN of iterations.jl:80-99
+ * (samplepointcloud4! -- or the level-weighted octree sampling when oct != NULL, with the level distribution P --, then
+ * forcefitshapes!, fitting.jl:165-173).  sampling_streams = 1: set i draws from its own stream, a function of
+ * (rng->s[0], k, i); else from rng itself.  The candidates come out in (set, type) order. */
+int64_t orc_sample_fit_iteration(const orc_cloud *c, const orc_params *p, orc_rng *rng, int64_t k, const orc_linoctree *oct,
+                                 const double *P, orc_set_rec *sets, int64_t *idx, orc_cand_rec *cands, int64_t cap,
+                                 int64_t *n_ok_out)
+{
+    int64_t sd[16], ncand = 0, n_ok = 0;
+    double fp[3 * 16], fn[3 * 16];
+    if (n_ok_out) *n_ok_out = 0;
+    if (p->drawN < 2 || p->drawN > 16) return -1;
+    const int64_t n_enabled = orc_cloud_count_enabled(c);
+    for (int i = 0; i < p->minsubsetN; i++) {
+        draw_src src = { rng, 0, p->sampling_streams };
+        if (p->sampling_streams)
+            src.x = mix64(rng->s[0] + (uint64_t)k * 0xD1B54A32D192ED03ULL) ^
+                    mix64((uint64_t)i * 0x8CB92BA72F3D8DD7ULL + 0x2545F4914F6CDD1DULL);
+        orc_set_rec rec;
+        memset(&rec, 0, sizeof rec);
+        rec.level = 1;
+        for (int q = 0; q < p->drawN; q++) sd[q] = 0;
+        const int64_t d0 = rng->draws;
+        int lvl = 1;
+        const int ok = oct ? sample_octree(c, (const lin_octree *)oct, P, p, &src, n_enabled, sd, &lvl, &rec)
+                           : sample4(c, p, &src, n_enabled, sd, &rec);
+        rec.ok = ok;
+        rec.draws = (int32_t)(rng->draws - d0);
+        if (sets) sets[i] = rec;
+        if (idx) {
+            const int drawn = rec.reject != ORC_REJ_CLOUD && rec.reject != ORC_REJ_CELL; /* else the set ended before its points */
+            for (int q = 0; q < p->drawN; q++) idx[(int64_t)i * p->drawN + q] = drawn ? sd[q] : 0;
+        }
+        if (!ok) continue;
+        n_ok++;
+        for (int q = 0; q < p->drawN; q++) {
+            memcpy(fp + 3 * q, &c->xyz[3 * (sd[q] - 1)], 24);
+            memcpy(fn + 3 * q, &c->nrm[3 * (sd[q] - 1)], 24);
+        }
+        for (int t = 0; t < p->n_shape_types; t++) { /* forcefitshapes!: fitting.jl:165-173 */
+            orc_shape fitted;
+            if (!(c->f32 ? orc32_fit(p->shape_types[t], fp, fn, p->drawN, p, &fitted)
+                         : orc_fit(p->shape_types[t], fp, fn, p->drawN, p, &fitted))) continue;
+            if (ncand < cap) {
+                orc_cand_rec *r = &cands[ncand];
+                r->set = i; r->type = t; r->level = lvl; r->pad = 0;
+                r->shape = fitted;
+            }
+            ncand++;
+        }
+    }
+    if (n_ok_out) *n_ok_out = n_ok;
+    return ncand;
+}
+
+orc_linoctree *orc_linoctree_build(const orc_cloud *c, int max_depth) { return (orc_linoctree *)lo_build(c, max_depth); }
+void orc_linoctree_destroy(orc_linoctree *o) { lo_free((lin_octree *)o); }
+int orc_linoctree_depth(const orc_linoctree *o) { return ((const lin_octree *)o)->depth; }
 
 typedef struct {
     orc_shape *shapes;
@@ -1610,13 +1680,11 @@ int orc_ransac(orc_cloud *c, const double *xyz, const double *nrm, const orc_par
 
     int64_t w = (c->s + 63) / 64;
     cand_store st = { 0 };
-    orc_shape *cands = NULL;
-    int32_t *levels = NULL;
-    int64_t ncand = 0, capcand = 0;
+    const int64_t capcand = (int64_t)(p->minsubsetN > 0 ? p->minsubsetN : 0) * (p->n_shape_types > 0 ? p->n_shape_types : 0);
+    orc_cand_rec *cands = (orc_cand_rec *)malloc(sizeof(orc_cand_rec) * (size_t)(capcand ? capcand : 1));
+    int64_t ncand = 0;
     int64_t countcandidates[4] = { 0, 0, 0, 0 };
     int64_t ext_cap = 0;
-    int64_t *sd = (int64_t *)malloc(8 * (size_t)p->drawN);
-    double *fp = (double *)malloc(8 * 3 * (size_t)p->drawN), *fn = (double *)malloc(8 * 3 * (size_t)p->drawN);
     int64_t *refit_idx = (int64_t *)malloc(8 * (size_t)(c->n ? c->n : 1));
     int rc = 0;
 
@@ -1631,47 +1699,19 @@ int orc_ransac(orc_cloud *c, const double *xyz, const double *nrm, const orc_par
     for (k = 1; k <= p->itermax; k++) {
         int64_t n_enabled = orc_cloud_count_enabled(c);
         if (n_enabled < p->tau) break; /* iterations.jl:75 */
-        for (int i = 0; i < p->minsubsetN; i++) {
-            draw_src src = { rng, 0, p->sampling_streams };
-            if (p->sampling_streams)
-                src.x = mix64(rng->s[0] + (uint64_t)k * 0xD1B54A32D192ED03ULL) ^
-                        mix64((uint64_t)i * 0x8CB92BA72F3D8DD7ULL + 0x2545F4914F6CDD1DULL);
-            int lvl;
-            if (oct) {
-                if (!sample_octree(c, oct, octP, p, &src, n_enabled, sd, &lvl)) continue;
-            } else {
-                if (!sample4(c, p, &src, n_enabled, sd)) continue;
-                /* fitting.jl:401: argmax(levelweight[1:max_depth]) must be 1 */
-                lvl = jl_argmax(levelweight, octree_depth) + 1;
-                if (lvl != 1) { rc = -2; goto done; }
-            }
-            for (int q = 0; q < p->drawN; q++) {
-                memcpy(fp + 3 * q, &c->xyz[3 * (sd[q] - 1)], 24);
-                memcpy(fn + 3 * q, &c->nrm[3 * (sd[q] - 1)], 24);
-            }
-            for (int t = 0; t < p->n_shape_types; t++) { /* forcefitshapes!: fitting.jl:165-173 */
-                orc_shape fitted;
-                if (!(c->f32 ? orc32_fit(p->shape_types[t], fp, fn, p->drawN, p, &fitted)
-                             : orc_fit(p->shape_types[t], fp, fn, p->drawN, p, &fitted))) continue;
-                if (ncand == capcand) {
-                    capcand = capcand ? capcand * 2 : 64;
-                    cands = (orc_shape *)realloc(cands, sizeof(orc_shape) * (size_t)capcand);
-                    levels = (int32_t *)realloc(levels, 4 * (size_t)capcand);
-                }
-                cands[ncand] = fitted;
-                levels[ncand] = lvl;
-                ncand++;
-            }
-        }
+        int64_t n_ok = 0;
+        ncand = orc_sample_fit_iteration(c, p, rng, k, (const orc_linoctree *)oct, octP, NULL, NULL, cands, capcand, &n_ok);
+        /* fitting.jl:401: argmax(levelweight[1:max_depth]) must be 1 for every set that was drawn */
+        if (!oct && n_ok > 0 && jl_argmax(levelweight, octree_depth) != 0) { rc = -2; goto done; }
         countcandidates[2] += ncand;
         /* scorecandidates!: fitting.jl:181-190 */
         for (int64_t i = 0; i < ncand; i++) {
             uint64_t *mask = (uint64_t *)malloc(8 * (size_t)(w ? w : 1));
-            int64_t cnt = orc_scorecandidate(c, &cands[i], p, NULL, mask);
+            int64_t cnt = orc_scorecandidate(c, &cands[i].shape, p, NULL, mask);
             orc_ci sc = orc_estimatescore(c->s, c->n, cnt, p->score_mode);
-            if (oct) octS[levels[i] - 1] += sc.E;
-            else levelscore[levels[i] - 1] += sc.E;
-            store_push(&st, &cands[i], sc, mask);
+            if (oct) octS[cands[i].level - 1] += sc.E;
+            else levelscore[cands[i].level - 1] += sc.E;
+            store_push(&st, &cands[i].shape, sc, mask);
         }
         ncand = 0;
         countcandidates[3] = k * p->minsubsetN;
@@ -1754,7 +1794,7 @@ done:
     out->scored_left = st.n;
     for (int64_t i = 0; i < st.n; i++) free(st.masks[i]);
     free(st.shapes); free(st.scores); free(st.masks);
-    free(cands); free(levels); free(sd); free(fp); free(fn); free(refit_idx);
+    free(cands); free(refit_idx);
     free(levelweight); free(levelscore);
     lo_free(oct);
     out->seconds = now_s() - t0;

@@ -220,6 +220,33 @@ typedef struct {
     double seconds;
 } orc_result;
 
+/* One iteration's minimal sets and the candidates fitted to them (the loop over minsubsetN of iterations.jl:80-99): what
+ * orc_ransac runs per iteration, exported so that a sampler can be held to it set by set.  oct = NULL: samplepointcloud4! on
+ * the root cell; else the level-weighted sampling on the linear octree `oct` with the level distribution P[depth].
+ * sampling_streams = 1: set i draws from its own stream, a function of (rng->s[0], k, i).  sets[minsubsetN], idx[minsubsetN x
+ * drawN] (1-based; 0 where the set ended before its points were drawn) and cands[cap] are optional; returns the number of
+ * candidates (the first `cap` are written, in (set, type) order), -1 for a drawN outside 2..16. */
+enum { ORC_REJ_NONE = 0, ORC_REJ_CLOUD = 1 /* fewer enabled points than drawN */, ORC_REJ_CELL = 2 /* ... in the cell */,
+       ORC_REJ_SAME = 3 /* not all different */ };
+typedef struct {
+    int32_t ok;          /* the set went on to the fits */
+    int32_t level;       /* the level it was drawn at (root cell: 1) */
+    int32_t draws;       /* rand() calls of the set */
+    int32_t first_draws; /* of them: until the first point was an enabled one */
+    int32_t redraw;      /* picks that hit the first point and were drawn once more (fitting.jl:416-419) */
+    int32_t reject;      /* ORC_REJ_* */
+    int32_t last_cell;   /* octree: the last cell of its level (it holds the bounding cube's maximum corner) */
+    int32_t pad;
+} orc_set_rec;
+typedef struct { int32_t set, type, level, pad; orc_shape shape; } orc_cand_rec;
+typedef struct orc_linoctree orc_linoctree;   /* the linear (Morton) octree of octree_sampling = 1, with the cloud's enabled bits as they were */
+orc_linoctree *orc_linoctree_build(const orc_cloud *c, int max_depth);
+void orc_linoctree_destroy(orc_linoctree *o);
+int orc_linoctree_depth(const orc_linoctree *o);
+int64_t orc_sample_fit_iteration(const orc_cloud *c, const orc_params *p, orc_rng *rng, int64_t k, const orc_linoctree *oct,
+                                 const double *P, orc_set_rec *sets, int64_t *idx, orc_cand_rec *cands, int64_t cap,
+                                 int64_t *n_ok_out);
+
 int orc_ransac(orc_cloud *c, const double *xyz, const double *nrm, const orc_params *p,
                orc_rng *rng, int octree_depth, orc_result *out);
 void orc_result_free(orc_result *r);

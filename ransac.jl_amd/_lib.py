@@ -239,8 +239,15 @@ SIGNATURES = {
                                          C.c_int64, _i64p, _dp, C.POINTER(OutlierStats)]),
 }
 
+class DbgCand(C.Structure):
+    """rh_dbg_cand (include/ransac_hip_diag.h)"""
+    _fields_ = [("slot", C.c_int64), ("level", C.c_int32), ("pad", C.c_int32), ("shape", Shape)]
+
+
 # include/ransac_hip_diag.h: exported by the diag build only
 DIAG_SIGNATURES = {
+    "rh_dbg_sample_fit": (C.c_int, [_vp, _pp, C.c_uint64, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_int32, C.POINTER(DbgCand),
+                                    C.c_int32, _i32p, _u64p, _i32p, _i32p]),
     "rh_dbg_cls_audit": (C.c_int, [_vp, _sp, C.c_int32, _pp, _dp]),
     "rh_dbg_cls_soundness": (C.c_int, [_vp, _sp, C.c_int32, _pp, C.POINTER(C.c_uint64)]),
     "rh_dbg_cls_soundness_tiles": (C.c_int, [_vp, _sp, C.c_int32, _pp, C.POINTER(C.c_uint64)]),

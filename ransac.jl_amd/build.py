@@ -44,7 +44,7 @@ STAMP = SO + ".stamp"
 
 
 def _headers():
-    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "ransac_hip.h")]
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", h) for h in ("ransac_hip.h", "ransac_hip_diag.h")]
 
 
 def _digest(paths, extra):
@@ -61,7 +61,7 @@ def source_hash(variant="product"):
     """sha256 over the sources, the public header, the flags and this file: what the library was built from
     (modification times do not survive a copy of the tree, e.g. onto a GPU box)."""
     deps = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
-                  if f.endswith((".hip", ".h", ".cpp"))) + [os.path.join(ROOT, "include", "ransac_hip.h"), __file__]
+                  if f.endswith((".hip", ".h", ".cpp"))) + [os.path.join(ROOT, "include", h) for h in ("ransac_hip.h", "ransac_hip_diag.h")] + [__file__]
     return _digest(deps, " ".join(FLAGS + VARIANTS[variant][1] + SOURCES + os.environ.get("RH_EXTRA_FLAGS", "").split()))
 
 

@@ -401,6 +401,11 @@ struct rh_cloud {
 
     // rh_ransac_mp: this process's share of every iteration's minimal sets (set j belongs to rank j % world)
     int32_t mp_rank = 0, mp_world = 1;
+#ifdef RH_DIAG
+    // what the last rhk_sample_fit launched (rh_dbg_sample_fit): kernels (1 ranks-fused, 2 oct-fused, 3 two-kernel),
+    // DN instantiation, CONE instantiation, select list handed over, compact records handed over, cell directory handed over
+    int32_t dbg_sampler_path[6] = { 0, 0, 0, 0, 0, 0 };
+#endif
 
     // rh_ransac's reusable buffers, parked here between calls (driver.hip owns the layout and the deleter)
     void *drv_cache = nullptr;

@@ -7,6 +7,14 @@
 // restores the reference's candidate order exactly.
 #include "fit_shared.h"
 #include "rh_internal.h"
+#ifdef RH_DIAG
+#include <stddef.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "ransac_hip_diag.h"
+#endif
 
 namespace {
 
@@ -875,9 +883,19 @@ int rhk_sample_fit(rh_cloud *c, const rh_params *prm, uint64_t seed, int64_t k0,
     if (!rh_opt_on(c, RH_OPT_NO_OCT_TAB)) { oc.tab = c->oct_tab; oc.tab_level = c->oct_tab_level; oc.code_o = c->oct_code_o; }
     // (octree sampling is a chain of dependent random reads per set: one wave per block spreads a window of a few thousand
     // sets over four times as many compute units -- each with its own address translation -- as 256-thread blocks would)
+#ifdef RH_DIAG
+    auto took = [&](int kernels, bool cone_inst) {
+        const int32_t path[6] = { kernels, prm->drawN == 3 ? 3 : 0, cone_inst ? 1 : 0, en.sel != nullptr ? 1 : 0,
+                                  crec != nullptr ? 1 : 0, (d_P != nullptr && oc.tab != nullptr) ? 1 : 0 };
+        for (int i = 0; i < 6; i++) c->dbg_sampler_path[i] = path[i];
+    };
+#else
+    auto took = [](int, bool) { };
+#endif
     const int sblock = d_P != nullptr ? 64 : 256;
     const dim3 gs((unsigned)((total + sblock - 1) / sblock)), gf((unsigned)((total + 127) / 128));
     if (d_P == nullptr && n_enabled > 0 && !cone && !no_fused) {   // rank-space sampling + fits in one kernel, no hand-over
+        took(1, false);
         const dim3 gk((unsigned)((total + 127) / 128));
         if (prm->drawN == 3)
             hipLaunchKernelGGL(sample_fit_ranks_kernel<3>, gk, dim3(128), 0, c->stream, crec, c->rec, c->n, en, n_enabled, *prm,
@@ -889,6 +907,7 @@ int rhk_sample_fit(rh_cloud *c, const rh_params *prm, uint64_t seed, int64_t k0,
         return RH_OK;
     }
     if (d_P != nullptr && !cone && !no_fused) {   // octree sampling: sampler + fits in one launch (sample_fit_oct_kernel)
+        took(2, false);
         const dim3 go((unsigned)((total + 63) / 64));
         if (prm->drawN == 3)
             hipLaunchKernelGGL(sample_fit_oct_kernel<3>, go, dim3(64), 0, c->stream, c->rec, c->n, en, n_enabled, oc, d_P, *prm, seed, k0,
@@ -905,6 +924,7 @@ int rhk_sample_fit(rh_cloud *c, const rh_params *prm, uint64_t seed, int64_t k0,
 #define RH_FIT(DN, CONE)                                                                                               \
     hipLaunchKernelGGL((fit_sets_kernel<DN, CONE>), gf, dim3(128), 0, c->stream, c->set_ws, c->set_level, total, *prm, \
                        d_out, cap, d_count, d_nk_zero, sh, it0, ost, c->f32 ? 1 : 0)
+    took(3, cone);
     if (prm->drawN == 3) {   // the reference's default: fully unrolled, no scratch
         RH_SAMPLE(3);
         if (cone) RH_FIT(3, true); else RH_FIT(3, false);
@@ -917,6 +937,91 @@ int rhk_sample_fit(rh_cloud *c, const rh_params *prm, uint64_t seed, int64_t k0,
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
+
+#ifdef RH_DIAG
+// diagnostics (tests/test_sampler_gpu.py): one window of rhk_sample_fit on a cloud prepared as the driver prepares it before
+// its first window, and everything the window made (include/ransac_hip_diag.h)
+extern "C" int rh_dbg_sample_fit(rh_cloud *c, const rh_params *p, uint64_t seed, int64_t k0, int32_t n_iters, const double *P,
+                                 int32_t rank, int32_t world, rh_dbg_cand *out, int32_t cap, int32_t *n_out, uint64_t *draws_out,
+                                 int32_t *gave_up_out, int32_t *info_out)
+{
+    static_assert(sizeof(rh_dbg_cand) == sizeof(rh_cand_entry) && offsetof(rh_dbg_cand, shape) == offsetof(rh_cand_entry, shape),
+                  "rh_dbg_cand is rh_cand_entry");
+    if (c == nullptr || p == nullptr || n_out == nullptr || n_iters < 1 || n_iters > 512 || cap < 0 || (cap > 0 && out == nullptr) ||
+        world < 1 || rank < 0 || rank >= world || p->minsubsetN < 1 || p->n_shape_types < 1 || p->n_shape_types > 8 || p->drawN < 2) {
+        rh_set_error("rh_dbg_sample_fit: bad arguments");
+        return RH_E_INVALID;
+    }
+    *n_out = 0;
+    RH_TRY(rh_cloud_join(c));
+    if (c->n == 0) { rh_set_error("rh_dbg_sample_fit: the cloud is empty"); return RH_E_INVALID; }
+    if (!c->select_valid) RH_TRY(rhk_build_select(c));
+    int32_t count = 0;
+    RH_HIP(hipMemcpyAsync(&count, c->d_total, sizeof count, hipMemcpyDeviceToHost, c->stream));
+    RH_HIP(hipStreamSynchronize(c->stream));
+    if (count <= 0) { rh_set_error("rh_dbg_sample_fit: no enabled point"); return RH_E_INVALID; }
+    const double *d_P = nullptr;
+    if (P != nullptr) {
+        RH_TRY(rh_octree_ensure(c, nullptr, p->octree_max_depth));
+        const int64_t need = (int64_t)n_iters * c->oct_depth;
+        if (need > c->oct_P_cap) {
+            RH_HIP(hipStreamSynchronize(c->stream));
+            (void)hipFree(c->oct_P);
+            c->oct_P = nullptr;
+            c->oct_P_cap = 0;
+            RH_HIP(hipMalloc((void **)&c->oct_P, sizeof(double) * (size_t)(512 * 32)));
+            c->oct_P_cap = 512 * 32;
+        }
+        RH_HIP(hipMemcpyAsync(c->oct_P, P, sizeof(double) * (size_t)need, hipMemcpyHostToDevice, c->stream));
+        d_P = c->oct_P;
+    }
+    const size_t status_bytes = (size_t)((8 + 8 * (int64_t)n_iters + 63) / 64 * 64);
+    rh_cand_entry *d_entries = nullptr;
+    void *d_status = nullptr;
+    std::vector<unsigned long long> h_status(status_bytes / 8);
+    std::vector<rh_cand_entry> h_entries;
+    int rc = RH_OK;
+    auto done = [&](int code) { (void)hipFree(d_entries); (void)hipFree(d_status); return code; };
+#define RH_DBG_HIP(x) do { if ((x) != hipSuccess) { rh_set_error("rh_dbg_sample_fit: HIP call failed: %s", #x); return done(RH_E_INTERNAL); } } while (0)
+    RH_DBG_HIP(hipMalloc((void **)&d_entries, sizeof(rh_cand_entry) * (size_t)(cap > 0 ? cap : 1)));
+    RH_DBG_HIP(hipMalloc(&d_status, status_bytes));
+    const int32_t rank0 = c->mp_rank, world0 = c->mp_world;
+    c->mp_rank = rank;
+    c->mp_world = world;
+    for (int i = 0; i < 6; i++) c->dbg_sampler_path[i] = 0;
+    rc = rhk_sample_fit(c, p, seed, k0, n_iters, count, d_P, d_entries, cap, d_status, 0, nullptr, 0, nullptr);
+    c->mp_rank = rank0;
+    c->mp_world = world0;
+    if (rc != RH_OK) { (void)hipStreamSynchronize(c->stream); return done(rc); }
+    RH_DBG_HIP(hipMemcpyAsync(h_status.data(), d_status, status_bytes, hipMemcpyDeviceToHost, c->stream));
+    RH_DBG_HIP(hipStreamSynchronize(c->stream));
+    const int32_t made = (int32_t)(h_status[0] & 0xffffffffULL);
+    const int32_t have = made < cap ? made : cap;
+    h_entries.resize((size_t)(have > 0 ? have : 0));
+    if (have > 0) {
+        RH_DBG_HIP(hipMemcpyAsync(h_entries.data(), d_entries, sizeof(rh_cand_entry) * (size_t)have, hipMemcpyDeviceToHost, c->stream));
+        RH_DBG_HIP(hipStreamSynchronize(c->stream));
+    }
+#undef RH_DBG_HIP
+    std::sort(h_entries.begin(), h_entries.end(), [](const rh_cand_entry &a, const rh_cand_entry &b) { return a.slot < b.slot; });
+    if (have > 0) memcpy(out, h_entries.data(), sizeof(rh_cand_entry) * (size_t)have);
+    *n_out = made;
+    if (draws_out != nullptr)
+        for (int32_t it = 0; it < n_iters; it++) draws_out[it] = h_status[1 + (size_t)it];
+    if (gave_up_out != nullptr) *gave_up_out = (int32_t)(h_status[0] >> 32);
+    if (info_out != nullptr) {
+        info_out[0] = P != nullptr ? c->oct_depth : 0;
+        info_out[1] = P != nullptr ? c->oct_tab_level : 0;
+        info_out[2] = c->dbg_sampler_path[0];
+        info_out[3] = c->dbg_sampler_path[1];
+        info_out[4] = c->dbg_sampler_path[2];
+        info_out[5] = c->dbg_sampler_path[3];
+        info_out[6] = c->dbg_sampler_path[4];
+        info_out[7] = c->dbg_sampler_path[5];
+    }
+    return done(RH_OK);
+}
+#endif   // RH_DIAG
 
 int rhk_oct_advance(rh_cloud *c, const rh_params *prm, rh_oct_state *ost, const rh_cand_entry *d_entries, const void *d_status,
                     int32_t cap, const int32_t *d_counts, int32_t it, int64_t k, rh_cand_entry *h_entries, int32_t *h_counts,

@@ -440,3 +440,7 @@ def test_fit_sets_equals_forcefitshapes_per_set(f32):
     rc = R.lib().rh_fit_sets(xyz.ctypes.data_as(C.POINTER(C.c_double)), nrm.ctypes.data_as(C.POINTER(C.c_double)), sets.ctypes.data_as(C.POINTER(C.c_int64)),
                              None, nsets, 3, C.byref(cp), 0, arr, None, 1, C.byref(n_out))
     assert rc == L.RH_E_CAPACITY and n_out.value > 1
+    # sets of two points (rh_sample_sets draws them) are refused: a plane is fitted to three (documented in ransac_hip.h)
+    rc = R.lib().rh_fit_sets(xyz.ctypes.data_as(C.POINTER(C.c_double)), nrm.ctypes.data_as(C.POINTER(C.c_double)), sets.ctypes.data_as(C.POINTER(C.c_int64)),
+                             None, 4, 2, C.byref(cp), 0, arr, None, 1, C.byref(n_out))
+    assert rc == L.RH_E_INVALID and b"outside 3..16" in R.lib().rh_last_error()

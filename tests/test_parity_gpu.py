@@ -1066,7 +1066,7 @@ def test_reference_loop_with_three_call_sites_swapped(batched):
     assert np.array_equal(pc.enabled_chunks(), oc.get_enabled())
 
 
-@pytest.mark.parametrize("drawN,frac,inject", [(3, 1.0, False), (3, 0.4, True), (4, 0.02, False), (2, 0.5, True), (5, 0.0005, False)])
+@pytest.mark.parametrize("drawN,frac,inject", [(3, 1.0, False), (3, 0.4, True), (4, 0.02, False), (2, 0.5, True), (5, 0.0005, False), (3, 0.0005, False)])
 def test_sample_sets_equals_sequential_calls(small_scene, drawN, frac, inject):
     """rh_sample_sets = samplepointcloud4! k times in a row (fitting.jl:383-430) as one launch: the same sets, the same
     accept / reject flags and the same number of draws as the per-point calls (rh_rng_range + rh_select_enabled) on the same
@@ -1094,6 +1094,7 @@ def test_sample_sets_equals_sequential_calls(small_scene, drawN, frac, inject):
     rng_a, rng_b = make_rng(), make_rng()
     sets, ok, lev = R.sample_sets(pc, drawN, rng_a, k)
     n_en = int(en.sum())
+    n_same = 0
     for j in range(k):
         first = lib.rh_rng_range(C.byref(rng_b), n)
         while not en[first - 1]:
@@ -1108,11 +1109,16 @@ def test_sample_sets_equals_sequential_calls(small_scene, drawN, frac, inject):
                 pick = int(R.select_enabled(pc, [lib.rh_rng_range(C.byref(rng_b), n_en)])[0])
             sd.append(pick)
         assert list(sets[j]) == sd, j
+        # (level 0 with ok = 0 also for a set that is not all different, where the reference's second return value is 1,
+        # fitting.jl:427: the deviation ransac_hip.h states)
         assert bool(ok[j]) == (len(set(sd)) == drawN) and lev[j] == int(ok[j])
+        n_same += not ok[j]
     assert rng_a.draws == rng_b.draws and rng_a.stream_pos == rng_b.stream_pos
     assert [rng_a.s[i] for i in range(4)] == [rng_b.s[i] for i in range(4)]
     if frac >= 0.02:
         assert ok.sum() > 250
+    if n_en == drawN:     # three enabled points, sets of three: most sets repeat a point -- the case the deviation is about occurs
+        assert n_same >= 50 and ok.sum() >= 20
     pc.enable_all()
 
 
