@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 118
+#define RH_VERSION 119
 
 enum {
     RH_OK = 0,
@@ -781,6 +781,97 @@ int rh_cloud_distance(const double *ref_xyz_aos, const double *ref_nrm_aos_or_nu
 int rh_cloud_distance_f32(const float *ref_xyz_aos, const float *ref_nrm_aos_or_null, int64_t n, const float *qry_xyz_aos,
                           int64_t m, const rh_distance_params *p, int device, double *dist_out, int32_t *nn_idx_out_or_null,
                           rh_distance_stats *stats_or_null);
+
+/* ---- rigid registration of one cloud onto another: iterative closest point (no counterpart in the reference, which
+ *      works on one cloud) ----
+ * Brings the query cloud q_1 .. q_m into the frame of the reference cloud r_1 .. r_n, so that rh_knn_query,
+ * rh_cloud_distance and the labels carried across mean what they say.  Every output is one fixed sequence of IEEE binary64
+ * operations (+, -, *, /, sqrt; no contraction); the _f32 entry widens all arrays exactly and computes in binary64.
+ * Below, S(..) = T(..) + 0.0 with T() the tree of rh_remove_outliers over the query index order j = 0 .. m-1 (the device's
+ * blocks pad with +0.0, so a root of -0.0 is read as +0.0; every other value is unchanged), one tree per component.
+ *  1. CENTRE.  lo_k / hi_k = the smallest / largest reference coordinate along axis k; c_k = 0.5*(lo_k + hi_k).
+ *     s = r - c and y = q - c componentwise are the centred points.
+ *  2. STATE.  A 3x3 matrix R (row-major R_kl) and a vector t act on centred queries:
+ *         y'_k = ((R_k0*y_0 + R_k1*y_1) + R_k2*y_2) + t_k.
+ *     With init = [A | u] (3x4 row-major, x' = A x + u in the caller's frame; A is used as given, it is neither checked
+ *     nor made orthogonal), or A = I, u = 0 when init is null:
+ *         R = A,   t_k = (((A_k0*c_0 + A_k1*c_1) + A_k2*c_2) + u_k) - c_k.
+ *  3. CORRESPONDENCE, every iteration anew: p_j = y'_j + c componentwise; nn_j = the first entry of rh_knn_query's order
+ *     for the query point p_j (k = 1, the params' radius, 0 = no limit); query j is VALID when there is such an entry.
+ *     n_valid = the number of valid queries.
+ *  4. LEAVES of a valid query, with s = r_nn - c and e = s - y' componentwise (a query that is not valid has +0.0 in
+ *     every leaf):
+ *     RH_DIST_PLANE, n the normal stored for r_nn, used as given:
+ *         a_0 = y'_1*n_2 - y'_2*n_1,  a_1 = y'_2*n_0 - y'_0*n_2,  a_2 = y'_0*n_1 - y'_1*n_0,  a_3 = n_0, a_4 = n_1, a_5 = n_2,
+ *         b = (e_0*n_0 + e_1*n_1) + e_2*n_2;
+ *         the 28 leaves a_u*a_v (0 <= u <= v <= 5), a_u*b (u = 0 .. 5) and b*b.  H_uv = H_vu = S(a_u*a_v), g_u = S(a_u*b),
+ *         E = S(b*b).
+ *     RH_DIST_POINT (the three rows n = e_x, e_y, e_z of the plane metric, written out; no product with a literal zero
+ *     is formed): the 16 leaves
+ *         P_00 = y'_0*y'_0, P_11 = y'_1*y'_1, P_22 = y'_2*y'_2, P_01 = y'_0*y'_1, P_02 = y'_0*y'_2, P_12 = y'_1*y'_2,
+ *         Y_k = y'_k,   X_0 = y'_1*e_2 - y'_2*e_1,  X_1 = y'_2*e_0 - y'_0*e_2,  X_2 = y'_0*e_1 - y'_1*e_0,   D_k = e_k,
+ *         (e_0*e_0 + e_1*e_1) + e_2*e_2;
+ *         H_00 = S(P_11) + S(P_22), H_11 = S(P_00) + S(P_22), H_22 = S(P_00) + S(P_11),
+ *         H_01 = -S(P_01), H_02 = -S(P_02), H_12 = -S(P_12),
+ *         H_04 = -S(Y_2), H_05 = S(Y_1), H_13 = S(Y_2), H_15 = -S(Y_0), H_23 = -S(Y_1), H_24 = S(Y_0),
+ *         H_03 = H_14 = H_25 = +0.0;  H_33 = H_44 = H_55 = (double)n_valid, H_34 = H_35 = H_45 = +0.0;
+ *         g_u = S(X_u), g_(3+k) = S(D_k), E = S(the last leaf).
+ *     rms = sqrt(E / (double)n_valid), 0 when n_valid = 0: the residual BEFORE this iteration's step.
+ *  5. n_valid < 6 (fewer residuals than unknowns, whichever metric): the call ends with status RH_REG_TOO_FEW.
+ *  6. SOLVE H x = g by Cholesky, H = L L^T, row by row:
+ *         for i = 0 .. 5:  for j = 0 .. i:  v = H_ji;  for k = 0 .. j-1 ascending: v = v - L_ik*L_jk;
+ *                              j < i:  L_ij = v / L_jj;
+ *                              j = i:  the pivot: accepted when v > 1e-10*H_ii (H_ii the original diagonal); L_ii = sqrt(v).
+ *     A pivot that is not accepted (NaN included) ends the call with status RH_REG_DEGENERATE.  Then
+ *         for i = 0 .. 5:       v = g_i;  for k = 0 .. i-1 ascending: v = v - L_ik*z_k;  z_i = v / L_ii;
+ *         for i = 5 down to 0:  v = z_i;  for k = i+1 .. 5 ascending: v = v - L_ki*x_k;  x_i = v / L_ii.
+ *  7. UPDATE.  w = (x_0, x_1, x_2), tau = (x_3, x_4, x_5), a_k = 0.5*w_k, aa = (a_0*a_0 + a_1*a_1) + a_2*a_2, d = 1.0 + aa,
+ *     f = 1.0 - aa.  The rotation step is the Cayley map of a (rational: no sin, no cos):
+ *         C_kk = (f + 2.0*(a_k*a_k)) / d,
+ *         C_01 = (2.0*(a_0*a_1) - 2.0*a_2) / d,   C_10 = (2.0*(a_0*a_1) + 2.0*a_2) / d,
+ *         C_02 = (2.0*(a_0*a_2) + 2.0*a_1) / d,   C_20 = (2.0*(a_0*a_2) - 2.0*a_1) / d,
+ *         C_12 = (2.0*(a_1*a_2) - 2.0*a_0) / d,   C_21 = (2.0*(a_1*a_2) + 2.0*a_0) / d;
+ *         R_kl <- (C_k0*R_0l + C_k1*R_1l) + C_k2*R_2l   (all nine from the old R),
+ *         t_k  <- ((C_k0*t_0 + C_k1*t_1) + C_k2*t_2) + tau_k   (all three from the old t).
+ *  8. STOP after the update: sqrt((w_0*w_0 + w_1*w_1) + w_2*w_2) <= rot_tol and sqrt((tau_0*tau_0 + tau_1*tau_1) +
+ *     tau_2*tau_2) <= trans_tol: status RH_REG_CONVERGED.  Otherwise, after max_iter iterations: RH_REG_MAX_ITER.
+ *  9. OUTPUTS.  transform_out: 3x4 row-major [R | t_out] in the caller's frame, x' = R x + t_out,
+ *         t_out_k = (t_k + c_k) - ((R_k0*c_0 + R_k1*c_1) + R_k2*c_2)
+ *     -- the state reached so far, whatever the status.  result (optional): status; iterations = the number of iterations
+ *     whose steps 3 and 4 ran (each but possibly the last was followed by an update; with RH_REG_TOO_FEW and
+ *     RH_REG_DEGENERATE the last was not); n_valid and rms of the last of them.  n_valid_it_out / rms_it_out (optional,
+ *     int32 / double [max_iter]): n_valid and rms of iteration 0, 1, ..; 0 behind `iterations`.
+ * The reference's grid is built once per call; the queries' pass (box, margin, cell keys, sort) runs on p_j every
+ * iteration, and nothing that could change a neighbour is carried from one iteration to the next.  No floating-point
+ * atomics: the same bits on every run; a permutation of the queries can change the result in its last bits (the trees run
+ * over the query index order).  The array arguments may be host or device pointers (hipMemcpyDefault); params, init,
+ * transform_out, result and the two histories are host memory.
+ * The function returns RH_OK whatever the status.  RH_E_INVALID, before the device is touched: a null ref / qry / params /
+ * transform_out, n and m outside the limits of rh_knn_query, radius negative or not finite, rot_tol or trans_tol negative
+ * or NaN (+inf is allowed: that test always holds), max_iter outside 1 .. RH_REG_MAX_ITERATIONS, an unknown metric,
+ * RH_DIST_PLANE without normals, an init entry that is not finite; on the device: a coordinate of either cloud, or of a
+ * p_j, that is not finite (nothing is written). */
+#define RH_REG_MAX_ITERATIONS 1000
+enum { RH_REG_CONVERGED = 0, RH_REG_MAX_ITER = 1, RH_REG_DEGENERATE = 2, RH_REG_TOO_FEW = 3 };
+typedef struct {
+    double radius;           /* 0 = no limit */
+    double rot_tol;          /* on |w|, radians to first order */
+    double trans_tol;        /* on |tau|, the clouds' unit */
+    int32_t metric;          /* RH_DIST_* */
+    int32_t max_iter;        /* 1 .. RH_REG_MAX_ITERATIONS */
+} rh_register_params;
+typedef struct {
+    int32_t status;          /* RH_REG_* */
+    int32_t iterations;
+    int64_t n_valid;         /* of the last iteration */
+    double rms;              /* of the last iteration, before its step */
+} rh_register_result;
+int rh_register(const double *ref_xyz_aos, const double *ref_nrm_aos_or_null, int64_t n, const double *qry_xyz_aos, int64_t m,
+                const rh_register_params *p, const double *init_3x4_or_null, int device, double *transform_out_3x4,
+                rh_register_result *result_or_null, int32_t *n_valid_it_out_or_null, double *rms_it_out_or_null);
+int rh_register_f32(const float *ref_xyz_aos, const float *ref_nrm_aos_or_null, int64_t n, const float *qry_xyz_aos, int64_t m,
+                    const rh_register_params *p, const double *init_3x4_or_null, int device, double *transform_out_3x4,
+                    rh_register_result *result_or_null, int32_t *n_valid_it_out_or_null, double *rms_it_out_or_null);
 
 /* ---- tuning options ----
  * The library reads NO environment variable: what a caller may tune goes through this call, for one cloud or, with

@@ -771,6 +771,74 @@ function cloud_distance(reference::AbstractVector{SVector{3,T}}, queries::Abstra
     return dist, nn, st[]
 end
 
+# ---- rigid registration of one cloud onto another (rh_register) ----
+# typedef struct { double radius, rot_tol, trans_tol; int32_t metric, max_iter; } rh_register_params;   (32 bytes)
+struct RhRegisterParams
+    radius::Cdouble
+    rot_tol::Cdouble
+    trans_tol::Cdouble
+    metric::Cint
+    max_iter::Cint
+end
+# typedef struct { int32_t status, iterations; int64_t n_valid; double rms; } rh_register_result;   (24 bytes)
+struct RhRegisterResult
+    status::Cint
+    iterations::Cint
+    n_valid::Int64
+    rms::Cdouble
+end
+const REG_STATUS = (:converged, :max_iter, :degenerate, :too_few)
+
+"""
+    register(reference, queries; normals = nothing, metric = nothing, radius = 0.0, max_iter = 50, rot_tol = 1e-9,
+             trans_tol = 1e-9, init = nothing) -> (T, info)
+
+The rigid motion that brings `queries` onto `reference` by iterative closest point (`rh_register`, include/ransac_hip.h
+has the definition in full).  `metric = :point` minimises the distance to the nearest reference point, `:plane` the
+distance to its tangent plane with `normals` the reference's; the default is `:plane` when normals are given.
+`radius > 0`: a query without a reference point within it takes no part in an iteration.  `init`: a 3x4 or 4x4 start.
+`T` is a 4x4 `Matrix{Float64}` with `x' = T[1:3, 1:3] * x + T[1:3, 4]`; `info` a named tuple `status` (`:converged`,
+`:max_iter`, `:degenerate`, `:too_few`), `iterations`, `n_valid`, `rms` and the per-iteration `n_valid_it`, `rms_it`.
+"""
+function register(reference::AbstractVector{SVector{3,T}}, queries::AbstractVector{SVector{3,T}}; normals = nothing,
+                  metric = nothing, radius::Real = 0.0, max_iter::Integer = 50, rot_tol::Real = 1e-9, trans_tol::Real = 1e-9,
+                  init = nothing, device::Integer = 0) where {T<:Union{Float32,Float64}}
+    metric === nothing && (metric = normals === nothing ? :point : :plane)
+    metric in (:point, :plane) || error("register: metric is :point or :plane")
+    rs = convert(Vector{SVector{3,T}}, reference)
+    qs = convert(Vector{SVector{3,T}}, queries)
+    ns = normals === nothing ? nothing : convert(Vector{SVector{3,T}}, normals)
+    n, m = length(rs), length(qs)
+    ns === nothing || length(ns) == n || error("register: $(length(ns)) normals for $n reference points")
+    ini = init === nothing ? nothing : collect(Float64, permutedims(Matrix{Float64}(init)[1:3, 1:4]))   # row-major 3x4
+    p = RhRegisterParams(radius, rot_tol, trans_tol, metric === :point ? 0 : 1, max_iter)
+    out = zeros(Float64, 4, 3)                   # the library's row-major 3x4, read here column by column
+    hist = 1 <= max_iter <= 1000 ? Int(max_iter) : 1
+    nv = zeros(Int32, hist)
+    rms = zeros(Float64, hist)
+    res = Ref(RhRegisterResult(0, 0, 0, 0.0))
+    GC.@preserve rs qs ns ini out nv rms begin
+        if T == Float32
+            check(ccall((:rh_register_f32, LIB), Cint,
+                (Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ptr{Cfloat}, Int64, Ref{RhRegisterParams}, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+                 Ref{RhRegisterResult}, Ptr{Int32}, Ptr{Cdouble}),
+                pointer(reinterpret(Float32, rs)), ns === nothing ? C_NULL : pointer(reinterpret(Float32, ns)), n,
+                pointer(reinterpret(Float32, qs)), m, p, ini === nothing ? C_NULL : pointer(ini), device, out, res, nv, rms))
+        else
+            check(ccall((:rh_register, LIB), Cint,
+                (Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ref{RhRegisterParams}, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+                 Ref{RhRegisterResult}, Ptr{Int32}, Ptr{Cdouble}),
+                pointer(reinterpret(Float64, rs)), ns === nothing ? C_NULL : pointer(reinterpret(Float64, ns)), n,
+                pointer(reinterpret(Float64, qs)), m, p, ini === nothing ? C_NULL : pointer(ini), device, out, res, nv, rms))
+        end
+    end
+    r = res[]
+    it = Int(r.iterations)
+    Tm = vcat(permutedims(out), [0.0 0.0 0.0 1.0])
+    return Tm, (status = REG_STATUS[r.status + 1], iterations = it, n_valid = r.n_valid, rms = r.rms,
+                n_valid_it = nv[1:it], rms_it = rms[1:it])
+end
+
 _assign_shape(x::ExtractedShape) = toC(x.shape)
 _assign_shape(x::FittedShape) = toC(x)
 

@@ -98,8 +98,22 @@ class DistanceStats(C.Structure):
                 ("rms", C.c_double), ("max", C.c_double), ("median", C.c_double)]
 
 
+class RegisterParams(C.Structure):
+    """rh_register_params (include/ransac_hip.h)"""
+    _fields_ = [("radius", C.c_double), ("rot_tol", C.c_double), ("trans_tol", C.c_double), ("metric", C.c_int32),
+                ("max_iter", C.c_int32)]
+
+
+class RegisterResult(C.Structure):
+    """rh_register_result (include/ransac_hip.h)"""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("n_valid", C.c_int64), ("rms", C.c_double)]
+
+
 KNN_MAX_K = 63
 DIST_POINT, DIST_PLANE = 0, 1
+REG_CONVERGED, REG_MAX_ITER, REG_DEGENERATE, REG_TOO_FEW = 0, 1, 2, 3
+REG_STATUS_NAMES = {REG_CONVERGED: "converged", REG_MAX_ITER: "max_iter", REG_DEGENERATE: "degenerate", REG_TOO_FEW: "too_few"}
+REG_MAX_ITERATIONS = 1000
 OUT_BLOCK_POINTS = 1024
 OUT_STATISTICAL, OUT_ABSOLUTE, OUT_RADIUS = 0, 1, 2
 CLUSTER_BY_INDEX, CLUSTER_BY_SIZE = 0, 1
@@ -233,6 +247,10 @@ SIGNATURES = {
                                     C.POINTER(DistanceStats)]),
     "rh_cloud_distance_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float), C.c_int64,
                                         C.POINTER(DistanceParams), C.c_int, _dp, _i32p, C.POINTER(DistanceStats)]),
+    "rh_register": (C.c_int, [_dp, _dp, C.c_int64, _dp, C.c_int64, C.POINTER(RegisterParams), _dp, C.c_int, _dp,
+                              C.POINTER(RegisterResult), _i32p, _dp]),
+    "rh_register_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float), C.c_int64,
+                                  C.POINTER(RegisterParams), _dp, C.c_int, _dp, C.POINTER(RegisterResult), _i32p, _dp]),
     "rh_remove_outliers": (C.c_int, [_dp, C.c_int64, C.POINTER(OutlierParams), C.c_int, _u8p, _i32p, C.c_int64, _i64p, _dp,
                                      C.POINTER(OutlierStats)]),
     "rh_remove_outliers_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(OutlierParams), C.c_int, _u8p, _i32p,

@@ -895,6 +895,75 @@ def transfer_labels(reference, labels, queries, radius=0.0, fill=0, device=0):
     return out
 
 
+def register(reference, queries, normals=None, metric=None, radius=0.0, max_iter=50, rot_tol=1e-9, trans_tol=1e-9, init=None,
+             device=0, return_info=False):
+    """The rigid motion that brings the cloud `queries` onto the cloud `reference` by iterative closest point
+    (rh_register; include/ransac_hip.h has the definition in full).  metric "point": the distance to the nearest
+    reference point is minimised; "plane": the distance to its tangent plane, with `normals` the reference's (used as
+    given); the default is "plane" when normals are given and "point" otherwise.  radius > 0: a query without a reference
+    point within it takes no part in an iteration.  init: a 3x4 or 4x4 start (the identity by default); ICP finds the
+    nearest minimum, so it has to be roughly right.  The iteration stops when a step turns by at most rot_tol and moves by
+    at most trans_tol, or after max_iter iterations.
+    Returns the 4x4 float64 matrix T with x' = T[:3, :3] @ x + T[:3, 3]; with return_info also a dict status ("converged",
+    "max_iter", "degenerate", "too_few"), iterations, n_valid and rms of the last iteration, and history: n_valid and rms
+    of every iteration run.  transform_points(T, queries) moves the cloud."""
+    metrics = {"point": L.DIST_POINT, "plane": L.DIST_PLANE}
+    if metric is None:
+        metric = "point" if normals is None else "plane"
+    if isinstance(metric, str) and metric not in metrics:
+        raise ValueError("register: metric %r is neither 'point' nor 'plane'" % (metric,))
+    f32, ct, arrs = _cloud_pair("register", reference, queries, normals)
+    ref, qry, nrm = arrs[0], arrs[1], (arrs[2] if normals is not None else None)
+    n, m = ref.shape[0], qry.shape[0]
+    ini = None
+    if init is not None:
+        ini = np.asarray(init, dtype=np.float64)
+        if ini.shape not in ((3, 4), (4, 4)):
+            raise ValueError("register: init must be 3x4 or 4x4, not %r" % (ini.shape,))
+        ini = np.ascontiguousarray(ini[:3])
+    max_iter = int(max_iter)
+    prm = L.RegisterParams(radius=float(radius), rot_tol=float(rot_tol), trans_tol=float(trans_tol),
+                           metric=int(metrics.get(metric, metric)), max_iter=max_iter)
+    hist = max_iter if 1 <= max_iter <= L.REG_MAX_ITERATIONS else 1      # (the library refuses the call; nothing is written)
+    out = np.zeros((3, 4))
+    res = L.RegisterResult()
+    nv_it, rms_it = np.zeros(hist, dtype=np.int32), np.zeros(hist)
+    fn = lib().rh_register_f32 if f32 else lib().rh_register
+    check(fn(_p(ref, ct), None if nrm is None else _p(nrm, ct), n, _p(qry, ct), m, C.byref(prm),
+             None if ini is None else _p(ini, C.c_double), device, _p(out, C.c_double), C.byref(res), _p(nv_it, C.c_int32),
+             _p(rms_it, C.c_double)))
+    T = np.vstack([out, [0.0, 0.0, 0.0, 1.0]])
+    if not return_info:
+        return T
+    it = int(res.iterations)
+    return T, dict(status=L.REG_STATUS_NAMES.get(res.status, res.status), iterations=it, n_valid=int(res.n_valid),
+                   rms=float(res.rms), history=dict(n_valid=nv_it[:it].copy(), rms=rms_it[:it].copy()))
+
+
+def _rigid(who, T):
+    T = np.asarray(T, dtype=np.float64)
+    if T.shape not in ((3, 4), (4, 4)):
+        raise ValueError("%s: the transform must be 3x4 or 4x4, not %r" % (who, T.shape))
+    return T
+
+
+def transform_points(T, points):
+    """x' = T[:3, :3] @ x + T[:3, 3] for every row of points (n, 3), in float64 and in register's operation order:
+    ((R_k0*x + R_k1*y) + R_k2*z) + t_k.  T: 3x4 or 4x4, e.g. what register returns."""
+    T = _rigid("transform_points", T)
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([((T[k, 0] * x + T[k, 1] * y) + T[k, 2] * z) + T[k, 3] for k in range(3)], axis=1)
+
+
+def transform_normals(T, normals):
+    """n' = T[:3, :3] @ n for every row of normals (n, 3): directions turn with a rigid motion and do not move."""
+    T = _rigid("transform_normals", T)
+    p = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([(T[k, 0] * x + T[k, 1] * y) + T[k, 2] * z for k in range(3)], axis=1)
+
+
 def removeoutliers(vertices, k=16, std_mul=2.0, mode="statistical", radius=0.0, threshold=None, normals=None, device=0,
                    return_index=False, return_stats=False, return_mean_dist=False):
     """Drop the stray points of a raw cloud (rh_remove_outliers; include/ransac_hip.h has the definition in full).  With

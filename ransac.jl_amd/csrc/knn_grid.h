@@ -1,6 +1,6 @@
 // knn_grid.h -- the uniform grid of the exact k-nearest-neighbour search (knn_device.h has the query), shared by
-// normals.hip (rh_estimate_normals), knn.hip (rh_knn, rh_remove_outliers), knn_query.hip (rh_knn_query,
-// rh_cloud_distance: the grid holds the reference cloud) and cluster.hip (rh_cluster, which walks the cells itself):
+// normals.hip (rh_estimate_normals), knn.hip (rh_knn, rh_remove_outliers), knn_query.hip and register.hip (rh_knn_query,
+// rh_cloud_distance, rh_register: the grid holds the reference cloud) and cluster.hip (rh_cluster, which walks the cells itself):
 //   points radix-sorted by cell key, an open-addressing hash table key -> [start, end) of the occupied cells only (empty
 //   space costs nothing; table and bounding box are cell_grid.h's), the coordinates gathered into cell order.  KnnIndex
 //   holds the grid's buffers in the call's scope (call_scope.h) and rebuilds the grid for any cell width.
@@ -100,13 +100,17 @@ __global__ void nrm_hash_kernel(const uint64_t *__restrict__ key, int64_t n, uin
     if (end) hrange[2 * (size_t)sl + 1] = (int32_t)(i + 1);
 }
 
-// the bounding box of the n points of d_xyz; RH_E_INVALID on a coordinate that is not finite (one round trip to the host)
-inline int cloud_box(CallScope &S, const double *d_xyz, int64_t n, double lo[3], double hi[3])
+// the words cloud_box folds through for a cloud of n points
+inline int64_t cloud_box_words(int64_t n) { return MM_WORDS * (1 + std::min<int64_t>(blocks_for(n), GRID_MM_BLOCKS)); }
+
+// the bounding box of the n points of d_xyz; RH_E_INVALID on a coordinate that is not finite (one round trip to the host).
+// d_scal: cloud_box_words(n) words of the caller's (a call that asks again and again), or null: allocated here.
+inline int cloud_box(CallScope &S, const double *d_xyz, int64_t n, double lo[3], double hi[3], unsigned long long *d_scal = nullptr)
 {
     const hipStream_t st = S.st;
     const int64_t nb = std::min<int64_t>(blocks_for(n), GRID_MM_BLOCKS);
-    unsigned long long *d_scal = nullptr, h_scal[MM_COUNT + 1];
-    RH_TRY(S.alloc(&d_scal, MM_WORDS * (1 + nb)));
+    unsigned long long h_scal[MM_COUNT + 1];
+    if (!d_scal) RH_TRY(S.alloc(&d_scal, cloud_box_words(n)));
     hipLaunchKernelGGL(nrm_minmax_kernel, dim3((unsigned)nb), dim3(256), 0, st, d_xyz, n, d_scal + MM_WORDS);
     hipLaunchKernelGGL(grid_minmax_fold_kernel, dim3(1), dim3(256), 0, st, d_scal + MM_WORDS, (int)nb, d_scal, (int)MM_WORDS);
     SCOPE_HIP(S, hipGetLastError());

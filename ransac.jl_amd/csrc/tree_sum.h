@@ -1,5 +1,5 @@
-// tree_sum.h -- T() of include/ransac_hip.h, the order-fixed sum of rh_remove_outliers (knn.hip) and rh_cloud_distance
-// (knn_query.hip): the root of the perfect binary tree over ADJACENT pairs of the leaves, padded with +0.0.  A lane's four
+// tree_sum.h -- T() of include/ransac_hip.h, the order-fixed sum of rh_remove_outliers (knn.hip), rh_cloud_distance
+// (knn_query.hip) and rh_register (register.hip, whose kernels fold many components in this very tree): the root of the perfect binary tree over ADJACENT pairs of the leaves, padded with +0.0.  A lane's four
 // values, a butterfly over lanes with xor 1, 2, .. 32, adjacent pairs of the four wave sums and then the same kernel over
 // the block partials are that very tree, so the bits do not depend on the launch geometry.  No floating-point atomics.
 // Everything lives in an anonymous namespace: each translation unit that includes the header gets its own kernels.
