@@ -38,7 +38,7 @@ enum {
     RH_OK = 0,
     RH_E_INVALID = -1,   /* bad argument (the reference would hit an @assert) */
     RH_E_NODEVICE = -2,  /* no HIP device / HIP runtime error */
-    RH_E_NOMEM = -3,
+    RH_E_NOMEM = -3,     /* out of device, pinned or host memory: every entry says so (a failed allocation is never RH_E_NODEVICE) */
     RH_E_CAPACITY = -4,  /* caller-provided output too small; *n_out holds the needed size */
     RH_E_INTERNAL = -5,
 };

@@ -403,14 +403,9 @@ int assign_cloud_enqueue(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const
     J.n = c->n; J.b = b; J.nruns = runs_of(c->n); J.stride = c->n_pad;
     fill_thresholds(J, p);
     const asg_ws_layout W = ws_layout(c->n, b, d_counts != nullptr || d_idx != nullptr);
-    if ((int64_t)W.bytes > c->asg_ws_bytes) RH_TRY(rh_grow_buffer(c, &c->asg_ws, &c->asg_ws_bytes, (int64_t)W.bytes, W.bytes));
+    if ((int64_t)W.bytes > c->asg_ws.count()) RH_TRY(c->asg_ws.grow(c->stream, (int64_t)W.bytes));
     ws_bind(J, c->asg_ws, W);
-    if (b > 0) {   // the records, made on the device by the score path's own prep kernel (a view of a batch workspace: shapes in, records out)
-        rh_batch_ws view;
-        view.d_shapes = const_cast<rh_shape *>(d_shapes);
-        view.d_prep = const_cast<rh_prep *>(J.prep);
-        RH_TRY(rhk_prep_sorted(c, view, b));
-    }
+    if (b > 0) RH_TRY(rhk_prep_records(c, d_shapes, b, const_cast<rh_prep *>(J.prep)));   // made on the device by the score path's own prep kernel
     J.shapes = d_shapes;
     const bool use_nrm = !(flags & RH_ASSIGN_NO_NORMALS);
     if (c->f32) { J.xyz = c->full32; J.nrm = use_nrm ? c->full32 + 3 * c->n_pad : nullptr; }
@@ -467,8 +462,8 @@ extern "C" int rh_cloud_assign(rh_cloud *c, const rh_shape *shapes, int32_t b, c
                  o_cnt = o_dist + up16(dist_out_or_null ? sizeof(double) * (size_t)n : 0),
                  o_off = o_cnt + up16(sizeof(int64_t) * (size_t)(b + 1)), o_idx = o_off + up16(sizeof(int64_t) * (size_t)(b + 2)),
                  bytes = o_idx + up16(idx_out_or_null ? sizeof(int64_t) * (size_t)n : 0);
-    if ((int64_t)bytes > c->asg_io_bytes) RH_TRY(rh_grow_buffer(c, &c->asg_io, &c->asg_io_bytes, (int64_t)bytes, bytes));
-    char *d = (char *)c->asg_io;
+    if ((int64_t)bytes > c->asg_io.count()) RH_TRY(c->asg_io.grow(c->stream, (int64_t)bytes));
+    char *d = c->asg_io;
     if (b > 0) {
         RH_TRY(rh_ensure_pin(c, (int64_t)o_lab));
         memcpy(c->h_pin, shapes, sizeof(rh_shape) * (size_t)b);

@@ -1,7 +1,7 @@
 // call_scope.h -- what an entry point on raw host arrays (rh_voxel_downsample, rh_knn, rh_remove_outliers, rh_knn_query,
 // rh_cloud_distance, rh_register, rh_cluster, rh_estimate_normals, rh_assign_points, rh_largestconncomp) owns for the length of the call: the device, a stream of its
 // own and its device buffers, released on every way out.  Host code only.  The cloud-bound paths do not come here: a
-// cloud has its stream and its grown buffers (rh_grow_buffer, RH_HIP).
+// cloud has its stream and its grown buffers (rh_dev::grow, RH_HIP).
 // Everything lives in an anonymous namespace: each translation unit that includes the header gets its own widen kernel.
 #pragma once
 
@@ -27,14 +27,14 @@ __global__ void scope_widen_kernel(const T *__restrict__ in, double *__restrict_
 struct CallScope {
     const char *who = "";    // the entry point, for error texts
     hipStream_t st = nullptr;
-    std::vector<void *> ptrs;
+    std::vector<rh_dev<char>> bufs;
     CallScope() = default;
     CallScope(const CallScope &) = delete;
     CallScope &operator=(const CallScope &) = delete;
     // the buffers first (hipFree waits for the device: copies still in flight at an early return end there), then the stream
     ~CallScope()
     {
-        for (void *p : ptrs) (void)hipFree(p);
+        bufs.clear();
         if (st) (void)hipStreamDestroy(st);
     }
 
@@ -55,22 +55,22 @@ struct CallScope {
     int alloc(T **p, int64_t count)
     {
         *p = nullptr;
-        const size_t bytes = sizeof(T) * (size_t)(count > 0 ? count : 1);
-        const hipError_t e = hipMalloc((void **)p, bytes);
-        if (e != hipSuccess) {
+        rh_dev<char> b;
+        const int rc = b.alloc((int64_t)sizeof(T) * (count > 0 ? count : 1), who);
+        if (rc != RH_OK) {
             (void)hipGetLastError();
-            rh_set_error("%s: hipMalloc(%zu bytes) failed: %s", who, bytes, hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? RH_E_NOMEM : RH_E_NODEVICE;
+            return rc;
         }
-        ptrs.push_back(*p);
+        *p = (T *)b.get();
+        bufs.push_back(std::move(b));
         return RH_OK;
     }
 
     // before the call ends (null and foreign pointers are ignored)
     void release(void *p)
     {
-        for (auto &q : ptrs)
-            if (q == p) { (void)hipFree(q); q = nullptr; }
+        for (auto &b : bufs)
+            if (b.get() == p) b.reset();
     }
 
     // cnt values of T from the caller's array into doubles on the device, widened exactly

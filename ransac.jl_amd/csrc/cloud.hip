@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <new>
 #include <utility>
 #include <vector>
@@ -56,40 +57,10 @@ int rh_validate_params(const rh_params *p)
 }
 
 // ------------------------------------------------------------ allocation ----
-template <typename T>
-static int dev_alloc(T **p, int64_t count)
-{
-    *p = nullptr;
-    const size_t bytes = sizeof(T) * (size_t)(count > 0 ? count : 1);
-    hipError_t e = hipMalloc((void **)p, bytes);
-    if (e != hipSuccess) {
-        rh_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? RH_E_NOMEM : RH_E_NODEVICE;
-    }
-    return RH_OK;
-}
-
 int rh_ensure_pin(rh_cloud *c, int64_t bytes)
 {
-    if (bytes <= c->h_pin_cap) return RH_OK;
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    c->h_pin = nullptr;
-    c->h_pin_cap = 0;
-    int64_t cap = std::max<int64_t>(bytes, 1 << 20);
-    RH_HIP(hipHostMalloc(&c->h_pin, (size_t)cap, hipHostMallocDefault));
-    c->h_pin_cap = cap;
-    return RH_OK;
-}
-
-int rh_grow_buffer(rh_cloud *c, void **buf, int64_t *cap, int64_t new_cap, size_t bytes)
-{
-    RH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    if (cap) *cap = 0;
-    RH_TRY(dev_alloc((char **)buf, (int64_t)bytes));
-    if (cap) *cap = new_cap;
-    return RH_OK;
+    if (bytes <= c->h_pin.count()) return RH_OK;
+    return c->h_pin.alloc(std::max<int64_t>(bytes, 1 << 20));
 }
 
 int rh_ensure_batch(rh_cloud *c, rh_batch_ws &w, int64_t b)
@@ -97,12 +68,12 @@ int rh_ensure_batch(rh_cloud *c, rh_batch_ws &w, int64_t b)
     if (b <= w.batch_cap) return RH_OK;
     const int64_t cap = std::max<int64_t>(b, std::max<int64_t>(1024, w.batch_cap * 2));
     w.batch_cap = 0;
-    RH_TRY(rh_grow_buffer(c, (void **)&w.d_shapes, nullptr, 0, sizeof(rh_shape) * (size_t)cap));
-    RH_TRY(rh_grow_buffer(c, (void **)&w.d_prep, nullptr, 0, sizeof(rh_prep) * (size_t)(4 * cap)));
-    RH_TRY(rh_grow_buffer(c, &w.d_qpre, nullptr, 0, (size_t)(4 * cap) * 64));   // rh4::rh_cls (64 B) per slot
-    RH_TRY(rh_grow_buffer(c, (void **)&w.d_box, nullptr, 0, sizeof(float) * (size_t)rh4::RH_BOX_FIELDS * (size_t)(4 * cap)));
-    RH_TRY(rh_grow_buffer(c, (void **)&w.d_orig, nullptr, 0, sizeof(int32_t) * (size_t)(4 * cap)));
-    RH_TRY(rh_grow_buffer(c, (void **)&w.d_counts, nullptr, 0, sizeof(int32_t) * (size_t)cap));
+    RH_TRY(w.d_shapes.grow(c->stream, cap));
+    RH_TRY(w.d_prep.grow(c->stream, 4 * cap));
+    RH_TRY(w.d_qpre.grow(c->stream, 4 * cap * 64));   // rh4::rh_cls (64 B) per slot
+    RH_TRY(w.d_box.grow(c->stream, (int64_t)rh4::RH_BOX_FIELDS * 4 * cap));
+    RH_TRY(w.d_orig.grow(c->stream, 4 * cap));
+    RH_TRY(w.d_counts.grow(c->stream, cap));
     w.batch_cap = cap;
     return RH_OK;
 }
@@ -115,19 +86,19 @@ static int rh_masks_begin(rh_cloud *c, rh_batch_ws &w, int32_t b, bool culled)
     if (culled) {
         w.mstride4 = (c->ngroups + 7) / 8 * 8;
         const int64_t words = 2 * b * w.mstride4;      // (two 64-bit words per entry)
-        if (words > w.masks_int_cap) RH_TRY(rh_grow_buffer(c, (void **)&w.d_masks_int, &w.masks_int_cap, words, sizeof(uint64_t) * (size_t)words));
+        if (words > w.d_masks_int.count()) RH_TRY(w.d_masks_int.grow(c->stream, words));
         const int64_t cur_bytes = 4 * (int64_t)b;
-        if (cur_bytes > w.occ_cap) {
-            w.occ_cap = 0;
-            RH_TRY(rh_grow_buffer(c, (void **)&w.d_occ, nullptr, 0, (size_t)cur_bytes));
-            RH_HIP(hipMemsetAsync(w.d_occ, 0, (size_t)cur_bytes, c->stream));
-            w.occ_cap = cur_bytes;
+        if (cur_bytes > w.d_occ.count()) {
+            RH_TRY(w.d_occ.grow(c->stream, cur_bytes));
+            const hipError_t ez = hipMemsetAsync(w.d_occ, 0, (size_t)cur_bytes, c->stream);
+            if (ez != hipSuccess) w.d_occ.reset();   // (cursors that are not zero are no cursors)
+            RH_HIP(ez);
         }
         w.masks4 = true;
         return RH_OK;
     }
     const int64_t words = (int64_t)b * c->swords;
-    if (words > w.masks_int_cap) RH_TRY(rh_grow_buffer(c, (void **)&w.d_masks_int, &w.masks_int_cap, words, sizeof(uint64_t) * (size_t)words));
+    if (words > w.d_masks_int.count()) RH_TRY(w.d_masks_int.grow(c->stream, words));
     RH_HIP(hipMemsetAsync(w.d_masks_int, 0, sizeof(uint64_t) * (size_t)words, c->stream));
     return RH_OK;
 }
@@ -152,15 +123,10 @@ static inline uint64_t spread21(uint64_t v)
     return v;
 }
 
-// everything a batch workspace owns (and nothing else does): the one list of its buffers
+// a batch workspace goes: its stream is waited for and destroyed, the assignment releases its buffers and events
 static void batch_ws_free(rh_batch_ws &w)
 {
     if (w.stream) (void)hipStreamSynchronize(w.stream);
-    (void)hipFree(w.d_shapes); (void)hipFree(w.d_prep); (void)hipFree(w.d_orig); (void)hipFree(w.d_counts); (void)hipFree(w.d_nk2);
-    (void)hipFree(w.d_qpre); (void)hipFree(w.d_box); (void)hipFree(w.d_masks_int); (void)hipFree(w.d_occ);
-    (void)hipFree(w.d_stlist); (void)hipFree(w.d_stcount); (void)hipFree(w.d_segmask);
-    if (w.done) (void)hipEventDestroy(w.done);
-    if (w.start) (void)hipEventDestroy(w.start);
     if (w.stream) (void)hipStreamDestroy(w.stream);
     w = rh_batch_ws();
 }
@@ -173,24 +139,6 @@ static void cloud_free(rh_cloud *c)
     if (c->stream != c->own_stream) (void)hipDeviceSynchronize();
     else if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     for (rh_batch_ws &w : c->ws) batch_ws_free(w);
-    (void)hipFree(c->full); (void)hipFree(c->rec); (void)hipFree(c->crec); (void)hipFree(c->sel_list); (void)hipFree(c->set_ws); (void)hipFree(c->set_level); (void)hipFree(c->sub); (void)hipFree(c->dis);
-    (void)hipFree(c->sub_idx0); (void)hipFree(c->enabled); (void)hipFree(c->sub_enabled);
-    (void)hipFree(c->sub_perm); (void)hipFree(c->gb);
-    (void)hipFree(c->full32); (void)hipFree(c->sub32); (void)hipFree(c->d_zero);
-    (void)hipFree(c->s4_stats); (void)hipFree(c->gb32); (void)hipFree(c->st32); (void)hipFree(c->tile32);
-    (void)hipFree(c->oct_code); (void)hipFree(c->oct_perm); (void)hipFree(c->oct_pos); (void)hipFree(c->oct_men);
-    (void)hipFree(c->oct_prefix); (void)hipFree(c->oct_P); (void)hipFree(c->oct_tab); (void)hipFree(c->oct_code_o);
-    (void)hipFree(c->oct_state); (void)hipFree(c->oct_adv_tab); (void)hipFree(c->oct_adv_bits); (void)hipFree(c->oct_adv_E);
-    (void)hipFree(c->fullk); (void)hipFree(c->fullk32); (void)hipFree(c->kgb); (void)hipFree(c->klist); (void)hipFree(c->kctr); (void)hipFree(c->kflag);
-    (void)hipFree(c->en_block_sums); (void)hipFree(c->dis_gb); (void)hipFree(c->dis_gb32);
-    (void)hipFree(c->d_ndis); (void)hipFree(c->refit_mask); (void)hipFree(c->block_sums);
-    (void)hipFree(c->word_prefix); (void)hipFree(c->idx_out); (void)hipFree(c->d_total);
-    (void)hipFree(c->d_nk); (void)hipFree(c->d_masks); (void)hipFree(c->d_ranks); (void)hipFree(c->d_stage);
-    (void)hipFree(c->comp_tab); (void)hipFree(c->comp_scal);
-    (void)hipFree(c->ext_part); (void)hipFree(c->ext_flag); (void)hipFree(c->ext_in);
-    (void)hipFree(c->asg_ws); (void)hipFree(c->asg_io);
-    if (c->comp_h) (void)hipHostFree(c->comp_h);
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int k = 0; k < 5; k++)
@@ -203,7 +151,7 @@ static void cloud_free(rh_cloud *c)
     if (c->ev_sync) (void)hipEventDestroy(c->ev_sync);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;   // (the buffers go with it: every stream that used them has been waited for above)
 }
 
 static int set_all_enabled(rh_cloud *c)
@@ -361,7 +309,8 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
     c->dis_stride = c->s_pad + RH_SC_TILE;
 
     int rc = RH_OK;
-    double *t_xyz = nullptr, *t_nrm = nullptr;
+    rh_dev<double> t_xyz, t_nrm;
+    std::unique_ptr<int32_t[]> h_idx_own;
     int32_t *h_idx = nullptr;
     auto stamp = [&](const char *what) {
         if (!prof) return;
@@ -371,8 +320,6 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
         t_prev = t;
     };
     auto fail = [&](int code) {
-        (void)hipFree(t_xyz); (void)hipFree(t_nrm);
-        delete[] h_idx;
         cloud_free(c);
         return code;
     };
@@ -386,24 +333,24 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
     CKH(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     CKH(hipEventCreateWithFlags(&c->ev_copied, hipEventDisableTiming));
     CKH(hipEventCreateWithFlags(&c->ev_sync, hipEventDisableTiming));
-    CK(dev_alloc(&c->full, 6 * c->n_pad));
-    CK(dev_alloc(&c->rec, 8 * std::max<int64_t>(n, 1)));
-    CK(dev_alloc(&c->sel_list, c->nwords * 64 + 64));
-    CK(dev_alloc(&c->sub, 6 * c->s_pad));
-    CK(dev_alloc(&c->dis, 6 * c->dis_stride));
-    CK(dev_alloc(&c->sub_idx0, s));
-    CK(dev_alloc(&c->sub_perm, c->s_pad));   // (whole 64-lane reads of the last group stay inside the allocation: the mask pass, score4.hip)
+    CK(c->full.alloc(6 * c->n_pad));
+    CK(c->rec.alloc(8 * std::max<int64_t>(n, 1)));
+    CK(c->sel_list.alloc(c->nwords * 64 + 64));
+    CK(c->sub.alloc(6 * c->s_pad));
+    CK(c->dis.alloc(6 * c->dis_stride));
+    CK(c->sub_idx0.alloc(s));
+    CK(c->sub_perm.alloc(c->s_pad));   // (whole 64-lane reads of the last group stay inside the allocation: the mask pass, score4.hip)
     CKH(hipMemsetAsync(c->sub_perm, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(c->s_pad, 1), c->stream));
     c->ngroups = (s + 63) / 64;
     c->ng_pad = ((c->ngroups + RH_G2_TG - 1) / RH_G2_TG) * RH_G2_TG + RH_G2_TG;
-    CK(dev_alloc(&c->gb, 7 * c->ng_pad));
-    CK(dev_alloc(&c->gb32, 8 * c->ng_pad));
+    CK(c->gb.alloc(7 * c->ng_pad));
+    CK(c->gb32.alloc(8 * c->ng_pad));
     c->nst = (c->ngroups + 15) / 16;
-    CK(dev_alloc(&c->st32, 8 * std::max<int64_t>(1, c->nst)));
+    CK(c->st32.alloc(8 * std::max<int64_t>(1, c->nst)));
     c->ntile = (c->ngroups + 3) / 4;
-    CK(dev_alloc(&c->tile32, 8 * std::max<int64_t>(1, c->ntile)));
-    CK(dev_alloc(&c->dis_gb, 7 * c->ng_pad));
-    CK(dev_alloc(&c->dis_gb32, 8 * c->ng_pad));
+    CK(c->tile32.alloc(8 * std::max<int64_t>(1, c->ntile)));
+    CK(c->dis_gb.alloc(7 * c->ng_pad));
+    CK(c->dis_gb32.alloc(8 * c->ng_pad));
     CKH(hipMemsetAsync(c->dis_gb, 0, sizeof(double) * 7 * (size_t)c->ng_pad, c->stream));
     CKH(hipMemsetAsync(c->gb, 0, sizeof(double) * 7 * (size_t)c->ng_pad, c->stream));
     {
@@ -412,17 +359,17 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
         if (e == RH_SCORE_PATH_BRUTE) c->use_groups = false;
         if (e == RH_SCORE_PATH_GROUPS) c->use_groups = s > 0;
     }
-    CK(dev_alloc(&c->enabled, c->nwords));
-    CK(dev_alloc(&c->sub_enabled, c->swords));
-    CK(dev_alloc(&c->d_ndis, 1));
-    CK(dev_alloc(&c->refit_mask, c->nwords));
-    CK(dev_alloc(&c->block_sums, std::max<int64_t>(c->nblocks, (c->swords + RH_WORDS_PER_BLOCK - 1) / RH_WORDS_PER_BLOCK) + 2));
-    CK(dev_alloc(&c->en_block_sums, c->nblocks + 2));
-    CK(dev_alloc(&c->word_prefix, c->nwords + 1));
-    CK(dev_alloc(&c->idx_out, n));
-    CK(dev_alloc(&c->d_total, 1));
-    CK(dev_alloc(&c->d_nk, 4));
-    CK(dev_alloc(&c->ws[0].d_nk2, 8));
+    CK(c->enabled.alloc(c->nwords));
+    CK(c->sub_enabled.alloc(c->swords));
+    CK(c->d_ndis.alloc(1));
+    CK(c->refit_mask.alloc(c->nwords));
+    CK(c->block_sums.alloc(std::max<int64_t>(c->nblocks, (c->swords + RH_WORDS_PER_BLOCK - 1) / RH_WORDS_PER_BLOCK) + 2));
+    CK(c->en_block_sums.alloc(c->nblocks + 2));
+    CK(c->word_prefix.alloc(c->nwords + 1));
+    CK(c->idx_out.alloc(n));
+    CK(c->d_total.alloc(1));
+    CK(c->d_nk.alloc(4));
+    CK(c->ws[0].d_nk2.alloc(8));
     CKH(hipMemsetAsync(c->full, 0, sizeof(double) * 6 * (size_t)c->n_pad, c->stream));
     CKH(hipMemsetAsync(c->sub, 0, sizeof(double) * 6 * (size_t)c->s_pad, c->stream));
     CKH(hipMemsetAsync(c->dis, 0, sizeof(double) * 6 * (size_t)c->dis_stride, c->stream));
@@ -430,8 +377,8 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
     stamp("streams, allocations, memsets");
 
     if (n > 0) {
-        CK(dev_alloc(&t_xyz, 3 * n));
-        CK(dev_alloc(&t_nrm, 3 * n));
+        CK(t_xyz.alloc(3 * n));
+        CK(t_nrm.alloc(3 * n));
         CKH(hipMemcpyAsync(t_xyz, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
         CKH(hipMemcpyAsync(t_nrm, nrm, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
         stamp("upload (xyz, nrm)");
@@ -446,7 +393,8 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
         if (s > 0) {
             // internal order of subset 1: 64 consecutive points are spatially compact, which is what the
             // culled score kernel's per-group boxes need (k-d leaves, below)
-            h_idx = new (std::nothrow) int32_t[2 * (size_t)s];
+            h_idx_own.reset(new (std::nothrow) int32_t[2 * (size_t)s]);
+            h_idx = h_idx_own.get();
             if (!h_idx) { rh_set_error("out of host memory"); return fail(RH_E_NOMEM); }
             ms_before_kd = ms_since(tc0);
             const auto tkd0 = std::chrono::steady_clock::now();
@@ -457,13 +405,11 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
             const bool kd_device = !rh_opt_on(nullptr, RH_OPT_KD_HOST) && !ord_morton;
             if (kd_device) {
                 for (int64_t j = 0; j < s; j++) h_idx[j] = (int32_t)(subset1[j] - 1);
-                int32_t *d_idx_in = nullptr;
-                CK(dev_alloc(&d_idx_in, s));
-                hipError_t ec = hipMemcpyAsync(d_idx_in, h_idx, sizeof(int32_t) * (size_t)s, hipMemcpyHostToDevice, c->stream);
-                rc = ec == hipSuccess ? rhk_kd_order(c, t_xyz, t_nrm, d_idx_in) : RH_E_NODEVICE;
-                (void)hipFree(d_idx_in);
-                if (ec != hipSuccess) rh_set_error("hipMemcpyAsync(subset indices): %s", hipGetErrorString(ec));
-                if (rc != RH_OK) return fail(rc);
+                rh_dev<int32_t> d_idx_in;
+                CK(d_idx_in.alloc(s));
+                CKH(hipMemcpyAsync(d_idx_in, h_idx, sizeof(int32_t) * (size_t)s, hipMemcpyHostToDevice, c->stream));
+                CK(rhk_kd_order(c, t_xyz, t_nrm, d_idx_in));
+                d_idx_in.reset();
                 ms_kd = ms_since(tkd0);
                 CK(rhk_transpose_aos(c, t_xyz, t_nrm, n, c->sub_idx0, s, c->sub, c->s_pad));
                 CK(rhk_group_bounds(c));
@@ -601,9 +547,9 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
     stamp("enabled bits");
 #undef CK
 #undef CKH
-    (void)hipFree(t_xyz);
-    (void)hipFree(t_nrm);
-    delete[] h_idx;
+    t_xyz.reset();   // (inside the time below, as ever)
+    t_nrm.reset();
+    h_idx_own.reset();
     c->create_ms[0] = ms_since(tc0);
     c->create_ms[1] = ms_kd;
     c->create_ms[2] = ms_before_kd;
@@ -651,8 +597,8 @@ extern "C" int rh_cloud_create_f32(const float *xyz, const float *nrm, int64_t n
     c->f32 = true;
     c->f32_groups = c->use_groups;   // culled kernel with a binary32 exact test where a Float64 cloud would use the culled kernel
     c->use_groups = false;           // (the Float64 dispatch below never runs for this cloud)
-    int rc = dev_alloc(&c->full32, 6 * std::max<int64_t>(c->n_pad, 1));
-    if (rc == RH_OK) rc = dev_alloc(&c->sub32, 6 * std::max<int64_t>(c->s_pad, 1));
+    int rc = c->full32.alloc(6 * std::max<int64_t>(c->n_pad, 1));
+    if (rc == RH_OK) rc = c->sub32.alloc(6 * std::max<int64_t>(c->s_pad, 1));
     if (rc == RH_OK) rc = rhk_f32_build(c);
     if (rc == RH_OK && hipStreamSynchronize(c->stream) != hipSuccess) { rh_set_error("rh_cloud_create_f32: device error"); rc = RH_E_NODEVICE; }
     if (rc != RH_OK) { cloud_free(c); return rc; }
@@ -763,7 +709,7 @@ static int score_bins_subset(rh_cloud *c, rh_batch_ws &w, const rh_score_job &jo
     if (rh_score_v4_enabled(c)) {
         if (!ms_kind) return rhk_score4_all(c, w, job, launch_info);
         if (c->d_zero == nullptr) {
-            RH_HIP(hipMalloc((void **)&c->d_zero, 64));
+            RH_TRY(c->d_zero.alloc(16));
             RH_HIP(hipMemsetAsync(c->d_zero, 0, 64, c->stream));
         }
         for (int k = 0; k < 4; k++) {
@@ -783,7 +729,7 @@ static int score_bins_subset(rh_cloud *c, rh_batch_ws &w, const rh_score_job &jo
             return rhk_score_kind(c, k, pts, c->s_pad, c->s, job.en[k], job.bins.prep[k], job.bins.orig[k], job.nk[k], job.kind_bound[k],
                                   job.eps[k], job.cosa[k], job.d_counts, job.d_masks_int, c->swords);
         };
-        RH_TRY(c->f32 ? score(c->sub32) : score(c->sub));
+        RH_TRY(c->f32 ? score(c->sub32.get()) : score(c->sub.get()));
     }
     return RH_OK;
 }
@@ -821,8 +767,8 @@ extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, co
     const size_t o_box = o_cls + (size_t)b * 64;   // culling records: RH_BOX_FIELDS arrays of b floats
     const size_t stage_bytes = staged_cls ? o_box + (size_t)rh4::RH_BOX_FIELDS * b * sizeof(float) : o_counts + (size_t)b * sizeof(int32_t);
     RH_TRY(rh_ensure_pin(c, (int64_t)stage_bytes));
-    if (staged && c->d_stage == nullptr) RH_HIP(hipMalloc((void **)&c->d_stage, 32 * (rec_bytes + 8 + 64 + 4 * rh4::RH_BOX_FIELDS) + 512));
-    char *hp = (char *)c->h_pin, *dp = (char *)c->d_stage;
+    if (staged && c->d_stage == nullptr) RH_TRY(c->d_stage.alloc(32 * (rec_bytes + 8 + 64 + 4 * rh4::RH_BOX_FIELDS) + 512));
+    char *hp = (char *)c->h_pin.get(), *dp = (char *)c->d_stage;
     rh_shape *h_sorted = (rh_shape *)hp;
     rh_prep *h_prep = (rh_prep *)hp;
     int32_t *h_orig = (int32_t *)(hp + o_orig);
@@ -871,7 +817,7 @@ extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, co
     uint64_t *d_masks = nullptr, *d_masks_int = nullptr;
     if (masks_out && c->swords > 0) {
         const int64_t words = (int64_t)b * c->swords;
-        if (words > c->masks_cap) RH_TRY(rh_grow_buffer(c, (void **)&c->d_masks, &c->masks_cap, words, sizeof(uint64_t) * (size_t)words));
+        if (words > c->d_masks.count()) RH_TRY(c->d_masks.grow(c->stream, words));
         d_masks = c->d_masks;
         RH_TRY(rh_masks_begin(c, w, b, d_cls_use != nullptr));
         d_masks_int = w.d_masks_int;
@@ -910,9 +856,9 @@ static int pick_concurrent_stream(const hipStream_t *busy, int nbusy, hipStream_
 {
     hipStream_t tried[8];
     int ntried = 0, chosen = -1;
-    hipEvent_t eb[RH_MAX_IN_FLIGHT], ec;
-    for (int i = 0; i < nbusy; i++) RH_HIP(hipEventCreateWithFlags(&eb[i], hipEventDisableTiming));
-    RH_HIP(hipEventCreateWithFlags(&ec, hipEventDisableTiming));
+    rh_event eb[RH_MAX_IN_FLIGHT], ec;
+    for (int i = 0; i < nbusy; i++) RH_TRY(eb[i].create(hipEventDisableTiming));
+    RH_TRY(ec.create(hipEventDisableTiming));
     int rc = RH_OK;
     for (; ntried < 8 && chosen < 0 && rc == RH_OK; ntried++) {
         if (hipStreamCreateWithFlags(&tried[ntried], hipStreamNonBlocking) != hipSuccess) { rc = RH_E_NODEVICE; rh_set_error("hipStreamCreateWithFlags failed"); break; }
@@ -931,8 +877,6 @@ static int pick_concurrent_stream(const hipStream_t *busy, int nbusy, hipStream_
     if (rc == RH_OK && chosen < 0) chosen = ntried - 1;   // (none found: the last one -- correct, only not concurrent)
     for (int i = 0; i < ntried; i++)
         if (i != chosen) (void)hipStreamDestroy(tried[i]);
-    for (int i = 0; i < nbusy; i++) (void)hipEventDestroy(eb[i]);
-    (void)hipEventDestroy(ec);
     (void)hipGetLastError();
     if (rc != RH_OK) return rc;
     *out = tried[chosen];
@@ -940,7 +884,7 @@ static int pick_concurrent_stream(const hipStream_t *busy, int nbusy, hipStream_
 }
 
 // What makes c->ws[slot] (slot >= 1) a slot of the pipeline: a stream beside the cloud's and the other slots', two events and
-// the bin-size buffer.  Made into locals and published only when all four exist, so a slot is never half made.
+// the bin-size buffer.  Made into local owners and moved in only when all four exist, so a slot is never half made.
 static int batch_slot_create(rh_cloud *c, int slot)
 {
     hipStream_t busy[RH_MAX_IN_FLIGHT];
@@ -948,21 +892,18 @@ static int batch_slot_create(rh_cloud *c, int slot)
     busy[nbusy++] = c->stream;
     for (int q = 1; q < RH_MAX_IN_FLIGHT; q++) if (q != slot && c->ws[q].stream != nullptr) busy[nbusy++] = c->ws[q].stream;
     hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr, start = nullptr;
-    int32_t *d_nk2 = nullptr;
+    rh_event done, start;
+    rh_dev<int32_t> d_nk2;
     RH_TRY(pick_concurrent_stream(busy, nbusy, &stream));
-    hipError_t e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&start, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_nk2, 8 * sizeof(int32_t));
-    if (e != hipSuccess) {   // (d_nk2 came last: there is none)
-        if (done) (void)hipEventDestroy(done);
-        if (start) (void)hipEventDestroy(start);
+    int rc = done.create(hipEventDisableTiming);
+    if (rc == RH_OK) rc = start.create(hipEventDisableTiming);
+    if (rc == RH_OK) rc = d_nk2.alloc(8);
+    if (rc != RH_OK) {
         (void)hipStreamDestroy(stream);
-        rh_set_error("rh_score_batch_dev: batch slot %d: %s", slot, hipGetErrorString(e));
-        return RH_E_NODEVICE;
+        return rc;
     }
     rh_batch_ws &w = c->ws[slot];
-    w.stream = stream; w.done = done; w.start = start; w.d_nk2 = d_nk2;
+    w.stream = stream; w.done = std::move(done); w.start = std::move(start); w.d_nk2 = std::move(d_nk2);
     return RH_OK;
 }
 
@@ -1172,20 +1113,14 @@ extern "C" int rh_select_enabled(rh_cloud *c, const int64_t *ranks, int32_t k, i
     if (k < 0 || (k > 0 && (!ranks || !idx_out))) { rh_set_error("rh_select_enabled: bad arguments"); return RH_E_INVALID; }
     if (k == 0) return RH_OK;
     if (c->nwords == 0) { for (int i = 0; i < k; i++) idx_out[i] = 0; return RH_OK; }
-    if (k > c->ranks_cap) {
-        RH_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_ranks);
-        c->d_ranks = nullptr;
-        c->ranks_cap = 0;
-        RH_TRY(dev_alloc(&c->d_ranks, 2 * (int64_t)k));
-        c->ranks_cap = k;
-    }
+    if (2 * (int64_t)k > c->d_ranks.count()) RH_TRY(c->d_ranks.grow(c->stream, 2 * (int64_t)k));   // ranks in the first half, indices in the second
+    const int64_t ranks_cap = c->d_ranks.count() / 2;
     if (!c->select_valid) RH_TRY(rhk_build_select(c));
     if (k <= 1024) {
         // the per-sample call of the reference's loop (a couple of ranks): the kernel reads the ranks from the pinned
         // block and writes the indices back into it -- one launch and one wait, no transfer operation
         RH_TRY(rh_ensure_pin(c, 2 * (int64_t)sizeof(int64_t) * k));
-        int64_t *h_ranks = (int64_t *)c->h_pin, *h_out = h_ranks + k;
+        int64_t *h_ranks = (int64_t *)c->h_pin.get(), *h_out = h_ranks + k;
         memcpy(h_ranks, ranks, sizeof(int64_t) * (size_t)k);
         RH_TRY(rhk_select(c, h_ranks, k, h_out));
         RH_HIP(hipStreamSynchronize(c->stream));
@@ -1193,8 +1128,8 @@ extern "C" int rh_select_enabled(rh_cloud *c, const int64_t *ranks, int32_t k, i
         return RH_OK;
     }
     RH_HIP(hipMemcpyAsync(c->d_ranks, ranks, sizeof(int64_t) * (size_t)k, hipMemcpyHostToDevice, c->stream));
-    RH_TRY(rhk_select(c, c->d_ranks, k, c->d_ranks + c->ranks_cap));
-    RH_HIP(hipMemcpyAsync(idx_out, c->d_ranks + c->ranks_cap, sizeof(int64_t) * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+    RH_TRY(rhk_select(c, c->d_ranks, k, c->d_ranks + ranks_cap));
+    RH_HIP(hipMemcpyAsync(idx_out, c->d_ranks + ranks_cap, sizeof(int64_t) * (size_t)k, hipMemcpyDeviceToHost, c->stream));
     RH_HIP(hipStreamSynchronize(c->stream));
     return RH_OK;
 }
@@ -1226,19 +1161,12 @@ extern "C" int rh_sample_sets(rh_cloud *c, int32_t drawN, rh_rng *rng, int32_t k
         rh_rng tmp = *rng;
         const size_t bytes_raw = sizeof(uint64_t) * (size_t)L, bytes_rec = sizeof(int64_t) * (size_t)L * (size_t)W;
         RH_TRY(rh_ensure_pin(c, (int64_t)(bytes_raw + bytes_rec)));
-        uint64_t *h_raw = (uint64_t *)c->h_pin;
+        uint64_t *h_raw = (uint64_t *)c->h_pin.get();
         int64_t *h_rec = (int64_t *)(h_raw + L);
         for (int32_t i = 0; i < L; i++) h_raw[i] = rh_rng_next_raw(&tmp);
         const int64_t need = (int64_t)L * (1 + W);
-        if (need > 2 * c->ranks_cap) {   // (d_ranks holds 2 x ranks_cap words)
-            RH_HIP(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->d_ranks);
-            c->d_ranks = nullptr;
-            c->ranks_cap = 0;
-            RH_TRY(dev_alloc(&c->d_ranks, 2 * ((need + 1) / 2)));
-            c->ranks_cap = (need + 1) / 2;
-        }
-        uint64_t *d_raw = (uint64_t *)c->d_ranks;
+        if (need > c->d_ranks.count()) RH_TRY(c->d_ranks.grow(c->stream, 2 * ((need + 1) / 2)));   // (an even count: rh_select_enabled halves it)
+        uint64_t *d_raw = (uint64_t *)c->d_ranks.get();
         int64_t *d_rec = c->d_ranks + L;
         RH_HIP(hipMemcpyAsync(d_raw, h_raw, bytes_raw, hipMemcpyHostToDevice, c->stream));
         RH_TRY(rhk_sample_sets_seq(c, d_raw, L, drawN, d_rec));
@@ -1302,9 +1230,9 @@ extern "C" int rh_dev_alloc(rh_cloud *c, int64_t bytes, void **d_out)
 {
     RH_TRY(enter(c));
     if (!d_out || bytes < 0) { rh_set_error("rh_dev_alloc: bad arguments"); return RH_E_INVALID; }
-    char *p = nullptr;
-    RH_TRY(dev_alloc(&p, bytes));
-    *d_out = p;
+    rh_dev<char> buf;
+    RH_TRY(buf.alloc(bytes));
+    *d_out = buf.release();   // the caller's from here on: back through rh_dev_free
     return RH_OK;
 }
 
@@ -1312,7 +1240,7 @@ extern "C" int rh_dev_free(rh_cloud *c, void *d)
 {
     RH_TRY(enter(c));
     RH_HIP(hipStreamSynchronize(c->stream));
-    RH_HIP(hipFree(d));
+    RH_HIP(rh_free_callers_block(d));
     return RH_OK;
 }
 

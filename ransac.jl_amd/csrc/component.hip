@@ -198,10 +198,10 @@ int rhk_component_filter(rh_cloud *c, double beta, int conn26, int64_t *n_refit_
     RH_TRY(rh_component_check_beta("component filter", beta));
     if (c->n >= ((int64_t)1 << 31)) { rh_set_error("component filter: clouds of 2^31 points or more are not supported"); return RH_E_INVALID; }
     if (!c->comp_scal) {
-        RH_HIP(hipMalloc((void **)&c->comp_scal, sizeof(uint64_t) * (CS_WORDS + MM_WORDS * GRID_MM_BLOCKS)));
-        RH_HIP(hipHostMalloc((void **)&c->comp_h, sizeof(uint64_t) * CS_WORDS, hipHostMallocDefault));
+        RH_TRY(c->comp_scal.alloc(CS_WORDS + MM_WORDS * GRID_MM_BLOCKS));
+        RH_TRY(c->comp_h.alloc(CS_WORDS));
     }
-    unsigned long long *scal = (unsigned long long *)c->comp_scal;
+    unsigned long long *scal = (unsigned long long *)c->comp_scal.get();
     if (c->nwords == 0) return RH_OK;
     const int64_t stride = c->n_pad;
     {
@@ -227,9 +227,13 @@ int rhk_component_filter(rh_cloud *c, double beta, int conn26, int64_t *n_refit_
     }
     int64_t cap = 64;
     while (cap < 2 * ni) cap <<= 1;
-    if (cap > c->comp_cap) RH_TRY(rh_grow_buffer(c, &c->comp_tab, &c->comp_cap, cap, (size_t)cap * 20));
+    if (cap > c->comp_cap) {
+        c->comp_cap = 0;
+        RH_TRY(c->comp_tab.grow(c->stream, cap * 20));
+        c->comp_cap = cap;
+    }
     comp_table T;
-    T.key = (uint64_t *)c->comp_tab;
+    T.key = (uint64_t *)c->comp_tab.get();
     T.parent = (int32_t *)(T.key + cap);
     T.count = T.parent + cap;
     T.minidx = T.count + cap;
@@ -252,7 +256,7 @@ int rhk_component_stats(rh_cloud *c, int64_t *h_ncomp)
 {
     *h_ncomp = 0;
     if (!c->comp_scal) return RH_OK;
-    RH_HIP(hipMemcpyAsync(h_ncomp, (const uint64_t *)c->comp_scal + CS_NCOMP, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    RH_HIP(hipMemcpyAsync(h_ncomp, c->comp_scal + CS_NCOMP, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     return RH_OK;
 }
 

@@ -47,33 +47,23 @@ Driver::~Driver()
     arena_release(arena);   // null once the result owns it
     if (c && clean && c->drv_cache == nullptr && !rh_opt_on(c, RH_OPT_NO_DRIVER_CACHE)) {
         DriverCache *dc = new DriverCache;
-        dc->win[0] = win[0]; dc->win[1] = win[1];
-        dc->st = st;
-        dc->h_scr = h_scr; dc->h_scr_cap = h_scr_cap;
-        dc->ring = ring;   // (the stream has been waited for above: no block is busy)
+        dc->win[0] = std::move(win[0]); dc->win[1] = std::move(win[1]);
+        dc->st = std::move(st);
+        dc->h_scr = std::move(h_scr);
+        dc->ring = std::move(ring);   // (the stream has been waited for above: no block is busy)
         for (bool &b : dc->ring.busy) b = false;
         c->drv_cache = dc;
         c->drv_cache_free = driver_cache_free;
         return;
     }
-    (void)hipHostFree(h_scr);
-    pin_ring_free(ring);
-    store_free(c, st);
-    for (Window &w : win) window_free(w);
+    pin_ring_wait(ring);   // (the members release the rest)
 }
 
 // pinned scratch of at least `ints` int32 (contents are not preserved when it grows)
 int Driver::ensure_scratch(int64_t ints)
 {
-    if (ints <= h_scr_cap) return RH_OK;
-    RUNH(hipStreamSynchronize(c->stream));
-    (void)hipHostFree(h_scr);
-    h_scr = nullptr;
-    h_scr_cap = 0;
-    const int64_t cap = std::max<int64_t>(ints, 1 << 16);
-    RUNH(hipHostMalloc((void **)&h_scr, sizeof(int32_t) * (size_t)cap));
-    h_scr_cap = cap;
-    return RH_OK;
+    if (ints <= h_scr.count()) return RH_OK;
+    return h_scr.grow(c->stream, std::max<int64_t>(ints, 1 << 16));
 }
 
 int Driver::init()
@@ -89,10 +79,10 @@ int Driver::init()
     if (c->drv_cache != nullptr) {   // the buffers the previous run on this cloud parked
         DriverCache *dc = (DriverCache *)c->drv_cache;
         c->drv_cache = nullptr;
-        win[0] = dc->win[0]; win[1] = dc->win[1];
-        st = dc->st;
-        h_scr = dc->h_scr; h_scr_cap = dc->h_scr_cap;
-        ring = dc->ring;
+        win[0] = std::move(dc->win[0]); win[1] = std::move(dc->win[1]);
+        st = std::move(dc->st);
+        h_scr = std::move(dc->h_scr);
+        ring = std::move(dc->ring);
         delete dc;
         for (int q = 0; q < 4; q++) st.n[q] = 0;
         for (Window &w : win) { w.pending = false; w.scored = false; }
@@ -109,9 +99,9 @@ int Driver::init()
     RUNH(hipStreamSynchronize(c->stream));
     c->n_dis = ndis;
     c->select_valid = false;
-    if (!st.d_nk) RUNH(hipMalloc((void **)&st.d_nk, sizeof(int32_t) * 8));
+    if (!st.d_nk) RUN(st.d_nk.alloc(8));
     if (!st.live) {
-        RUNH(hipMalloc((void **)&st.live, sizeof(int32_t) * (size_t)LIVE_MAX));
+        RUN(st.live.alloc(LIVE_MAX));
         RUNH(hipMemsetAsync(st.live, 0, sizeof(int32_t) * (size_t)LIVE_MAX, c->stream));
     }
     octree = p->octree_sampling != 0;
@@ -269,15 +259,8 @@ int Driver::record(const rh_shape *cands, const int32_t *levels, int32_t ncand, 
         slot_r = ring.next;
         ring.next = (ring.next + 1) & 3;
         if (ring.busy[slot_r]) { RUNH(hipEventSynchronize(ring.ev[slot_r])); ring.busy[slot_r] = false; }
-        if (ring.cap[slot_r] < ncand) {
-            if (ring.buf[slot_r]) (void)hipHostFree(ring.buf[slot_r]);
-            ring.buf[slot_r] = nullptr;
-            ring.cap[slot_r] = 0;
-            const int64_t cap = std::max<int64_t>(2 * (int64_t)ncand, 4096);
-            RUNH(hipHostMalloc((void **)&ring.buf[slot_r], sizeof(rh_prep) * (size_t)cap));
-            ring.cap[slot_r] = cap;
-        }
-        if (!ring.ev[slot_r]) RUNH(hipEventCreateWithFlags(&ring.ev[slot_r], hipEventDisableTiming));
+        if (ring.buf[slot_r].count() < ncand) RUN(ring.buf[slot_r].alloc(std::max<int64_t>(2 * (int64_t)ncand, 4096)));
+        if (!ring.ev[slot_r]) RUN(ring.ev[slot_r].create(hipEventDisableTiming));
         pin = ring.buf[slot_r];
     }
     int64_t poff = 0;

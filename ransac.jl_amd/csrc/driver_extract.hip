@@ -24,22 +24,20 @@ int Driver::prune_managed_store(const size_t extracted_pos, const int64_t sum_n,
         // list is staged in st.d_idx (as long as the store)
         const int64_t best_at = ((2 * nblocks + 16 + 3) / 4) * 4, work_ints = best_at + 4 * nblocks;
         if (st.work_cap < work_ints) {
-            RUNH(hipStreamSynchronize(c->stream));
-            (void)hipFree(st.d_work);
-            st.d_work = nullptr; st.work_cap = 0;
+            st.work_cap = 0;
             const int64_t cap = std::max<int64_t>(2 * work_ints, 4096);
-            RUNH(hipMalloc((void **)&st.d_work, sizeof(int32_t) * (size_t)cap));
+            RUN(st.d_work.grow(c->stream, cap));
             st.work_cap = cap;
         }
         rh_store_best *d_best = (rh_store_best *)(st.d_work + best_at);
         for (int q = 0; q < 4; q++) {
             if (st.n[q] == 0 || (st.spare_cap[q] >= st.cap[q] && st.spare_id[q] != nullptr)) continue;
+            st.spare_cap[q] = 0;
             RUNH(hipStreamSynchronize(c->stream));
-            (void)hipFree(st.spare[q]); (void)hipFree(st.spare_id[q]); (void)hipFree(st.spare_E[q]);
-            st.spare[q] = nullptr; st.spare_id[q] = nullptr; st.spare_E[q] = nullptr; st.spare_cap[q] = 0;
-            RUNH(hipMalloc((void **)&st.spare[q], sizeof(rh_prep) * (size_t)st.cap[q]));
-            RUNH(hipMalloc((void **)&st.spare_id[q], sizeof(int32_t) * (size_t)st.cap[q]));
-            RUNH(hipMalloc((void **)&st.spare_E[q], sizeof(double) * (size_t)st.cap[q]));
+            st.spare[q].reset(); st.spare_id[q].reset(); st.spare_E[q].reset();
+            RUN(st.spare[q].alloc(st.cap[q]));
+            RUN(st.spare_id[q].alloc(st.cap[q]));
+            RUN(st.spare_E[q].alloc(st.cap[q]));
             st.spare_cap[q] = st.cap[q];
         }
         RUNH(hipMemsetAsync(st.counts, 0, sizeof(int32_t) * (size_t)pbase[4], c->stream));
@@ -50,16 +48,17 @@ int Driver::prune_managed_store(const size_t extracted_pos, const int64_t sum_n,
             // the culled binary32-classified kernel of the batch path, over the new entries of the disabled list:
             // its records are made from the stored prepared candidates on the fly
             if (st.cls_cap < pbase[4]) {
+                st.cls_cap = 0;
                 RUNH(hipStreamSynchronize(c->stream));
-                (void)hipFree(st.d_cls); (void)hipFree(st.d_box);
-                st.d_cls = nullptr; st.d_box = nullptr; st.cls_cap = 0;
+                st.d_cls.reset(); st.d_box.reset();
                 const int64_t cap = std::max<int64_t>(2 * (int64_t)pbase[4], 1 << 16);
-                RUNH(hipMalloc(&st.d_cls, 64 * (size_t)cap));
-                RUNH(hipMalloc((void **)&st.d_box, sizeof(float) * 11 * (size_t)cap));
+                RUN(st.d_cls.alloc(64 * cap));
+                RUN(st.d_box.alloc(11 * cap));
                 st.cls_cap = cap;
             }
             RUNH(hipMemcpyAsync(st.d_nk, h_nk, 8 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            RUN(rhk_store_cls(c, st.prep, st.n, pbase, p->eps, p->cos_alpha, st.d_cls, st.d_box, st.cls_cap));
+            const rh_prep *const store_prep[4] = { st.prep[0], st.prep[1], st.prep[2], st.prep[3] };
+            RUN(rhk_store_cls(c, store_prep, st.n, pbase, p->eps, p->cos_alpha, st.d_cls, st.d_box, st.cls_cap));
             // kinds that look at the same stretch of the list go in one launch (faithful-mode spheres look at all of it)
             for (int pass = 0; pass < 2; pass++) {
                 rh_score_job job;   // (every point of the stretch counts: no enabled words)
@@ -309,11 +308,8 @@ int Driver::maybe_extract(int64_t k, bool *did)
         if (alive != st.n[q]) {
             if (alive > 0) {
                 if (st.spare_cap[q] < st.cap[q]) {
-                    RUNH(hipStreamSynchronize(c->stream));
-                    (void)hipFree(st.spare[q]);
-                    st.spare[q] = nullptr;
                     st.spare_cap[q] = 0;
-                    RUNH(hipMalloc((void **)&st.spare[q], sizeof(rh_prep) * (size_t)st.cap[q]));
+                    RUN(st.spare[q].grow(c->stream, st.cap[q]));
                     st.spare_cap[q] = st.cap[q];
                 }
                 RUNH(hipMemcpyAsync(st.d_idx + base[q], lst, sizeof(int32_t) * (size_t)alive, hipMemcpyHostToDevice, c->stream));

@@ -118,32 +118,29 @@ struct Stored {
 
 // device-resident store of prepared candidates, one growable array per kind
 struct DeviceStore {
-    rh_prep *prep[4] = { nullptr, nullptr, nullptr, nullptr };
-    rh_prep *spare[4] = { nullptr, nullptr, nullptr, nullptr };   // compaction target, same capacity
+    rh_dev<rh_prep> prep[4];
+    rh_dev<rh_prep> spare[4];     // compaction target, same capacity
     int64_t spare_cap[4] = { 0, 0, 0, 0 };
     // device-managed mode (chained octree windows): the host's candidate number of every entry, the spare twin, and the
     // scratch of rhk_store_compact
-    int32_t *id[4] = { nullptr, nullptr, nullptr, nullptr };
-    int32_t *spare_id[4] = { nullptr, nullptr, nullptr, nullptr };
-    double *Eb[4] = { nullptr, nullptr, nullptr, nullptr };        // the entries' scores (the compaction finds the best survivor)
-    double *spare_E[4] = { nullptr, nullptr, nullptr, nullptr };
-    int32_t *d_work = nullptr;
+    rh_dev<int32_t> id[4], spare_id[4];
+    rh_dev<double> Eb[4], spare_E[4];   // the entries' scores (the compaction finds the best survivor)
+    rh_dev<int32_t> d_work;
     int64_t work_cap = 0;
-    void *d_cls = nullptr;        // classifier + culling records of the whole store for a liveness pass of the v4 kernel
-    float *d_box = nullptr;       //   (made on the fly by rhk_store_cls), cls_cap entries
+    rh_dev<char> d_cls;           // classifier + culling records of the whole store for a liveness pass of the v4 kernel
+    rh_dev<float> d_box;          //   (made on the fly by rhk_store_cls), cls_cap entries
     int64_t cls_cap = 0;
     int64_t cap[4] = { 0, 0, 0, 0 };
     int32_t n[4] = { 0, 0, 0, 0 };
-    int32_t *iota = nullptr;      // 0..iota_cap-1
+    rh_dev<int32_t> iota;         // 0..iota_cap-1
     int64_t iota_cap = 0;
-    int32_t *counts = nullptr;    // liveness / score counts, iota_cap entries
-    int32_t *live = nullptr;      // LIVE_MAX liveness flags of the one-wait extraction path, zero between uses
-    int32_t *d_idx = nullptr;     // gather lists
-    int32_t *d_nk = nullptr;      // one int per launch slot (8)
+    rh_dev<int32_t> counts;       // liveness / score counts, iota_cap entries
+    rh_dev<int32_t> live;         // LIVE_MAX liveness flags of the one-wait extraction path, zero between uses
+    rh_dev<int32_t> d_idx;        // gather lists
+    rh_dev<int32_t> d_nk;         // one int per launch slot (8)
 };
 
-int store_free(rh_cloud *c, DeviceStore &st);                       // driver_store.hip
-int store_reserve(rh_cloud *c, DeviceStore &st, int kind, int64_t need);
+int store_reserve(rh_cloud *c, DeviceStore &st, int kind, int64_t need);   // driver_store.hip
 int store_reserve_aux(rh_cloud *c, DeviceStore &st, int64_t need);
 void *arena_acquire(size_t bytes);                                   // result arenas (driver_store.hip)
 void arena_release(void *p);
@@ -154,26 +151,39 @@ void arena_release(void *p);
 // a sampled window in flight: device list + status, pinned landing zones, completion event
 constexpr int RH_CHAIN_MAX = 64;   // iterations per chained octree window, at most
 struct Window {
-    rh_cand_entry *d_entries = nullptr, *h_entries = nullptr;   // h_entries: pinned, head of the list
-    int32_t entries_cap = 0;
-    char *d_status = nullptr, *h_status = nullptr;              // int32 count, int32 gave_up, u64 draws[W]
-    int32_t *d_counts = nullptr, *h_counts = nullptr;           // inlier counts per list entry (h: pinned head)
+    rh_dev<rh_cand_entry> d_entries;                            // the list ...
+    rh_pinned<rh_cand_entry> h_entries;                         // ... and its head
+    int32_t entries_cap = 0;                                    // of d_entries and d_counts (window_list_grow)
+    rh_dev<char> d_status;                                      // int32 count, int32 gave_up, u64 draws[W]
+    rh_pinned<char> h_status;
+    rh_dev<int32_t> d_counts;                                   // inlier counts per list entry
+    rh_pinned<int32_t> h_counts;                                // (the head's)
     bool scored = false;                                        // the counts were computed with the window
     // chained octree windows (run_streams_device): pinned state as uploaded, per-iteration headers + events, and pinned
     // twins of the whole list and its counts (every iteration's slice lands at its list positions)
-    rh_oct_state *h_ost = nullptr;
-    rh_oct_iter_hdr *h_hdr = nullptr;
-    rh_cand_entry *h_list = nullptr;
-    int32_t *h_list_counts = nullptr, *h_list_rank = nullptr, *h_list_slot = nullptr;
-    int32_t h_list_cap = 0;
-    hipEvent_t ev_it[RH_CHAIN_MAX] = {};
-    hipEvent_t ev = nullptr;
+    rh_pinned<rh_oct_state> h_ost;
+    rh_pinned<rh_oct_iter_hdr> h_hdr;
+    rh_pinned<rh_cand_entry> h_list;
+    rh_pinned<int32_t> h_list_counts, h_list_rank, h_list_slot;   // (as long as h_list)
+    rh_event ev_it[RH_CHAIN_MAX];
+    rh_event ev;
     int64_t k = 0;
     int32_t W = 0;
     bool pending = false;
 };
 
-void window_free(Window &w);
+// the one way a window's list grows: d_entries / d_counts of `cap` entries after a wait for `stream`, the cloud's (contents
+// are not kept); entries_cap says so last, so it never promises more than there is
+inline int window_list_grow(hipStream_t stream, Window &w, int64_t cap)
+{
+    w.entries_cap = 0;
+    RH_HIP(hipStreamSynchronize(stream));
+    w.d_entries.reset(); w.d_counts.reset();
+    RH_TRY(w.d_entries.alloc(cap));
+    RH_TRY(w.d_counts.alloc(cap));
+    w.entries_cap = (int32_t)cap;
+    return RH_OK;
+}
 
 // What a run allocates and the next run on the same cloud can use again (two windows, the device store, the
 // pinned scratch: a dozen hipMalloc / hipHostMalloc / hipFree pairs, ~3 ms per call): parked on the cloud
@@ -183,20 +193,18 @@ void window_free(Window &w);
 // ring of four, each guarded by an event -- a copy from pageable memory is a blocking staged copy inside the runtime
 // (~15 us per call, three calls per octree window)
 struct PinRing {
-    rh_prep *buf[4] = { nullptr, nullptr, nullptr, nullptr };
-    int64_t cap[4] = { 0, 0, 0, 0 };
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    rh_pinned<rh_prep> buf[4];
+    rh_event ev[4];
     bool busy[4] = { false, false, false, false };
     int next = 0;
 };
 
-void pin_ring_free(PinRing &r);
+void pin_ring_wait(PinRing &r);   // for the blocks still busy: before the ring goes
 
 struct DriverCache {
     Window win[2];
     DeviceStore st;
-    int32_t *h_scr = nullptr;
-    int64_t h_scr_cap = 0;
+    rh_pinned<int32_t> h_scr;
     PinRing ring;
 };
 
@@ -260,8 +268,7 @@ struct Driver {
     Window win[2];
     static constexpr int32_t ENTRIES_HEAD = 4096;   // list entries that travel with the window (pack_window_kernel copies min(count, this))
 
-    int32_t *h_scr = nullptr;           // pinned scratch: scalars read back, liveness counts, gather lists
-    int64_t h_scr_cap = 0;              // in int32
+    rh_pinned<int32_t> h_scr;           // pinned scratch: scalars read back, liveness counts, gather lists
     int64_t *arena = nullptr;           // pinned block for the extracted index lists (result arenas, above)
     int64_t arena_used = 0, arena_cap = 0;
     bool list_copy_pending = false;     // a list is (or may still be) on its way from idx_out to the arena

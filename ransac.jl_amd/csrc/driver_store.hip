@@ -1,36 +1,25 @@
-// driver_store.hip -- lifetimes of what a run of rh_ransac allocates: the device store of prepared candidates, the
-// sampled windows, the pinned staging ring, the buffers parked on the cloud between runs, and the result arenas
+// driver_store.hip -- how what a run of rh_ransac allocates grows and goes: the device store of prepared candidates, the
+// windows' lists, the pinned staging ring, the buffers parked on the cloud between runs, and the result arenas
 #include "driver_internal.h"
 
 namespace rhdrv {
-
-int store_free(rh_cloud *c, DeviceStore &st)
-{
-    (void)hipStreamSynchronize(c->stream);
-    for (int k = 0; k < 4; k++) { (void)hipFree(st.prep[k]); (void)hipFree(st.spare[k]); (void)hipFree(st.id[k]); (void)hipFree(st.spare_id[k]);
-                                  (void)hipFree(st.Eb[k]); (void)hipFree(st.spare_E[k]); }
-    (void)hipFree(st.d_work); (void)hipFree(st.d_cls); (void)hipFree(st.d_box);
-    (void)hipFree(st.iota); (void)hipFree(st.counts); (void)hipFree(st.d_idx); (void)hipFree(st.d_nk);
-    (void)hipFree(st.live);
-    return RH_OK;
-}
 
 int store_reserve(rh_cloud *c, DeviceStore &st, int kind, int64_t need)
 {
     if (need <= st.cap[kind]) {
         if (st.id[kind] == nullptr && st.cap[kind] > 0) {   // (a store parked by a run that kept no ids)
-            RH_HIP(hipMalloc((void **)&st.id[kind], sizeof(int32_t) * (size_t)st.cap[kind]));
-            RH_HIP(hipMalloc((void **)&st.Eb[kind], sizeof(double) * (size_t)st.cap[kind]));
+            RH_TRY(st.id[kind].alloc(st.cap[kind]));
+            RH_TRY(st.Eb[kind].alloc(st.cap[kind]));
         }
         return RH_OK;
     }
     const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(4096, st.cap[kind] * 2));
-    rh_prep *np = nullptr;
-    int32_t *ni = nullptr;
-    RH_HIP(hipMalloc((void **)&np, sizeof(rh_prep) * (size_t)cap));
-    double *ne = nullptr;
-    RH_HIP(hipMalloc((void **)&ni, sizeof(int32_t) * (size_t)cap));
-    RH_HIP(hipMalloc((void **)&ne, sizeof(double) * (size_t)cap));
+    rh_dev<rh_prep> np;   // (local owners: a failure below loses nothing and leaves the store as it was)
+    rh_dev<int32_t> ni;
+    rh_dev<double> ne;
+    RH_TRY(np.alloc(cap));
+    RH_TRY(ni.alloc(cap));
+    RH_TRY(ne.alloc(cap));
     if (st.n[kind] > 0) {
         RH_HIP(hipMemcpyAsync(np, st.prep[kind], sizeof(rh_prep) * (size_t)st.n[kind], hipMemcpyDeviceToDevice, c->stream));
         if (st.id[kind] != nullptr) {
@@ -39,12 +28,9 @@ int store_reserve(rh_cloud *c, DeviceStore &st, int kind, int64_t need)
         }
     }
     RH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(st.prep[kind]);
-    (void)hipFree(st.id[kind]);
-    (void)hipFree(st.Eb[kind]);
-    st.prep[kind] = np;
-    st.id[kind] = ni;
-    st.Eb[kind] = ne;
+    st.prep[kind] = std::move(np);
+    st.id[kind] = std::move(ni);
+    st.Eb[kind] = std::move(ne);
     st.cap[kind] = cap;
     return RH_OK;
 }
@@ -53,12 +39,12 @@ int store_reserve_aux(rh_cloud *c, DeviceStore &st, int64_t need)
 {
     if (need <= st.iota_cap) return RH_OK;
     const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(4096, st.iota_cap * 2));
+    st.iota_cap = 0;
     RH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(st.iota); (void)hipFree(st.counts); (void)hipFree(st.d_idx);
-    st.iota = st.counts = st.d_idx = nullptr;
-    RH_HIP(hipMalloc((void **)&st.iota, sizeof(int32_t) * (size_t)cap));
-    RH_HIP(hipMalloc((void **)&st.counts, sizeof(int32_t) * (size_t)cap));
-    RH_HIP(hipMalloc((void **)&st.d_idx, sizeof(int32_t) * (size_t)cap));
+    st.iota.reset(); st.counts.reset(); st.d_idx.reset();
+    RH_TRY(st.iota.alloc(cap));
+    RH_TRY(st.counts.alloc(cap));
+    RH_TRY(st.d_idx.alloc(cap));
     RH_TRY(rhk_iota(c, st.iota, (int32_t)cap, 0));
     st.iota_cap = cap;
     return RH_OK;
@@ -106,35 +92,21 @@ void arena_release(void *p)
     }
 }
 
-void window_free(Window &w)
-{
-    (void)hipFree(w.d_entries); (void)hipFree(w.d_status); (void)hipFree(w.d_counts);
-    (void)hipHostFree(w.h_status); (void)hipHostFree(w.h_entries); (void)hipHostFree(w.h_counts);
-    (void)hipHostFree(w.h_ost); (void)hipHostFree(w.h_hdr); (void)hipHostFree(w.h_list); (void)hipHostFree(w.h_list_counts);
-    (void)hipHostFree(w.h_list_rank); (void)hipHostFree(w.h_list_slot);
-    for (hipEvent_t e : w.ev_it) if (e) (void)hipEventDestroy(e);
-    if (w.ev) (void)hipEventDestroy(w.ev);
-    w = Window();
-}
-
-void pin_ring_free(PinRing &r)
+void pin_ring_wait(PinRing &r)
 {
     for (int i = 0; i < 4; i++) {
         if (r.busy[i] && r.ev[i]) (void)hipEventSynchronize(r.ev[i]);
-        if (r.buf[i]) (void)hipHostFree(r.buf[i]);
-        if (r.ev[i]) (void)hipEventDestroy(r.ev[i]);
-        r.buf[i] = nullptr; r.cap[i] = 0; r.ev[i] = nullptr; r.busy[i] = false;
+        r.busy[i] = false;
     }
 }
 
+// the buffers a run parked on the cloud (cloud_free, while c->stream is valid): the waits, then everything goes with the struct
 void driver_cache_free(rh_cloud *c, void *p)
 {
     DriverCache *dc = (DriverCache *)p;
     if (!dc) return;
-    (void)hipHostFree(dc->h_scr);
-    pin_ring_free(dc->ring);
-    store_free(c, dc->st);
-    for (Window &w : dc->win) window_free(w);
+    pin_ring_wait(dc->ring);
+    (void)hipStreamSynchronize(c->stream);
     delete dc;
 }
 

@@ -31,22 +31,20 @@ int Driver::run_chained_windows(const size_t status_bytes)
     const int T = p->n_shape_types;
     int64_t Kchain = 8;
     if (const int64_t e = rh_opt_int(c, RH_OPT_OCT_CHAIN_W, 0)) Kchain = std::max<int64_t>(1, std::min<int64_t>(e, RH_CHAIN_MAX));
-    if (c->oct_state == nullptr) RUNH(hipMalloc((void **)&c->oct_state, sizeof(rh_oct_state)));
+    if (c->oct_state == nullptr) RUN(c->oct_state.alloc(1));
     managed = !rh_opt_on(c, RH_OPT_NO_MANAGED_STORE);   // (the store is empty here: run_streams_device is where a run starts)
     auto ensure_pinned = [&](Window &w) -> int {
         if (w.h_ost == nullptr) {
-            RUNH(hipHostMalloc((void **)&w.h_ost, sizeof(rh_oct_state)));
-            RUNH(hipHostMalloc((void **)&w.h_hdr, sizeof(rh_oct_iter_hdr) * RH_CHAIN_MAX));
-            for (hipEvent_t &e : w.ev_it) RUNH(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            RUN(w.h_ost.alloc(1));
+            RUN(w.h_hdr.alloc(RH_CHAIN_MAX));
+            for (rh_event &e : w.ev_it) RUN(e.create(hipEventDisableTiming));
         }
-        if (w.h_list_cap < w.entries_cap) {
-            (void)hipHostFree(w.h_list); (void)hipHostFree(w.h_list_counts); (void)hipHostFree(w.h_list_rank); (void)hipHostFree(w.h_list_slot);
-            w.h_list = nullptr; w.h_list_counts = w.h_list_rank = w.h_list_slot = nullptr; w.h_list_cap = 0;
-            RUNH(hipHostMalloc((void **)&w.h_list, sizeof(rh_cand_entry) * (size_t)w.entries_cap));
-            RUNH(hipHostMalloc((void **)&w.h_list_counts, sizeof(int32_t) * (size_t)w.entries_cap));
-            RUNH(hipHostMalloc((void **)&w.h_list_rank, sizeof(int32_t) * (size_t)w.entries_cap));
-            RUNH(hipHostMalloc((void **)&w.h_list_slot, sizeof(int32_t) * (size_t)w.entries_cap));
-            w.h_list_cap = w.entries_cap;
+        if (w.h_list_slot.count() < w.entries_cap) {   // the pinned twins of the list (the last of the four says how long they are)
+            w.h_list.reset(); w.h_list_counts.reset(); w.h_list_rank.reset(); w.h_list_slot.reset();
+            RUN(w.h_list.alloc(w.entries_cap));
+            RUN(w.h_list_counts.alloc(w.entries_cap));
+            RUN(w.h_list_rank.alloc(w.entries_cap));
+            RUN(w.h_list_slot.alloc(w.entries_cap));
         }
         return RH_OK;
     };
@@ -62,14 +60,7 @@ int Driver::run_chained_windows(const size_t status_bytes)
     // returns at once (stop flag) or is simply not replayed, and the next window starts from the host's state.
     auto enqueue = [&](Window &w, int64_t k0, int32_t W, bool upload, int64_t ahead) -> int {
         // one iteration's candidates must fit the list (a longer list is only a matter of how far a window gets)
-        if (w.entries_cap < per_it + per_it / 4) {
-            RUNH(hipStreamSynchronize(c->stream));
-            (void)hipFree(w.d_entries); (void)hipFree(w.d_counts);
-            w.d_entries = nullptr; w.d_counts = nullptr;
-            w.entries_cap = per_it + per_it / 4;
-            RUNH(hipMalloc((void **)&w.d_entries, sizeof(rh_cand_entry) * (size_t)w.entries_cap));
-            RUNH(hipMalloc((void **)&w.d_counts, sizeof(int32_t) * (size_t)w.entries_cap));
-        }
+        if (w.entries_cap < per_it + per_it / 4) RUN(window_list_grow(c->stream, w, per_it + per_it / 4));
         RUN(ensure_pinned(w));
         if (upload) {
             rh_oct_state &h = *w.h_ost;
@@ -105,7 +96,7 @@ int Driver::run_chained_windows(const size_t status_bytes)
         for (int32_t it = 0; it < W && rc == RH_OK; it++) {
             rc = rhk_sample_fit(c, p, rng->s[0], k0 + it, 1, (int32_t)en.count, c->oct_state->P, w.d_entries, w.entries_cap, w.d_status, 1,
                                 c->d_nk, it, c->oct_state);
-            if (rc == RH_OK) rc = rhk_prep_entries(c, ws, w.d_entries, (const int32_t *)w.d_status, w.entries_cap, per_it, w.d_counts, 1, p->eps,
+            if (rc == RH_OK) rc = rhk_prep_entries(c, ws, w.d_entries, (const int32_t *)w.d_status.get(), w.entries_cap, per_it, w.d_counts, 1, p->eps,
                                                    p->cos_alpha, c->oct_state);
             if (rc == RH_OK) rc = rhk_score4_all(c, ws, job);
             if (rc == RH_OK) rc = rhk_oct_advance(c, p, c->oct_state, w.d_entries, w.d_status, w.entries_cap, w.d_counts, it, k0 + it, w.h_list,
@@ -207,16 +198,8 @@ int Driver::run_chained_windows(const size_t status_bytes)
             k_enq = k;
             need_upload = true;
         }
-        if (regrow) {
-            RUNH(hipStreamSynchronize(c->stream));
-            for (Window &g : win) {
-                (void)hipFree(g.d_entries); (void)hipFree(g.d_counts);
-                g.d_entries = nullptr; g.d_counts = nullptr;
-                g.entries_cap *= 2;
-                RUNH(hipMalloc((void **)&g.d_entries, sizeof(rh_cand_entry) * (size_t)g.entries_cap));
-                RUNH(hipMalloc((void **)&g.d_counts, sizeof(int32_t) * (size_t)g.entries_cap));
-            }
-        }
+        if (regrow)
+            for (Window &g : win) RUN(window_list_grow(c->stream, g, 2 * (int64_t)g.entries_cap));
         if (stop) break;
     }
     // the tail of a window that was cut short may still be in the queue; the status blocks go back zeroed
@@ -242,15 +225,13 @@ int Driver::run_streams_device()
     const size_t status_bytes = (8 + sizeof(unsigned long long) * (size_t)512 + 63) / 64 * 64;
     for (Window &w : win) {
         if (w.d_status != nullptr) continue;   // parked by the previous run
-        RUNH(hipMalloc((void **)&w.d_status, status_bytes));
+        RUN(w.d_status.alloc((int64_t)status_bytes));
         RUNH(hipMemsetAsync(w.d_status, 0, status_bytes, c->stream));   // kept zero by pack_window_kernel from here on
-        RUNH(hipHostMalloc((void **)&w.h_status, status_bytes));
-        RUNH(hipHostMalloc((void **)&w.h_entries, sizeof(rh_cand_entry) * (size_t)ENTRIES_HEAD));
-        w.entries_cap = 1 << 16;
-        RUNH(hipMalloc((void **)&w.d_entries, sizeof(rh_cand_entry) * (size_t)w.entries_cap));
-        RUNH(hipMalloc((void **)&w.d_counts, sizeof(int32_t) * (size_t)w.entries_cap));
-        RUNH(hipHostMalloc((void **)&w.h_counts, sizeof(int32_t) * (size_t)ENTRIES_HEAD));
-        RUNH(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+        RUN(w.h_status.alloc((int64_t)status_bytes));
+        RUN(w.h_entries.alloc(ENTRIES_HEAD));
+        RUN(window_list_grow(c->stream, w, 1 << 16));
+        RUN(w.h_counts.alloc(ENTRIES_HEAD));
+        RUN(w.ev.create(hipEventDisableTiming));
     }
     // With the culled score kernel (it takes its candidate counts from device memory) the window's
     // candidates are scored on the device right after they are fitted, in the same stream: the
@@ -282,13 +263,7 @@ int Driver::run_streams_device()
                 for (int i = 0; i < od; i++) Pwin[(size_t)it * od + i] = Pw[i];
                 rhfit::update_level_probs(Pw, oS, od);
             }
-            if ((int64_t)Pwin.size() > c->oct_P_cap) {
-                RUNH(hipStreamSynchronize(c->stream));
-                (void)hipFree(c->oct_P);
-                c->oct_P = nullptr;
-                c->oct_P_cap = (int64_t)K * 32;
-                RUNH(hipMalloc((void **)&c->oct_P, sizeof(double) * (size_t)c->oct_P_cap));
-            }
+            RUN(rh_ensure_oct_P(c, (int64_t)Pwin.size(), (int64_t)K * 32));
             RUNH(hipMemcpyAsync(c->oct_P, Pwin.data(), sizeof(double) * Pwin.size(), hipMemcpyHostToDevice, c->stream));
             d_P = c->oct_P;
         }
@@ -301,7 +276,7 @@ int Driver::run_streams_device()
             // launch sizes from the previous windows' list lengths; any length is handled (the
             // kernels read the true count), a longer list only gets fewer blocks per candidate
             const int32_t bound = std::min<int32_t>(w.entries_cap, std::max<int32_t>(4 * cnt_est, 1024));
-            RUN(rhk_prep_entries(c, ws, w.d_entries, (const int32_t *)w.d_status, w.entries_cap, w.entries_cap, w.d_counts, 1, p->eps, p->cos_alpha));
+            RUN(rhk_prep_entries(c, ws, w.d_entries, (const int32_t *)w.d_status.get(), w.entries_cap, w.entries_cap, w.d_counts, 1, p->eps, p->cos_alpha));
             RUN(rhk_score4_all(c, ws, window_score_job(c, ws, p, bound, w.d_counts)));
             w.scored = true;
         }
@@ -340,20 +315,13 @@ int Driver::run_streams_device()
         tw[1] += now_s() - tw0;
         nwin++;
         A.pending = false;
-        int32_t cnt = ((const int32_t *)A.h_status)[0];
-        const int32_t gave_up = ((const int32_t *)A.h_status)[1];
+        int32_t cnt = ((const int32_t *)A.h_status.get())[0];
+        const int32_t gave_up = ((const int32_t *)A.h_status.get())[1];
         const unsigned long long *draws = (const unsigned long long *)(A.h_status + 8);
         if (gave_up && mp == nullptr) { rh_set_error("rh_ransac: sampling did not find an enabled point"); return RH_E_INTERNAL; }
         if (cnt > A.entries_cap && mp == nullptr) {   // the list overflowed: grow it and draw the window again
-            RUNH(hipStreamSynchronize(c->stream));
             B.pending = false;
-            (void)hipFree(A.d_entries);
-            A.d_entries = nullptr;
-            A.entries_cap = cnt + cnt / 4;
-            RUNH(hipMalloc((void **)&A.d_entries, sizeof(rh_cand_entry) * (size_t)A.entries_cap));
-            (void)hipFree(A.d_counts);
-            A.d_counts = nullptr;
-            RUNH(hipMalloc((void **)&A.d_counts, sizeof(int32_t) * (size_t)A.entries_cap));
+            RUN(window_list_grow(c->stream, A, cnt + cnt / 4));
             t_sample += now_s() - t0;
             continue;
         }
@@ -408,15 +376,7 @@ int Driver::run_streams_device()
             if (any_overflow) {   // some rank's list overflowed: it grows, and everybody draws the window again
                 RUNH(hipStreamSynchronize(c->stream));
                 B.pending = false;
-                if (overflow) {
-                    (void)hipFree(A.d_entries);
-                    A.d_entries = nullptr;
-                    A.entries_cap = cnt_est + cnt_est / 4;
-                    RUNH(hipMalloc((void **)&A.d_entries, sizeof(rh_cand_entry) * (size_t)A.entries_cap));
-                    (void)hipFree(A.d_counts);
-                    A.d_counts = nullptr;
-                    RUNH(hipMalloc((void **)&A.d_counts, sizeof(int32_t) * (size_t)A.entries_cap));
-                }
+                if (overflow) RUN(window_list_grow(c->stream, A, cnt_est + cnt_est / 4));
                 t_sample += now_s() - t0;
                 continue;
             }

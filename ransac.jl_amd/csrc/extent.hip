@@ -393,9 +393,12 @@ int extents_enqueue(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const int6
 {
     const int64_t nchunks = total / EXT_CHUNK + b;
     if (nchunks > 0x7FFFFFFF) { rh_set_error("rh_shape_extents: %lld list entries are more than one call takes", (long long)total); return RH_E_INVALID; }
-    if (!c->ext_flag) RH_HIP(hipMalloc((void **)&c->ext_flag, 64));
-    if (nchunks > c->ext_part_rows)
-        RH_TRY(rh_grow_buffer(c, (void **)&c->ext_part, &c->ext_part_rows, nchunks, sizeof(double) * EXT_ROW * (size_t)nchunks));
+    if (!c->ext_flag) RH_TRY(c->ext_flag.alloc(16));
+    if (nchunks > c->ext_part_rows) {
+        c->ext_part_rows = 0;
+        RH_TRY(c->ext_part.grow(c->stream, (int64_t)EXT_ROW * nchunks));
+        c->ext_part_rows = nchunks;
+    }
     RH_HIP(hipMemsetAsync(c->ext_flag, 0, sizeof(int32_t), c->stream));
     ext_job J;
     J.shapes = d_shapes; J.off = d_off; J.idx = d_idx; J.out = d_out;
@@ -419,9 +422,9 @@ int extents_host(rh_cloud *c, const char *who, const rh_shape *shapes, size_t sh
     const int64_t total = offsets[b];
     const size_t o_shapes = 0, o_off = up16(sizeof(rh_shape) * (size_t)b), o_out = o_off + up16(sizeof(int64_t) * (size_t)(b + 1)),
                  o_idx = o_out + up16(sizeof(rh_extent) * (size_t)b), bytes = o_idx + sizeof(int64_t) * (size_t)total;
-    if ((int64_t)bytes > c->ext_in_bytes) RH_TRY(rh_grow_buffer(c, &c->ext_in, &c->ext_in_bytes, (int64_t)bytes, bytes));
+    if ((int64_t)bytes > c->ext_in.count()) RH_TRY(c->ext_in.grow(c->stream, (int64_t)bytes));
     RH_TRY(rh_ensure_pin(c, (int64_t)(o_idx + 16)));
-    char *h = (char *)c->h_pin, *d = (char *)c->ext_in;
+    char *h = c->h_pin, *d = c->ext_in;
     for (int32_t j = 0; j < b; j++)
         memcpy(h + o_shapes + sizeof(rh_shape) * (size_t)j, (const char *)shapes + shape_stride * (size_t)j, sizeof(rh_shape));
     memcpy(h + o_off, offsets, sizeof(int64_t) * (size_t)(b + 1));

@@ -218,18 +218,15 @@ int rhk_cloud_aabb(rh_cloud *c, const double *d_xyz, int64_t n, double lo[3], do
     for (int k = 0; k < 3; k++) { lo[k] = hi[k] = 0; has[k] = false; }
     *mag = 0;
     if (n <= 0) return RH_OK;
-    unsigned long long *d = nullptr, h[7];
-    RH_HIP(hipMalloc((void **)&d, sizeof h));
+    unsigned long long h[7];
+    rh_dev<unsigned long long> d;
+    RH_TRY(d.alloc(7));
     for (int k = 0; k < 7; k++) h[k] = k < 3 ? ~0ULL : 0ULL;
-    hipError_t e = hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(aabb_kernel, dim3((unsigned)std::min<int64_t>(4096, (n + 255) / 256)), dim3(256), 0, c->stream, d_xyz, n, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) { rh_set_error("rhk_cloud_aabb: %s", hipGetErrorString(e)); return RH_E_NODEVICE; }
+    RH_HIP(hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(aabb_kernel, dim3((unsigned)std::min<int64_t>(4096, (n + 255) / 256)), dim3(256), 0, c->stream, d_xyz, n, d.get());
+    RH_HIP(hipGetLastError());
+    RH_HIP(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    RH_HIP(hipStreamSynchronize(c->stream));
     auto un = [](unsigned long long u) { const unsigned long long b = (u >> 63) ? (u & 0x7fffffffffffffffULL) : ~u; return __builtin_bit_cast(double, b); };
     for (int k = 0; k < 3; k++) {
         has[k] = h[k] <= h[3 + k];
@@ -246,20 +243,14 @@ int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const in
     const int64_t s = c->s;
     if (s <= 0) return RH_OK;
     if (s > (int64_t)0x7fffffff) { rh_set_error("rhk_kd_order: subset of %lld points", (long long)s); return RH_E_INVALID; }
-    float *pf = nullptr;
-    int32_t *ord[2] = { nullptr, nullptr };
-    uint64_t *keys[2] = { nullptr, nullptr };
-    uint32_t *box = nullptr;
-    int32_t *seg_lo = nullptr;
-    uint8_t *seg_act = nullptr;
-    unsigned long long *mags = nullptr;
-    void *tmp = nullptr;
+    rh_dev<float> pf;   // (temporaries of the call: gone on every way out)
+    rh_dev<int32_t> ord[2], seg_lo;
+    rh_dev<uint64_t> keys[2];
+    rh_dev<uint32_t> box;
+    rh_dev<uint8_t> seg_act;
+    rh_dev<unsigned long long> mags;
+    rh_dev<char> tmp;
     size_t tmp_bytes = 0;
-    auto cleanup = [&]() {
-        (void)hipFree(pf); (void)hipFree(ord[0]); (void)hipFree(ord[1]); (void)hipFree(keys[0]); (void)hipFree(keys[1]); (void)hipFree(box);
-        (void)hipFree(seg_lo); (void)hipFree(seg_act); (void)hipFree(mags); (void)hipFree(tmp);
-    };
-#define QH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rh_set_error("%s: %s", #x, hipGetErrorString(e_)); cleanup(); return RH_E_NODEVICE; } } while (0)
     // the levels: every node of a level in position order, finished ones (<= 64 points) included
     std::vector<std::vector<KdNode>> levels;
     {
@@ -283,20 +274,20 @@ int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const in
     }
     size_t max_seg = 1;
     for (const auto &lv : levels) max_seg = std::max(max_seg, lv.size());
-    QH(hipMalloc((void **)&pf, sizeof(float) * 3 * (size_t)s));
-    QH(hipMalloc((void **)&ord[0], sizeof(int32_t) * (size_t)s));
-    QH(hipMalloc((void **)&ord[1], sizeof(int32_t) * (size_t)s));
-    QH(hipMalloc((void **)&keys[0], sizeof(uint64_t) * (size_t)s));
-    QH(hipMalloc((void **)&keys[1], sizeof(uint64_t) * (size_t)s));
-    QH(hipMalloc((void **)&box, sizeof(uint32_t) * 6 * max_seg));
-    QH(hipMalloc((void **)&mags, sizeof(unsigned long long) * 2));
-    QH(hipMemsetAsync(mags, 0, sizeof(unsigned long long) * 2, c->stream));
+    RH_TRY(pf.alloc(3 * s));
+    RH_TRY(ord[0].alloc(s));
+    RH_TRY(ord[1].alloc(s));
+    RH_TRY(keys[0].alloc(s));
+    RH_TRY(keys[1].alloc(s));
+    RH_TRY(box.alloc(6 * (int64_t)max_seg));
+    RH_TRY(mags.alloc(2));
+    RH_HIP(hipMemsetAsync(mags, 0, sizeof(unsigned long long) * 2, c->stream));
     float *px = pf, *py = pf + s, *pz = pf + 2 * s;
     const dim3 gs(cdivq(s, 256)), blk(256);
     hipLaunchKernelGGL(kd_gather_kernel, gs, blk, 0, c->stream, d_xyz, d_nrm, d_idx0, s, px, py, pz, ord[0], mags);
-    QH(hipGetLastError());
-    QH(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys[0], keys[1], ord[0], ord[1], (int)s, 0, 64, c->stream));
-    QH(hipMalloc(&tmp, tmp_bytes > 0 ? tmp_bytes : 1));
+    RH_HIP(hipGetLastError());
+    RH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys[0].get(), keys[1].get(), ord[0].get(), ord[1].get(), (int)s, 0, 64, c->stream));
+    RH_TRY(tmp.alloc((int64_t)tmp_bytes));
     // every level's node starts / flags, uploaded once (pageable source: the arrays live until the final wait)
     std::vector<int32_t> h_lo;
     std::vector<uint8_t> h_act;
@@ -307,12 +298,10 @@ int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const in
         for (const KdNode &nd : lv) { h_lo.push_back(nd.lo); h_act.push_back(nd.hi - nd.lo > 64 ? 1 : 0); }
         h_lo.push_back((int32_t)s);
     }
-    (void)hipFree(seg_lo); (void)hipFree(seg_act);
-    seg_lo = nullptr; seg_act = nullptr;
-    QH(hipMalloc((void **)&seg_lo, sizeof(int32_t) * std::max<size_t>(h_lo.size(), 1)));
-    QH(hipMalloc((void **)&seg_act, std::max<size_t>(h_act.size(), 1)));
-    if (!h_lo.empty()) QH(hipMemcpyAsync(seg_lo, h_lo.data(), sizeof(int32_t) * h_lo.size(), hipMemcpyHostToDevice, c->stream));
-    if (!h_act.empty()) QH(hipMemcpyAsync(seg_act, h_act.data(), h_act.size(), hipMemcpyHostToDevice, c->stream));
+    RH_TRY(seg_lo.alloc((int64_t)h_lo.size()));
+    RH_TRY(seg_act.alloc((int64_t)h_act.size()));
+    if (!h_lo.empty()) RH_HIP(hipMemcpyAsync(seg_lo, h_lo.data(), sizeof(int32_t) * h_lo.size(), hipMemcpyHostToDevice, c->stream));
+    if (!h_act.empty()) RH_HIP(hipMemcpyAsync(seg_act, h_act.data(), h_act.size(), hipMemcpyHostToDevice, c->stream));
     int cur = 0;
     for (size_t L = 0; L < levels.size(); L++) {
         const int nseg = (int)levels[L].size();
@@ -321,20 +310,18 @@ int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const in
         hipLaunchKernelGGL(kd_fill_box_kernel, dim3(cdivq((int64_t)nseg * 6, 256)), blk, 0, c->stream, box, nseg);
         hipLaunchKernelGGL(kd_box_kernel, gs, blk, 0, c->stream, px, py, pz, ord[cur], s, lo_l, act_l, nseg, box);
         hipLaunchKernelGGL(kd_key_kernel, gs, blk, 0, c->stream, px, py, pz, ord[cur], s, lo_l, act_l, nseg, box, keys[0]);
-        QH(hipGetLastError());
+        RH_HIP(hipGetLastError());
         int seg_bits = 1;
         while ((1 << seg_bits) < nseg) seg_bits++;
-        QH(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys[0], keys[1], ord[cur], ord[cur ^ 1], (int)s, 0, 32 + seg_bits, c->stream));
+        RH_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(), tmp_bytes, keys[0].get(), keys[1].get(), ord[cur].get(), ord[cur ^ 1].get(), (int)s, 0, 32 + seg_bits, c->stream));
         cur ^= 1;
     }
     hipLaunchKernelGGL(kd_finish_kernel, gs, blk, 0, c->stream, ord[cur], d_idx0, s, c->sub_perm, c->sub_idx0);
-    QH(hipGetLastError());
+    RH_HIP(hipGetLastError());
     unsigned long long h_mags[2] = { 0, 0 };
-    QH(hipMemcpyAsync(h_mags, mags, sizeof h_mags, hipMemcpyDeviceToHost, c->stream));
-    QH(hipStreamSynchronize(c->stream));
-#undef QH
+    RH_HIP(hipMemcpyAsync(h_mags, mags, sizeof h_mags, hipMemcpyDeviceToHost, c->stream));
+    RH_HIP(hipStreamSynchronize(c->stream));
     c->coord_mag = __builtin_bit_cast(double, h_mags[0]);
     c->nrm_mag = __builtin_bit_cast(double, h_mags[1]);
-    cleanup();
     return RH_OK;
 }

@@ -935,7 +935,19 @@ int rhk_prep_sorted(rh_cloud *c, rh_batch_ws &w, int32_t b, int32_t *d_counts_to
     const PreArgs QA = pre_args(c, w, both ? eps : nullptr, both ? cosa : nullptr);
     if (b == 0) return RH_OK;
     hipLaunchKernelGGL(prep_sorted_kernel, dim3(cdiv(b, 256)), dim3(256), 0, c->stream, (const rh_shape *)w.d_shapes, b, w.d_prep,
-                       d_counts_to_zero, w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre : (rh4::rh_cls *)nullptr, QA);
+                       d_counts_to_zero, w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre.get() : (rh4::rh_cls *)nullptr, QA);
+    RH_HIP(hipGetLastError());
+    return RH_OK;
+}
+
+// the records alone of shapes that are binned nowhere (rh_cloud_assign: assign.hip): no workspace, no classifier records
+int rhk_prep_records(rh_cloud *c, const rh_shape *d_shapes, int32_t b, rh_prep *d_prep)
+{
+    rh_batch_ws none;
+    const PreArgs QA = pre_args(c, none, nullptr, nullptr);
+    if (b == 0) return RH_OK;
+    hipLaunchKernelGGL(prep_sorted_kernel, dim3(cdiv(b, 256)), dim3(256), 0, c->stream, d_shapes, b, d_prep, (int32_t *)nullptr,
+                       (rh4::rh_cls *)nullptr, QA);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
@@ -950,7 +962,7 @@ int rhk_prep_entries(rh_cloud *c, rh_batch_ws &w, const rh_cand_entry *d_entries
     if (launch_bound <= 0) return RH_OK;
     hipLaunchKernelGGL(prep_entries_kernel, dim3(cdiv(launch_bound, 256)), dim3(256), 0, c->stream, d_entries, d_count,
                        cap_entries, w.d_prep, w.d_orig, c->d_nk, w.batch_cap, d_counts,
-                       w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre : (rh4::rh_cls *)nullptr, QA, ost);
+                       w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre.get() : (rh4::rh_cls *)nullptr, QA, ost);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
@@ -977,7 +989,7 @@ int rhk_prep_binned(rh_cloud *c, rh_batch_ws &w, const rh_shape *d_shapes, int32
 #endif
     hipLaunchKernelGGL(prep_binned_kernel, dim3(cdiv(b, RH_PREP_BLOCK)), dim3(RH_PREP_BLOCK), 0, c->stream, d_shapes, b, w.d_prep, w.d_orig,
                        d_nk, w.batch_cap, d_counts_to_zero, d_nk_other, no_spread ? 1 : rh_spread_multiplier(b),
-                       w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre : (rh4::rh_cls *)nullptr, QA, zero_extra, zero_extra_n);
+                       w.qpre_v4 ? (rh4::rh_cls *)w.d_qpre.get() : (rh4::rh_cls *)nullptr, QA, zero_extra, zero_extra_n);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
@@ -1027,7 +1039,7 @@ int rhk_refit_mask(rh_cloud *c, const rh_prep &P, int kind, double eps, double c
         c->k_sums_ready = apply;
         return RH_OK;
     }
-    return c->f32 ? launch_refit(c, c->full32, prepf_of_kind(P, kind), kind, eps, cosa) : launch_refit(c, c->full, P, kind, eps, cosa);
+    return c->f32 ? launch_refit(c, c->full32.get(), prepf_of_kind(P, kind), kind, eps, cosa) : launch_refit(c, c->full.get(), P, kind, eps, cosa);
 }
 
 int rhk_compact_mask(rh_cloud *c, const uint64_t *mask, int64_t nwords, int64_t *idx_out, int64_t cap,
@@ -1456,17 +1468,15 @@ oct_code_o_kernel(const uint64_t *__restrict__ code, const int32_t *__restrict__
 
 int rhk_oct_build_tab(rh_cloud *c)
 {
-    (void)hipFree(c->oct_tab);
-    (void)hipFree(c->oct_code_o);
-    c->oct_tab = nullptr;
-    c->oct_code_o = nullptr;
+    c->oct_tab.reset();
+    c->oct_code_o.reset();
     c->oct_tab_level = 0;
     if (c->n == 0) return RH_OK;
-    RH_HIP(hipMalloc((void **)&c->oct_code_o, sizeof(uint64_t) * (size_t)c->n));
+    RH_TRY(c->oct_code_o.alloc(c->n));
     hipLaunchKernelGGL(oct_code_o_kernel, dim3(cdiv(c->n, 256)), dim3(256), 0, c->stream, c->oct_code, c->oct_perm, c->n, c->oct_code_o);
     const int level = c->oct_depth < 8 ? c->oct_depth : 8;   // 8^7 + 1 entries at most (8 MB)
     const int64_t entries = ((int64_t)1 << (3 * (level - 1))) + 1;
-    RH_HIP(hipMalloc((void **)&c->oct_tab, sizeof(int32_t) * (size_t)entries));
+    RH_TRY(c->oct_tab.alloc(entries));
     hipLaunchKernelGGL(oct_tab_kernel, dim3(cdiv(entries, 256)), dim3(256), 0, c->stream, c->oct_code, c->n, 3 * (21 - (level - 1)),
                        entries, c->oct_tab);
     RH_HIP(hipGetLastError());

@@ -189,42 +189,37 @@ int rhk_korder_build(rh_cloud *c, const double *d_xyz, const double *d_nrm, cons
     if (n == 0) return RH_OK;
     c->k_mag = mag;
     c->kg_pad = ((c->nwords + 63) / 64) * 64 + 64;
-    uint64_t *code_in = nullptr;
-    int32_t *idx_in = nullptr;
-    void *tmp = nullptr;
+    rh_dev<uint64_t> code_in;   // (the sort's inputs and scratch: gone on every way out)
+    rh_dev<int32_t> idx_in;
+    rh_dev<char> tmp;
     size_t tmp_bytes = 0;
-    auto cleanup = [&]() { (void)hipFree(code_in); (void)hipFree(idx_in); (void)hipFree(tmp); };
-#define KH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rh_set_error("%s: %s", #x, hipGetErrorString(e_)); cleanup(); return RH_E_NODEVICE; } } while (0)
-    KH(hipMalloc((void **)&code_in, sizeof(uint64_t) * (size_t)n));
-    KH(hipMalloc((void **)&idx_in, sizeof(int32_t) * (size_t)n));
-    KH(hipMalloc((void **)&c->oct_code, sizeof(uint64_t) * (size_t)n));
-    KH(hipMalloc((void **)&c->oct_perm, sizeof(int32_t) * (size_t)n));
-    KH(hipMalloc((void **)&c->oct_pos, sizeof(int32_t) * (size_t)n));
-    KH(hipMalloc((void **)&c->oct_men, sizeof(uint64_t) * (size_t)c->nwords));
-    KH(hipMalloc((void **)&c->oct_prefix, sizeof(int32_t) * (size_t)(c->nwords + 1)));
-    KH(hipMalloc((void **)&c->fullk, sizeof(double) * 6 * (size_t)c->n_pad));
-    KH(hipMalloc((void **)&c->kgb, sizeof(double) * 7 * (size_t)c->kg_pad));
-    KH(hipMalloc((void **)&c->klist, sizeof(int32_t) * (size_t)c->nwords));
-    KH(hipMalloc((void **)&c->kctr, sizeof(int32_t) * 2));
-    KH(hipMemsetAsync(c->kctr, 0, sizeof(int32_t) * 2, c->stream));
-    KH(hipMalloc((void **)&c->kflag, (size_t)c->n_pad));
-    KH(hipMemsetAsync(c->kflag, 0, (size_t)c->n_pad, c->stream));
-    KH(hipMemsetAsync(c->fullk, 0, sizeof(double) * 6 * (size_t)c->n_pad, c->stream));
-    KH(hipMemsetAsync(c->kgb, 0, sizeof(double) * 7 * (size_t)c->kg_pad, c->stream));
+    RH_TRY(code_in.alloc(n));
+    RH_TRY(idx_in.alloc(n));
+    RH_TRY(c->oct_code.alloc(n));
+    RH_TRY(c->oct_perm.alloc(n));
+    RH_TRY(c->oct_pos.alloc(n));
+    RH_TRY(c->oct_men.alloc(c->nwords));
+    RH_TRY(c->oct_prefix.alloc(c->nwords + 1));
+    RH_TRY(c->fullk.alloc(6 * c->n_pad));
+    RH_TRY(c->kgb.alloc(7 * c->kg_pad));
+    RH_TRY(c->klist.alloc(c->nwords));
+    RH_TRY(c->kctr.alloc(2));
+    RH_HIP(hipMemsetAsync(c->kctr, 0, sizeof(int32_t) * 2, c->stream));
+    RH_TRY(c->kflag.alloc(c->n_pad));
+    RH_HIP(hipMemsetAsync(c->kflag, 0, (size_t)c->n_pad, c->stream));
+    RH_HIP(hipMemsetAsync(c->fullk, 0, sizeof(double) * 6 * (size_t)c->n_pad, c->stream));
+    RH_HIP(hipMemsetAsync(c->kgb, 0, sizeof(double) * 7 * (size_t)c->kg_pad, c->stream));
     hipLaunchKernelGGL(morton_kernel, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, d_xyz, n, lo[0], lo[1], lo[2], size, code_in,
                        idx_in);
     // stable LSD radix sort of (code, index) pairs by code: equal codes keep ascending indices = sort by (code, index)
-    KH(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, code_in, c->oct_code, idx_in, c->oct_perm, (int)n, 0, 63, c->stream));
-    KH(hipMalloc(&tmp, tmp_bytes > 0 ? tmp_bytes : 1));
-    KH(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, code_in, c->oct_code, idx_in, c->oct_perm, (int)n, 0, 63, c->stream));
+    RH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, code_in.get(), c->oct_code.get(), idx_in.get(), c->oct_perm.get(), (int)n, 0, 63, c->stream));
+    RH_TRY(tmp.alloc((int64_t)tmp_bytes));
+    RH_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(), tmp_bytes, code_in.get(), c->oct_code.get(), idx_in.get(), c->oct_perm.get(), (int)n, 0, 63, c->stream));
     hipLaunchKernelGGL(invert_perm_kernel, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, c->oct_perm, n, c->oct_pos);
-    KH(hipGetLastError());
-    int rc = rhk_transpose_aos(c, d_xyz, d_nrm, n, c->oct_perm, n, c->fullk, c->n_pad);
-    if (rc == RH_OK) rc = rhk_group_bounds_of(c, c->fullk, c->n_pad, n, c->nwords, c->kgb, c->kg_pad);
-    if (rc != RH_OK) { cleanup(); return rc; }
-    KH(hipStreamSynchronize(c->stream));
-#undef KH
-    cleanup();
+    RH_HIP(hipGetLastError());
+    RH_TRY(rhk_transpose_aos(c, d_xyz, d_nrm, n, c->oct_perm, n, c->fullk, c->n_pad));
+    RH_TRY(rhk_group_bounds_of(c, c->fullk, c->n_pad, n, c->nwords, c->kgb, c->kg_pad));
+    RH_HIP(hipStreamSynchronize(c->stream));
     c->k_built = true;
     return RH_OK;
 }
@@ -239,7 +234,7 @@ int rhk_f32_build(rh_cloud *c)
     to_float(c->full, 6 * c->n_pad, c->full32);
     to_float(c->sub, 6 * c->s_pad, c->sub32);
     if (c->k_built) {
-        RH_HIP(hipMalloc((void **)&c->fullk32, sizeof(float) * 6 * (size_t)c->n_pad));
+        RH_TRY(c->fullk32.alloc(6 * c->n_pad));
         to_float(c->fullk, 6 * c->n_pad, c->fullk32);
     }
     RH_HIP(hipGetLastError());
@@ -311,6 +306,6 @@ static int launch_refitk(rh_cloud *c, const T *pts, const PREP &PX, const rh_pre
 int rhk_refitk_mask(rh_cloud *c, const rh_prep &P, int kind, double eps, double cosa, bool apply)
 {
     if (c->nwords == 0) return RH_OK;
-    if (c->f32) return launch_refitk(c, c->fullk32, prepf_of_kind(P, kind), P, kind, eps, cosa, apply);
-    return launch_refitk(c, c->fullk, P, P, kind, eps, cosa, apply);
+    if (c->f32) return launch_refitk(c, c->fullk32.get(), prepf_of_kind(P, kind), P, kind, eps, cosa, apply);
+    return launch_refitk(c, c->fullk.get(), P, P, kind, eps, cosa, apply);
 }

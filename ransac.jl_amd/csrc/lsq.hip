@@ -227,10 +227,9 @@ extern "C" int rh_refit_lsq(rh_cloud *c, const rh_shape *shape, const rh_params 
         }
     }
     const int nblocks = 512;
-    double *d_part = nullptr, *d_out = nullptr;
-    RH_HIP(hipMalloc((void **)&d_part, sizeof(double) * 64 * nblocks));
-    RH_HIP(hipMalloc((void **)&d_out, sizeof(double) * 64));
-    auto done = [&](int rc) { (void)hipFree(d_part); (void)hipFree(d_out); return rc; };
+    rh_dev<double> d_part, d_out;
+    RH_TRY(d_part.alloc(64 * nblocks));
+    RH_TRY(d_out.alloc(64));
 
     rh_shape cur = *shape;
     double M[64];
@@ -267,7 +266,7 @@ extern "C" int rh_refit_lsq(rh_cloud *c, const rh_shape *shape, const rh_params 
         hipLaunchKernelGGL(lsq_reduce_kernel, dim3(1), dim3(64), 0, c->stream, d_part, nblocks, d_out);
         hipError_t e = hipMemcpyAsync(M, d_out, sizeof M, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { rh_set_error("rh_refit_lsq: %s", hipGetErrorString(e)); return done(RH_E_NODEVICE); }
+        if (e != hipSuccess) { rh_set_error("rh_refit_lsq: %s", hipGetErrorString(e)); return RH_E_NODEVICE; }
 
         if (kind == RH_PLANE) {
             const double N = M[3 * 8 + 3];
@@ -295,7 +294,7 @@ extern "C" int rh_refit_lsq(rh_cloud *c, const rh_shape *shape, const rh_params 
             b[i] = -M[i * 8 + m];
         }
         const double rr = M[m * 8 + m];
-        if (!solve_sym(m, A, b, x)) { rh_set_error("rh_refit_lsq: singular normal equations"); return done(RH_E_INVALID); }
+        if (!solve_sym(m, A, b, x)) { rh_set_error("rh_refit_lsq: singular normal equations"); return RH_E_INVALID; }
         if (kind == RH_SPHERE) {
             for (int i = 0; i < 4; i++) cur.v[i] += x[i];
         } else if (kind == RH_CYLINDER) {
@@ -324,5 +323,5 @@ extern "C" int rh_refit_lsq(rh_cloud *c, const rh_shape *shape, const rh_params 
     if (n_used) *n_used = cnt;
     if (rms) *rms = last_rms;
     if (iters_done) *iters_done = it;
-    return done(RH_OK);
+    return RH_OK;
 }

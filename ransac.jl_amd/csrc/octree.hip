@@ -35,8 +35,7 @@ struct rh_octree {
     int64_t n = 0;
     int overflow = 0;
     // device copy of the index lists (made on the first gather, for that cloud's device)
-    int64_t *d_idx = nullptr;          // rh_octree_cell_enabled's device scratch (the requested cell's list, its enabled points, their number)
-    int64_t d_cap = 0;
+    rh_dev<int64_t> d_idx;             // rh_octree_cell_enabled's device scratch (the requested cell's list, its enabled points, their number)
     int d_device = -1;
 };
 
@@ -165,10 +164,7 @@ extern "C" int rh_octree_build_f32(const float *xyz, int64_t n, rh_octree **out)
 extern "C" int rh_octree_destroy(rh_octree *t)
 {
     if (!t) return RH_OK;
-    if (t->d_idx) {
-        if (t->d_device >= 0) (void)hipSetDevice(t->d_device);
-        (void)hipFree(t->d_idx);
-    }
+    if (t->d_idx && t->d_device >= 0) (void)hipSetDevice(t->d_device);   // (the scratch goes on the device it lives on)
     delete t;
     return RH_OK;
 }
@@ -253,12 +249,9 @@ extern "C" int rh_octree_cell_enabled(rh_cloud *c, rh_octree *t, int32_t node, i
     // scratch the tree keeps for the next call: [cell list | enabled list | count]
     const int64_t ocap = cap < nd.count ? cap : nd.count;
     const int64_t need = nd.count + (ocap > 0 ? ocap : 1) + 1;
-    if (t->d_idx == nullptr || t->d_device != c->device || t->d_cap < need) {
-        if (t->d_idx) { if (t->d_device >= 0) (void)hipSetDevice(t->d_device); (void)hipFree(t->d_idx); (void)hipSetDevice(c->device); }
-        t->d_idx = nullptr;
-        t->d_cap = 0;
-        RH_HIP(hipMalloc((void **)&t->d_idx, sizeof(int64_t) * (size_t)need));
-        t->d_cap = need;
+    if (t->d_idx == nullptr || t->d_device != c->device || t->d_idx.count() < need) {
+        if (t->d_idx) { if (t->d_device >= 0) (void)hipSetDevice(t->d_device); t->d_idx.reset(); (void)hipSetDevice(c->device); }
+        RH_TRY(t->d_idx.alloc(need));
         t->d_device = c->device;
     }
     int64_t *d_out = t->d_idx + nd.count, *d_n = d_out + (ocap > 0 ? ocap : 1);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ransac_hip.h"
+#include "dev_buf.h"
 
 // ---- error plumbing -------------------------------------------------------
 void rh_set_error(const char *fmt, ...);
@@ -172,7 +173,7 @@ struct rh_s4_points {   // what the v4 score kernel runs over (score4.hip): poin
     int64_t stride, s, ngroups;
     const float *gb32;
 };
-// Everything that belongs to ONE batch being prepared and scored: its buffers (grown on demand: rh_grow_buffer) and what the
+// Everything that belongs to ONE batch being prepared and scored: its buffers (grown on demand: rh_dev::grow) and what the
 // launchers leave in them.  A cloud has RH_MAX_IN_FLIGHT of them (rh_cloud::ws).  ws[0] is the workspace of the cloud's own
 // stream: every path but the pipelined rh_score_batch_dev uses it alone.  With rh_set_option "batches_in_flight" = F > 1 the
 // batches of rh_score_batch_dev take turns on ws[0 .. F-1], slot k >= 1 on a stream of its own, so one batch's prepare + score
@@ -182,36 +183,36 @@ struct rh_s4_points {   // what the v4 score kernel runs over (score4.hip): poin
 struct rh_batch_ws {
     // the slot in the pipeline (made by batch_slot_create for slots >= 1; null in ws[0], whose batches run on the cloud's stream)
     hipStream_t stream = nullptr;      // rh_cloud::stream is this one while the slot's batch is queued
-    hipEvent_t done = nullptr, start = nullptr;   // behind the slot's last batch / where `stream` was ordered behind the cloud's
+    rh_event done, start;   // behind the slot's last batch / where `stream` was ordered behind the cloud's
     bool dirty = false;                // work on `stream` the cloud's own stream has not waited for yet
     bool started = false;              // `stream` has been ordered behind the cloud's stream since the last join
     const void *out_counts = nullptr, *out_masks = nullptr;   // (ws[0] too) the buffers the slot's batch in flight writes (null: none)
     // the bins (rh_ensure_batch) and what the prep kernels leave in them
     int64_t batch_cap = 0;
-    rh_shape *d_shapes = nullptr;      // [batch_cap]
-    rh_prep *d_prep = nullptr;         // [4 * batch_cap], kind-major
-    int32_t *d_orig = nullptr, *d_counts = nullptr;   // [4 * batch_cap], [batch_cap]
-    void *d_qpre = nullptr;            // [4 * batch_cap] classifier records (rh4::rh_cls, 64 B) of the bins in d_prep; culling records: d_box
-    float *d_box = nullptr;            // [RH_BOX_FIELDS][4 * batch_cap] culling records of the same bins (v4 score kernel), structure of arrays
+    rh_dev<rh_shape> d_shapes;         // [batch_cap]
+    rh_dev<rh_prep> d_prep;            // [4 * batch_cap], kind-major
+    rh_dev<int32_t> d_orig, d_counts;   // [4 * batch_cap], [batch_cap]
+    rh_dev<char> d_qpre;               // [4 * batch_cap] classifier records (rh4::rh_cls, 64 B) of the bins in d_prep; culling records: d_box
+    rh_dev<float> d_box;               // [RH_BOX_FIELDS][4 * batch_cap] culling records of the same bins (v4 score kernel), structure of arrays
     bool qpre_v4 = false;              // ... made by the last prep kernel (for the thresholds it was given)
-    int32_t *d_nk2 = nullptr;          // [8] rh_score_batch_dev's bin sizes: two halves used alternately, each batch zeroes the other
+    rh_dev<int32_t> d_nk2;             // [8] rh_score_batch_dev's bin sizes: two halves used alternately, each batch zeroes the other
     int nk2_flip = 0;
     bool nk2_ready = false;
     // masks in internal order, before un-permuting (rh_masks_begin / rh_masks_finish).  Culled kernel (masks4): per candidate
     // row a list of (internal word number, inlier word) entries, 16 bytes each, at most one per group (mstride4 of them), and
     // in d_occ one int32 cursor per row, zero between batches.  Brute-force kernels: dense rows.
-    uint64_t *d_masks_int = nullptr;
-    uint8_t *d_occ = nullptr;
-    int64_t masks_int_cap = 0, occ_cap = 0, mstride4 = 0;   // (in 64-bit words, bytes, entries)
+    rh_dev<uint64_t> d_masks_int;      // (its count: 64-bit words)
+    rh_dev<uint8_t> d_occ;             // (bytes)
+    int64_t mstride4 = 0;              // (entries)
     bool masks4 = false;
     // per-super-tile candidate lists of the batch being scored (score4.hip, st_cull_kernel): [nst][4 kinds][stlist_cap] slots, [nst][4] counts
-    uint16_t *d_stlist = nullptr;
-    int32_t *d_stcount = nullptr;
+    rh_dev<uint16_t> d_stlist;
+    rh_dev<int32_t> d_stcount;
     int64_t stlist_cap = 0, stlist_nst = 0;
     int64_t stlist_nomem = 0;          // bytes of the list allocation that failed last (0: none did): not tried again at that size or above
     // mask un-permutation of rows that span 2..16 segments (rhk_unpermute_masks4): per output segment and internal word, the bits
     // that land in the segment.  Built on the slot's own stream, so stream order alone puts it in front of the slot's readers.
-    uint64_t *d_segmask = nullptr;
+    rh_dev<uint64_t> d_segmask;
     int64_t segmask_words = 0;         // ... made for this segment width (0: none yet)
 };
 // the four kinds' bins of a prepared batch: candidate records, original positions, classifier and culling records
@@ -270,37 +271,36 @@ struct rh_cloud {
     int64_t nblocks = 0;               // ceil(nwords / RH_WORDS_PER_BLOCK)
 
     // HBM layout: six SoA planes of n_pad (resp. s_pad) doubles: x y z nx ny nz
-    double *full = nullptr;            // full cloud, original order
-    double *set_ws = nullptr;          // sampler -> fitter hand-over: gathered minimal sets, [drawN * 6][sets]
-    int32_t *set_level = nullptr;      // per set: octree level it was drawn from, 0 = no set
-    int64_t set_ws_sets = 0, set_ws_doubles = 0;
-    double *crec = nullptr;            // 64-byte records of the ENABLED points in rank order (long sampling windows)
-    int64_t crec_cap = 0;              // in records
+    rh_dev<double> full;               // full cloud, original order
+    rh_dev<double> set_ws;             // sampler -> fitter hand-over: gathered minimal sets, [drawN * 6][sets]
+    rh_dev<int32_t> set_level;         // per set: octree level it was drawn from, 0 = no set
+    int64_t set_ws_sets = 0;
+    rh_dev<double> crec;               // 64-byte records (8 doubles each) of the ENABLED points in rank order (long sampling windows)
     bool crec_valid = false;           // cleared whenever the select list is rebuilt
     int very_long_windows = 0;         // windows of >= 2^19 sets sampled since the select directory was last built
-    int32_t *sel_list = nullptr;       // sel_list[r] = 0-based index of the (r+1)-th enabled point (valid with sel_valid)
+    rh_dev<int32_t> sel_list;          // sel_list[r] = 0-based index of the (r+1)-th enabled point (valid with sel_valid)
     bool sel_valid = false;            // built on demand by rhk_build_sel_list, dropped with the select directory
-    double *rec = nullptr;             // the same points as 64-byte records (x y z nx ny nz 0 0): one line per random gather
-    double *sub = nullptr;             // subset 1, subset order
-    double *dis = nullptr;             // disabled subset-1 points (append-only), capacity s_pad + tile
+    rh_dev<double> rec;                // the same points as 64-byte records (x y z nx ny nz 0 0): one line per random gather
+    rh_dev<double> sub;                // subset 1, subset order
+    rh_dev<double> dis;                // disabled subset-1 points (append-only), capacity s_pad + tile
     int64_t dis_stride = 0;
-    int32_t *sub_idx0 = nullptr;       // [s] 0-based original index of subset position j
-    uint64_t *enabled = nullptr;       // [nwords]  pc.isenabled chunks
-    uint64_t *sub_enabled = nullptr;   // [swords]  enabled bits gathered into subset order
-    int32_t *sub_perm = nullptr;       // [s] internal (k-d leaf order) position -> subset position j
-    double *gb = nullptr;              // 7 planes x ng_pad: box centre cx cy cz, half extents hx hy hz, radius hr
+    rh_dev<int32_t> sub_idx0;          // [s] 0-based original index of subset position j
+    rh_dev<uint64_t> enabled;          // [nwords]  pc.isenabled chunks
+    rh_dev<uint64_t> sub_enabled;      // [swords]  enabled bits gathered into subset order
+    rh_dev<int32_t> sub_perm;          // [s] internal (k-d leaf order) position -> subset position j
+    rh_dev<double> gb;                 // 7 planes x ng_pad: box centre cx cy cz, half extents hx hy hz, radius hr
     int64_t ngroups = 0, ng_pad = 0;   // 64-point groups of the subset (internal order)
     double create_ms[4] = { 0, 0, 0, 0 };   // rh_cloud_create: total, host k-d leaf order of subset 1, everything before it, everything after it
     double coord_mag = 0;              // max |coordinate| over the subset (rounding slack of the bounds)
     double nrm_mag = 0;                // max |normal component| over the subset (margins of the binary32 classifier)
     bool use_groups = false;           // culled scoring path available (s large enough)
-    float *gb32 = nullptr;             // the same boxes in binary32, 8 floats per group (v4 score kernel: scalar loads)
-    float *st32 = nullptr;             // boxes of the super-tiles (16 consecutive groups = 4 tiles of the k-d leaf order), 8 floats each
+    rh_dev<float> gb32;                // the same boxes in binary32, 8 floats per group (v4 score kernel: scalar loads)
+    rh_dev<float> st32;                // boxes of the super-tiles (16 consecutive groups = 4 tiles of the k-d leaf order), 8 floats each
     int64_t nst = 0;
-    float *tile32 = nullptr;           // boxes of the tiles (4 consecutive groups: what a block of the culled score kernel stages; the diag build's pair census reads them), 8 floats each
+    rh_dev<float> tile32;              // boxes of the tiles (4 consecutive groups: what a block of the culled score kernel stages; the diag build's pair census reads them), 8 floats each
     int64_t ntile = 0;
-    double *dis_gb = nullptr;          // boxes of the dis segment in use (7 x ng_pad)
-    int32_t *d_ndis = nullptr;         // device counter: entries in dis
+    rh_dev<double> dis_gb;             // boxes of the dis segment in use (7 x ng_pad)
+    rh_dev<int32_t> d_ndis;            // device counter: entries in dis
     int64_t n_dis = 0;                 // host mirror
 
     // The cloud in Morton order (korder.hip), built on the device with the cloud: the order of the linear octree of
@@ -311,66 +311,62 @@ struct rh_cloud {
     bool k_sums_ready = false;         // ... and left the per-block popcounts of refit_mask in block_sums
     double k_lo[3] = { 0, 0, 0 }, k_size = 1;   // bounding cube of the cloud (findAABB, utilities.jl:125-136)
     double k_mag = 0;                  // max |coordinate| over the cloud (rounding slack of the box tests)
-    double *fullk = nullptr;           // 6 planes x n_pad, Morton order
-    float *fullk32 = nullptr;          // the same as float (Float32 clouds)
-    double *kgb = nullptr;             // 7 planes x kg_pad: box of every 64 consecutive points of fullk
+    rh_dev<double> fullk;              // 6 planes x n_pad, Morton order
+    rh_dev<float> fullk32;             // the same as float (Float32 clouds)
+    rh_dev<double> kgb;                // 7 planes x kg_pad: box of every 64 consecutive points of fullk
     int64_t kg_pad = 0;
-    int32_t *klist = nullptr;          // [nwords] groups that survive the box test of the scan in flight
-    int32_t *kctr = nullptr;           // [2] list length (zero between scans)
-    uint8_t *kflag = nullptr;          // [n_pad] one byte per point, original order: inlier of the scan in flight (zero between scans)
+    rh_dev<int32_t> klist;             // [nwords] groups that survive the box test of the scan in flight
+    rh_dev<int32_t> kctr;              // [2] list length (zero between scans)
+    rh_dev<uint8_t> kflag;             // [n_pad] one byte per point, original order: inlier of the scan in flight (zero between scans)
     bool oct_built = false;            // depth + host twins of the octree (rh_octree_ensure)
     int oct_depth = 0, oct_max_depth = 0;
-    uint64_t *oct_code = nullptr;      // [n] sorted Morton codes (device)
-    int32_t *oct_perm = nullptr;       // [n] Morton position -> original index0
-    int32_t *oct_pos = nullptr;        // [n] original index0 -> Morton position
-    uint64_t *oct_men = nullptr;       // [nwords] enabled bits in Morton order
-    int32_t *oct_prefix = nullptr;     // [nwords + 1]
-    rh_oct_state *oct_state = nullptr; // chained octree windows: the window's state,
-    float *dis_gb32 = nullptr;         // binary32 twins of dis_gb
-    void *s4_stats = nullptr;          // diag build: event counters of the score launches (rh_dbg_s4_stats), 128 x u64 on the device
-    int32_t *oct_adv_tab = nullptr;    //   the (level, slot) table of rhk_oct_advance, its bitmap (kept zero) and the sorted scores
-    unsigned long long *oct_adv_bits = nullptr;
+    rh_dev<uint64_t> oct_code;         // [n] sorted Morton codes (device)
+    rh_dev<int32_t> oct_perm;          // [n] Morton position -> original index0
+    rh_dev<int32_t> oct_pos;           // [n] original index0 -> Morton position
+    rh_dev<uint64_t> oct_men;          // [nwords] enabled bits in Morton order
+    rh_dev<int32_t> oct_prefix;        // [nwords + 1]
+    rh_dev<rh_oct_state> oct_state;    // chained octree windows: the window's state,
+    rh_dev<float> dis_gb32;            // binary32 twins of dis_gb
+    rh_dev<unsigned long long> s4_stats;   // diag build: event counters of the score launches (rh_dbg_s4_stats), 128 x u64 on the device
+    rh_dev<int32_t> oct_adv_tab;       //   the (level, slot) table of rhk_oct_advance, its bitmap (kept zero) and the sorted scores
+    rh_dev<unsigned long long> oct_adv_bits;
     int64_t oct_adv_cells = 0;
-    double *oct_adv_E = nullptr;
-    uint64_t *oct_code_o = nullptr;    // [n] the Morton codes in original point order (built with oct_tab)
-    int32_t *oct_tab = nullptr;        // first Morton position of every level-oct_tab_level cell (+ n at the end)
+    rh_dev<double> oct_adv_E;
+    rh_dev<uint64_t> oct_code_o;       // [n] the Morton codes in original point order (built with oct_tab)
+    rh_dev<int32_t> oct_tab;           // first Morton position of every level-oct_tab_level cell (+ n at the end)
     int oct_tab_level = 0;
-    double *oct_P = nullptr;           // level distributions of a speculation window
-    int64_t oct_P_cap = 0;
+    rh_dev<double> oct_P;              // level distributions of a speculation window
     std::vector<uint64_t> h_oct_code;  // host twins (host-side sampling, enabled mirror)
     std::vector<int32_t> h_oct_perm, h_oct_pos;
 
     // refit / select workspaces
-    uint64_t *refit_mask = nullptr;    // [nwords]
-    int32_t *block_sums = nullptr;     // [nblocks + 1]
-    int32_t *en_block_sums = nullptr;  // [nblocks + 1] popcounts of the enabled words per block (select directory)
+    rh_dev<uint64_t> refit_mask;       // [nwords]
+    rh_dev<int32_t> block_sums;        // [nblocks + 1]
+    rh_dev<int32_t> en_block_sums;     // [nblocks + 1] popcounts of the enabled words per block (select directory)
     bool en_sums_valid = false;        // left behind by rhk_compact_refit_apply for the next rhk_build_select
-    int32_t *word_prefix = nullptr;    // [nwords + 1] exclusive prefix of popcount(enabled) (select)
+    rh_dev<int32_t> word_prefix;       // [nwords + 1] exclusive prefix of popcount(enabled) (select)
     bool select_valid = false;
-    int64_t *idx_out = nullptr;        // [n] compacted indices
-    int32_t *d_total = nullptr;        // scalar
+    rh_dev<int64_t> idx_out;           // [n] compacted indices
+    rh_dev<int32_t> d_total;           // scalar
 
     // largest-connected-component filter of a refit set (component.hip): the setting rh_ransac's extractions read
     // (rh_cloud_set_component_filter; 0: off) and the workspace, grown on demand and kept between calls
     double comp_beta = 0;
     int32_t comp_conn26 = 1;
-    void *comp_tab = nullptr;          // the cell table: per slot key (8 B), parent, point count, smallest index (4 B each)
+    rh_dev<char> comp_tab;             // the cell table: per slot key (8 B), parent, point count, smallest index (4 B each)
     int64_t comp_cap = 0;              // in slots
-    uint64_t *comp_scal = nullptr;     // the call's scalars on the device (minimum, maximum, |I|, winner, components) ...
-    uint64_t *comp_h = nullptr;        // ... and where the host reads the first seven (pinned)
+    rh_dev<uint64_t> comp_scal;        // the call's scalars on the device (minimum, maximum, |I|, winner, components) ...
+    rh_pinned<uint64_t> comp_h;        // ... and where the host reads the first seven (pinned)
 
     // oriented extents of extracted shapes (extent.hip): workspaces, grown on demand and kept between calls
-    double *ext_part = nullptr;        // one row of partial sums / minima / maxima per chunk of list entries
+    rh_dev<double> ext_part;           // one row of partial sums / minima / maxima per chunk of list entries
     int64_t ext_part_rows = 0;
-    int32_t *ext_flag = nullptr;       // the call's error word (RH_EXT_BAD_* bits of extent.hip), raised by the kernels
-    void *ext_in = nullptr;            // the host entry's uploads: shapes, offsets, records, index lists
-    int64_t ext_in_bytes = 0;
+    rh_dev<int32_t> ext_flag;          // the call's error word (RH_EXT_BAD_* bits of extent.hip), raised by the kernels
+    rh_dev<char> ext_in;               // the host entry's uploads: shapes, offsets, records, index lists
 
     // per-point labels (assign.hip): workspaces, grown on demand and kept between calls
-    void *asg_ws = nullptr;            // prepared shape records, the lists' count matrix, label totals and offsets
-    int64_t asg_ws_bytes = 0;
-    void *asg_io = nullptr;            // the host entry's shapes and its outputs on their way to the host
-    int64_t asg_io_bytes = 0;
+    rh_dev<char> asg_ws;               // prepared shape records, the lists' count matrix, label totals and offsets
+    rh_dev<char> asg_io;               // the host entry's shapes and its outputs on their way to the host
 
     // the batch workspaces: ws[0] the cloud's own, ws[1 ..] the other slots of rh_score_batch_dev's pipeline (rh_batch_ws)
     rh_batch_ws ws[RH_MAX_IN_FLIGHT];
@@ -382,22 +378,20 @@ struct rh_cloud {
     //     (rh_score_batch, rh_score_batch_dev_timed, rh_ransac's windows) -- no other batch is in flight then.
     //   last_s4: host-side record of the last sized batch launch, whichever slot it was on (a cloud is used by one host thread at a time).
     // Whatever else a score launch is told travels in its rh_score_job.
-    int32_t *d_nk = nullptr;           // [4] bin sizes of a batch whose sizes the host uploads (rh_score_batch) or the sampler leaves (rh_ransac)
-    uint64_t *d_masks = nullptr;       // rh_score_batch: the masks in subset order on their way to the host (grown on demand)
-    int64_t masks_cap = 0;
-    int32_t *d_zero = nullptr;         // 64 zero bytes: the bin size a kind left out of a launch reads (per-kind timing leg)
+    rh_dev<int32_t> d_nk;              // [4] bin sizes of a batch whose sizes the host uploads (rh_score_batch) or the sampler leaves (rh_ransac)
+    rh_dev<uint64_t> d_masks;          // rh_score_batch: the masks in subset order on their way to the host (grown on demand)
+    rh_dev<int32_t> d_zero;            // 64 zero bytes: the bin size a kind left out of a launch reads (per-kind timing leg)
     hipEvent_t ev_cull = nullptr;      // timed launches (rh_score_batch_dev_timed): behind the list launch, in front of the score launch
     float last_cull_ms = 0.f;
     int32_t last_s4[4] = { 0, 0, 0, 0 };   // the last sized batch launch of the culled score kernel: R, lists taken (0 / 1), rows, tiles (rh_score_launch_info)
 
-    int64_t *d_ranks = nullptr;        // select in/out
-    int64_t ranks_cap = 0;
+    rh_dev<int64_t> d_ranks;           // select in/out
 
     // Float32 clouds (rh_cloud_create_f32): float copies of the two point sets (fullk32: the Morton-order twin of full32)
     bool f32 = false;
     bool f32_groups = false;           // scored by the culled kernel; else by the brute-force kernel (both: exact test in binary32)
-    float *full32 = nullptr;           // 6 planes x n_pad, original order (the refit scan streams these: 24 B per point)
-    float *sub32 = nullptr;            // 6 planes x s_pad, subset 1 in k-d leaf order (the brute-force batch score reads these)
+    rh_dev<float> full32;              // 6 planes x n_pad, original order (the refit scan streams these: 24 B per point)
+    rh_dev<float> sub32;               // 6 planes x s_pad, subset 1 in k-d leaf order (the brute-force batch score reads these)
 
     // rh_ransac_mp: this process's share of every iteration's minimal sets (set j belongs to rank j % world)
     int32_t mp_rank = 0, mp_world = 1;
@@ -412,11 +406,10 @@ struct rh_cloud {
     void (*drv_cache_free)(rh_cloud *, void *) = nullptr;
 
     // rh_score_batch with host buffers: device twin of the pinned staging block of a small batch (one upload)
-    void *d_stage = nullptr;
+    rh_dev<char> d_stage;
 
     // pinned staging
-    void *h_pin = nullptr;
-    int64_t h_pin_cap = 0;
+    rh_pinned<char> h_pin;
 };
 
 // the job of scoring prepared bins (sizes: d_nk[0 .. 3]) against subset 1 with p's thresholds; the caller adds the bounds, the
@@ -428,7 +421,7 @@ static inline rh_score_job rh_subset_job(const rh_cloud *c, const rh_params *p, 
     J.bins = bins;
     J.bstride = bstride;
     for (int k = 0; k < 4; k++) {
-        J.en[k] = (k == RH_SPHERE && !p->sphere_uses_enabled) ? nullptr : c->sub_enabled;
+        J.en[k] = (k == RH_SPHERE && !p->sphere_uses_enabled) ? nullptr : c->sub_enabled.get();
         J.nk[k] = d_nk + k;
     }
     J.eps = p->eps;
@@ -455,6 +448,7 @@ int rhk_pack_records(rh_cloud *c, const double *d_xyz, const double *d_nrm, int6
 // cosa they also leave the bins' classifier / culling records in w.d_qpre / w.d_box and say so in w.qpre_v4.
 int rhk_prep_sorted(rh_cloud *c, rh_batch_ws &w, int32_t b, int32_t *d_counts_to_zero = nullptr, const double *eps = nullptr,
                     const double *cosa = nullptr);   // w.d_shapes[0 .. b), sorted by kind -> w.d_prep, slot for slot
+int rhk_prep_records(rh_cloud *c, const rh_shape *d_shapes, int32_t b, rh_prep *d_prep);   // d_shapes[0 .. b) -> d_prep, slot for slot, and nothing else
 struct rh_cand_entry;
 struct rh_oct_state;
 int rhk_prep_entries(rh_cloud *c, rh_batch_ws &w, const rh_cand_entry *d_entries, const int32_t *d_count, int32_t cap_entries,
@@ -614,9 +608,7 @@ int rhk_word_prefix(rh_cloud *c, const uint64_t *words, int64_t nwords, int32_t 
 int32_t rh_spread_multiplier(int32_t b);   // t -> (t * m) mod b: a permutation of the batch that separates neighbours
 
 // ---- host helpers (cloud.hip) -----------------------------------------------
-// the one way a device buffer of the cloud grows: c->stream (the stream of the workspace in use) is synchronised, the old buffer
-// freed, `bytes` allocated, and only then the capacity published (*cap = new_cap; cap may be null); a failure leaves null / 0
-int rh_grow_buffer(rh_cloud *c, void **buf, int64_t *cap, int64_t new_cap, size_t bytes);
+// (a device buffer of the cloud grows through rh_dev::grow on c->stream, the stream of the workspace in use)
 int rh_ensure_batch(rh_cloud *c, rh_batch_ws &w, int64_t b);
 // rh_score_batch_dev whose prepare launch also zeroes zero_extra_n ints from zero_extra (null: nothing besides the counts)
 int rh_score_batch_dev_zeroing(rh_cloud *c, const rh_shape *d_shapes, int32_t b, const rh_params *p, int32_t *d_counts, uint64_t *d_masks,
@@ -624,4 +616,6 @@ int rh_score_batch_dev_zeroing(rh_cloud *c, const rh_shape *d_shapes, int32_t b,
 int rh_join_batches(rh_cloud *c);   // the cloud's stream waits for what the other batch slots have in flight ("batches_in_flight")
 int rh_cloud_join(rh_cloud *c);     // the same with the cloud's device made current first (options.cpp)
 int rh_ensure_pin(rh_cloud *c, int64_t bytes);
+// the level distributions of a window: room for `need` doubles, `cap` of them when the buffer has to grow
+static inline int rh_ensure_oct_P(rh_cloud *c, int64_t need, int64_t cap) { return need > c->oct_P.count() ? c->oct_P.grow(c->stream, cap) : RH_OK; }
 int rh_validate_params(const rh_params *p);

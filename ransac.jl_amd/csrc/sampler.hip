@@ -828,16 +828,10 @@ int rhk_sample_fit(rh_cloud *c, const rh_params *prm, uint64_t seed, int64_t k0,
     if (total == 0) return RH_OK;
     // hand-over workspace (grown on demand; a window of 128 x 4096 sets of 3 points is 75 MB)
     const int64_t need = total * 6 * prm->drawN;
-    if (c->set_ws_doubles < need) {
-        (void)hipFree(c->set_ws);
-        c->set_ws = nullptr; c->set_ws_doubles = 0;
-        RH_HIP(hipMalloc((void **)&c->set_ws, sizeof(double) * (size_t)need));
-        c->set_ws_doubles = need;
-    }
+    if (c->set_ws.count() < need) RH_TRY(c->set_ws.alloc(need));
     if (c->set_ws_sets < total) {
-        (void)hipFree(c->set_level);
-        c->set_level = nullptr; c->set_ws_sets = 0;
-        RH_HIP(hipMalloc((void **)&c->set_level, sizeof(int32_t) * (size_t)total));
+        c->set_ws_sets = 0;
+        RH_TRY(c->set_level.alloc(total));
         c->set_ws_sets = total;
     }
     bool cone = false;
@@ -858,12 +852,7 @@ int rhk_sample_fit(rh_cloud *c, const rh_params *prm, uint64_t seed, int64_t k0,
         if (total >= 8 * long_sets) c->very_long_windows++;
         if (!no_crec && (c->crec_valid || (total >= 8 * long_sets && c->very_long_windows >= 2))) {
             if (!c->crec_valid) {
-                if (c->crec_cap < n_enabled) {
-                    (void)hipFree(c->crec);
-                    c->crec = nullptr; c->crec_cap = 0;
-                    RH_HIP(hipMalloc((void **)&c->crec, sizeof(double) * 8 * (size_t)n_enabled));
-                    c->crec_cap = n_enabled;
-                }
+                if (c->crec.count() < 8 * (int64_t)n_enabled) RH_TRY(c->crec.alloc(8 * (int64_t)n_enabled));
                 hipLaunchKernelGGL(compact_records_kernel, dim3((unsigned)(((int64_t)n_enabled + 255) / 256)), dim3(256), 0,
                                    c->stream, c->rec, c->sel_list, (int64_t)n_enabled, c->crec);
                 c->crec_valid = true;
@@ -964,27 +953,18 @@ extern "C" int rh_dbg_sample_fit(rh_cloud *c, const rh_params *p, uint64_t seed,
     if (P != nullptr) {
         RH_TRY(rh_octree_ensure(c, nullptr, p->octree_max_depth));
         const int64_t need = (int64_t)n_iters * c->oct_depth;
-        if (need > c->oct_P_cap) {
-            RH_HIP(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->oct_P);
-            c->oct_P = nullptr;
-            c->oct_P_cap = 0;
-            RH_HIP(hipMalloc((void **)&c->oct_P, sizeof(double) * (size_t)(512 * 32)));
-            c->oct_P_cap = 512 * 32;
-        }
+        RH_TRY(rh_ensure_oct_P(c, need, 512 * 32));
         RH_HIP(hipMemcpyAsync(c->oct_P, P, sizeof(double) * (size_t)need, hipMemcpyHostToDevice, c->stream));
         d_P = c->oct_P;
     }
     const size_t status_bytes = (size_t)((8 + 8 * (int64_t)n_iters + 63) / 64 * 64);
-    rh_cand_entry *d_entries = nullptr;
-    void *d_status = nullptr;
+    rh_dev<rh_cand_entry> d_entries;
+    rh_dev<char> d_status;
     std::vector<unsigned long long> h_status(status_bytes / 8);
     std::vector<rh_cand_entry> h_entries;
     int rc = RH_OK;
-    auto done = [&](int code) { (void)hipFree(d_entries); (void)hipFree(d_status); return code; };
-#define RH_DBG_HIP(x) do { if ((x) != hipSuccess) { rh_set_error("rh_dbg_sample_fit: HIP call failed: %s", #x); return done(RH_E_INTERNAL); } } while (0)
-    RH_DBG_HIP(hipMalloc((void **)&d_entries, sizeof(rh_cand_entry) * (size_t)(cap > 0 ? cap : 1)));
-    RH_DBG_HIP(hipMalloc(&d_status, status_bytes));
+    RH_TRY(d_entries.alloc(cap));
+    RH_TRY(d_status.alloc((int64_t)status_bytes));
     const int32_t rank0 = c->mp_rank, world0 = c->mp_world;
     c->mp_rank = rank;
     c->mp_world = world;
@@ -992,17 +972,16 @@ extern "C" int rh_dbg_sample_fit(rh_cloud *c, const rh_params *p, uint64_t seed,
     rc = rhk_sample_fit(c, p, seed, k0, n_iters, count, d_P, d_entries, cap, d_status, 0, nullptr, 0, nullptr);
     c->mp_rank = rank0;
     c->mp_world = world0;
-    if (rc != RH_OK) { (void)hipStreamSynchronize(c->stream); return done(rc); }
-    RH_DBG_HIP(hipMemcpyAsync(h_status.data(), d_status, status_bytes, hipMemcpyDeviceToHost, c->stream));
-    RH_DBG_HIP(hipStreamSynchronize(c->stream));
+    if (rc != RH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    RH_HIP(hipMemcpyAsync(h_status.data(), d_status, status_bytes, hipMemcpyDeviceToHost, c->stream));
+    RH_HIP(hipStreamSynchronize(c->stream));
     const int32_t made = (int32_t)(h_status[0] & 0xffffffffULL);
     const int32_t have = made < cap ? made : cap;
     h_entries.resize((size_t)(have > 0 ? have : 0));
     if (have > 0) {
-        RH_DBG_HIP(hipMemcpyAsync(h_entries.data(), d_entries, sizeof(rh_cand_entry) * (size_t)have, hipMemcpyDeviceToHost, c->stream));
-        RH_DBG_HIP(hipStreamSynchronize(c->stream));
+        RH_HIP(hipMemcpyAsync(h_entries.data(), d_entries, sizeof(rh_cand_entry) * (size_t)have, hipMemcpyDeviceToHost, c->stream));
+        RH_HIP(hipStreamSynchronize(c->stream));
     }
-#undef RH_DBG_HIP
     std::sort(h_entries.begin(), h_entries.end(), [](const rh_cand_entry &a, const rh_cand_entry &b) { return a.slot < b.slot; });
     if (have > 0) memcpy(out, h_entries.data(), sizeof(rh_cand_entry) * (size_t)have);
     *n_out = made;
@@ -1019,7 +998,7 @@ extern "C" int rh_dbg_sample_fit(rh_cloud *c, const rh_params *p, uint64_t seed,
         info_out[6] = c->dbg_sampler_path[4];
         info_out[7] = c->dbg_sampler_path[5];
     }
-    return done(RH_OK);
+    return RH_OK;
 }
 #endif   // RH_DIAG
 
@@ -1033,20 +1012,20 @@ int rhk_oct_advance(rh_cloud *c, const rh_params *prm, rh_oct_state *ost, const 
     const int64_t cells = (int64_t)od * per_it;
     const int64_t nw = (cells + 63) / 64, nws = (per_it + 63) / 64;
     if (c->oct_adv_cells < cells) {
+        c->oct_adv_cells = 0;
         RH_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->oct_adv_tab); (void)hipFree(c->oct_adv_bits); (void)hipFree(c->oct_adv_E);
-        c->oct_adv_tab = nullptr; c->oct_adv_bits = nullptr; c->oct_adv_E = nullptr; c->oct_adv_cells = 0;
-        RH_HIP(hipMalloc((void **)&c->oct_adv_tab, sizeof(double) * (size_t)cells + sizeof(int32_t) * (size_t)nws));   // score table, then the slot prefixes
-        RH_HIP(hipMalloc((void **)&c->oct_adv_bits, sizeof(unsigned long long) * (size_t)(nw + nws)));   // both bitmaps
+        c->oct_adv_tab.reset(); c->oct_adv_bits.reset(); c->oct_adv_E.reset();
+        RH_TRY(c->oct_adv_tab.alloc(2 * cells + nws));   // score table (doubles), then the slot prefixes
+        RH_TRY(c->oct_adv_bits.alloc(nw + nws));   // both bitmaps
         RH_HIP(hipMemsetAsync(c->oct_adv_bits, 0, sizeof(unsigned long long) * (size_t)(nw + nws), c->stream));   // the kernel leaves them zero
-        RH_HIP(hipMalloc((void **)&c->oct_adv_E, sizeof(double) * (size_t)per_it));
+        RH_TRY(c->oct_adv_E.alloc(per_it));
         c->oct_adv_cells = cells;
     }
     OctAdvArgs A;
     A.ost = ost; A.entries = d_entries; A.status = (const unsigned long long *)d_status; A.counts = d_counts;
     A.cap = cap; A.it = it; A.od = od; A.score_mode = prm->score_mode; A.extract_s = prm->extract_s; A.minsubsetN = prm->minsubsetN;
     A.drawN = prm->drawN; A.k = k; A.per_it = per_it; A.S1length = c->s; A.Plength = c->n; A.prob_det = prm->prob_det;
-    A.Etab = (double *)c->oct_adv_tab; A.spref = (int32_t *)((double *)c->oct_adv_tab + cells); A.bits = c->oct_adv_bits; A.sbits = c->oct_adv_bits + nw; A.Esort = c->oct_adv_E;
+    A.Etab = (double *)c->oct_adv_tab.get(); A.spref = (int32_t *)((double *)c->oct_adv_tab.get() + cells); A.bits = c->oct_adv_bits; A.sbits = c->oct_adv_bits + nw; A.Esort = c->oct_adv_E;
     A.bin_prep = c->ws[0].d_prep; A.bin_orig = c->ws[0].d_orig; A.bin_nk = c->d_nk; A.bin_cap = c->ws[0].batch_cap;
     A.h_entries = h_entries; A.h_counts = h_counts; A.h_rank = h_rank; A.h_slot = h_slot; A.h_hdr = h_hdr;
     hipLaunchKernelGGL(oct_advance_kernel, dim3(1), dim3(OA_THREADS), 0, c->stream, A);

@@ -1049,8 +1049,9 @@ static int ensure_stlists(rh_cloud *c, rh_batch_ws &w, int64_t cap)
     if (w.d_stlist != nullptr && cap <= w.stlist_cap && w.stlist_nst == c->nst) return RH_OK;
     const int64_t ncap = std::max<int64_t>(cap, 1024);
     w.stlist_cap = 0;
-    RH_TRY(rh_grow_buffer(c, (void **)&w.d_stcount, nullptr, 0, sizeof(int32_t) * (size_t)c->nst * 4));
-    RH_TRY(rh_grow_buffer(c, (void **)&w.d_stlist, &w.stlist_cap, ncap, (size_t)stlist_bytes(c, ncap)));
+    RH_TRY(w.d_stcount.grow(c->stream, c->nst * 4));
+    RH_TRY(w.d_stlist.grow(c->stream, c->nst * 4 * ncap));
+    w.stlist_cap = ncap;
     w.stlist_nst = c->nst;
     return RH_OK;
 }
@@ -1088,7 +1089,7 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
     A.mstride = d_masks_int ? w.mstride4 : 0;
     A.stats = nullptr;
 #ifdef RH_DIAG
-    A.stats = (unsigned long long *)c->s4_stats;   // (rh_dbg_s4_stats switched the counters on)
+    A.stats = c->s4_stats;  // (rh_dbg_s4_stats switched the counters on)
 #endif
     // Super-tile lists (round 5): a candidate meets only ~13 / 3 / 10 % of the groups (plane / sphere / cylinder at cfg3), yet
     // every block of every tile walks ALL the candidates of its row through stage 1 -- loads of their culling records, four box
@@ -1290,10 +1291,10 @@ extern "C" int rh_dbg_cls_audit(rh_cloud *c, const rh_shape *shapes, int32_t b, 
         Q.cNhi = d4[0]; Q.wN = d4[1]; Q.eDlo = d4[2]; Q.wD = d4[3]; Q.cosa = p->cos_alpha[Q.kind];
         Q.usable = !(Q.C.f[RH_CLS_FLAG] != Q.C.f[RH_CLS_FLAG]) && Q.wN > 0 && Q.wD > 0;
     }
-    S4AuditCand *d_c = nullptr;
-    unsigned long long *d_o = nullptr;
-    RH_HIP(hipMalloc((void **)&d_c, sizeof(S4AuditCand) * (size_t)b));
-    RH_HIP(hipMalloc((void **)&d_o, sizeof(unsigned long long) * 12));
+    rh_dev<S4AuditCand> d_c;
+    rh_dev<unsigned long long> d_o;
+    RH_TRY(d_c.alloc(b));
+    RH_TRY(d_o.alloc(12));
     RH_HIP(hipMemcpyAsync(d_c, h.data(), sizeof(S4AuditCand) * (size_t)b, hipMemcpyHostToDevice, c->stream));
     RH_HIP(hipMemsetAsync(d_o, 0, sizeof(unsigned long long) * 12, c->stream));
     for (int32_t c0 = 0; c0 < b; c0 += 32768) {
@@ -1304,8 +1305,6 @@ extern "C" int rh_dbg_cls_audit(rh_cloud *c, const rh_shape *shapes, int32_t b, 
     unsigned long long ho[12];
     RH_HIP(hipMemcpyAsync(ho, d_o, sizeof ho, hipMemcpyDeviceToHost, c->stream));
     RH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_c);
-    (void)hipFree(d_o);
     for (int i = 0; i < 8; i++) out[i] = __builtin_bit_cast(double, ho[i]);
     for (int i = 8; i < 12; i++) out[i] = (double)ho[i];
     return RH_OK;
@@ -1334,10 +1333,10 @@ static int cls_soundness_run(rh_cloud *c, const rh_shape *shapes, int32_t b, con
     S4SoundArgs A;
     for (int k = 0; k < 4; k++) { A.eps[k] = p->eps[k]; A.cosa[k] = p->cos_alpha[k]; }
     A.f32 = c->f32 ? 1 : 0;
-    S4SoundCand *d_c = nullptr;
-    unsigned long long *d_o = nullptr;
-    RH_HIP(hipMalloc((void **)&d_c, sizeof(S4SoundCand) * (size_t)b));
-    RH_HIP(hipMalloc((void **)&d_o, sizeof(unsigned long long) * 64));
+    rh_dev<S4SoundCand> d_c;
+    rh_dev<unsigned long long> d_o;
+    RH_TRY(d_c.alloc(b));
+    RH_TRY(d_o.alloc(64));
     RH_HIP(hipMemcpyAsync(d_c, h.data(), sizeof(S4SoundCand) * (size_t)b, hipMemcpyHostToDevice, c->stream));
     RH_HIP(hipMemsetAsync(d_o, 0, sizeof(unsigned long long) * 64, c->stream));
     hipLaunchKernelGGL(cls_sound_kernel, dim3((unsigned)c->ngroups, (unsigned)std::min<int32_t>(b, 64)), dim3(64), 0, c->stream, c->sub, c->s_pad, c->s,
@@ -1345,8 +1344,6 @@ static int cls_soundness_run(rh_cloud *c, const rh_shape *shapes, int32_t b, con
     unsigned long long ho[64];
     RH_HIP(hipMemcpyAsync(ho, d_o, sizeof ho, hipMemcpyDeviceToHost, c->stream));
     RH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_c);
-    (void)hipFree(d_o);
     for (int i = 0; i < nout; i++) out[i] = (uint64_t)ho[first + i];
     return RH_OK;
 }
@@ -1374,11 +1371,10 @@ extern "C" int rh_dbg_s4_stats(rh_cloud *c, int mode, uint64_t *out)
     RH_HIP(hipSetDevice(c->device));
     RH_HIP(hipStreamSynchronize(c->stream));
     if (mode == 1) {
-        if (c->s4_stats == nullptr) RH_HIP(hipMalloc((void **)&c->s4_stats, sizeof(unsigned long long) * 128));
+        if (c->s4_stats == nullptr) RH_TRY(c->s4_stats.alloc(128));
         RH_HIP(hipMemset(c->s4_stats, 0, sizeof(unsigned long long) * 128));
     } else if (mode == 2) {
-        if (c->s4_stats != nullptr) (void)hipFree(c->s4_stats);
-        c->s4_stats = nullptr;
+        c->s4_stats.reset();
     } else if (out != nullptr) {
         for (int i = 0; i < 128; i++) out[i] = 0;
         if (c->s4_stats != nullptr) RH_HIP(hipMemcpy(out, c->s4_stats, sizeof(unsigned long long) * 128, hipMemcpyDeviceToHost));
@@ -1407,7 +1403,9 @@ int rhk_unpermute_masks4(rh_cloud *c, rh_batch_ws &w, int32_t b, uint64_t *d_out
     const uint64_t *sm = nullptr;
     if (nseg > 1 && nseg <= 16) {   // which bits of a word belong to which segment: made once per workspace and segment width, on its stream
         if (w.d_segmask == nullptr || w.segmask_words != seg_words) {
-            RH_TRY(rh_grow_buffer(c, (void **)&w.d_segmask, &w.segmask_words, seg_words, sizeof(uint64_t) * (size_t)nseg * (size_t)c->ng_pad));
+            w.segmask_words = 0;
+            RH_TRY(w.d_segmask.grow(c->stream, (int64_t)nseg * c->ng_pad));
+            w.segmask_words = seg_words;
             hipLaunchKernelGGL(segmask_kernel, dim3((unsigned)cdiv4(c->ngroups, 256)), dim3(256), 0, c->stream, c->sub_perm, c->s, c->ngroups,
                                seg_words * 64, nseg, c->ng_pad, w.d_segmask);
             RH_HIP(hipGetLastError());

@@ -347,6 +347,30 @@ def test_prep_records(tmp_path):
     assert out.stdout.strip().endswith("48 checks, 0 bad")
 
 
+def test_buffer_owners(tmp_path):
+    """The owners of csrc/dev_buf.h (rh_dev, rh_pinned, rh_event) and the window list growth step of
+    csrc/driver_internal.h on a HIP runtime made of the check itself (live-block set, call log, the k-th allocation
+    fails on request), under AddressSanitizer and UBSan: one free per block whichever way an owner goes (scope end, move
+    construction, move assignment, self-move, reset twice); grow waits, frees, allocates in that order; a failed
+    alloc / grow leaves null / 0 and says RH_E_NOMEM for out of memory, RH_E_NODEVICE otherwise; a failed wait in grow leaves
+    the old block in place and names the caller; a failed event creation leaves no event; a block released to the caller
+    comes back with the runtime's verdict; a count of 0 is one element; a struct of arrays of owners survives std::swap of members and a whole-struct move; failing any allocation
+    of "reserve three, then publish" keeps the old buffers and loses no block; a window's entries_cap never exceeds what
+    is allocated; nothing is live at exit."""
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = os.path.realpath(shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "dev_buf_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fsanitize=address,undefined", "-D__HIP_PLATFORM_AMD__",
+                           "-I", os.path.join(os.path.dirname(os.path.dirname(hipcc)), "include"),
+                           "-I", os.path.join(root, "include"), "-I", os.path.join(root, "ransac.jl_amd", "csrc"),
+                           os.path.join(root, "tests", "native", "dev_buf_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-2000:])
+    assert out.stdout.strip().endswith("112 checks, 0 bad")
+
+
 def test_product_library_reads_no_environment_and_ships_no_diagnostics():
     """libransac_hip.so sits under someone else's process: it must not change what it computes because of a variable in
     that process's environment.  The A/B switches of the experiments (RH_NO_PIPELINE, ...), the skeleton-only launch
