@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 119
+#define RH_VERSION 120
 
 enum {
     RH_OK = 0,
@@ -892,6 +892,10 @@ int rh_register_f32(const float *ref_xyz_aos, const float *ref_nrm_aos_or_null, 
  *   "st_list_mb"  0 (default: 512) or the most MiB the candidate lists of one batch slot may take (8 bytes per super-tile of
  *                 1024 subset points and candidate); a launch that would need more, or whose allocation fails, takes no lists.
  *                 Read on every launch.
+ *   "nsig"        0 (default: on) / 2 (off) -- the culled score kernel and its list launch also rule a (plane, group) pair out
+ *                 when no point of the group has its normal in one of the 96 direction cells the candidate can accept (masks
+ *                 per 64-point group, made once when the cloud is created).  Counts and masks do not depend on it.  Read on
+ *                 every launch.
  *   "batches_in_flight"  1 (default) .. 4 -- with F > 1, rh_score_batch_dev calls take turns on the cloud's
  *                 stream and F - 1 more with workspaces of their own, so one batch's prepare + score launches start while
  *                 the previous batches' launches drain.  The caller keeps F count (and mask) buffers and gives call k of a

@@ -36,6 +36,16 @@ int rh_dbg_cls_soundness(rh_cloud *c, const rh_shape *shapes, int32_t b, const r
  * (candidate, group) whose tile's box rules the candidate out, out[4 + k] = VIOLATION: such a pair with an exact inlier
  * (must be 0). */
 int rh_dbg_cls_soundness_tiles(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out /* [8] */);
+/* the same census for the normal-cell masks of the plane pairs (csrc/score4_device.h): out[0] = pairs (candidate, group) that the
+ * GROUP's mask rules out, out[1] = VIOLATION: such a pair with an exact inlier (must be 0), out[2], out[3] = the same for the
+ * SUPER-TILE's mask (what the list launch applies). */
+int rh_dbg_cls_soundness_nsig(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out /* [4] */);
+/* The normal-cell mask of a plane candidate as the host builds it (cls_make on the host's record; M, Nm, Ln: max |coordinate|,
+ * max |normal component| and largest normal length of the point set, Ln = 0: not known; f32: a Float32 cloud's margins) into
+ * mask_out[3] (shape = NULL: skipped), and the cell (0..95) of each of the ndirs directions dirs[3 i ..] into cells_out[i]
+ * (-1: a zero vector or a NaN, which set no bit; -2: an infinite component, which sets all).  Needs no GPU. */
+int rh_dbg_nsig(const rh_shape *shape, const rh_params *p, double M, double Nm, double Ln, int f32, uint32_t *mask_out /* [3] */,
+                const double *dirs, int64_t ndirs, int32_t *cells_out);
 /* The device's octree sampler finds a point's cell and the r-th enabled point of a cell with a cell directory and
  * bracketed 8-ary searches (csrc/fit_shared.h: cell_bounds_code, lower_bound_in, select_in, select_in_many, select_bit)
  * where the host form uses plain binary searches.  Host-only self-check of those routines against the plain ones on a

@@ -349,6 +349,8 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
     CK(c->st32.alloc(8 * std::max<int64_t>(1, c->nst)));
     c->ntile = (c->ngroups + 3) / 4;
     CK(c->tile32.alloc(8 * std::max<int64_t>(1, c->ntile)));
+    CK(c->gm32.alloc(4 * c->ng_pad));
+    CK(c->stm32.alloc(4 * std::max<int64_t>(1, c->nst)));
     CK(c->dis_gb.alloc(7 * c->ng_pad));
     CK(c->dis_gb32.alloc(8 * c->ng_pad));
     CKH(hipMemsetAsync(c->dis_gb, 0, sizeof(double) * 7 * (size_t)c->ng_pad, c->stream));
@@ -788,7 +790,7 @@ extern "C" int rh_score_batch(rh_cloud *c, const rh_shape *shapes, int32_t b, co
             rh_prep_host(shapes[i], &h_prep[fill[k]]);
             if (staged_cls)
                 rh4::cls_make(h_prep[fill[k]], k, p->eps[k], p->cos_alpha[k], c->coord_mag, c->nrm_mag, ((rh4::rh_cls *)(hp + o_cls))[fill[k]],
-                              (float *)(hp + o_box) + fill[k], b);
+                              (float *)(hp + o_box) + fill[k], b, nullptr, false, c->nrm_len);
         } else h_sorted[fill[k]] = shapes[i];
         h_orig[fill[k]] = i;
         fill[k]++;

@@ -27,7 +27,7 @@ using namespace rhdev;
 // -------------------------------------------------------------- prep ------
 // (the record makers themselves: prep_one / prep_derived, rh_internal.h)
 // thresholds and magnitudes behind the classifier / culling records (rh4::cls_make) the prep kernels leave beside the bins
-struct PreArgs { double eps[4]; double cosa[4]; double coord_mag, nrm_mag; int f32; float *box; int64_t bstride; };
+struct PreArgs { double eps[4]; double cosa[4]; double coord_mag, nrm_mag, nrm_len; int f32; float *box; int64_t bstride; };
 
 __global__ void prep_sorted_kernel(const rh_shape *__restrict__ shapes, int32_t b, rh_prep *__restrict__ prep,
                                    int32_t *__restrict__ counts_zero, rh4::rh_cls *__restrict__ cls, const PreArgs QA)
@@ -40,7 +40,7 @@ __global__ void prep_sorted_kernel(const rh_shape *__restrict__ shapes, int32_t 
         prep[i] = P;
         if (counts_zero != nullptr) counts_zero[i] = 0;
         if (cls != nullptr && kind >= 0 && kind <= 3)
-            rh4::cls_make(P, kind, QA.eps[kind], QA.cosa[kind], QA.coord_mag, QA.nrm_mag, cls[i], QA.box + i, QA.bstride, nullptr, QA.f32 != 0);
+            rh4::cls_make(P, kind, QA.eps[kind], QA.cosa[kind], QA.coord_mag, QA.nrm_mag, cls[i], QA.box + i, QA.bstride, nullptr, QA.f32 != 0, QA.nrm_len);
     }
 }
 
@@ -95,7 +95,7 @@ __global__ void prep_binned_kernel(const rh_shape *__restrict__ shapes, int32_t 
     orig[(int64_t)kind * cap + slot] = i;
     if (cls != nullptr)
         rh4::cls_make(P, kind, QA.eps[kind], QA.cosa[kind], QA.coord_mag, QA.nrm_mag, cls[(int64_t)kind * cap + slot],
-                      QA.box + ((int64_t)kind * cap + slot), QA.bstride, nullptr, QA.f32 != 0);
+                      QA.box + ((int64_t)kind * cap + slot), QA.bstride, nullptr, QA.f32 != 0, QA.nrm_len);
 }
 
 // the sampler's candidate list (count on the device): bin by kind like prep_binned_kernel, zero the counts
@@ -139,7 +139,7 @@ __global__ void prep_entries_kernel(const rh_cand_entry *__restrict__ entries, c
     orig[(int64_t)kind * cap + slot] = i;
     if (cls != nullptr)
         rh4::cls_make(P, kind, QA.eps[kind], QA.cosa[kind], QA.coord_mag, QA.nrm_mag, cls[(int64_t)kind * cap + slot],
-                      QA.box + ((int64_t)kind * cap + slot), QA.bstride, nullptr, QA.f32 != 0);
+                      QA.box + ((int64_t)kind * cap + slot), QA.bstride, nullptr, QA.f32 != 0, QA.nrm_len);
 }
 
 // ------------------------------------------------------------- score ------
@@ -922,6 +922,7 @@ static PreArgs pre_args(rh_cloud *c, rh_batch_ws &w, const double *eps, const do
     for (int k = 0; k < 4; k++) { QA.eps[k] = eps ? eps[k] : 0.0; QA.cosa[k] = cosa ? cosa[k] : 0.0; }
     QA.coord_mag = c->coord_mag;
     QA.nrm_mag = c->nrm_mag;
+    QA.nrm_len = c->nrm_len;
     QA.f32 = c->f32 ? 1 : 0;
     QA.box = w.d_box;
     QA.bstride = 4 * w.batch_cap;

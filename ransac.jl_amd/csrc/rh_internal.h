@@ -39,6 +39,7 @@ enum rh_opt_id {
     RH_OPT_REFIT_PATH,
     RH_OPT_BATCHES_IN_FLIGHT,
     RH_OPT_ST_LIST_MB,
+    RH_OPT_NSIG,
     RH_OPT_N_PRODUCT,
     // A/B switches and diagnostics: alive in the diag build only (in the product build they read as unset)
     RH_OPT_CREATE_PROF = RH_OPT_N_PRODUCT, RH_OPT_AABB_HOST, RH_OPT_SUB_ORDER, RH_OPT_KD_HOST, RH_OPT_NO_SPREAD, RH_OPT_OCT_CHAIN_W,
@@ -299,6 +300,9 @@ struct rh_cloud {
     int64_t nst = 0;
     rh_dev<float> tile32;              // boxes of the tiles (4 consecutive groups: what a block of the culled score kernel stages; the diag build's pair census reads them), 8 floats each
     int64_t ntile = 0;
+    rh_dev<uint32_t> gm32;             // normal-cell masks of the groups (score4_device.h, nsig_cell): 96 bits in 4 words each, over ALL points of the group -- never rebuilt
+    rh_dev<uint32_t> stm32;            // ... of the super-tiles: the OR of their 16 groups' masks, 4 words each
+    double nrm_len = 0;                // largest finite normal length over the subset (0: not known), made with the masks
     rh_dev<double> dis_gb;             // boxes of the dis segment in use (7 x ng_pad)
     rh_dev<int32_t> d_ndis;            // device counter: entries in dis
     int64_t n_dis = 0;                 // host mirror

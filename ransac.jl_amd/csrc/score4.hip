@@ -43,6 +43,7 @@ using namespace rh4;
 typedef float rh_f32x4 __attribute__((ext_vector_type(4)));
 typedef float rh_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned long long rh_u64x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t rh_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int S4_TG = 4;                 // groups per tile (8, measured in round 4 -- the per-chunk work of stage 1 paid once per 8 box tests,
                                          // fuller batches: cfg3 0.0906 -> 0.0959 ms, cfg2 0.078 -> 0.104, cfg5 0.384 -> 0.375; R = 4 with it: worse still)
@@ -60,6 +61,7 @@ struct S4Shared {
     rh_f32x2 pb[S4_TG][S4_ROW];          // (ny, nz)
     uint64_t len[S4_TG];                 // enabled & valid bits of the groups
     rh_f32x4 gbox[S4_TG][2];             // the groups' binary32 boxes (cx cy cz hx | hy hz hr 0): stage 1 reads them as broadcasts
+    rh_u32x4 gmask[S4_TG];               // the groups' normal-cell masks (96 bits; all ones without masks: another point set, "nsig" off)
     uint16_t plist[R * 64 * S4_TG + 2];  // the block's surviving pairs: candidate of the row << S4_GB | group (+ a dump slot)
     uint16_t ctab[LIST ? R * 64 : 2];    // LIST: the bin slot of every candidate of the row (the row walks its super-tile's list)
     int32_t cntb[S4_W][64];              // cone: per-wave inlier counts of the batch's pairs
@@ -96,6 +98,7 @@ struct S4AllArgs {
     S4KindArgs k[4];
     int64_t ntiles, bstride, ngroups;
     const float *gb32;      // binary32 boxes of the groups, 8 floats each
+    const uint32_t *gm32;   // normal-cell masks of the groups, 4 words each (score4_device.h); null: no pair is ruled out by its normals
     // masks wanted: per candidate (as the caller numbers it) a LIST of its non-zero inlier words in internal (k-d leaf)
     // order -- entries of 16 bytes (word number, word), mstride of them per row at most; occ = one int32 cursor per row
     // (zero on entry)
@@ -122,7 +125,14 @@ struct S4AllArgs {
 #define S4_STAT(stats, idx, val) do { } while (0)
 #endif
 
-template <int KIND> struct S4Fields { static constexpr int NBOX = KIND == RH_PLANE || KIND == RH_SPHERE ? 5 : (KIND == RH_CYLINDER ? 9 : 11); };
+template <int KIND> struct S4Fields { static constexpr int NBOX = KIND == RH_PLANE ? 8 : (KIND == RH_SPHERE ? 5 : (KIND == RH_CYLINDER ? 9 : 11)); };
+
+// may a plane candidate (fields 5-7 of its culling record: the cells its inliers' normals can lie in) meet a group / super-tile
+// whose points' normals lie in the cells of gm?  (score4_device.h, normal cells)
+static __device__ __forceinline__ bool nsig_meet(const float (&B)[RH_BOX_FIELDS], const rh_u32x4 gm)
+{
+    return (((__builtin_bit_cast(uint32_t, B[5]) & gm.x) | (__builtin_bit_cast(uint32_t, B[6]) & gm.y)) | (__builtin_bit_cast(uint32_t, B[7]) & gm.z)) != 0u;
+}
 
 #define RH4_CONST_AS __attribute__((address_space(4)))
 
@@ -409,7 +419,9 @@ score4_segment(S4Shared<R, MASK, LIST> &sh, const S4KindArgs &K, const int32_t *
             const rh_f32x4 g0v = sh.gbox[g][0], g1v = sh.gbox[g][1];
             rh_box32 G;
             G.cx = g0v.x; G.cy = g0v.y; G.cz = g0v.z; G.hx = g0v.w; G.hy = g1v.x; G.hz = g1v.y; G.hr = g1v.z;
-            surv |= box_skip32<KIND>(B[h & 1], G) ? 0u : (1u << g);
+            bool skip = box_skip32<KIND>(B[h & 1], G);
+            if (KIND == RH_PLANE) skip |= !nsig_meet(B[h & 1], sh.gmask[g]);   // (no point of the group has a normal the candidate accepts)
+            surv |= skip ? 0u : (1u << g);
         }
         if (dbg == 2) surv = (1u << S4_TG) - 1u;
         surv &= live;
@@ -452,7 +464,7 @@ score4_segment(S4Shared<R, MASK, LIST> &sh, const S4KindArgs &K, const int32_t *
 template <class SH>
 static __device__ __forceinline__ void s4_stage(SH &sh, const double *__restrict__ pts, int64_t stride, int64_t s,
                                                 const uint64_t *__restrict__ enabled_words, const int64_t p0, const float *__restrict__ gb32,
-                                                const int64_t ngroups)
+                                                const uint32_t *__restrict__ gm32, const int64_t ngroups)
 {
     static_assert(S4_TG % S4_W == 0, "every wave stages S4_TG / S4_W groups");
     const int tid = threadIdx.x, lane = tid & 63;
@@ -490,6 +502,12 @@ static __device__ __forceinline__ void s4_stage(SH &sh, const double *__restrict
     if (tid < 2 * S4_TG) {   // the boxes, 32 bytes each
         const int64_t g = p0 / 64 + (tid >> 1);
         sh.gbox[tid >> 1][tid & 1] = ((const rh_f32x4 *)gb32)[(g < ngroups ? g : ngroups - 1) * 2 + (tid & 1)];
+    }
+    if (tid >= 64 && tid < 64 + S4_TG) {   // the normal-cell masks, 16 bytes each (the second wave: not behind the boxes' loads)
+        const int64_t g = p0 / 64 + (tid - 64);
+        rh_u32x4 m = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u };
+        if (gm32 != nullptr) m = ((const rh_u32x4 *)gm32)[g < ngroups ? g : ngroups - 1];
+        sh.gmask[tid - 64] = m;
     }
 }
 
@@ -545,7 +563,7 @@ score4_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const S
         if (slo < shi) {                                                                                               \
             if (ran) __syncthreads();   /* the previous segment's waves are done with the tile and the list */        \
             if (!ran || A.k[K].en != staged_en) {                                                                      \
-                s4_stage(sh, pts, stride, s, A.k[K].en, g0 * 64, A.gb32, A.ngroups);                                   \
+                s4_stage(sh, pts, stride, s, A.k[K].en, g0 * 64, A.gb32, A.gm32, A.ngroups);                                   \
                 staged_en = A.k[K].en;                                                                                 \
                 S4_STAT(A.stats, 96 + 1, 1);                                                                           \
             } else { S4_STAT(A.stats, 96 + 2, 1); if (threadIdx.x == 0) { sh.npairs = 0; sh.next_batch = 0; } }   /* same tile, same enabled words */   \
@@ -696,7 +714,7 @@ struct S4SoundArgs { double eps[4], cosa[4]; int f32; };
 
 template <int KIND>
 static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4SoundArgs &A, double x, double y, double z, double nx, double ny,
-                                                 double nz, const uint64_t valid, const rh_box32 &G, const rh_box32 &GS, const rh_box32 &GT, const int lane, unsigned long long *__restrict__ out)
+                                                 double nz, const uint64_t valid, const rh_box32 &G, const rh_box32 &GS, const rh_box32 &GT, const rh_u32x4 gm, const rh_u32x4 sm, const int lane, unsigned long long *__restrict__ out)
 {
     const double eps = A.eps[KIND], cosa = A.cosa[KIND];
     uint64_t ex;
@@ -735,6 +753,15 @@ static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4S
         if (stskip && ex != 0) atomicAdd(&out[52 + KIND], 1ULL);
         if (tlskip) atomicAdd(&out[56 + KIND], 1ULL);
         if (tlskip && ex != 0) atomicAdd(&out[60 + KIND], 1ULL);
+        if (KIND == RH_PLANE) {
+            // the normal-cell masks (planes): out[64] pairs the GROUP's mask rules out, out[65] VIOLATION: such a pair with an exact
+            // inlier, out[66] / out[67] the same for the SUPER-TILE's mask (the list launch)
+            const bool gskip = !nsig_meet(Q.box, gm), sskip = !nsig_meet(Q.box, sm);
+            if (gskip) atomicAdd(&out[64], 1ULL);
+            if (gskip && ex != 0) atomicAdd(&out[65], 1ULL);
+            if (sskip) atomicAdd(&out[66], 1ULL);
+            if (sskip && ex != 0) atomicAdd(&out[67], 1ULL);
+        }
         unsigned long long *o = out + KIND * 10;
         atomicAdd(&o[0], 1ULL);
         if (skip) atomicAdd(&o[1], 1ULL);
@@ -750,7 +777,7 @@ static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4S
 }
 
 __global__ void __launch_bounds__(64)
-cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const float *__restrict__ gb32, const float *__restrict__ st32, const float *__restrict__ tile32, const S4SoundCand *__restrict__ cands,
+cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const float *__restrict__ gb32, const float *__restrict__ st32, const float *__restrict__ tile32, const uint32_t *__restrict__ gm32, const uint32_t *__restrict__ stm32, const S4SoundCand *__restrict__ cands,
                  int ncand, const S4SoundArgs A, unsigned long long *__restrict__ out)
 {
     const int lane = threadIdx.x;
@@ -773,13 +800,14 @@ cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, cons
         const float *b = tile32 + (g / S4_TG) * 8;
         GT.cx = b[0]; GT.cy = b[1]; GT.cz = b[2]; GT.hx = b[3]; GT.hy = b[4]; GT.hz = b[5]; GT.hr = b[6];
     }
+    const rh_u32x4 gm = ((const rh_u32x4 *)gm32)[g], sm = ((const rh_u32x4 *)stm32)[g / S4_STG];
     for (int c = blockIdx.y; c < ncand; c += gridDim.y) {
         const S4SoundCand &Q = cands[c];
         switch (Q.kind) {
-        case RH_PLANE: sound_one<RH_PLANE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, lane, out); break;
-        case RH_SPHERE: sound_one<RH_SPHERE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, lane, out); break;
-        case RH_CYLINDER: sound_one<RH_CYLINDER>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, lane, out); break;
-        case RH_CONE: sound_one<RH_CONE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, lane, out); break;
+        case RH_PLANE: sound_one<RH_PLANE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
+        case RH_SPHERE: sound_one<RH_SPHERE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
+        case RH_CYLINDER: sound_one<RH_CYLINDER>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
+        case RH_CONE: sound_one<RH_CONE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
         default: break;
         }
     }
@@ -954,6 +982,48 @@ __global__ void st32_kernel(const double *__restrict__ gb, int64_t gstride, int6
     for (int k = 0; k < 8; k++) out[st * 8 + k] = bad ? __builtin_nanf("") : o[k];
 }
 
+// normal-cell masks of the groups (score4_device.h): a wave per group, lane = point; every point of the group counts, enabled
+// or not.  out: 4 words per group (96 bits + 0).  maxlen: the largest finite normal length seen (bits of a non-negative double).
+__global__ void __launch_bounds__(256)
+nsig_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, int64_t ngroups, uint32_t *__restrict__ out, unsigned long long *__restrict__ maxlen)
+{
+    __shared__ uint32_t m[4][4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t g = (int64_t)blockIdx.x * 4 + wv;
+    if (lane < 4) m[wv][lane] = 0u;
+    __syncthreads();
+    const int64_t i = g * 64 + lane;
+    double len = 0.0;
+    if (g < ngroups && i < s) {
+        const double nx = pts[3 * stride + i], ny = pts[4 * stride + i], nz = pts[5 * stride + i];
+        uint32_t w[3];
+        nsig_point_bits(nx, ny, nz, w);
+        if (w[0] != 0u) atomicOr(&m[wv][0], w[0]);
+        if (w[1] != 0u) atomicOr(&m[wv][1], w[1]);
+        if (w[2] != 0u) atomicOr(&m[wv][2], w[2]);
+        const double l = sqrt((nx * nx + ny * ny) + nz * nz);
+        if (l < __builtin_inf()) len = l;   // (NaN and inf: not a length; such a normal sets no bit or all of them)
+    }
+    unsigned long long lb = __builtin_bit_cast(unsigned long long, len);
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long v = __shfl_down(lb, off); lb = v > lb ? v : lb; }
+    if (lane == 0 && lb != 0ULL) atomicMax(maxlen, lb);
+    __syncthreads();
+    if (g < ngroups && lane < 4) out[g * 4 + lane] = m[wv][lane];
+}
+
+// ... of the super-tiles: the OR of their groups' masks
+__global__ void nsig_st_kernel(const uint32_t *__restrict__ gm, int64_t ngroups, int k_groups, int64_t nst, uint32_t *__restrict__ out)
+{
+    const int64_t st = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (st >= nst) return;
+    uint32_t w[4] = { 0u, 0u, 0u, 0u };
+    for (int64_t g = st * k_groups; g < (st + 1) * k_groups && g < ngroups; g++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) w[k] |= gm[g * 4 + k];
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[st * 4 + k] = w[k];
+}
+
 // ---- the super-tile lists of a batch.  One block per (super-tile, kind): the kind's candidates in bin order, 256 at a time,
 // lane = candidate, the culling record against the super-tile's box with the very test of stage 1 (box_skip32: a box that
 // holds all the points of its groups may be skipped only when none of them can pass) -- the survivors' bin slots, in order.
@@ -962,6 +1032,7 @@ struct StCullArgs {
     const int32_t *nk[4];
     int64_t bstride, stcap;
     const float *st32;
+    const uint32_t *stm32;   // normal-cell masks of the super-tiles (the OR of their groups'), 4 words each; null: not looked at
     uint16_t *stlist;
     int32_t *stcount;
 };
@@ -980,6 +1051,8 @@ static __device__ __forceinline__ void st_cull_kind(const StCullArgs &A, const i
         const float *b = A.st32 + st * 8;
         G.cx = b[0]; G.cy = b[1]; G.cz = b[2]; G.hx = b[3]; G.hy = b[4]; G.hz = b[5]; G.hr = b[6];
     }
+    rh_u32x4 GM = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u };
+    if (KIND == RH_PLANE && A.stm32 != nullptr) GM = ((const rh_u32x4 *)A.stm32)[st];
     uint16_t *__restrict__ list = A.stlist + (st * 4 + KIND) * A.stcap;
     constexpr int NB = S4Fields<KIND>::NBOX;
     const float *__restrict__ box = A.box[KIND];
@@ -997,6 +1070,7 @@ static __device__ __forceinline__ void st_cull_kind(const StCullArgs &A, const i
 #pragma unroll
         for (int q = 0; q < Q; q++) {
             keep[q] = j0 + q * 256 + tid < nk && !box_skip32<KIND>(B[q], G);
+            if (KIND == RH_PLANE) keep[q] = keep[q] && nsig_meet(B[q], GM);   // (no group of the super-tile holds a normal the candidate accepts)
             m[q] = WB(keep[q]);
             if (lane == 0) wsum[it & 1][q * 4 + wv] = __popcll(m[q]);
         }
@@ -1039,6 +1113,21 @@ int rhk_gb32_build(rh_cloud *c)
     if (c->tile32 != nullptr && c->ntile > 0)
         hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->ntile, 64)), dim3(64), 0, c->stream, c->gb, c->ng_pad, c->ngroups, S4_TG, c->ntile, c->tile32);
     RH_HIP(hipGetLastError());
+    // the normal-cell masks of subset 1 (score4_device.h), once per cloud: the points' normals never change, and the masks
+    // do not look at the enabled bits.  The largest normal length comes back with them (one wait, at creation).
+    c->nrm_len = 0.0;
+    if (c->gm32 != nullptr && c->stm32 != nullptr && c->s > 0) {
+        rh_dev<unsigned long long> d_len;
+        RH_TRY(d_len.alloc(1));
+        RH_HIP(hipMemsetAsync(d_len, 0, sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(nsig_kernel, dim3(cdiv4(c->ngroups, 4)), dim3(256), 0, c->stream, c->sub, c->s_pad, c->s, c->ngroups, c->gm32, d_len);
+        hipLaunchKernelGGL(nsig_st_kernel, dim3(cdiv4(c->nst, 64)), dim3(64), 0, c->stream, c->gm32, c->ngroups, S4_STG, c->nst, c->stm32);
+        RH_HIP(hipGetLastError());
+        unsigned long long h_len = 0;
+        RH_HIP(hipMemcpyAsync(&h_len, d_len, sizeof h_len, hipMemcpyDeviceToHost, c->stream));
+        RH_HIP(hipStreamSynchronize(c->stream));
+        c->nrm_len = __builtin_bit_cast(double, h_len);
+    }
     return RH_OK;
 }
 
@@ -1084,6 +1173,10 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
     A.bstride = job.bstride;
     A.ngroups = PS.ngroups;
     A.gb32 = PS.gb32;
+    // "nsig" (read on every launch; 0 = on, 2 = off): plane pairs are also ruled out by the groups' normal-cell masks -- on subset 1,
+    // whose masks the cloud holds; any other point set is walked by its boxes alone.  Counts and masks do not depend on it.
+    const bool nsig_on = on_subset && c->gm32 != nullptr && rh_opt_int(c, RH_OPT_NSIG, 0) != 2;
+    A.gm32 = nsig_on ? (const uint32_t *)c->gm32 : nullptr;
     A.masks = d_masks_int;
     A.occ = d_masks_int ? w.d_occ : nullptr;
     A.mstride = d_masks_int ? w.mstride4 : 0;
@@ -1132,7 +1225,7 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
     if (use_lists) {
         StCullArgs SA;
         for (int k = 0; k < 4; k++) { SA.box[k] = B.box[k]; SA.nk[k] = job.nk[k]; }
-        SA.bstride = job.bstride; SA.stcap = w.stlist_cap; SA.st32 = c->st32; SA.stlist = w.d_stlist; SA.stcount = w.d_stcount;
+        SA.bstride = job.bstride; SA.stcap = w.stlist_cap; SA.st32 = c->st32; SA.stm32 = nsig_on && c->stm32 != nullptr ? (const uint32_t *)c->stm32 : nullptr; SA.stlist = w.d_stlist; SA.stcount = w.d_stcount;
         hipLaunchKernelGGL(st_cull_kernel, dim3((unsigned)c->nst, 4), dim3(256), 0, c->stream, SA);
         A.stlist = w.d_stlist; A.stcount = w.d_stcount; A.stcap = w.stlist_cap;
         if (job.ev_listed != nullptr) RH_HIP(hipEventRecord(job.ev_listed, c->stream));
@@ -1231,7 +1324,7 @@ namespace {
 __global__ void __launch_bounds__(256)
 store_cls_kernel(const rh_prep *p0, const rh_prep *p1, const rh_prep *p2, const rh_prep *p3, int32_t n0, int32_t n1, int32_t n2, int32_t n3,
                  int32_t b1, int32_t b2, int32_t b3, int32_t total, double e0, double e1, double e2, double e3, double c0, double c1, double c2,
-                 double c3, double M, double Nm, rh_cls *__restrict__ cls, float *__restrict__ box, int64_t bstride)
+                 double c3, double M, double Nm, double Ln, rh_cls *__restrict__ cls, float *__restrict__ box, int64_t bstride)
 {
     const int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= total) return;
@@ -1242,7 +1335,7 @@ store_cls_kernel(const rh_prep *p0, const rh_prep *p1, const rh_prep *p2, const 
     const rh_prep *pp = q == 0 ? p0 : (q == 1 ? p1 : (q == 2 ? p2 : p3));
     const double eps = q == 0 ? e0 : (q == 1 ? e1 : (q == 2 ? e2 : e3)), cosa = q == 0 ? c0 : (q == 1 ? c1 : (q == 2 ? c2 : c3));
     const rh_prep P = pp[slot];
-    cls_make(P, q, eps, cosa, M, Nm, cls[g], box + g, bstride);
+    cls_make(P, q, eps, cosa, M, Nm, cls[g], box + g, bstride, nullptr, false, Ln);
 }
 }  // namespace
 
@@ -1252,7 +1345,7 @@ int rhk_store_cls(rh_cloud *c, const rh_prep *const prep[4], const int32_t n[4],
     if (pbase[4] <= 0) return RH_OK;
     hipLaunchKernelGGL(store_cls_kernel, dim3((unsigned)cdiv4(pbase[4], 256)), dim3(256), 0, c->stream, prep[0], prep[1], prep[2], prep[3], n[0], n[1],
                        n[2], n[3], pbase[1], pbase[2], pbase[3], pbase[4], eps[0], eps[1], eps[2], eps[3], cosa[0], cosa[1], cosa[2], cosa[3],
-                       c->coord_mag, c->nrm_mag, (rh_cls *)d_cls, d_box, bstride);
+                       c->coord_mag, c->nrm_mag, c->nrm_len, (rh_cls *)d_cls, d_box, bstride);
     RH_HIP(hipGetLastError());
     return RH_OK;
 }
@@ -1311,14 +1404,14 @@ extern "C" int rh_dbg_cls_audit(rh_cloud *c, const rh_shape *shapes, int32_t b, 
 }
 
 // diagnostics (tests, tools/fuzz_score.py): the decisions of the box test and of the classifier against the exact test
-// on every (candidate, point) of a batch x subset 1 (all points taken as enabled): 64 counters, layout at sound_one.
+// on every (candidate, point) of a batch x subset 1 (all points taken as enabled): 72 counters, layout at sound_one.
 // rh_dbg_cls_soundness hands out the first 56 (its callers' buffers hold that many), rh_dbg_cls_soundness_tiles the 8 of the
-// tile level.
+// tile level, rh_dbg_cls_soundness_nsig the 4 of the normal-cell masks.
 static int cls_soundness_run(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out, const int first, const int nout)
 {
     if (c == nullptr || out == nullptr || p == nullptr || b < 0 || (b > 0 && shapes == nullptr)) { rh_set_error("rh_dbg_cls_soundness: bad arguments"); return RH_E_INVALID; }
     for (int i = 0; i < nout; i++) out[i] = 0;
-    if (b == 0 || c->s == 0 || c->ngroups == 0 || c->gb32 == nullptr || c->st32 == nullptr || c->tile32 == nullptr) return RH_OK;
+    if (b == 0 || c->s == 0 || c->ngroups == 0 || c->gb32 == nullptr || c->st32 == nullptr || c->tile32 == nullptr || c->gm32 == nullptr || c->stm32 == nullptr) return RH_OK;
     RH_HIP(hipSetDevice(c->device));
     std::vector<S4SoundCand> h((size_t)b);
     for (int32_t i = 0; i < b; i++) {
@@ -1328,7 +1421,7 @@ static int cls_soundness_run(rh_cloud *c, const rh_shape *shapes, int32_t b, con
         if (Q.kind < 0 || Q.kind > 3) { Q.kind = -1; continue; }
         rh_prep_host(shapes[i], &Q.P);
         Q.Pf = prepf_of_kind(Q.P, Q.kind);
-        cls_make(Q.P, Q.kind, p->eps[Q.kind], p->cos_alpha[Q.kind], c->coord_mag, c->nrm_mag, Q.C, Q.box, 1, nullptr, c->f32);
+        cls_make(Q.P, Q.kind, p->eps[Q.kind], p->cos_alpha[Q.kind], c->coord_mag, c->nrm_mag, Q.C, Q.box, 1, nullptr, c->f32, c->nrm_len);
     }
     S4SoundArgs A;
     for (int k = 0; k < 4; k++) { A.eps[k] = p->eps[k]; A.cosa[k] = p->cos_alpha[k]; }
@@ -1336,12 +1429,12 @@ static int cls_soundness_run(rh_cloud *c, const rh_shape *shapes, int32_t b, con
     rh_dev<S4SoundCand> d_c;
     rh_dev<unsigned long long> d_o;
     RH_TRY(d_c.alloc(b));
-    RH_TRY(d_o.alloc(64));
+    RH_TRY(d_o.alloc(72));
     RH_HIP(hipMemcpyAsync(d_c, h.data(), sizeof(S4SoundCand) * (size_t)b, hipMemcpyHostToDevice, c->stream));
-    RH_HIP(hipMemsetAsync(d_o, 0, sizeof(unsigned long long) * 64, c->stream));
+    RH_HIP(hipMemsetAsync(d_o, 0, sizeof(unsigned long long) * 72, c->stream));
     hipLaunchKernelGGL(cls_sound_kernel, dim3((unsigned)c->ngroups, (unsigned)std::min<int32_t>(b, 64)), dim3(64), 0, c->stream, c->sub, c->s_pad, c->s,
-                       c->gb32, c->st32, c->tile32, d_c, b, A, d_o);
-    unsigned long long ho[64];
+                       c->gb32, c->st32, c->tile32, c->gm32, c->stm32, d_c, b, A, d_o);
+    unsigned long long ho[72];
     RH_HIP(hipMemcpyAsync(ho, d_o, sizeof ho, hipMemcpyDeviceToHost, c->stream));
     RH_HIP(hipStreamSynchronize(c->stream));
     for (int i = 0; i < nout; i++) out[i] = (uint64_t)ho[first + i];
@@ -1358,6 +1451,41 @@ extern "C" int rh_dbg_cls_soundness(rh_cloud *c, const rh_shape *shapes, int32_t
 extern "C" int rh_dbg_cls_soundness_tiles(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out)
 {
     return cls_soundness_run(c, shapes, b, p, out, 56, 8);
+}
+
+// the normal-cell masks in the same census (planes): out[0] = pairs (candidate, group) the group's mask rules out, out[1] =
+// VIOLATION: such a pair with an exact inlier, out[2] / out[3] = the same for the super-tile's mask
+extern "C" int rh_dbg_cls_soundness_nsig(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out)
+{
+    return cls_soundness_run(c, shapes, b, p, out, 64, 4);
+}
+
+// the candidate mask as the host builds it (cls_make on rh_prep_host's record: what the staged path uploads), and the cell
+// function on `ndirs` directions (-1: a zero or NaN vector, -2: an infinite component).  Host only: needs no GPU.
+extern "C" int rh_dbg_nsig(const rh_shape *shape, const rh_params *p, double M, double Nm, double Ln, int f32, uint32_t *mask_out,
+                           const double *dirs, int64_t ndirs, int32_t *cells_out)
+{
+    if (p == nullptr || ndirs < 0 || (ndirs > 0 && (dirs == nullptr || cells_out == nullptr)) || (shape != nullptr && mask_out == nullptr)) {
+        rh_set_error("rh_dbg_nsig: bad arguments");
+        return RH_E_INVALID;
+    }
+    if (shape != nullptr) {
+        if (shape->kind != RH_PLANE) { rh_set_error("rh_dbg_nsig: planes only"); return RH_E_INVALID; }
+        rh_prep P;
+        rh_prep_host(*shape, &P);
+        rh_cls C;
+        float box[RH_BOX_FIELDS];
+        cls_make(P, RH_PLANE, p->eps[RH_PLANE], p->cos_alpha[RH_PLANE], M, Nm, C, box, 1, nullptr, f32 != 0, Ln);
+        for (int k = 0; k < 3; k++) mask_out[k] = __builtin_bit_cast(uint32_t, box[5 + k]);
+    }
+    for (int64_t i = 0; i < ndirs; i++) {
+        uint32_t w[3];
+        nsig_point_bits(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], w);
+        if ((w[0] & w[1] & w[2]) == 0xffffffffu) cells_out[i] = -2;
+        else if ((w[0] | w[1] | w[2]) == 0u) cells_out[i] = -1;
+        else cells_out[i] = nsig_cell(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+    }
+    return RH_OK;
 }
 
 #endif   // RH_DIAG

@@ -70,7 +70,7 @@ constexpr int RH_CLS_FLAG = 15;   // NaN = exact-only
 // culling record of a candidate, structure-of-arrays over the batch (field f of slot i at box[f * stride + i]): what
 // the box tests of stage 1 read, coalesced, with lane = candidate
 constexpr int RH_BOX_FIELDS = 11;
-// plane:    0-2 oz | 3 -(oz . P0) | 4 eps + slack
+// plane:    0-2 oz | 3 -(oz . P0) | 4 eps + slack | 5-7 the 96 bits of the normal-cell mask, bit-cast (all ones: never skip)
 // sphere:   0-2 o | 3 A2 | 4 B2
 // cylinder: 0-2 a | 3-5 c0 | 6 (R + eps) + slack | 7 (R - eps) - slack | 8 max(1, |1 - |a|^2|)
 // cone:     0-2 apex | 3-5 a^ | 6 kk | 7 1 / cn | 8 (eps + slack) / cn | 9 beta | 10 alpha
@@ -85,13 +85,120 @@ __host__ __device__ inline float cls_up(double v) { return (float)(v + fabs(v) *
 // the old kernel's slack of the conservative stages: covers the exact test's own binary64 rounding (score_device.h)
 __host__ __device__ inline double cls_slack64(const rh_prep &P, double M) { return 1e-9 * ((1.0 + M) + P.f[11]); }
 
+// ---- Normal cells (planes).  The boxes of stage 1 know where a group's points lie, not where their normals point: three
+// quarters of the plane pairs that survive the boxes fail on the normal half of the test in every point.  The unit sphere
+// of directions is cut into RH_NSIG_CELLS = 96 cells (a cube map: 6 faces x 4 x 4); a group of subset 1 carries the set of
+// cells its points' normals fall in (96 bits, made once per cloud: nsig_kernel, score4.hip -- ALL points, enabled or not, so
+// that the set stays a superset through every extraction), a plane candidate the set of cells that can hold the normal of a
+// point it accepts (cls_make, fields 5-7 of the culling record).  A pair whose two sets do not meet is not walked.
+// Soundness -- a skipped pair holds no inlier:
+//   1. a point the exact test accepts has n . np > cos(alpha) as the exact test evaluates it; the true value of n . np
+//      then exceeds cos(alpha) - mN, mN being the margin cls_make derives for the classifier's normal half: it bounds a
+//      binary32 evaluation of this very dot product (tripled on a Float32 cloud, whose exact test IS such a chain), and the
+//      binary64 chain's rounding is 2^-29 of that;
+//   2. with |np| <= L (the largest finite normal length of the subset, nsig_kernel; without it sqrt(3) Nm) the direction
+//      d = np / |np| has n^ . d > (cos(alpha) - mN) / (L |n|) =: T, so d lies in the cone of half-angle theta = acos(T)
+//      about n^ -- normals of other lengths than 1 widen the cone, they never break it.  T <= 0 (a cone of 90 degrees or
+//      more), an exact-only candidate, cos(alpha) - mN <= 0 or anything non-finite: all 96 bits, never skip;
+//   3. nsig_cell(np) is the ONE definition of a cell, evaluated on the point side only (exact comparisons of the
+//      components, no division: a direction on a border belongs to the cell the comparisons say).  Every direction that
+//      nsig_cell maps to cell k lies within the angular radius r_k of the cell's centre c_k (closed cell: its borders and
+//      corners included; the radius is the angle to the farthest corner -- c . d along a great-circle arc shorter than pi
+//      takes its minimum at an end);
+//   4. hence angle(n^, c_k) <= theta + r_k, and the candidate's mask holds every cell with
+//      n^ . c_k >= cos(theta + r_k + slack) = T cos(r_k + slack) - sqrt(1 - T^2) sin(r_k + slack)  (theta + r_k < pi).
+// Slack: 2e-6 rad inside the table's cos / sin (the table's 17 digits and the candidate side's binary64 arithmetic -- the
+// normalisation of n, T, the square root where T is within 1e-16 of 1: together below 1e-7) and 1e-9 on T itself.
+constexpr int RH_NSIG_CELLS = 96;
+
+// cell of a direction with finite components, not all zero: face = the component of largest magnitude with its sign,
+// the other two components against +-1/2 of that magnitude and 0 (their quotients cut at -1/2, 0, 1/2)
+__host__ __device__ inline int nsig_cell(double x, double y, double z)
+{
+    const double ax = fabs(x), ay = fabs(y), az = fabs(z);
+    double m, a, b;
+    int axis;
+    if (ax >= ay && ax >= az) { axis = 0; m = x; a = y; b = z; }
+    else if (ay >= az) { axis = 1; m = y; a = z; b = x; }
+    else { axis = 2; m = z; a = x; b = y; }
+    const double h = 0.5 * fabs(m);
+    const int i = (a >= -h ? 1 : 0) + (a >= 0.0 ? 1 : 0) + (a >= h ? 1 : 0);
+    const int j = (b >= -h ? 1 : 0) + (b >= 0.0 ? 1 : 0) + (b >= h ? 1 : 0);
+    return (axis * 2 + (m < 0.0 ? 1 : 0)) * 16 + i * 4 + j;
+}
+
+// the bits a point's normal sets in its group's mask: an infinite component -- the exact test's dot product may be +inf --
+// sets all 96; a NaN or the zero vector nothing (n . np > cos(alpha) is false for them whenever cos(alpha) > 0, and a
+// candidate with cos(alpha) - mN <= 0 skips nothing)
+__host__ __device__ inline void nsig_point_bits(double nx, double ny, double nz, uint32_t w[3])
+{
+    w[0] = w[1] = w[2] = 0u;
+    const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
+    if (ax == __builtin_inf() || ay == __builtin_inf() || az == __builtin_inf()) { w[0] = w[1] = w[2] = 0xffffffffu; return; }
+    if (!(nx == nx) || !(ny == ny) || !(nz == nz) || (ax == 0.0 && ay == 0.0 && az == 0.0)) return;
+    const int k = nsig_cell(nx, ny, nz);
+    w[k >> 5] = 1u << (k & 31);
+}
+
+// the cells that can hold a direction d with n . d >= thr / L: the candidate's mask (all ones: never skip)
+__host__ __device__ inline void nsig_cand_mask(double nx, double ny, double nz, double thr, double L, uint32_t m[3])
+{
+    // centre (major, a, b) of the 16 cells of a face at quotients (-3/4, -1/4, 1/4, 3/4)^2, and cos / sin of the cell's angular
+    // radius (the angle to its farthest corner) + 2e-6: rows i * 4 + j as nsig_cell numbers them; the six faces permute them
+    static constexpr double tab[16][5] = {
+        { 0.68599434057003528, -0.51449575542752646, -0.51449575542752646, 0.97182484440108552, 0.23570420404567663 },
+        { 0.78446454055273618, -0.58834840541455213, -0.19611613513818404, 0.96076836812840516, 0.27735201964990502 },
+        { 0.78446454055273618, -0.58834840541455213, 0.19611613513818404, 0.96076836812840516, 0.27735201964990502 },
+        { 0.68599434057003528, -0.51449575542752646, 0.51449575542752646, 0.97182484440108552, 0.23570420404567663 },
+        { 0.78446454055273618, -0.19611613513818404, -0.58834840541455213, 0.96076836812840516, 0.27735201964990502 },
+        { 0.94280904158206347, -0.23570226039551587, -0.23570226039551587, 0.94280837491351122, 0.33333521895074958 },
+        { 0.94280904158206347, -0.23570226039551587, 0.23570226039551587, 0.94280837491351122, 0.33333521895074958 },
+        { 0.78446454055273618, -0.19611613513818404, 0.58834840541455213, 0.96076836812840516, 0.27735201964990502 },
+        { 0.78446454055273618, 0.19611613513818404, -0.58834840541455213, 0.96076836812840516, 0.27735201964990502 },
+        { 0.94280904158206347, 0.23570226039551587, -0.23570226039551587, 0.94280837491351122, 0.33333521895074958 },
+        { 0.94280904158206347, 0.23570226039551587, 0.23570226039551587, 0.94280837491351122, 0.33333521895074958 },
+        { 0.78446454055273618, 0.19611613513818404, 0.58834840541455213, 0.96076836812840516, 0.27735201964990502 },
+        { 0.68599434057003528, 0.51449575542752646, -0.51449575542752646, 0.97182484440108552, 0.23570420404567663 },
+        { 0.78446454055273618, 0.58834840541455213, -0.19611613513818404, 0.96076836812840516, 0.27735201964990502 },
+        { 0.78446454055273618, 0.58834840541455213, 0.19611613513818404, 0.96076836812840516, 0.27735201964990502 },
+        { 0.68599434057003528, 0.51449575542752646, 0.51449575542752646, 0.97182484440108552, 0.23570420404567663 },
+    };
+    m[0] = m[1] = m[2] = 0xffffffffu;
+    const double nn = sqrt((nx * nx + ny * ny) + nz * nz);
+    if (!(thr > 0.0) || !(L > 0.0) || !(nn > 0.0) || !cls_fin(thr) || !cls_fin(L) || !cls_fin(nn)) return;
+    double T = thr / (L * nn) * (1.0 - 1e-9);   // cos(theta), rounded towards the wider cone
+    if (!(T > 0.0)) return;
+    if (T > 1.0) T = 1.0;
+    const double Sn = sqrt(fmax(0.0, 1.0 - T * T));
+    const double ux = nx / nn, uy = ny / nn, uz = nz / nn;
+    // per face: (major, a, b) of the unit normal in the face's frame, nsig_cell's permutation
+    const double fm[3] = { ux, uy, uz }, fa[3] = { uy, uz, ux }, fb[3] = { uz, ux, uy };
+    uint32_t w0 = 0u, w1 = 0u, w2 = 0u;
+#pragma unroll
+    for (int axis = 0; axis < 3; axis++)
+#pragma unroll
+        for (int neg = 0; neg < 2; neg++) {
+            uint32_t bits = 0u;
+            for (int r = 0; r < 16; r++) {
+                const double c = ((neg ? -tab[r][0] : tab[r][0]) * fm[axis] + tab[r][1] * fa[axis]) + tab[r][2] * fb[axis];
+                bits |= c >= T * tab[r][3] - Sn * tab[r][4] ? (1u << r) : 0u;
+            }
+            const int f = axis * 2 + neg;   // 16 bits per face, two faces per word
+            if (f < 2) w0 |= bits << (16 * (f & 1));
+            else if (f < 4) w1 |= bits << (16 * (f & 1));
+            else w2 |= bits << (16 * (f & 1));
+        }
+    m[0] = w0; m[1] = w1; m[2] = w2;
+}
+
 // P: the binary64 record of the candidate (rh_prep, kernels.hip prep_one, with prep_derived); eps, cosa: the kind's
 // thresholds; M, Nm: max |coordinate| / max |normal component| of the point set.  o: classifier record; box: the culling
 // record's fields go to box[f * bstride] (f < RH_BOX_FIELDS).
 // dbg4 (audit): the unscaled thresholds and widths behind a scaled record: cN_hi, wN, eD_lo, wD
 __host__ __device__ inline void cls_make(const rh_prep &P, int kind, double eps, double cosa, double M, double Nm, rh_cls &o,
-                                         float *box, int64_t bstride, double *dbg4 = nullptr, bool f32cloud = false)
+                                         float *box, int64_t bstride, double *dbg4 = nullptr, bool f32cloud = false, double Ln = 0.0)
 {
+    // Ln: the largest finite normal LENGTH of the point set (0: not known -- sqrt(3) Nm bounds it), for the plane's normal-cell mask
     // f32cloud: the EXACT test of this cloud is itself a binary32 chain without fused operations (Float32 cloud,
     // score_device.h with T = float: 1.3 - 2 x the rounding steps of the classifier's chain on the same magnitudes).  Every margin
     // is tripled: one part for the classifier's own error, two for the exact chain's.
@@ -133,6 +240,13 @@ __host__ __device__ inline void cls_make(const rh_prep &P, int kind, double eps,
             if (dbg4 != nullptr) { dbg4[0] = cNhi; dbg4[1] = wN; dbg4[2] = eDlo; dbg4[3] = wD; }
             for (int i = 0; i < 9; i++) ok = ok && fabs((double)o.f[i]) < 1e30;
         }
+        // the normal-cell mask (nsig_cand_mask above): whatever the box fields are, all ones unless the record decides points
+        uint32_t cm[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu };
+        if (ok) {
+            const double Lb = 1.7320508075688774 * Nm * (1.0 + 1e-12);
+            nsig_cand_mask(P.f[3], P.f[4], P.f[5], cosa - mN, (Ln > 0.0 && Ln < Lb ? Ln * (1.0 + 1e-12) : Lb), cm);
+        }
+        bx[5] = __builtin_bit_cast(float, cm[0]); bx[6] = __builtin_bit_cast(float, cm[1]); bx[7] = __builtin_bit_cast(float, cm[2]);
         if (fin && cls_fin(zp) && cls_fin(eps) && cls_fin(M)) {
             // box: d(centre) against eps + sum |oz_i| h_i; binary32 error of both sides + the binary64 test's own slack
             const double sB = S * 10.1 * u * (z1 * M + fabs(zp)) + mRef + slack64;

@@ -76,6 +76,7 @@ def one(case, rng, f32=False):
     else:
         pc = R.RANSACCloud(xyz, nrm, subs)
         oc = orc.Cloud(xyz, nrm, subs[0])
+    R.set_option("nsig", 2 if case % 3 == 2 else None, cloud=pc)   # normal-cell masks of the plane pairs: on, every third case off (this cloud only; by the case number: the draws stay what they were)
     en = rng.random(n) < float(rng.choice([1.0, 0.9, 0.3, 0.01]))
     pc.set_enabled(en)
     bits = np.zeros(((n + 63) // 64) * 64, dtype=np.uint8); bits[:n] = en
