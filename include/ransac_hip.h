@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 120
+#define RH_VERSION 121
 
 enum {
     RH_OK = 0,
@@ -716,6 +716,65 @@ int rh_cluster(const double *xyz_aos, int64_t n, const rh_cluster_params *p, int
 int rh_cluster_f32(const float *xyz_aos, int64_t n, const rh_cluster_params *p, int device, int32_t *labels_out,
                    uint8_t *kind_out_or_null, int64_t cap, int64_t *counts_out_or_null, int64_t *offsets_out_or_null,
                    int64_t *idx_out_or_null, int64_t *n_clusters_out, rh_cluster_stats *stats_or_null);
+
+/* ---- consistent orientation of normals without a viewpoint: sign propagation along a minimum spanning forest of the
+ *      neighbour graph (Hoppe et al. 1992; no counterpart in the reference, which starts from oriented normals) ----
+ * Every per-point test of the engine is sign sensitive (isparallel is dot(v1, v2) > cos(alpha), src/utilities.jl:115-117),
+ * and rh_estimate_normals can fix the sign only from a viewpoint or hints.  A merged, thinned or registered cloud has
+ * neither; this call turns its normals so that neighbouring normals agree.  Points p_0 .. p_(n-1) and normals n_i (binary64
+ * array-of-structures, the normals used as given, not renormalised), k in 1 .. RH_KNN_MAX_K, radius (0 = none), anchor, up.
+ *  1. VERTICES.  V = the points whose normal is not (0, 0, 0) (all three components == 0.0).  The degenerate points of
+ *     rh_estimate_normals take no part and come back untouched;
+ *  2. EDGES.  {i, j}, i < j, is an edge when both are in V and j is among rh_knn's neighbours of i for (k, radius) or i is
+ *     among those of j.  The search runs over all n points, exactly rh_knn's; edges that touch a point outside V are
+ *     dropped afterwards;
+ *  3. WEIGHT.  dot_ij = (ni.x*nj.x + ni.y*nj.y) + ni.z*nj.z in binary64, each operation rounded on its own, no contraction
+ *     (bit-symmetric in i and j).  a_ij = |dot_ij|, s_ij = (dot_ij < 0);
+ *  4. ORDER.  The edges are totally ordered by descending a, then ascending i, then ascending j (Hoppe's 1 - |ni.nj|
+ *     without the subtraction);
+ *  5. FOREST.  F = the minimum spanning forest under that order.  The order is total, so F is unique and depends on no
+ *     order of processing;
+ *  6. PARITY.  Within a tree par(i) ^ par(j) = the XOR of s along the tree path from i to j;
+ *  7. ANCHOR of every component (tree):
+ *     RH_ORI_ANCHOR_FIRST: the component's smallest index, kept as given: want = 0;
+ *     RH_ORI_ANCHOR_TOP:   the point of largest t = ((x*up.x + y*up.y) + z*up.z) + 0.0 (a NaN t counts as -inf), ties to the
+ *                          smaller index; want = (((n.x*up.x + n.y*up.y) + n.z*up.z) < 0) for its normal n: the topmost
+ *                          normal points up (Hoppe's rule: outward normals on a closed surface);
+ *  8. FLIP.  flip_i = par(i) ^ par(anchor) ^ want.  The output normal is the input with all three components negated when
+ *     flip_i is set and bit-identical otherwise;
+ *  9. OUTPUTS.  nrm_out: n x 3, may be the input pointer.  flip_out (optional) int32 [n]: 1 flipped, 0 kept, -1 outside V.
+ *     comp_out (optional) int32 [n]: the components numbered 1 .. M by their smallest index, 0 outside V.  stats (optional):
+ *       n_vertices = |V|; n_edges; n_components = M; n_tree_edges = n_vertices - n_components; n_flipped;
+ *       n_inconsistent = the edges with s_ij ^ flip_i ^ flip_j set: their ends disagree in sign AFTER the orientation, and
+ *                        every one of them is a non-tree edge;
+ *       largest_component = the size of the largest component (0 when V is empty);
+ *       min_tree_absdot = the smallest a over F, +inf without a tree edge.
+ *     The last two say how far to trust the result;
+ * 10. RH_E_INVALID, decided before the device is touched: k outside 1 .. 63, radius negative or not finite, anchor outside
+ *     0 .. 1, with RH_ORI_ANCHOR_TOP an up that is not finite or all zero, n < 1, n >= 2^31 - 1, n*k >= 2^31 (the directed
+ *     pairs are counted in 31 bits), a null xyz / nrm / params / nrm_out; found on the device, nothing is written: a
+ *     coordinate that is not finite, a normal component that is not finite or exceeds 2 in magnitude;
+ * 11. the _f32 entry widens coordinates and normals exactly, decides everything in binary64 and negates the float normals:
+ *     negation is exact, no rounding appears anywhere.
+ * Every decision is a comparison of binary64 values of fixed expressions or integer arithmetic: the same bits on every
+ * run.  The array arguments may be host or device pointers (the copies are hipMemcpyDefault); params and stats are host
+ * memory.  The neighbour lists never leave the device. */
+enum { RH_ORI_ANCHOR_FIRST = 0, RH_ORI_ANCHOR_TOP = 1 };
+typedef struct {
+    int32_t k;               /* 1 .. RH_KNN_MAX_K */
+    int32_t anchor;          /* RH_ORI_ANCHOR_* */
+    double radius;           /* 0 = no limit */
+    double up[3];            /* RH_ORI_ANCHOR_TOP */
+} rh_orient_params;
+typedef struct {
+    int64_t n_vertices, n_edges, n_components, n_tree_edges;
+    int64_t n_flipped, n_inconsistent, largest_component;
+    double min_tree_absdot;
+} rh_orient_stats;
+int rh_orient_normals(const double *xyz_aos, const double *nrm_aos, int64_t n, const rh_orient_params *p, int device,
+                      double *nrm_out_aos, int32_t *flip_out_or_null, int32_t *comp_out_or_null, rh_orient_stats *stats_or_null);
+int rh_orient_normals_f32(const float *xyz_aos, const float *nrm_aos, int64_t n, const rh_orient_params *p, int device,
+                          float *nrm_out_aos, int32_t *flip_out_or_null, int32_t *comp_out_or_null, rh_orient_stats *stats_or_null);
 
 /* ---- nearest neighbours of query points in ANOTHER cloud, and cloud-to-cloud distances on them (no counterpart in the
  *      reference, which works on one cloud) ----

@@ -480,6 +480,66 @@ function estimatenormals(vertices::AbstractVector{SVector{3,T}}; k::Integer = 16
     return out
 end
 
+# ---- consistent orientation of normals without a viewpoint (rh_orient_normals) ----
+# typedef struct { int32_t k; int32_t anchor; double radius; double up[3]; } rh_orient_params;   (40 bytes)
+struct RhOrientParams
+    k::Cint
+    anchor::Cint
+    radius::Cdouble
+    up::NTuple{3,Cdouble}
+end
+# typedef struct { int64_t n_vertices, n_edges, n_components, n_tree_edges, n_flipped, n_inconsistent, largest_component;
+#                  double min_tree_absdot; } rh_orient_stats;   (64 bytes)
+struct RhOrientStats
+    n_vertices::Int64
+    n_edges::Int64
+    n_components::Int64
+    n_tree_edges::Int64
+    n_flipped::Int64
+    n_inconsistent::Int64
+    largest_component::Int64
+    min_tree_absdot::Cdouble
+end
+
+"""
+    orientnormals(vertices, normals; k = 16, radius = 0.0, anchor = :top, up = (0, 0, 1)) -> (normals, flip, component, stats)
+
+Turns the normals of a cloud without a viewpoint so that neighbouring normals agree (`rh_orient_normals`,
+include/ransac_hip.h has the definition in full): the sign is carried along the minimum spanning forest of the
+k-nearest-neighbour graph, edges ordered by descending `|ni . nj|`, then by index.  Every connected part is turned as a
+whole: `anchor = :top` makes the normal of its topmost point along `up` point up, `:first` keeps the normal of its
+smallest index.  Points with a zero normal take no part.  `flip[i]`: 1 flipped, 0 kept, -1 zero normal; `component[i]`:
+1 to M by smallest index, 0 for a zero normal; `stats`: an `RhOrientStats`.
+"""
+function orientnormals(vertices::AbstractVector{SVector{3,T}}, normals::AbstractVector{SVector{3,T}}; k::Integer = 16,
+                       radius::Real = 0.0, anchor::Symbol = :top, up = (0, 0, 1),
+                       device::Integer = 0) where {T<:Union{Float32,Float64}}
+    anchor in (:first, :top) || error("orientnormals: anchor is :first or :top")
+    length(normals) == length(vertices) || error("orientnormals: $(length(normals)) normals for $(length(vertices)) points")
+    p = RhOrientParams(k, anchor === :first ? 0 : 1, radius, ntuple(i -> Cdouble(up[i]), 3))
+    vs = convert(Vector{SVector{3,T}}, vertices)
+    ns = convert(Vector{SVector{3,T}}, normals)
+    n = length(vs)
+    out = Vector{SVector{3,T}}(undef, n)
+    flip = zeros(Int32, max(n, 1))
+    comp = zeros(Int32, max(n, 1))
+    st = Ref(RhOrientStats(0, 0, 0, 0, 0, 0, 0, Inf))
+    GC.@preserve vs ns out flip comp begin
+        if T == Float32
+            check(ccall((:rh_orient_normals_f32, LIB), Cint,
+                (Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ref{RhOrientParams}, Cint, Ptr{Cfloat}, Ptr{Int32}, Ptr{Int32}, Ref{RhOrientStats}),
+                pointer(reinterpret(Float32, vs)), pointer(reinterpret(Float32, ns)), n, p, device,
+                pointer(reinterpret(Float32, out)), flip, comp, st))
+        else
+            check(ccall((:rh_orient_normals, LIB), Cint,
+                (Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ref{RhOrientParams}, Cint, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Ref{RhOrientStats}),
+                pointer(reinterpret(Float64, vs)), pointer(reinterpret(Float64, ns)), n, p, device,
+                pointer(reinterpret(Float64, out)), flip, comp, st))
+        end
+    end
+    return out, resize!(flip, n), resize!(comp, n), st[]
+end
+
 # ---- voxel-grid downsampling of a raw cloud (rh_voxel_downsample; the reference leaves thinning to the user) ----
 # typedef struct { double beta; int32_t mode; int32_t flags; } rh_voxel_params;   (16 bytes)
 struct RhVoxelParams

@@ -87,6 +87,18 @@ class ClusterStats(C.Structure):
                 ("n_small", C.c_int64), ("largest", C.c_int64)]
 
 
+class OrientParams(C.Structure):
+    """rh_orient_params (include/ransac_hip.h)"""
+    _fields_ = [("k", C.c_int32), ("anchor", C.c_int32), ("radius", C.c_double), ("up", C.c_double * 3)]
+
+
+class OrientStats(C.Structure):
+    """rh_orient_stats (include/ransac_hip.h)"""
+    _fields_ = [("n_vertices", C.c_int64), ("n_edges", C.c_int64), ("n_components", C.c_int64), ("n_tree_edges", C.c_int64),
+                ("n_flipped", C.c_int64), ("n_inconsistent", C.c_int64), ("largest_component", C.c_int64),
+                ("min_tree_absdot", C.c_double)]
+
+
 class DistanceParams(C.Structure):
     """rh_distance_params (include/ransac_hip.h)"""
     _fields_ = [("radius", C.c_double), ("threshold", C.c_double), ("metric", C.c_int32), ("reserved", C.c_int32)]
@@ -118,6 +130,7 @@ OUT_BLOCK_POINTS = 1024
 OUT_STATISTICAL, OUT_ABSOLUTE, OUT_RADIUS = 0, 1, 2
 CLUSTER_BY_INDEX, CLUSTER_BY_SIZE = 0, 1
 PT_NOISE, PT_BORDER, PT_CORE = 0, 1, 2
+ORI_ANCHOR_FIRST, ORI_ANCHOR_TOP = 0, 1
 VOX_FIRST, VOX_CENTROID = 0, 1
 VOX_ALIGN_NORMALS = 1
 EXT_EMPTY, EXT_NO_DIRECTION, EXT_INVALID = 1, 2, 4
@@ -234,6 +247,9 @@ SIGNATURES = {
                              C.POINTER(ClusterStats)]),
     "rh_cluster_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(ClusterParams), C.c_int, _i32p, _u8p, C.c_int64, _i64p,
                                  _i64p, _i64p, _i64p, C.POINTER(ClusterStats)]),
+    "rh_orient_normals": (C.c_int, [_dp, _dp, C.c_int64, C.POINTER(OrientParams), C.c_int, _dp, _i32p, _i32p, C.POINTER(OrientStats)]),
+    "rh_orient_normals_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(OrientParams), C.c_int,
+                                        C.POINTER(C.c_float), _i32p, _i32p, C.POINTER(OrientStats)]),
     "rh_voxel_downsample": (C.c_int, [_dp, _dp, C.c_int64, C.POINTER(VoxelParams), C.c_int, _dp, _dp, _i64p, _i32p, C.c_int64,
                                       _i32p, _i64p, _i64p]),
     "rh_voxel_downsample_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(VoxelParams), C.c_int,

@@ -761,15 +761,25 @@ def refit_lsq(s, pc, params, max_iter=10):
 
 
 def estimatenormals(vertices, k=16, radius=0.0, viewpoint=None, hints=None, device=0, return_curvature=False,
-                    return_flags=False):
+                    return_flags=False, consistent=False):
     """Oriented normals for a cloud without them (rh_estimate_normals: PCA of the k nearest neighbours, the step
     docs/src/ransac.md:13 leaves to the user).  vertices: (n, 3) float64 or float32; the result has that dtype and
     feeds RANSACCloud(vertices, normals, subsets) as is.  radius > 0 drops neighbours farther than it; viewpoint
     (3-vector) turns every normal towards it, hints ((n, 3), e.g. scanner directions or rough normals) along them;
     neither: the largest component positive.  Degenerate points get (0, 0, 0) and flag 1.
+    consistent=True (a cloud with neither viewpoint nor hints): the normals of the canonical sign are then turned by
+    orientnormals with the same k (63 at most) and radius (anchor "top", up = +z), so that neighbouring normals agree.
     Returns normals, then curvature and / or flags when asked for."""
     if viewpoint is not None and hints is not None:
         raise ValueError("estimatenormals: give a viewpoint or hints, not both")
+    if consistent:
+        if viewpoint is not None or hints is not None:
+            raise ValueError("estimatenormals: consistent=True is for clouds with neither a viewpoint nor hints")
+        out = estimatenormals(vertices, k=k, radius=radius, device=device, return_curvature=return_curvature,
+                              return_flags=return_flags)
+        out = out if isinstance(out, tuple) else (out,)
+        out = (orientnormals(vertices, out[0], k=k, radius=radius, device=device),) + out[1:]
+        return out[0] if len(out) == 1 else out
     f32 = np.asarray(vertices).dtype == np.float32
     t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
     xyz = np.ascontiguousarray(vertices, dtype=t).reshape(-1, 3)
@@ -792,6 +802,44 @@ def estimatenormals(vertices, k=16, radius=0.0, viewpoint=None, hints=None, devi
              None if curv is None else _p(curv, ct), None if flags is None else _p(flags, C.c_int32)))
     out = (nrm,) + ((curv,) if return_curvature else ()) + ((flags,) if return_flags else ())
     return out[0] if len(out) == 1 else out
+
+
+def orientnormals(vertices, normals, k=16, radius=0.0, anchor="top", up=(0, 0, 1), device=0, return_info=False):
+    """Turn the normals of a cloud so that neighbouring normals agree, without a viewpoint (rh_orient_normals;
+    include/ransac_hip.h has the definition in full): the sign is carried along the minimum spanning forest of the
+    k-nearest-neighbour graph (knn's neighbours for k and radius, either way round), whose edges are ordered by descending
+    |ni . nj|, then by their indices (Hoppe et al. 1992).  Every connected part of the graph is turned as a whole:
+    anchor "top" makes the normal of its topmost point along `up` point up (outward normals on a closed surface),
+    "first" keeps the normal of its smallest index as given.  Points with a zero normal (the degenerate points of
+    estimatenormals) take no part.  vertices, normals: (n, 3), both float32 take the float32 entry, otherwise float64.
+    Returns the normals (a normal is either kept bit for bit or negated), with return_info also a dict: flip (int32 per
+    point: 1 flipped, 0 kept, -1 zero normal), component (int32, 1 .. M by smallest index, 0 for a zero normal) and the
+    stats n_vertices, n_edges, n_components, n_tree_edges, n_flipped, n_inconsistent (edges whose ends still disagree),
+    largest_component and min_tree_absdot (the weakest link the sign was carried over)."""
+    anchors = {"first": L.ORI_ANCHOR_FIRST, "top": L.ORI_ANCHOR_TOP}
+    if isinstance(anchor, str) and anchor not in anchors:
+        raise ValueError("orientnormals: anchor %r is neither 'first' nor 'top'" % (anchor,))
+    f32 = np.asarray(vertices).dtype == np.float32 and np.asarray(normals).dtype == np.float32
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    xyz = np.ascontiguousarray(vertices, dtype=t).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, dtype=t).reshape(-1, 3)
+    n = xyz.shape[0]
+    if nrm.shape[0] != n:
+        raise ValueError("orientnormals: %d normals for %d points" % (nrm.shape[0], n))
+    prm = L.OrientParams(k=int(k), anchor=int(anchors.get(anchor, anchor)), radius=float(radius))
+    prm.up[:] = [float(x) for x in np.asarray(up, dtype=np.float64).reshape(3)]
+    out = np.array(nrm)
+    flip = np.full(max(n, 1), -1, dtype=np.int32) if return_info else None
+    comp = np.zeros(max(n, 1), dtype=np.int32) if return_info else None
+    st = L.OrientStats()
+    fn = lib().rh_orient_normals_f32 if f32 else lib().rh_orient_normals
+    check(fn(_p(xyz, ct), _p(nrm, ct), n, C.byref(prm), device, _p(out, ct), None if flip is None else _p(flip, C.c_int32),
+             None if comp is None else _p(comp, C.c_int32), C.byref(st)))
+    if not return_info:
+        return out
+    info = {f: getattr(st, f) for f, _ in L.OrientStats._fields_}
+    info.update(flip=flip[:n], component=comp[:n])
+    return out, info
 
 
 def knn(vertices, k, radius=0.0, return_dist=True, return_count=False, device=0):
