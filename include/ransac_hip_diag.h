@@ -46,6 +46,17 @@ int rh_dbg_cls_soundness_nsig(rh_cloud *c, const rh_shape *shapes, int32_t b, co
  * (-1: a zero vector or a NaN, which set no bit; -2: an infinite component, which sets all).  Needs no GPU. */
 int rh_dbg_nsig(const rh_shape *shape, const rh_params *p, double M, double Nm, double Ln, int f32, uint32_t *mask_out /* [3] */,
                 const double *dirs, int64_t ndirs, int32_t *cells_out);
+/* The binary64 boxes of the 64-point groups of subset 1 in the library's own (k-d leaf) order: out[6 g ..] = centre and half
+ * extents of group g; *ngroups_out: their number (out = NULL or cap < that number: only the number is returned). */
+int rh_dbg_group_boxes(rh_cloud *c, double *out, int64_t cap, int64_t *ngroups_out);
+/* The box test of a cylinder candidate as the score kernel's stage 1 runs it, on the host (csrc/score4_device.h: cls_make on the
+ * host's record, box_to_f32, cyl_box_skip32 -- the very code of the kernel).  boxes[6 i ..]: centre and half extents of the n
+ * binary64 boxes; skip_out[i]: 1 = the box is skipped for the candidate; ball_out[i]: the same by the two clauses alone that
+ * bound the box by its half diagonal (the test without the support clause); fields_out (may be NULL): the RH_BOX_FIELDS = 11
+ * fields of the culling record (field 6: (R + eps) + slack, field 9: A^2 of the support clause; NaN: never skip).
+ * Needs no GPU. */
+int rh_dbg_cylbox(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, const double *boxes, int64_t n,
+                  uint8_t *skip_out, uint8_t *ball_out, float *fields_out /* [11] */);
 /* The device's octree sampler finds a point's cell and the r-th enabled point of a cell with a cell directory and
  * bracketed 8-ary searches (csrc/fit_shared.h: cell_bounds_code, lower_bound_in, select_in, select_in_many, select_bit)
  * where the host form uses plain binary searches.  Host-only self-check of those routines against the plain ones on a

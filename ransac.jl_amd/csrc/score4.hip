@@ -125,7 +125,7 @@ struct S4AllArgs {
 #define S4_STAT(stats, idx, val) do { } while (0)
 #endif
 
-template <int KIND> struct S4Fields { static constexpr int NBOX = KIND == RH_PLANE ? 8 : (KIND == RH_SPHERE ? 5 : (KIND == RH_CYLINDER ? 9 : 11)); };
+template <int KIND> struct S4Fields { static constexpr int NBOX = KIND == RH_PLANE ? 8 : (KIND == RH_SPHERE ? 5 : (KIND == RH_CYLINDER ? 10 : 11)); };
 
 // may a plane candidate (fields 5-7 of its culling record: the cells its inliers' normals can lie in) meet a group / super-tile
 // whose points' normals lie in the cells of gm?  (score4_device.h, normal cells)
@@ -1484,6 +1484,53 @@ extern "C" int rh_dbg_nsig(const rh_shape *shape, const rh_params *p, double M, 
         if ((w[0] & w[1] & w[2]) == 0xffffffffu) cells_out[i] = -2;
         else if ((w[0] | w[1] | w[2]) == 0u) cells_out[i] = -1;
         else cells_out[i] = nsig_cell(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+    }
+    return RH_OK;
+}
+
+// the binary64 boxes of the 64-point groups of subset 1, in group order: out[6 g ..] = centre, half extents; *ngroups_out: how
+// many there are (out = null or cap too small: only the number)
+extern "C" int rh_dbg_group_boxes(rh_cloud *c, double *out, int64_t cap, int64_t *ngroups_out)
+{
+    if (c == nullptr || ngroups_out == nullptr || cap < 0) { rh_set_error("rh_dbg_group_boxes: bad arguments"); return RH_E_INVALID; }
+    *ngroups_out = c->gb == nullptr ? 0 : c->ngroups;
+    if (out == nullptr || cap < *ngroups_out || *ngroups_out == 0) return RH_OK;
+    RH_HIP(hipSetDevice(c->device));
+    std::vector<double> h((size_t)c->ngroups * 6);
+    const double *gb = c->gb;
+    for (int k = 0; k < 6; k++)
+        RH_HIP(hipMemcpyAsync(h.data() + (size_t)k * c->ngroups, gb + (int64_t)k * c->ng_pad, sizeof(double) * (size_t)c->ngroups, hipMemcpyDeviceToHost, c->stream));
+    RH_HIP(hipStreamSynchronize(c->stream));
+    for (int64_t g = 0; g < c->ngroups; g++)
+        for (int k = 0; k < 6; k++) out[6 * g + k] = h[(size_t)k * c->ngroups + g];
+    return RH_OK;
+}
+
+// the cylinder's box test as the host runs it: the culling record cls_make builds for the shape (fields_out[RH_BOX_FIELDS]), and
+// for each of the n binary64 boxes (centre, half extents: boxes[6 i ..]), converted by box_to_f32 like a group's, the decision
+// of the kernel's own function (skip_out) and of its two ball clauses alone (ball_out).  Host only: needs no GPU.
+extern "C" int rh_dbg_cylbox(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, const double *boxes, int64_t n,
+                             uint8_t *skip_out, uint8_t *ball_out, float *fields_out)
+{
+    if (shape == nullptr || p == nullptr || n < 0 || (n > 0 && (boxes == nullptr || skip_out == nullptr || ball_out == nullptr))) {
+        rh_set_error("rh_dbg_cylbox: bad arguments");
+        return RH_E_INVALID;
+    }
+    if (shape->kind != RH_CYLINDER) { rh_set_error("rh_dbg_cylbox: cylinders only"); return RH_E_INVALID; }
+    rh_prep P;
+    rh_prep_host(*shape, &P);
+    rh_cls C;
+    float box[RH_BOX_FIELDS];
+    cls_make(P, RH_CYLINDER, p->eps[RH_CYLINDER], p->cos_alpha[RH_CYLINDER], M, Nm, C, box, 1, nullptr, f32 != 0);
+    if (fields_out != nullptr)
+        for (int k = 0; k < RH_BOX_FIELDS; k++) fields_out[k] = box[k];
+    for (int64_t i = 0; i < n; i++) {
+        float o[8];
+        box_to_f32(boxes + 6 * i, boxes + 6 * i + 3, o);
+        rh_box32 G;
+        G.cx = o[0]; G.cy = o[1]; G.cz = o[2]; G.hx = o[3]; G.hy = o[4]; G.hz = o[5]; G.hr = o[6];
+        skip_out[i] = cyl_box_skip32<true>(box, G) ? 1 : 0;
+        ball_out[i] = cyl_box_skip32<false>(box, G) ? 1 : 0;
     }
     return RH_OK;
 }

@@ -72,7 +72,7 @@ constexpr int RH_CLS_FLAG = 15;   // NaN = exact-only
 constexpr int RH_BOX_FIELDS = 11;
 // plane:    0-2 oz | 3 -(oz . P0) | 4 eps + slack | 5-7 the 96 bits of the normal-cell mask, bit-cast (all ones: never skip)
 // sphere:   0-2 o | 3 A2 | 4 B2
-// cylinder: 0-2 a | 3-5 c0 | 6 (R + eps) + slack | 7 (R - eps) - slack | 8 max(1, |1 - |a|^2|)
+// cylinder: 0-2 a | 3-5 c0 | 6 (R + eps) + slack | 7 (R - eps) - slack | 8 max(1, |1 - |a|^2|) | 9 A2 of the support clause
 // cone:     0-2 apex | 3-5 a^ | 6 kk | 7 1 / cn | 8 (eps + slack) / cn | 9 beta | 10 alpha
 constexpr float RH_CONE_ALPHA = (float)((RH_CLS_SAFETY * 49.0 + 64.0) * RH_CLS_U);
 
@@ -110,6 +110,40 @@ __host__ __device__ inline double cls_slack64(const rh_prep &P, double M) { retu
 // Slack: 2e-6 rad inside the table's cos / sin (the table's 17 digits and the candidate side's binary64 arithmetic -- the
 // normalisation of n, T, the square root where T is within 1e-16 of 1: together below 1e-7) and 1e-9 on T itself.
 constexpr int RH_NSIG_CELLS = 96;
+
+// ---- The cylinder's box by its support (cyl_box_skip32 below, field 9 of the culling record).  The two older clauses of the
+// cylinder's box test take the box for a ball: the distance from the axis at the centre, +- the Lipschitz constant x the half
+// diagonal hr.  A k-d leaf on a surface patch is flat, not round.  With t = c - c0, q = M t (M = I - a a', symmetric for any
+// axis a), rho_c = |q| and ANY unit vector v, every point p = c + d of the box (|d_k| <= h_k) has
+//     rho(p) = |M (t + d)| >= v . M (t + d) = v . q + (M v) . d >= v . q - sum_k |(M v)_k| h_k,
+// the tangent plane of the convex function rho; at v = q / rho_c it reads rho_c - s / rho_c with g = M q = q - a (a . q) and
+// s = sum |g_k| h_k.  The third clause skips when that lower bound clears the band: with w = rho_c^2 - s,
+//     w > 0  and  w^2 > A^2 rho_c^2                     (no square root; A = R + eps + slack > 0; A <= 0: stored as A^2 = 0).
+// It is ORed to the older two, so the pairs walked are a subset of what they were, and it says nothing about the inner
+// cylinder.  g is computed in the kernel (6 instructions) and not replaced by q: for a unit axis they agree, but q's direction
+// carries the error e_q / rho_c, which the box's LONG sides would multiply (a term h e_q / rho_c that no stored slack bounds);
+// M q^ costs that error a second-order effect only -- and the clause stays sound for an axis of any length, which is legal
+// input (cylinder.jl uses it as stored), with nothing to disable.
+// Soundness in binary32 -- a skipped pair holds no point of the band.  Hats are the kernel's values, rho' = |q^| and
+// s' = sum |g^_k| h_k the exact functions of them, v = q^ / rho':
+//   1. the binary32 box holds the binary64 one (box_to_f32), so c, h are the binary32 numbers; |q^_k - q_k| <= e_q
+//      (Margins above: the conversion of a and c0 included), hence v . q >= rho' - sqrt(3) e_q;
+//   2. g^ = fma(-a32, fl(a32 . q^), q^) against rho' M v, per component: the dot product is off by 4.1 u |a|_1 rho' (its 3
+//      roundings and the conversion of a), the fma by u (1 + 2 |a|_inf |a|_1) rho' more (a_k's conversion, its rounding):
+//      together u (1 + 6.1 |a|_inf |a|_1) rho' <= u c_g rho' with
+//      c_g = 2 + 8 |a|_inf |a|_1, and sum_k h_k <= 3.01 M (a box of the point set: h_k <= M, widened by box_to_f32 and the
+//      unions of st32_kernel by parts in 10^6 at most).  So  rho(p) >= rho' - s' / rho' - sqrt(3) e_q - 3.01 u c_g M;
+//   3. rho2^ = fl(sum q^_k^2) and s^ = fl(sum |g^_k| h_k) are sums of non-negative terms, three roundings each:
+//      rho2^ <= rho'^2 (1 + 3.01 u), s^ >= s' (1 - 3.01 u).  w^ = fma(rho2^, 0.999999f, -s^) takes 16.9 u of rho2^ off before
+//      the difference is formed: w^ > 0 implies rho'^2 - s' >= w^ (1 - u) -- the cancellation costs no absolute term;
+//   4. fl(w^ w^) <= w^2 (1 + u) and fl(A2 rho2^) >= A2 rho'^2 (1 - u)^4: the stored A2 = A^2 (1 + 16 u), rounded up, covers
+//      both.  Overflow: w^ <= rho2^ <= 3.1 T^2 (1 + |a|_inf |a|_1)^2, kept below 1e18 (else the field is NaN), its square
+//      below 3.4e38.  Underflow only lowers fl(w^ w^) or, where A2 rho2^ underflows, rho2^ < A2 (A >= 1e-9) and monotone
+//      rounding keeps fl(w^ w^) <= fl(rho2^ rho2^) <= fl(A2 rho2^): no skip;
+//   5. A = (R + eps) + sB + S 3.01 u c_g M, sB the slack of the older clauses: it holds S sqrt(3) e_q (item 1), the rounding of
+//      R and eps, the exact test's own slack (cls_slack64) and, on a Float32 cloud, the tripled part for the exact chain.
+// NaN anywhere (a record that is not usable, a NaN box) fails every comparison: no skip.  A centre on the axis has
+// w^ <= 0.  A ZERO axis is no cylinder: its record keeps NaN box fields, for the older clauses too.
 
 // cell of a direction with finite components, not all zero: face = the component of largest magnitude with its sign,
 // the other two components against +-1/2 of that magnitude and 0 (their quotients cut at -1/2, 0, 1/2)
@@ -263,12 +297,13 @@ __host__ __device__ inline void cls_make(const rh_prep &P, int kind, double eps,
         const double c0 = sph ? P.f[0] : P.f[3], c1 = sph ? P.f[1] : P.f[4], c2 = sph ? P.f[2] : P.f[5];
         const double T = M + fmax(fabs(c0), fmax(fabs(c1), fabs(c2)));
         double e, lipk = 1.0;   // e: error bound per component of the vector whose norm is taken
+        double a1 = 0.0, ai = 0.0;
         bool axis_ok = true;
         if (sph) {
             e = 2.01 * u * T;
         } else {
-            const double a1 = (fabs(P.f[0]) + fabs(P.f[1])) + fabs(P.f[2]);
-            const double ai = fmax(fabs(P.f[0]), fmax(fabs(P.f[1]), fabs(P.f[2])));
+            a1 = (fabs(P.f[0]) + fabs(P.f[1])) + fabs(P.f[2]);
+            ai = fmax(fabs(P.f[0]), fmax(fabs(P.f[1]), fabs(P.f[2])));
             axis_ok = ai <= 16.0;
             ok = ok && axis_ok;
             e = u * T * (3.01 + 8.04 * ai * a1);
@@ -302,7 +337,7 @@ __host__ __device__ inline void cls_make(const rh_prep &P, int kind, double eps,
             else { o.f[7] = s0; o.f[8] = s1; o.f[9] = s2; o.f[10] = s3f; }
             ok = ok && fabs((double)s0) < 1e30 && fabs((double)s1) < 1e30 && fabs((double)s2) < 1e30 && fabs((double)s3f) < 1e30;
         }
-        if (fin && axis_ok && cls_fin(eps) && cls_fin(M)) {
+        if (fin && axis_ok && (sph || a1 > 0.0) && cls_fin(eps) && cls_fin(M)) {
             // box: |p - o| (sphere) or the distance from the axis (cylinder, at the centre of the box +- Lipschitz) against
             // R +- eps; binary32 error of the norm at the centre + of the squares + the binary64 test's own slack
             const double sB = S * (s3 * e + 4.0 * u * (fabs(R) + fabs(eps)) + 4.0 * u * lipk * s3 * M) + slack64;
@@ -317,6 +352,10 @@ __host__ __device__ inline void cls_make(const rh_prep &P, int kind, double eps,
                     bx[6] = cls_up(A);
                     bx[7] = cls_dn(B);
                     bx[8] = cls_up(lipk);
+                    // the support clause ("The cylinder's box by its support" above): A^2, NaN where its squares could overflow
+                    const double As = A + S * 3.01 * u * (2.0 + 8.0 * ai * a1) * M;
+                    const double r2max = 3.1 * T * T * ((1.0 + ai * a1) * (1.0 + ai * a1));
+                    if (cls_fin(As) && r2max < 1e18) bx[9] = As > 0.0 ? cls_up(As * As * (1.0 + 16.0 * u)) : 0.0f;
                 }
             }
         }
@@ -423,6 +462,30 @@ __host__ __device__ inline void box_to_f32(const double c[3], const double h[3],
 // the box is wave-uniform.  Every comparison is written so that NaN means "do not skip".
 struct rh_box32 { float cx, cy, cz, hx, hy, hz, hr; };
 
+// the cylinder's decision, host and device (rh_dbg_cylbox runs this very code).  SUPPORT = false: the two clauses that take the
+// box for a ball, alone -- what the test was before the support clause, kept for the census of what the clause adds.
+template <bool SUPPORT>
+static __host__ __device__ __forceinline__ bool cyl_box_skip32(const float (&B)[RH_BOX_FIELDS], const rh_box32 &G)
+{
+    const float tx = G.cx - B[3], ty = G.cy - B[4], tz = G.cz - B[5];
+    const float sd = __builtin_fmaf(B[2], tz, __builtin_fmaf(B[1], ty, B[0] * tx));
+    const float qx = __builtin_fmaf(-B[0], sd, tx), qy = __builtin_fmaf(-B[1], sd, ty), qz = __builtin_fmaf(-B[2], sd, tz);
+    const float rho2 = __builtin_fmaf(qz, qz, __builtin_fmaf(qy, qy, qx * qx));
+    const float lip = B[8] * G.hr * 1.000001f;
+    const float X = B[6] + lip, Y = B[7] - lip;
+    const float X2 = X > 0.0f ? X * X * 1.000001f : (X <= 0.0f ? 0.0f : X);   // NaN stays NaN
+    bool skip = (rho2 * 0.999999f > X2) | ((Y > 0.0f) & (rho2 * 1.000001f < Y * Y));
+    if (SUPPORT) {
+        // rho >= rho_c - sum |g_k| h_k / rho_c over the box, g = q - a (a . q): "The cylinder's box by its support" above
+        const float aq = __builtin_fmaf(B[2], qz, __builtin_fmaf(B[1], qy, B[0] * qx));
+        const float gx = __builtin_fmaf(-B[0], aq, qx), gy = __builtin_fmaf(-B[1], aq, qy), gz = __builtin_fmaf(-B[2], aq, qz);
+        const float s = __builtin_fmaf(__builtin_fabsf(gz), G.hz, __builtin_fmaf(__builtin_fabsf(gy), G.hy, __builtin_fabsf(gx) * G.hx));
+        const float w = __builtin_fmaf(rho2, 0.999999f, -s);
+        skip |= (w > 0.0f) & (w * w > B[9] * rho2);
+    }
+    return skip;
+}
+
 template <int KIND>
 static __device__ __forceinline__ bool box_skip32(const float (&B)[RH_BOX_FIELDS], const rh_box32 &G)
 {
@@ -439,16 +502,7 @@ static __device__ __forceinline__ bool box_skip32(const float (&B)[RH_BOX_FIELDS
         const float dmax2 = __builtin_fmaf(fz, fz, __builtin_fmaf(fy, fy, fx * fx)) * 1.000001f;
         return (dmin2 * 0.999999f > B[3]) | (dmax2 < B[4]);
     }
-    if (KIND == RH_CYLINDER) {
-        const float tx = G.cx - B[3], ty = G.cy - B[4], tz = G.cz - B[5];
-        const float sd = __builtin_fmaf(B[2], tz, __builtin_fmaf(B[1], ty, B[0] * tx));
-        const float qx = __builtin_fmaf(-B[0], sd, tx), qy = __builtin_fmaf(-B[1], sd, ty), qz = __builtin_fmaf(-B[2], sd, tz);
-        const float rho2 = __builtin_fmaf(qz, qz, __builtin_fmaf(qy, qy, qx * qx));
-        const float lip = B[8] * G.hr * 1.000001f;
-        const float X = B[6] + lip, Y = B[7] - lip;
-        const float X2 = X > 0.0f ? X * X * 1.000001f : (X <= 0.0f ? 0.0f : X);   // NaN stays NaN
-        return (rho2 * 0.999999f > X2) | ((Y > 0.0f) & (rho2 * 1.000001f < Y * Y));
-    }
+    if (KIND == RH_CYLINDER) return cyl_box_skip32<true>(B, G);
     // cone: "surely outside the widened band", positive comparisons only
     const float tx = G.cx - B[0], ty = G.cy - B[1], tz = G.cz - B[2];
     const float tt = __builtin_fmaf(tz, tz, __builtin_fmaf(ty, ty, tx * tx));

@@ -223,7 +223,14 @@ static __device__ __forceinline__ bool box_skip(const rh_prep &P, double cx, dou
         const double lip = fmax(1.0, fabs(P.f[9] - 1.0)) * hr;   // |1 - |a|^2| = |k - 1| (prep_derived)
         const double X = ((P.f[6] + eps) + slack) + lip, Y = ((P.f[6] - eps) - slack) - lip;
         const double X2 = X > 0.0 ? X * X : (X <= 0.0 ? 0.0 : X);
-        return (rho2 > X2) | ((Y > 0.0) & (rho2 < Y * Y));
+        // the box by its support (score4_device.h, "The cylinder's box by its support"): rho >= rho_c - sum |g_k| h_k / rho_c over
+        // the box with g = q - a (a . q), any axis; `slack` is 10^5 x the rounding of these sums, the factor covers the squares
+        const double aq = dot3f(ax, ay, az, qx, qy, qz);
+        const double gx = __builtin_fma(-ax, aq, qx), gy = __builtin_fma(-ay, aq, qy), gz = __builtin_fma(-az, aq, qz);
+        const double w = __builtin_fma(rho2, 0.999999999, -dot3f(fabs(gx), fabs(gy), fabs(gz), hx, hy, hz));
+        const double A = (P.f[6] + eps) + slack;
+        const double A2 = A > 0.0 ? A * A * 1.000000001 : (A <= 0.0 ? 0.0 : A);
+        return (rho2 > X2) | ((Y > 0.0) & (rho2 < Y * Y)) | ((w > 0.0) & (w * w > A2 * rho2));
     }
     // cone: dist(p) = cos(w/2) rho(p) +- sin(w/2) h(p) (rho, h = radial / axial coordinate of p - apex;
     // the axis only enters through normalized cross products) is 1-Lipschitz in p
