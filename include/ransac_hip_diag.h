@@ -89,6 +89,16 @@ int rh_dbg_sample_fit(rh_cloud *c, const rh_params *p, uint64_t seed, int64_t k0
                       int32_t rank, int32_t world, rh_dbg_cand *out, int32_t cap, int32_t *n_out, uint64_t *draws_out,
                       int32_t *gave_up_out, int32_t *info_out /* [8] */);
 
+/* wave_each_key (csrc/wave_keys.h: one action per distinct key of a wave) in a kernel of its own: one block of 256 threads,
+ * thread i holds keys[i] (u32 = 0: as int32_t, 1: as uint32_t) and counts as active when i < n and act[i] != 0; an inactive
+ * thread below n keeps its key all the same.  slot[i] (0 .. nslots - 1): where thread i's key is tallied -- the caller numbers
+ * the distinct keys.  Every time the helper calls its function, the leader adds popcount(same) to sum_out[its slot], lowers
+ * minlead_out[its slot] to its thread index (0x7F7F7F7F: the slot never had a leader) and adds 1 to scal_out[0]; scal_out[1]
+ * counts violations (must be 0): a lane that did not see all 64 lanes of its wave inside the function, or whose bit of `same`
+ * is not "active and my key is the leader's".  n <= 256. */
+int rh_dbg_wave_keys(const uint32_t *keys, const uint8_t *act, const int32_t *slot, int32_t n, int32_t nslots, int u32, int device,
+                     int32_t *sum_out /* [nslots] */, int32_t *minlead_out /* [nslots] */, int32_t *scal_out /* [2] */);
+
 #ifdef __cplusplus
 }
 #endif

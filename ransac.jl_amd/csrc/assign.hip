@@ -22,6 +22,7 @@
 #include "assign_device.h"
 #include "call_scope.h"
 #include "rh_internal.h"
+#include "wave_keys.h"
 
 namespace {
 
@@ -130,14 +131,9 @@ __device__ __forceinline__ void count_quarter(const asg_job &J, int64_t k, int32
     for (int r = 0; r < ASG_WRUN / 64; r++) {
         if (wbase + r * 64 >= J.n) break;   // (wave-uniform)
         const int32_t key = key_of(J, wbase + r * 64 + lane);
-        uint64_t todo = WB(key >= 0);
-        while (todo != 0) {
-            const int leader = __builtin_ctzll(todo);
-            const int32_t L = __shfl(key, leader);
-            const uint64_t m = WB(key == L);
+        wave_each_key(key >= 0, key, [&](int leader, int32_t L, uint64_t m) {
             if (lane == leader) row[L] += __popcll(m);
-            todo &= ~m;
-        }
+        });
     }
 }
 
@@ -239,11 +235,7 @@ __global__ void __launch_bounds__(ASG_BLOCK) asg_scatter_kernel(const asg_job J)
         if (wbase + r * 64 >= J.n) break;   // (wave-uniform)
         const int64_t i = wbase + r * 64 + lane;
         const int32_t key = key_of(J, i);
-        uint64_t todo = WB(key >= 0);
-        while (todo != 0) {
-            const int leader = __builtin_ctzll(todo);
-            const int32_t L = __shfl(key, leader);
-            const uint64_t m = WB(key == L);
+        wave_each_key(key >= 0, key, [&](int leader, int32_t L, uint64_t m) {
             int32_t at = 0;
             if (lane == leader) { at = row[L]; row[L] = at + __popcll(m); }   // (the leader alone touches the cursor)
             at = __shfl(at, leader);
@@ -251,8 +243,7 @@ __global__ void __launch_bounds__(ASG_BLOCK) asg_scatter_kernel(const asg_job J)
                 const int64_t pos = (int64_t)at + __popcll(m & ((1ULL << lane) - 1ULL));
                 if ((uint64_t)pos < (uint64_t)J.n) J.idx[pos] = i + 1;
             }
-            todo &= ~m;
-        }
+        });
     }
 }
 

@@ -1,8 +1,9 @@
 // call_scope.h -- what an entry point on raw host arrays (rh_voxel_downsample, rh_knn, rh_remove_outliers, rh_knn_query,
 // rh_cloud_distance, rh_register, rh_cluster, rh_orient_normals, rh_estimate_normals, rh_assign_points, rh_largestconncomp) owns for the length of the call: the device, a stream of its
-// own and its device buffers, released on every way out.  Host code only.  The cloud-bound paths do not come here: a
-// cloud has its stream and its grown buffers (rh_dev::grow, RH_HIP).
-// Everything lives in an anonymous namespace: each translation unit that includes the header gets its own widen kernel.
+// own and its device buffers, released on every way out -- among them the ONE scratch block of the call's hipcub
+// launches (cub) -- and the read-back of the call's scalars (fetch).  The cloud-bound paths do not come here: a cloud has
+// its stream and its grown buffers (rh_dev::grow, RH_HIP).
+// Everything lives in an anonymous namespace: each translation unit that includes the header gets its own kernels.
 #pragma once
 
 #include <vector>
@@ -21,6 +22,20 @@ __global__ void scope_widen_kernel(const T *__restrict__ in, double *__restrict_
     if (i < cnt) out[i] = (double)in[i];
 }
 
+// *out = the number of flags set among flag[0 .. n - 1] (num = the exclusive scan of flag, n >= 1)
+__global__ void scan_total_kernel(const int32_t *__restrict__ flag, const int32_t *__restrict__ num, int64_t n, int32_t *out)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *out = num[n - 1] + flag[n - 1];
+}
+
+// the key bits a radix sort has to look at when the keys are 0 .. count - 1
+inline int sort_bits(uint64_t count)
+{
+    int bits = 1;
+    while (bits < 64 && (count - 1) >> bits) bits++;
+    return bits;
+}
+
 // a HIP call of scope S_ that must succeed
 #define SCOPE_HIP(S_, x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { rh_set_error("%s: %s", (S_).who, hipGetErrorString(e_)); return RH_E_NODEVICE; } } while (0)
 
@@ -28,6 +43,8 @@ struct CallScope {
     const char *who = "";    // the entry point, for error texts
     hipStream_t st = nullptr;
     std::vector<rh_dev<char>> bufs;
+    char *scratch = nullptr;    // hipcub's temporary storage: one block, as large as the largest request so far
+    size_t scratch_bytes = 0;
     CallScope() = default;
     CallScope(const CallScope &) = delete;
     CallScope &operator=(const CallScope &) = delete;
@@ -84,10 +101,47 @@ struct CallScope {
         T *d_in = nullptr;
         RH_TRY(alloc(&d_in, cnt));
         SCOPE_HIP(*this, hipMemcpyAsync(d_in, src, sizeof(T) * (size_t)cnt, kind, st));
-        hipLaunchKernelGGL(scope_widen_kernel<T>, dim3(blocks_for(cnt)), dim3(256), 0, st, d_in, dst, cnt);
-        SCOPE_HIP(*this, hipGetLastError());
+        RH_TRY(widen(d_in, dst, cnt));
         SCOPE_HIP(*this, hipStreamSynchronize(st));
         release(d_in);
+        return RH_OK;
+    }
+
+    // cnt values of T on the device into doubles (queued on the stream)
+    template <typename T>
+    int widen(const T *d_in, double *dst, int64_t cnt)
+    {
+        hipLaunchKernelGGL(scope_widen_kernel<T>, dim3(blocks_for(cnt)), dim3(256), 0, st, d_in, dst, cnt);
+        SCOPE_HIP(*this, hipGetLastError());
+        return RH_OK;
+    }
+
+    // One hipcub launch on the scope's scratch block: call(tmp, bytes) -> hipError_t is the hipcub call with these two as its
+    // first arguments.  It is made twice: with tmp = null it only states its size (host code, nothing is launched), then it
+    // runs on the block, which is replaced (never kept twice) when it is too small.  A replacement waits for the device
+    // (hipFree) and leaves an empty entry in bufs: expected a few times per call, where a later request is the larger one --
+    // not in a loop whose requests keep growing.
+    template <typename F>
+    int cub(F &&call)
+    {
+        size_t bytes = 0;
+        SCOPE_HIP(*this, call(nullptr, bytes));
+        if (!scratch || bytes > scratch_bytes) {
+            release(scratch);
+            scratch_bytes = 0;
+            RH_TRY(alloc(&scratch, (int64_t)bytes));
+            scratch_bytes = bytes;
+        }
+        SCOPE_HIP(*this, call(scratch, bytes));
+        return RH_OK;
+    }
+
+    // count values of T from the device, and the wait for them (and for everything queued before)
+    template <typename T>
+    int fetch(T *host, const T *dev, size_t count = 1)
+    {
+        SCOPE_HIP(*this, hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, st));
+        SCOPE_HIP(*this, hipStreamSynchronize(st));
         return RH_OK;
     }
 };

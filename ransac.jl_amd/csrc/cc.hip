@@ -115,8 +115,7 @@ extern "C" int rh_largestconncomp(const uint8_t *bitmap, int32_t xs, int32_t ys,
     }
     RH_TRY(rhk_compact_generic(S.st, d_mask, nwords, d_bs, d_idx, npx, d_total));
     int32_t total = 0;
-    SCOPE_HIP(S, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, S.st));
-    SCOPE_HIP(S, hipStreamSynchronize(S.st));
+    RH_TRY(S.fetch(&total, d_total));
     *n_out = total;
     if (total > cap) {
         rh_set_error("rh_largestconncomp: component has %d pixels, capacity %lld", total, (long long)cap);
@@ -124,8 +123,7 @@ extern "C" int rh_largestconncomp(const uint8_t *bitmap, int32_t xs, int32_t ys,
     }
     if (total > 0) {
         std::vector<int64_t> tmp((size_t)total);
-        SCOPE_HIP(S, hipMemcpyAsync(tmp.data(), d_idx, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, S.st));
-        SCOPE_HIP(S, hipStreamSynchronize(S.st));
+        RH_TRY(S.fetch(tmp.data(), d_idx, (size_t)total));
         for (int32_t i = 0; i < total; i++) out[i] = tmp[(size_t)i] - 1;   // compaction is 1-based
     }
     return RH_OK;

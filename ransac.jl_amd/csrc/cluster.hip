@@ -21,6 +21,7 @@
 // floating-point atomics: every output is a comparison of binary64 values or an integer.
 #include "knn_grid.h"
 #include "union_find.h"
+#include "wave_keys.h"
 
 namespace {
 
@@ -61,13 +62,6 @@ __global__ void cl_init_parent_kernel(int32_t *__restrict__ parent, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) parent[i] = (int32_t)i;
-}
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 template <int PASS>
@@ -169,14 +163,9 @@ __global__ void cl_size_kernel(const int32_t *__restrict__ root, int64_t n, int3
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int32_t r = i < n ? root[i] : -1;
-    uint64_t todo = __builtin_amdgcn_ballot_w64(r >= 0 && (int64_t)r < n);
-    while (todo != 0) {
-        const int leader = __builtin_ctzll(todo);
-        const int32_t R = __shfl(r, leader);
-        const uint64_t same = __builtin_amdgcn_ballot_w64(r == R);
+    wave_each_key(r >= 0 && (int64_t)r < n, r, [&](int leader, int32_t R, uint64_t same) {
         if (lane == leader) atomicAdd(&size[R], (int32_t)__popcll(same));
-        todo &= ~same;
-    }
+    });
 }
 
 // flag[r] = r is the root of a cluster that stays
@@ -185,12 +174,6 @@ __global__ void cl_keep_kernel(const int32_t *__restrict__ root, const int32_t *
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) flag[i] = root[i] == (int32_t)i && size[i] >= min_size;
-}
-
-// m = the number of clusters that stay (num = the exclusive scan of flag)
-__global__ void cl_m_kernel(const int32_t *__restrict__ flag, const int32_t *__restrict__ num, int64_t n, ClScal *sc)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0) sc->m = num[n - 1] + flag[n - 1];
 }
 
 // BY_INDEX: lab[r] = num[r] + 1.  BY_SIZE: the sort key of cluster num[r], descending size and then ascending root
@@ -278,7 +261,7 @@ int cluster(const char *who, const T *xyz_aos, int64_t n, const rh_cluster_param
 
     // items
     ClScal *d_sc = nullptr, h;
-    uint8_t *d_flag8 = nullptr, *d_tmp = nullptr;
+    uint8_t *d_flag8 = nullptr;
     int32_t *d_items = nullptr, *d_size = nullptr, *d_flag = nullptr, *d_num = nullptr, *d_lab = nullptr, *d_labels = nullptr;
     RH_TRY(S.alloc(&d_sc, 1));
     RH_TRY(S.alloc(&d_flag8, n));
@@ -289,22 +272,12 @@ int cluster(const char *who, const T *xyz_aos, int64_t n, const rh_cluster_param
     int32_t *d_lsorted = nullptr;
     if (idx_out) { RH_TRY(S.alloc(&d_one, n)); RH_TRY(S.alloc(&d_idx, n)); RH_TRY(S.alloc(&d_lsorted, n)); }
     hipcub::CountingInputIterator<int32_t> zero_based(0);
-    size_t sel_bytes = 0, scan_bytes = 0, msort_bytes = 0, lsort_bytes = 0, oscan_bytes = 0;
     uint64_t *d_mkey = ix.d_key[0], *d_msorted = nullptr;       // (the grid's unsorted keys are free once it is built)
-    SCOPE_HIP(S, hipcub::DeviceSelect::Flagged(nullptr, sel_bytes, zero_based, d_flag8, d_items, &d_sc->nitems, (int)n, st));
-    SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_flag, d_num, (int)n, st));
-    SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(nullptr, msort_bytes, d_mkey, d_msorted, (int)n, 0, 64, st));
-    if (idx_out) SCOPE_HIP(S, hipcub::DeviceRadixSort::SortPairs(nullptr, lsort_bytes, d_labels, d_lsorted, d_one, d_idx, (int)n, 0, 32, st));
-    if (tally) SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(nullptr, oscan_bytes, d_counts, d_offsets, (int)(cap + 2), st));
-    const size_t tmp_bytes = std::max(std::max(sel_bytes, scan_bytes), std::max(std::max(msort_bytes, lsort_bytes), oscan_bytes));
-    RH_TRY(S.alloc(&d_tmp, (int64_t)tmp_bytes));
     SCOPE_HIP(S, hipMemsetAsync(d_sc, 0, sizeof(ClScal), st));
     hipLaunchKernelGGL(cl_chunk_flag_kernel, dim3(blocks_for(n)), dim3(256), 0, st, ix.g, ix.d_key[1], n, d_flag8);
     SCOPE_HIP(S, hipGetLastError());
-    size_t tb = tmp_bytes;
-    SCOPE_HIP(S, hipcub::DeviceSelect::Flagged(d_tmp, tb, zero_based, d_flag8, d_items, &d_sc->nitems, (int)n, st));
-    SCOPE_HIP(S, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
-    SCOPE_HIP(S, hipStreamSynchronize(st));
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceSelect::Flagged(t, b, zero_based, d_flag8, d_items, &d_sc->nitems, (int)n, st); }));
+    RH_TRY(S.fetch(&h, d_sc));
     if (h.nitems < 1 || (int64_t)h.nitems > n) { rh_set_error("%s: %d work items for %lld points", who, h.nitems, (long long)n); return RH_E_INTERNAL; }
 
     // the three passes
@@ -325,20 +298,17 @@ int cluster(const char *who, const T *xyz_aos, int64_t n, const rh_cluster_param
     hipLaunchKernelGGL(cl_size_kernel, dim3(blocks_for(n)), dim3(256), 0, st, J.root, n, d_size);
     hipLaunchKernelGGL(cl_keep_kernel, dim3(blocks_for(n)), dim3(256), 0, st, J.root, d_size, n, p->min_size, d_flag);
     SCOPE_HIP(S, hipGetLastError());
-    tb = tmp_bytes;
-    SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_flag, d_num, (int)n, st));
-    hipLaunchKernelGGL(cl_m_kernel, dim3(1), dim3(64), 0, st, d_flag, d_num, n, d_sc);
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_flag, d_num, (int)n, st); }));
+    hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(64), 0, st, d_flag, d_num, n, &d_sc->m);   // the clusters that stay
     const int by_size = p->order == RH_CLUSTER_BY_SIZE;
     hipLaunchKernelGGL(cl_number_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_flag, d_num, d_size, n, by_size, d_lab, d_mkey);
     SCOPE_HIP(S, hipGetLastError());
-    SCOPE_HIP(S, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
-    SCOPE_HIP(S, hipStreamSynchronize(st));
+    RH_TRY(S.fetch(&h, d_sc));
     const int64_t m = h.m;
     if (m < 0 || m > n) { rh_set_error("%s: %lld clusters of %lld points", who, (long long)m, (long long)n); return RH_E_INTERNAL; }
     if (by_size && m > 0) {
         d_msorted = ix.d_key[1];                                // (the walk is over: the sorted cell keys are spent)
-        tb = tmp_bytes;
-        SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_mkey, d_msorted, (int)m, 0, 64, st));
+        RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortKeys(t, b, d_mkey, d_msorted, (int)m, 0, 64, st); }));
         hipLaunchKernelGGL(cl_rank_kernel, dim3(blocks_for(m)), dim3(256), 0, st, d_msorted, m, n, d_lab);
     }
 
@@ -371,16 +341,13 @@ int cluster(const char *who, const T *xyz_aos, int64_t n, const rh_cluster_param
     if (tally) {
         hipLaunchKernelGGL(cl_count0_kernel, dim3(1), dim3(64), 0, st, d_sc, d_counts);
         SCOPE_HIP(S, hipGetLastError());
-        tb = tmp_bytes;
-        SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_counts, d_offsets, (int)(cap + 2), st));
+        RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_counts, d_offsets, (int)(cap + 2), st); }));
         if (counts_out) SCOPE_HIP(S, hipMemcpyAsync(counts_out, d_counts, sizeof(int64_t) * (size_t)(cap + 1), hipMemcpyDefault, st));
         if (offsets_out) SCOPE_HIP(S, hipMemcpyAsync(offsets_out, d_offsets, sizeof(int64_t) * (size_t)(cap + 2), hipMemcpyDefault, st));
     }
     if (idx_out) {
-        int bits = 1;
-        while (bits < 32 && (m >> bits)) bits++;
-        tb = tmp_bytes;
-        SCOPE_HIP(S, hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_labels, d_lsorted, d_one, d_idx, (int)n, 0, bits, st));
+        const int bits = sort_bits((uint64_t)m + 1);            // (the labels are 0 .. m)
+        RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, d_labels, d_lsorted, d_one, d_idx, (int)n, 0, bits, st); }));
         SCOPE_HIP(S, hipMemcpyAsync(idx_out, d_idx, sizeof(int64_t) * (size_t)n, hipMemcpyDefault, st));
     }
     SCOPE_HIP(S, hipStreamSynchronize(st));

@@ -17,6 +17,7 @@
 #include "cell_grid.h"
 #include "rh_internal.h"
 #include "union_find.h"
+#include "wave_keys.h"
 
 namespace {
 
@@ -128,23 +129,14 @@ __global__ void __launch_bounds__(256) comp_flatten_kernel(comp_table T)
     }
     // lanes that share a root add up inside the wave first: a plane's one big component would otherwise queue
     // every cell of the table on one address (175 000 cells: 1.8 ms of atomics)
-    uint64_t todo = __builtin_amdgcn_ballot_w64(r >= 0);
-    while (todo != 0) {
-        const int lead = __ffsll((unsigned long long)todo) - 1;
-        const int32_t rl = __shfl(r, lead);
+    wave_each_key(r >= 0, r, [&](int leader, int32_t rl, uint64_t) {
         const bool mine = r == rl;
-        int32_t c = mine ? cnt : 0, m = mine ? mi : 0x7FFFFFFF;
-        for (int off = 32; off > 0; off >>= 1) {
-            c += __shfl_xor(c, off);
-            const int32_t o = __shfl_xor(m, off);
-            m = o < m ? o : m;
-        }
-        if (lane == lead) {
+        const int32_t c = wave_sum_i32(mine ? cnt : 0), m = wave_min_i32(mine ? mi : 0x7FFFFFFF);
+        if (lane == leader) {
             atomicAdd(&T.count[rl], c);
             atomicMin(&T.minidx[rl], m);
         }
-        todo &= ~__builtin_amdgcn_ballot_w64(mine);
-    }
+    });
 }
 
 // ---- 4. key = size << 32 | ~min_index: the maximum is the largest component, the smallest point index among equals

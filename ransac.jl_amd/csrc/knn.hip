@@ -195,16 +195,8 @@ int remove_outliers(const T *xyz_aos, int64_t n, const rh_outlier_params *p, int
                        d_keep, d_key);
     SCOPE_HIP(S, hipGetLastError());
     hipcub::CountingInputIterator<int32_t> one_based(1);
-    size_t sel_bytes = 0, sort_bytes = 0;
-    SCOPE_HIP(S, hipcub::DeviceSelect::Flagged(nullptr, sel_bytes, one_based, d_keep, d_kept, &d_sc->nkept, (int)n, st));
-    SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, d_key, d_sorted, (int)n, 0, 64, st));
-    uint8_t *d_tmp = nullptr;
-    const size_t tmp_bytes = std::max(sel_bytes, sort_bytes);
-    RH_TRY(S.alloc(&d_tmp, (int64_t)tmp_bytes));
-    size_t tb = tmp_bytes;
-    SCOPE_HIP(S, hipcub::DeviceSelect::Flagged(d_tmp, tb, one_based, d_keep, d_kept, &d_sc->nkept, (int)n, st));
-    tb = tmp_bytes;
-    SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_key, d_sorted, (int)n, 0, 64, st));
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceSelect::Flagged(t, b, one_based, d_keep, d_kept, &d_sc->nkept, (int)n, st); }));
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortKeys(t, b, d_key, d_sorted, (int)n, 0, 64, st); }));
     hipLaunchKernelGGL(out_median_kernel, dim3(1), dim3(64), 0, st, d_sc, d_sorted, n);
     SCOPE_HIP(S, hipGetLastError());
 

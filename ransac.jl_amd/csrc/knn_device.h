@@ -235,8 +235,7 @@ inline int knn_index_for_k(KnnIndex &ix, int k, double radius, KnnQuery &q)
     hipLaunchKernelGGL(knn_sample_kernel, dim3(blocks_for(ns, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, ix.S->st, ix.g, q, d_kth);
     SCOPE_HIP(*ix.S, hipGetLastError());
     std::vector<double> kth((size_t)ns);
-    SCOPE_HIP(*ix.S, hipMemcpyAsync(kth.data(), d_kth, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, ix.S->st));
-    SCOPE_HIP(*ix.S, hipStreamSynchronize(ix.S->st));
+    RH_TRY(ix.S->fetch(kth.data(), d_kth, (size_t)ns));
     std::nth_element(kth.begin(), kth.begin() + ns / 2, kth.end());
     const double med = kth[(size_t)(ns / 2)];
     const double h = (med > 0.0 && isfinite(med)) ? 2.0 * sqrt(med) : h0;

@@ -114,8 +114,7 @@ inline int cloud_box(CallScope &S, const double *d_xyz, int64_t n, double lo[3],
     hipLaunchKernelGGL(nrm_minmax_kernel, dim3((unsigned)nb), dim3(256), 0, st, d_xyz, n, d_scal + MM_WORDS);
     hipLaunchKernelGGL(grid_minmax_fold_kernel, dim3(1), dim3(256), 0, st, d_scal + MM_WORDS, (int)nb, d_scal, (int)MM_WORDS);
     SCOPE_HIP(S, hipGetLastError());
-    SCOPE_HIP(S, hipMemcpyAsync(h_scal, d_scal, sizeof h_scal, hipMemcpyDeviceToHost, st));
-    SCOPE_HIP(S, hipStreamSynchronize(st));
+    RH_TRY(S.fetch(h_scal, d_scal, MM_COUNT + 1));
     if ((int64_t)h_scal[MM_COUNT] != n) { rh_set_error("%s: a coordinate is not finite", S.who); return RH_E_INVALID; }
     for (int ax = 0; ax < 3; ax++) { lo[ax] = ord_back(h_scal[MM_MIN + ax]); hi[ax] = ord_back(h_scal[MM_MAX + ax]); }
     return RH_OK;
@@ -132,8 +131,6 @@ struct KnnIndex {
     int32_t *d_idx[2] = { nullptr, nullptr };
     double *d_s[3] = { nullptr, nullptr, nullptr };
     unsigned long long *d_count = nullptr;
-    uint8_t *d_tmp = nullptr;
-    size_t tmp_bytes = 0;
     uint64_t *d_hkey = nullptr;
     int32_t *d_hrange = nullptr;
     uint64_t hcap = 0;
@@ -149,13 +146,10 @@ struct KnnIndex {
             L = std::max(L, ext[ax]);
             omax = std::max(omax, std::max(fabs(lo[ax]), fabs(hi[ax])));
         }
-        const hipStream_t st = S->st;
         RH_TRY(S->alloc(&d_key[0], n)); RH_TRY(S->alloc(&d_key[1], n));
         RH_TRY(S->alloc(&d_idx[0], n)); RH_TRY(S->alloc(&d_idx[1], n));
         for (int ax = 0; ax < 3; ax++) RH_TRY(S->alloc(&d_s[ax], n));
         RH_TRY(S->alloc(&d_count, 1));
-        SCOPE_HIP(*S, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_key[0], d_key[1], d_idx[0], d_idx[1], (int)n, 0, 64, st));
-        RH_TRY(S->alloc(&d_tmp, (int64_t)tmp_bytes));
         return RH_OK;
     }
 
@@ -172,19 +166,16 @@ struct KnnIndex {
         g.h = h;
         g.margin = 1e-12 * (omax + L + h);
         g.xyz = d_xyz;
-        const uint64_t cells = (uint64_t)g.dim[0] * (uint64_t)g.dim[1] * (uint64_t)g.dim[2];
-        int bits = 1;
-        while (bits < 64 && (cells - 1) >> bits) bits++;
+        const int bits = sort_bits((uint64_t)g.dim[0] * (uint64_t)g.dim[1] * (uint64_t)g.dim[2]);
         hipLaunchKernelGGL(nrm_key_kernel, dim3(blocks_for(n)), dim3(256), 0, st, g, n, d_key[0], d_idx[0]);
         SCOPE_HIP(*S, hipGetLastError());
-        SCOPE_HIP(*S, hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_key[0], d_key[1], d_idx[0], d_idx[1], (int)n, 0, bits, st));
+        RH_TRY(S->cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, d_key[0], d_key[1], d_idx[0], d_idx[1], (int)n, 0, bits, st); }));
         hipLaunchKernelGGL(nrm_gather_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_xyz, d_idx[1], n, d_s[0], d_s[1], d_s[2]);
         SCOPE_HIP(*S, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
         hipLaunchKernelGGL(nrm_runs_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_key[1], n, d_count);
         SCOPE_HIP(*S, hipGetLastError());
         unsigned long long occupied = 0;
-        SCOPE_HIP(*S, hipMemcpyAsync(&occupied, d_count, sizeof occupied, hipMemcpyDeviceToHost, st));
-        SCOPE_HIP(*S, hipStreamSynchronize(st));
+        RH_TRY(S->fetch(&occupied, d_count));
         uint64_t cap = 64;
         while (cap < 2 * occupied) cap <<= 1;
         if (cap > hcap) {

@@ -123,14 +123,12 @@ int cloud_distance(const T *ref_aos, const T *nrm_aos, int64_t n, const T *qry_a
     RH_TRY(tree_root<3>(S, q.a.dist, q.a.nn, m, nullptr, nullptr, d_part2, &d_sq));
     hipLaunchKernelGGL(dist_key_kernel, dim3(blocks_for(m)), dim3(256), 0, st, q.a.dist, q.a.nn, m, p->threshold, q.d_key[0], d_sc);
     SCOPE_HIP(S, hipGetLastError());
-    size_t tb = q.tmp_bytes;
-    SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(q.d_tmp, tb, q.d_key[0], q.d_key[1], (int)m, 0, 64, st));
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortKeys(t, b, q.d_key[0], q.d_key[1], (int)m, 0, 64, st); }));
     hipLaunchKernelGGL(dist_scalars_kernel, dim3(1), dim3(64), 0, st, d_sc, d_sum, d_sq, q.d_key[1], m);
     hipLaunchKernelGGL(dist_argmax_kernel, dim3(blocks_for(m)), dim3(256), 0, st, q.a.dist, q.a.nn, m, d_sc);
     SCOPE_HIP(S, hipGetLastError());
     DistScal h;
-    SCOPE_HIP(S, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
-    SCOPE_HIP(S, hipStreamSynchronize(st));
+    RH_TRY(S.fetch(&h, d_sc));
     stats->n_valid = (int64_t)h.nvalid;
     stats->n_within = (int64_t)h.nwithin;
     stats->argmax = h.argmax == ~0ull ? 0 : (int64_t)h.argmax;

@@ -104,7 +104,8 @@ inline int check_query(const char *who, const void *ref, int64_t n, const void *
 // (no self entry: k, not k + 1), its margin widened to the box of both clouds, the queries in the order of their cells.
 //   open_reference()  once: the reference on the device, its box, the grid;
 //   reserve()         once: the buffers of a query pass over m points;
-//   bind()            per query array of those m points: box, margin, keys, sort -- nothing is allocated;
+//   bind()            per query array of those m points: box, margin, keys, sort -- nothing is allocated (the first sort sizes the
+//                     scope's scratch block, CallScope::cub);
 //   run()             the search of the bound queries.
 // open() is the four in a row for a call with one query array.
 struct QuerySearch {
@@ -116,8 +117,6 @@ struct QuerySearch {
     uint64_t *d_key[2] = { nullptr, nullptr };   // the queries' sort buffers, free again after bind()
     int32_t *d_idx[2] = { nullptr, nullptr };
     unsigned long long *d_box = nullptr;
-    uint8_t *d_tmp = nullptr;
-    size_t tmp_bytes = 0;
 
     template <typename T>
     int open_reference(CallScope &S, const T *ref_aos, int64_t n, int k, double radius)
@@ -138,11 +137,6 @@ struct QuerySearch {
         RH_TRY(S.alloc(&d_box, cloud_box_words(m)));
         RH_TRY(S.alloc(&d_key[0], m)); RH_TRY(S.alloc(&d_key[1], m));
         RH_TRY(S.alloc(&d_idx[0], m)); RH_TRY(S.alloc(&d_idx[1], m));
-        size_t pair_bytes = 0, key_bytes = 0;
-        SCOPE_HIP(S, hipcub::DeviceRadixSort::SortPairs(nullptr, pair_bytes, d_key[0], d_key[1], d_idx[0], d_idx[1], (int)m, 0, 64, S.st));
-        SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(nullptr, key_bytes, d_key[0], d_key[1], (int)m, 0, 64, S.st));
-        tmp_bytes = std::max(pair_bytes, key_bytes);
-        RH_TRY(S.alloc(&d_tmp, (int64_t)tmp_bytes));
         return RH_OK;
     }
 
@@ -161,13 +155,10 @@ struct QuerySearch {
         }
         g.margin = 1e-12 * (amax + span + g.h);
         a.qxyz = d_qry;
-        const uint64_t cells = (uint64_t)g.dim[0] * (uint64_t)g.dim[1] * (uint64_t)g.dim[2];
-        int bits = 1;
-        while (bits < 64 && (cells - 1) >> bits) bits++;
+        const int bits = sort_bits((uint64_t)g.dim[0] * (uint64_t)g.dim[1] * (uint64_t)g.dim[2]);
         hipLaunchKernelGGL(xq_key_kernel, dim3(blocks_for(m)), dim3(256), 0, st, g, d_qry, m, d_key[0], d_idx[0]);
         SCOPE_HIP(S, hipGetLastError());
-        size_t tb = tmp_bytes;
-        SCOPE_HIP(S, hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_key[0], d_key[1], d_idx[0], d_idx[1], (int)m, 0, bits, st));
+        RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, d_key[0], d_key[1], d_idx[0], d_idx[1], (int)m, 0, bits, st); }));
         a.order = d_idx[1];
         return RH_OK;
     }

@@ -24,6 +24,10 @@
 // Everything that crosses blocks crosses a kernel boundary; no kernel waits on another block.  No floating-point atomics:
 // integer atomics on indices, counts and bit patterns only.
 #include "knn_device.h"
+#include "wave_keys.h"
+#ifdef RH_DIAG
+#include "ransac_hip_diag.h"
+#endif
 
 namespace {
 
@@ -121,24 +125,6 @@ __global__ void ori_rank_kernel(const uint64_t *__restrict__ ekey, const uint32_
     live[r] = (uint32_t)r;
 }
 
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-    for (int d = 32; d > 0; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
-{
-    for (int d = 32; d > 0; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 __global__ void ori_init_kernel(uint32_t *__restrict__ link, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -149,14 +135,9 @@ __global__ void ori_init_kernel(uint32_t *__restrict__ link, int64_t n)
 // holds the root's smallest
 __device__ __forceinline__ void offer(bool act, uint32_t root, uint32_t rank, int lane, uint32_t *best)
 {
-    uint64_t todo = __builtin_amdgcn_ballot_w64(act);
-    while (todo != 0) {
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t R = (uint32_t)__shfl((int)root, leader);
-        const uint64_t same = __builtin_amdgcn_ballot_w64(act && root == R);
+    wave_each_key(act, root, [&](int leader, uint32_t R, uint64_t) {
         if (lane == leader) atomicMin(&best[R], rank);
-        todo &= ~same;
-    }
+    });
 }
 
 __global__ __launch_bounds__(256) void ori_select_kernel(const uint32_t *__restrict__ live, int64_t nlive, int64_t ne, int64_t n,
@@ -254,11 +235,7 @@ __global__ __launch_bounds__(256) void ori_comp_kernel(const uint32_t *__restric
     const bool act = i < n && inv[i] != 0;
     const uint32_t root = act ? link[i] >> 1 : 0u;
     const uint64_t tk = act && top ? top_key(xyz, i, up.v) : 0ULL;
-    uint64_t todo = __builtin_amdgcn_ballot_w64(act && (int64_t)root < n);
-    while (todo != 0) {
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t R = (uint32_t)__shfl((int)root, leader);
-        const uint64_t same = __builtin_amdgcn_ballot_w64(act && root == R);
+    wave_each_key(act && (int64_t)root < n, root, [&](int leader, uint32_t R, uint64_t same) {
         unsigned long long m = (act && root == R) ? tk : 0ULL;
         if (top) m = wave_max_u64(m);
         if (lane == leader) {
@@ -266,8 +243,7 @@ __global__ __launch_bounds__(256) void ori_comp_kernel(const uint32_t *__restric
             atomicAdd(&size[R], (int32_t)__popcll(same));
             if (top) atomicMax(&pmax[R], m);
         }
-        todo &= ~same;
-    }
+    });
 }
 
 // ANCHOR_TOP: the smallest index that reaches its root's largest t (one atomicMin per distinct root of a wave)
@@ -309,11 +285,6 @@ __global__ __launch_bounds__(256) void ori_root_kernel(const uint32_t *__restric
     if (__builtin_amdgcn_ballot_w64(isroot) == 0) return;         // wave-uniform
     sz = wave_max_u64(sz);
     if ((threadIdx.x & 63) == 0) atomicMax(&sc->largest, (int32_t)sz);
-}
-
-__global__ void ori_m_kernel(const int32_t *__restrict__ flag, const int32_t *__restrict__ num, int64_t n, OriScal *sc)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0) sc->m = num[n - 1] + flag[n - 1];
 }
 
 // the flips, on the caller's element type: negation is exact
@@ -358,13 +329,6 @@ __global__ void ori_incons_kernel(const uint64_t *__restrict__ redge, int64_t ne
 }
 
 template <typename T>
-__global__ void ori_widen_kernel(const T *__restrict__ in, double *__restrict__ out, int64_t cnt)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cnt) out[i] = (double)in[i];
-}
-
-template <typename T>
 int orient(const char *who, const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_orient_params *p, int device, T *nrm_out,
            int32_t *flip_out, int32_t *comp_out, rh_orient_stats *stats)
 {
@@ -401,7 +365,7 @@ int orient(const char *who, const T *xyz_aos, const T *nrm_aos, int64_t n, const
         RH_TRY(S.alloc(&d_out, 3 * n));
         RH_TRY(S.alloc(&d_nrm, 3 * n));
         SCOPE_HIP(S, hipMemcpyAsync(d_out, nrm_aos, sizeof(T) * 3 * (size_t)n, hipMemcpyDefault, st));
-        hipLaunchKernelGGL(ori_widen_kernel<T>, dim3(blocks_for(3 * n)), dim3(256), 0, st, d_out, d_nrm, 3 * n);
+        RH_TRY(S.widen(d_out, d_nrm, 3 * n));
     }
     OriScal *d_sc = nullptr, h;
     uint8_t *d_inv = nullptr;
@@ -418,8 +382,7 @@ int orient(const char *who, const T *xyz_aos, const T *nrm_aos, int64_t n, const
     KnnIndex ix;
     KnnQuery kq;
     RH_TRY(ix.init(S, d_xyz, n));
-    SCOPE_HIP(S, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
-    SCOPE_HIP(S, hipStreamSynchronize(st));
+    RH_TRY(S.fetch(&h, d_sc));
     if (h.n_bad != 0) { rh_set_error("%s: a normal component is not finite or exceeds 2 in magnitude", who); return RH_E_INVALID; }
     const int64_t nv = (int64_t)h.n_vertices;
     RH_TRY(knn_index_for_k(ix, k + 1, p->radius, kq));
@@ -429,31 +392,15 @@ int orient(const char *who, const T *xyz_aos, const T *nrm_aos, int64_t n, const
     int32_t *d_flagc = nullptr, *d_num = nullptr;
     RH_TRY(S.alloc(&d_flagc, n));
     RH_TRY(S.alloc(&d_num, n));
-    size_t b_sort = 0, b_uniq = 0, b_rank = 0, b_sel = 0, b_scan = 0;
-    {
-        uint32_t *v32 = nullptr;
-        uint8_t *f8 = nullptr;
-        SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(nullptr, b_sort, d_pairs, d_sorted, (int)nk, 0, 64, st));
-        SCOPE_HIP(S, hipcub::DeviceSelect::Unique(nullptr, b_uniq, d_sorted, d_pairs, &d_sc->n_unique, (int)nk, st));
-        SCOPE_HIP(S, hipcub::DeviceRadixSort::SortPairs(nullptr, b_rank, d_pairs, d_sorted, v32, v32, (int)nk, 0, 64, st));
-        SCOPE_HIP(S, hipcub::DeviceSelect::Flagged(nullptr, b_sel, v32, f8, v32, &d_sc->nlive, (int)nk, st));
-        SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(nullptr, b_scan, d_flagc, d_num, (int)n, st));
-    }
-    const size_t tmp_bytes = std::max(std::max(b_sort, b_uniq), std::max(std::max(b_rank, b_sel), b_scan));
-    uint8_t *d_tmp = nullptr;
-    RH_TRY(S.alloc(&d_tmp, (int64_t)tmp_bytes));
-    size_t tb = tmp_bytes;
     SCOPE_HIP(S, hipMemsetAsync(d_pairs, 0xFF, sizeof(uint64_t) * (size_t)nk, st));
     hipLaunchKernelGGL(ori_emit_kernel, dim3(blocks_for(n, NRM_BLOCK / 64)), dim3(NRM_BLOCK), 0, st, ix.g, kq, d_inv, d_pairs);
     SCOPE_HIP(S, hipGetLastError());
-    SCOPE_HIP(S, hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_pairs, d_sorted, (int)nk, 0, 64, st));
-    tb = tmp_bytes;
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortKeys(t, b, d_pairs, d_sorted, (int)nk, 0, 64, st); }));
     uint64_t *d_ekey = d_pairs;                                   // (the unsorted pairs are spent)
-    SCOPE_HIP(S, hipcub::DeviceSelect::Unique(d_tmp, tb, d_sorted, d_ekey, &d_sc->n_unique, (int)nk, st));
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceSelect::Unique(t, b, d_sorted, d_ekey, &d_sc->n_unique, (int)nk, st); }));
     hipLaunchKernelGGL(ori_count_kernel, dim3(1), dim3(64), 0, st, d_ekey, d_sc);
     SCOPE_HIP(S, hipGetLastError());
-    SCOPE_HIP(S, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
-    SCOPE_HIP(S, hipStreamSynchronize(st));
+    RH_TRY(S.fetch(&h, d_sc));
     const int64_t ne = h.n_edges;
     if (ne < 0 || ne > nk) { rh_set_error("%s: %lld edges of %lld pairs", who, (long long)ne, (long long)nk); return RH_E_INTERNAL; }
 
@@ -478,8 +425,7 @@ int orient(const char *who, const T *xyz_aos, const T *nrm_aos, int64_t n, const
         d_live[0] = d_eid;                                        // (the edge numbers are spent once the ranks stand)
         hipLaunchKernelGGL(ori_weight_kernel, dim3(blocks_for(ne)), dim3(256), 0, st, d_ekey, ne, n, d_nrm, d_akey, d_eid);
         SCOPE_HIP(S, hipGetLastError());
-        tb = tmp_bytes;
-        SCOPE_HIP(S, hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_akey, d_akey_sorted, d_eid, d_order, (int)ne, 0, 64, st));
+        RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, d_akey, d_akey_sorted, d_eid, d_order, (int)ne, 0, 64, st); }));
         hipLaunchKernelGGL(ori_rank_kernel, dim3(blocks_for(ne)), dim3(256), 0, st, d_ekey, d_order, ne, d_redge, d_live[0]);
         SCOPE_HIP(S, hipGetLastError());
 
@@ -492,8 +438,7 @@ int orient(const char *who, const T *xyz_aos, const T *nrm_aos, int64_t n, const
             hipLaunchKernelGGL(ori_select_kernel, dim3(blocks_for(nlive)), dim3(256), 0, st, d_live[cur], nlive, ne, n, d_redge, d_link,
                                d_best, d_flag);
             SCOPE_HIP(S, hipGetLastError());
-            tb = tmp_bytes;
-            SCOPE_HIP(S, hipcub::DeviceSelect::Flagged(d_tmp, tb, d_live[cur], d_flag, d_live[cur ^ 1], &d_sc->nlive, (int)nlive, st));
+            RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceSelect::Flagged(t, b, d_live[cur], d_flag, d_live[cur ^ 1], &d_sc->nlive, (int)nlive, st); }));
             hipLaunchKernelGGL(ori_hook_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_link, d_best, d_redge, d_akey_sorted, n, ne,
                                d_tmpl, d_sc);
             // doublings tmp -> link -> tmp -> link: three before the first read-back, two before every further one
@@ -507,8 +452,7 @@ int orient(const char *who, const T *xyz_aos, const T *nrm_aos, int64_t n, const
                                        n, &d_sc->unfin[jumps]);
                 }
                 SCOPE_HIP(S, hipGetLastError());
-                SCOPE_HIP(S, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
-                SCOPE_HIP(S, hipStreamSynchronize(st));
+                RH_TRY(S.fetch(&h, d_sc));
                 if (!h.unfin[jumps - 1]) break;
             }
             if (h.nlive < 0 || (int64_t)h.nlive > nlive) { rh_set_error("%s: %d live edges of %lld", who, h.nlive, (long long)nlive); return RH_E_INTERNAL; }
@@ -543,15 +487,13 @@ int orient(const char *who, const T *xyz_aos, const T *nrm_aos, int64_t n, const
     hipLaunchKernelGGL(ori_root_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_link, d_inv, n, d_nrm, top, up, d_minidx, d_anchor, d_size,
                        d_flagc, d_rootflip, d_sc);
     SCOPE_HIP(S, hipGetLastError());
-    tb = tmp_bytes;
-    SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_flagc, d_num, (int)n, st));
-    hipLaunchKernelGGL(ori_m_kernel, dim3(1), dim3(64), 0, st, d_flagc, d_num, n, d_sc);
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_flagc, d_num, (int)n, st); }));
+    hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(64), 0, st, d_flagc, d_num, n, &d_sc->m);
     hipLaunchKernelGGL(ori_flip_kernel<T>, dim3(blocks_for(n)), dim3(256), 0, st, d_link, d_inv, n, d_rootflip, d_minidx, d_num, d_out,
                        d_flip, d_comp, d_sc);
     if (ne > 0) hipLaunchKernelGGL(ori_incons_kernel, dim3(blocks_for(ne)), dim3(256), 0, st, d_redge, ne, n, d_link, d_sc);
     SCOPE_HIP(S, hipGetLastError());
-    SCOPE_HIP(S, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
-    SCOPE_HIP(S, hipStreamSynchronize(st));
+    RH_TRY(S.fetch(&h, d_sc));
     if ((int64_t)h.n_tree != nv - (int64_t)h.m) {
         rh_set_error("%s: %llu tree edges for %lld vertices in %d components", who, h.n_tree, (long long)nv, h.m);
         return RH_E_INTERNAL;
@@ -587,3 +529,61 @@ extern "C" int rh_orient_normals_f32(const float *xyz_aos, const float *nrm_aos,
     return orient<float>("rh_orient_normals_f32", xyz_aos, nrm_aos, n, p, device, nrm_out_aos, flip_out_or_null, comp_out_or_null,
                          stats_or_null);
 }
+
+#ifdef RH_DIAG
+namespace {
+
+// wave_each_key as a kernel of its own (ransac_hip_diag.h: rh_dbg_wave_keys).  A lane without `act` keeps its key: it
+// may equal an active lane's and must still be in no ballot.  scal[0]: the leader branch ran; scal[1]: a lane saw
+// anything but the whole wave inside f, or a ballot that is not "active and my key is L"
+template <typename K>
+__global__ void __launch_bounds__(256) dbg_wave_keys_kernel(const uint32_t *__restrict__ keys, const uint8_t *__restrict__ act,
+                                                            const int32_t *__restrict__ slot, int32_t n, int32_t *sum,
+                                                            int32_t *minlead, int32_t *scal)
+{
+    const int i = threadIdx.x, lane = i & 63;
+    const bool a = i < n && act[i] != 0;
+    const K key = i < n ? (K)keys[i] : (K)0;
+    const int32_t s = a ? slot[i] : 0;
+    wave_each_key(a, key, [&](int leader, K L, uint64_t same) {
+        const bool in = a && key == L;
+        if (__builtin_amdgcn_ballot_w64(true) != ~0ULL || (((same >> lane) & 1ULL) != 0) != in) atomicAdd(&scal[1], 1);
+        if (lane == leader) {
+            atomicAdd(&sum[s], (int32_t)__popcll(same));
+            atomicMin(&minlead[s], (int32_t)i);
+            atomicAdd(&scal[0], 1);
+        }
+    });
+}
+
+}  // namespace
+
+extern "C" int rh_dbg_wave_keys(const uint32_t *keys, const uint8_t *act, const int32_t *slot, int32_t n, int32_t nslots, int u32,
+                                int device, int32_t *sum_out, int32_t *minlead_out, int32_t *scal_out)
+{
+    static const char who[] = "rh_dbg_wave_keys";
+    bool ok = keys && act && slot && sum_out && minlead_out && scal_out && n >= 0 && n <= 256 && nslots >= 1;
+    for (int32_t i = 0; ok && i < n; i++) ok = slot[i] >= 0 && slot[i] < nslots;   // (a slot is an address on the device)
+    if (!ok) { rh_set_error("%s: bad arguments", who); return RH_E_INVALID; }
+    CallScope S;
+    RH_TRY(S.open(who, device));
+    const hipStream_t st = S.st;
+    uint32_t *d_keys = nullptr;
+    uint8_t *d_act = nullptr;
+    int32_t *d_slot = nullptr, *d_sum = nullptr, *d_min = nullptr, *d_scal = nullptr;
+    RH_TRY(S.alloc(&d_keys, n)); RH_TRY(S.alloc(&d_act, n)); RH_TRY(S.alloc(&d_slot, n));
+    RH_TRY(S.alloc(&d_sum, nslots)); RH_TRY(S.alloc(&d_min, nslots)); RH_TRY(S.alloc(&d_scal, 2));
+    SCOPE_HIP(S, hipMemcpyAsync(d_keys, keys, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    SCOPE_HIP(S, hipMemcpyAsync(d_act, act, (size_t)n, hipMemcpyHostToDevice, st));
+    SCOPE_HIP(S, hipMemcpyAsync(d_slot, slot, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    SCOPE_HIP(S, hipMemsetAsync(d_sum, 0, sizeof(int32_t) * (size_t)nslots, st));
+    SCOPE_HIP(S, hipMemsetAsync(d_min, 0x7F, sizeof(int32_t) * (size_t)nslots, st));   // 0x7F7F7F7F: no leader
+    SCOPE_HIP(S, hipMemsetAsync(d_scal, 0, sizeof(int32_t) * 2, st));
+    if (u32) hipLaunchKernelGGL(dbg_wave_keys_kernel<uint32_t>, dim3(1), dim3(256), 0, st, d_keys, d_act, d_slot, n, d_sum, d_min, d_scal);
+    else hipLaunchKernelGGL(dbg_wave_keys_kernel<int32_t>, dim3(1), dim3(256), 0, st, d_keys, d_act, d_slot, n, d_sum, d_min, d_scal);
+    SCOPE_HIP(S, hipGetLastError());
+    SCOPE_HIP(S, hipMemcpyAsync(sum_out, d_sum, sizeof(int32_t) * (size_t)nslots, hipMemcpyDeviceToHost, st));
+    SCOPE_HIP(S, hipMemcpyAsync(minlead_out, d_min, sizeof(int32_t) * (size_t)nslots, hipMemcpyDeviceToHost, st));
+    return S.fetch(scal_out, d_scal, 2);
+}
+#endif   // RH_DIAG

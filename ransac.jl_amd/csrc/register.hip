@@ -297,8 +297,7 @@ int reg_register(const T *ref_aos, const T *nrm_aos, int64_t n, const T *qry_aos
             len = nb;
         }
         double root[REG_NC_PLANE + 1];
-        SCOPE_HIP(S, hipMemcpyAsync(root, d_part[cur], sizeof(double) * (size_t)(nc + 1), hipMemcpyDeviceToHost, st));
-        SCOPE_HIP(S, hipStreamSynchronize(st));
+        RH_TRY(S.fetch(root, d_part[cur], (size_t)(nc + 1)));
         unsigned long long cnt;
         memcpy(&cnt, &root[nc], sizeof cnt);
         if (cnt > (unsigned long long)m) { rh_set_error("%s: the count of valid queries is out of range", who); return RH_E_INTERNAL; }

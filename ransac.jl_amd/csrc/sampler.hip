@@ -7,6 +7,7 @@
 // restores the reference's candidate order exactly.
 #include "fit_shared.h"
 #include "rh_internal.h"
+#include "wave_keys.h"
 #ifdef RH_DIAG
 #include <stddef.h>
 #include <string.h>
@@ -180,17 +181,11 @@ sample_sets_kernel(const double *__restrict__ rec, int64_t n, DevEnabled en, int
     // draws per iteration: one atomic per (wave, iteration) instead of one per set -- thousands of
     // same-address atomics serialise in L2 and dominated the kernel
     {
-        uint64_t todo = __builtin_amdgcn_ballot_w64(true);
         const int lane = threadIdx.x & 63;
-        while (todo != 0) {
-            const int leader = __builtin_ctzll(todo);
-            const int32_t it0 = __shfl(it, leader);
-            const uint64_t grp = __builtin_amdgcn_ballot_w64(it == it0) & todo;
-            unsigned v = (it == it0) ? nd : 0u;
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        wave_each_key(true, it, [&](int leader, int32_t it0, uint64_t) {
+            const unsigned v = (unsigned)wave_sum_i32((it == it0) ? (int32_t)nd : 0);
             if (lane == leader) atomicAdd(&draws_per_iter[it0], (unsigned long long)v);
-            todo &= ~grp;
-        }
+        });
     }
     if (gave_up) atomicExch(gave_up_flag, 1);
     set_level[t] = ok ? level : 0;
@@ -305,17 +300,11 @@ sample_fit_oct_kernel(const double *__restrict__ rec, int64_t n, DevEnabled en, 
     const bool ok = rhfit::sample_minimal_set_octree<DN>(en, oc, Pwin + (int64_t)it * oc.depth, n, (int64_t)n_enabled, drawN, &x, sd, &nd,
                                                          &gave_up, &level);
     {   // draws per iteration: one atomic per (wave, iteration)
-        uint64_t todo = __builtin_amdgcn_ballot_w64(true);
         const int lane = threadIdx.x & 63;
-        while (todo != 0) {
-            const int leader = __builtin_ctzll(todo);
-            const int32_t itl = __shfl(it, leader);
-            const uint64_t grp = __builtin_amdgcn_ballot_w64(it == itl) & todo;
-            unsigned v = (it == itl) ? nd : 0u;
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-            if (lane == leader) atomicAdd(&draws_per_iter[itl], (unsigned long long)v);
-            todo &= ~grp;
-        }
+        wave_each_key(true, it, [&](int leader, int32_t it0, uint64_t) {
+            const unsigned v = (unsigned)wave_sum_i32((it == it0) ? (int32_t)nd : 0);
+            if (lane == leader) atomicAdd(&draws_per_iter[it0], (unsigned long long)v);
+        });
     }
     if (gave_up) atomicExch(gave_up_flag, 1);
     if (!ok) return;
@@ -393,17 +382,11 @@ sample_fit_ranks_kernel(const double *__restrict__ crec, const double *__restric
     int64_t first_index = 0;
     const bool ok = sample_ranks<DN>(en, n, (int64_t)n_enabled, drawN, &x, sd, &nd, &gave_up, &first_index);
     {
-        uint64_t todo = __builtin_amdgcn_ballot_w64(true);
         const int lane = threadIdx.x & 63;
-        while (todo != 0) {
-            const int leader = __builtin_ctzll(todo);
-            const int32_t it0 = __shfl(it, leader);
-            const uint64_t grp = __builtin_amdgcn_ballot_w64(it == it0) & todo;
-            unsigned v = (it == it0) ? nd : 0u;
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        wave_each_key(true, it, [&](int leader, int32_t it0, uint64_t) {
+            const unsigned v = (unsigned)wave_sum_i32((it == it0) ? (int32_t)nd : 0);
             if (lane == leader) atomicAdd(&draws_per_iter[it0], (unsigned long long)v);
-            todo &= ~grp;
-        }
+        });
     }
     if (gave_up) atomicExch(gave_up_flag, 1);
     if (!ok) return;

@@ -34,6 +34,7 @@
 #endif
 #include "score_device.h"
 #include "score4_device.h"
+#include "wave_keys.h"
 
 namespace {
 
@@ -70,13 +71,6 @@ struct S4Shared {
     int weirdw[S4_TG];                   // per group: an enabled point with a non-finite value
     int npairs, next_batch;
 };
-
-static __device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 static __device__ __forceinline__ bool is_nan_bits(float v)
 {

@@ -307,8 +307,7 @@ int downsample(const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_voxel_par
         SCOPE_HIP(S, hipGetLastError());
     }
     unsigned long long h_scal[MM_WORDS];
-    SCOPE_HIP(S, hipMemcpyAsync(h_scal, d_scal, sizeof h_scal, hipMemcpyDeviceToHost, st));
-    SCOPE_HIP(S, hipStreamSynchronize(st));
+    RH_TRY(S.fetch(h_scal, d_scal, MM_WORDS));
     const int64_t nf = (int64_t)h_scal[MM_COUNT];
     if (n_dropped_out) *n_dropped_out = n - nf;
     auto download_map = [&]() -> int {
@@ -346,16 +345,12 @@ int downsample(const T *xyz_aos, const T *nrm_aos, int64_t n, const rh_voxel_par
     RH_TRY(S.alloc(&d_slot, n));
     RH_TRY(S.alloc(&d_flag, n));
     RH_TRY(S.alloc(&d_rank, n));
-    size_t tmp_bytes = 0;
-    SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_flag, d_rank, (int)n, st));
-    uint8_t *d_tmp = nullptr;
-    RH_TRY(S.alloc(&d_tmp, (int64_t)tmp_bytes));
     hipLaunchKernelGGL(vox_init_kernel, dim3(blocks_for((int64_t)tcap)), blk, 0, st, tab);
     hipLaunchKernelGGL(vox_insert_kernel, gp, blk, 0, st, d_xyz, n, d_rowof, g, tab, d_slot);
     // 3. ranks of the first points
     hipLaunchKernelGGL(vox_flag_kernel, gp, blk, 0, st, n, d_rowof, d_slot, tab, d_flag);
     SCOPE_HIP(S, hipGetLastError());
-    SCOPE_HIP(S, hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flag, d_rank, (int)n, st));
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_flag, d_rank, (int)n, st); }));
     int32_t last[2] = { 0, 0 };
     SCOPE_HIP(S, hipMemcpyAsync(&last[0], d_rank + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
     SCOPE_HIP(S, hipMemcpyAsync(&last[1], d_flag + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
