@@ -57,6 +57,15 @@ int rh_dbg_group_boxes(rh_cloud *c, double *out, int64_t cap, int64_t *ngroups_o
  * Needs no GPU. */
 int rh_dbg_cylbox(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, const double *boxes, int64_t n,
                   uint8_t *skip_out, uint8_t *ball_out, float *fields_out /* [11] */);
+/* The classifier of a sphere or cylinder candidate as the score kernel runs it, on the host (csrc/score4_device.h: cls_make on
+ * the host's record, then the kernel's own cls_round_ab on the n points xyz[3 i ..] with normals nrm[3 i ..], converted to
+ * binary32 as the kernel's staging converts them).  ua_out[i], ub_out[i]: the scaled values of the distance and the normal half
+ * (u = max of the two: u < 0 surely an inlier, u > 1 surely not, else undecided); rec_out: the 16 fields of the classifier
+ * record (field 15 NaN: the candidate is exact-only and the kernel does not read ua / ub); dbg4_out: the margins and widths of
+ * the squared form, m2, W2 = 2 m2, mv, Wv = 2 mv (zeros for an exact-only candidate).  M, Nm: max |coordinate| and max |normal
+ * component| of the point set the margins are made for; f32: a Float32 cloud's margins.  Needs no GPU. */
+int rh_dbg_cls_round(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
+                     const double *nrm, float *ua_out, float *ub_out, float *rec_out /* [16] */, double *dbg4_out /* [4] */);
 /* The device's octree sampler finds a point's cell and the r-th enabled point of a cell with a cell directory and
  * bracketed 8-ary searches (csrc/fit_shared.h: cell_bounds_code, lower_bound_in, select_in, select_in_many, select_bit)
  * where the host form uses plain binary searches.  Host-only self-check of those routines against the plain ones on a

@@ -13,8 +13,9 @@
 //    instruction, padded apart in the banks) with its candidate's record and its counters in vector registers: no
 //    scalar instruction in the loop but its control, no ballot, no reduction, no divergence.
 //  * The per-point work is the two-sided binary32 classifier of score4_device.h on a binary32 tile (24 B per point):
-//    t = min(a, b) per point with sure <=> t > 0 and maybe <=> t > -1 (plane, sphere, cylinder).  A pair whose "sure"
-//    and "maybe" counts differ -- some point lies within the rounding margin of a threshold -- is redone as a whole by
+//    u = max(ua, ub) per point with sure <=> u < 0 and maybe <=> u <= 1 (plane; sphere and cylinder in the squared
+//    quantities |q|^2 and qn |qn|: no root, no division).  A pair whose "sure" and "maybe" counts differ -- some point
+//    lies within the rounding margin of a threshold -- is redone as a whole by
 //    the reference's binary64 test (score_device.h, unchanged; lane = point, the points from global memory).  Cones
 //    are classified the same way (the closed form of project2cone's frame, score4_device.h); their undecided POINTS go
 //    through a per-wave ring to the exact test one by one (a redo of the whole group costs 247 binary64 instructions).
@@ -600,7 +601,7 @@ score4_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const S
 // construction (RH_CLS_SAFETY) it should stay below ~1/8.  out[kind * 2 + {0, 1}] = max over the batch of |a32 - a64|,
 // |b32 - b64| (sphere / cylinder: only where the distance half is not far outside, ua64 < 2 -- the norm's error is relative
 // to the norm); out[8 + kind] = pairs looked at.
-struct S4AuditCand { rh_prep P; rh_cls C; double cNhi, wN, eDlo, wD, cosa; int kind, usable; };
+struct S4AuditCand { rh_prep P; rh_cls C; double cNhi, wN, eDlo, wD, cosa, eps; int kind, usable; };   // (cNhi .. wD: cls_make's dbg4)
 
 __global__ void __launch_bounds__(256)
 cls_audit_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const S4AuditCand *__restrict__ cands, int ncand,
@@ -639,12 +640,13 @@ cls_audit_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, cons
                 qx = (x - P.f[0] * sd) - P.f[3]; qy = (y - P.f[1] * sd) - P.f[4]; qz = (z - P.f[2] * sd) - P.f[5];
                 R = P.f[6]; sgn = P.f[7];
             }
-            const double nr = sqrt((qx * qx + qy * qy) + qz * qz);
-            const double inv = 1.0 / nr;
-            const double dt = ((inv * qx) * nx + (inv * qy) * ny) + (inv * qz) * nz;
-            a64 = (fabs(nr - R) - Q.eDlo) / Q.wD;
-            b64 = (Q.cNhi - sgn * dt) / Q.wN;
-            // the norm's error is relative (4.5 u nr): far outside the band it exceeds any fixed margin and cannot matter
+            // the squared form (score4_device.h, "Round kinds without a square root"): dbg4 = m2, W2, mv, Wv
+            const double m2 = Q.cNhi, W2 = Q.wN, mv = Q.eDlo, Wv = Q.wD;
+            const double n2 = (qx * qx + qy * qy) + qz * qz;
+            const double qn = (qx * nx + qy * ny) + qz * nz;
+            a64 = (fabs(n2 - (R * R + Q.eps * Q.eps)) - (2.0 * R * Q.eps - m2)) / W2;
+            b64 = (mv + (Q.cosa * Q.cosa * n2 - sgn * qn * fabs(qn))) / Wv;
+            // the error of n2 is relative (3 u n2): far outside the band it exceeds any fixed margin and cannot matter
             // (ua is a few thousand widths above 1 there); what has to hold is the bound NEAR the band
             if (a64 < 2.0) { ea = fabs((double)a32 - a64); eb = fabs((double)b32 - b64); }
             counted = true;
@@ -1375,7 +1377,7 @@ extern "C" int rh_dbg_cls_audit(rh_cloud *c, const rh_shape *shapes, int32_t b, 
         rh_prep_host(shapes[i], &Q.P);
         double d4[4] = { 0, 0, 0, 0 };
         cls_make(Q.P, Q.kind, p->eps[Q.kind], p->cos_alpha[Q.kind], c->coord_mag, c->nrm_mag, Q.C, nullptr, 0, d4, c->f32);
-        Q.cNhi = d4[0]; Q.wN = d4[1]; Q.eDlo = d4[2]; Q.wD = d4[3]; Q.cosa = p->cos_alpha[Q.kind];
+        Q.cNhi = d4[0]; Q.wN = d4[1]; Q.eDlo = d4[2]; Q.wD = d4[3]; Q.cosa = p->cos_alpha[Q.kind]; Q.eps = p->eps[Q.kind];
         Q.usable = !(Q.C.f[RH_CLS_FLAG] != Q.C.f[RH_CLS_FLAG]) && Q.wN > 0 && Q.wD > 0;
     }
     rh_dev<S4AuditCand> d_c;
@@ -1525,6 +1527,34 @@ extern "C" int rh_dbg_cylbox(const rh_shape *shape, const rh_params *p, double M
         G.cx = o[0]; G.cy = o[1]; G.cz = o[2]; G.hx = o[3]; G.hy = o[4]; G.hz = o[5]; G.hr = o[6];
         skip_out[i] = cyl_box_skip32<true>(box, G) ? 1 : 0;
         ball_out[i] = cyl_box_skip32<false>(box, G) ? 1 : 0;
+    }
+    return RH_OK;
+}
+
+// the classifier of a round candidate as the host runs it: the record cls_make builds for the shape, its margins (dbg4: m2, W2,
+// mv, Wv) and the kernel's own cls_round_ab on n points.  Host only: needs no GPU.
+extern "C" int rh_dbg_cls_round(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
+                                const double *nrm, float *ua_out, float *ub_out, float *rec_out, double *dbg4_out)
+{
+    if (shape == nullptr || p == nullptr || n < 0 || (n > 0 && (xyz == nullptr || nrm == nullptr || ua_out == nullptr || ub_out == nullptr))) {
+        rh_set_error("rh_dbg_cls_round: bad arguments");
+        return RH_E_INVALID;
+    }
+    if (shape->kind != RH_SPHERE && shape->kind != RH_CYLINDER) { rh_set_error("rh_dbg_cls_round: spheres and cylinders only"); return RH_E_INVALID; }
+    rh_prep P;
+    rh_prep_host(*shape, &P);
+    rh_cls C;
+    double d4[4] = { 0, 0, 0, 0 };
+    cls_make(P, shape->kind, p->eps[shape->kind], p->cos_alpha[shape->kind], M, Nm, C, nullptr, 0, d4, f32 != 0);
+    if (rec_out != nullptr)
+        for (int k = 0; k < 16; k++) rec_out[k] = C.f[k];
+    if (dbg4_out != nullptr)
+        for (int k = 0; k < 4; k++) dbg4_out[k] = d4[k];
+    for (int64_t i = 0; i < n; i++) {
+        const float x = (float)xyz[3 * i], y = (float)xyz[3 * i + 1], z = (float)xyz[3 * i + 2];
+        const float nx = (float)nrm[3 * i], ny = (float)nrm[3 * i + 1], nz = (float)nrm[3 * i + 2];
+        if (shape->kind == RH_SPHERE) cls_round_ab<RH_SPHERE>(C, x, y, z, nx, ny, nz, ua_out[i], ub_out[i]);
+        else cls_round_ab<RH_CYLINDER>(C, x, y, z, nx, ny, nz, ua_out[i], ub_out[i]);
     }
     return RH_OK;
 }

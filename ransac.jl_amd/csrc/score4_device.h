@@ -18,9 +18,8 @@
 // |d| <= u.  With M = max |coordinate| of the point set, Nm = max |normal component|, T = M + max |centre coordinate|:
 //   plane     dn = n . np - c             |.32 - .|   <= u (5.05 |n|_1 Nm + 4.1 |c|)      (c = cos alpha, added first)
 //             d  = oz . p - oz . P0       |d32 - d|   <= 6.1 u (|oz|_1 M + |oz . P0|)
-//   sphere    dx = p - o (per component e = 2.01 u T);  nr = |dx| = n2 rsq(n2):  |nr32 - nr| <= sqrt(3) e + 4.5 u nr
-//             L = sgn dx . np - c nr  (c = cos alpha; the test is L > 0):
-//                                         |L32 - L| <= Nm (3 e + 8.7 u nr) + |c| (sqrt(3) e + 6 u nr)
+//   sphere    q = p - o (per component e = 2.01 u T), tested in the squared quantities n2 = |q|^2 and s |s|, s = sgn q . np:
+//             "Round kinds without a square root" below
 //   cylinder  q = t - a (a . t), t = p - c0: per component e_q = u T (3.01 + 8.04 |a|_inf |a|_1);  then as the sphere
 //             with e_q for e
 //   cone      the reference's frame in closed form (cone.jl:68-85 reduces to it, derivation at cls_cone_u): with w = p - apex,
@@ -63,8 +62,8 @@ struct rh_cls {
 };
 constexpr int RH_CLS_FLAG = 15;   // NaN = exact-only
 // plane:    0-2 -n / wN | 3 cN_hi / wN | 4-6 oz / wD | 7 -(oz . P0) / wD | 8 eD_lo / wD
-// sphere:   0-2 o | 3 R | 4 1 / wD | 5 -eD_lo / wD | 6 -sgn / wN | 7 cN_hi / wN
-// cylinder: 0-2 a | 3-5 c0 | 6 R | 7 1 / wD | 8 -eD_lo / wD | 9 -sgn / wN | 10 cN_hi / wN
+// sphere:   0-2 o | 3 K | 4 1 / W2 | 5 -(H - m2) / W2 | 6 -sgn / Wv | 7 cos^2(alpha) / Wv      (K = R^2 + eps^2, H = 2 R eps; the
+// cylinder: 0-2 a | 3-5 c0 | 6 K | 7 1 / W2 | 8 -(H - m2) / W2 | 9 -sgn / Wv | 10 cos^2(alpha) / Wv   sixth constant mv / Wv is 1/2)
 // cone:     0-2 apex | 3-5 a^ | 6 c' / wD | 7 s' / wD | 8 eD_lo / wD | 9 -sgn c' / wL | 10 -sgn s' / wL | 11 cos(alpha) / wL | 12 beta
 
 // culling record of a candidate, structure-of-arrays over the batch (field f of slot i at box[f * stride + i]): what
@@ -225,10 +224,49 @@ __host__ __device__ inline void nsig_cand_mask(double nx, double ny, double nz, 
     m[0] = w0; m[1] = w1; m[2] = w2;
 }
 
+// ---- Round kinds without a square root (cls_round_ab below; the records of the sphere and the cylinder).  The exact test is
+// |nr - R| < eps and s / nr > c with nr = |q|, s = sgn (q . np), c = cos(alpha).  Until round 10 the classifier formed
+// nr = n2 rsq(n2) and s / nr: a reciprocal root (8.1 issue cycles against 2.3 of a plain operation, ubench_valu_rates) and two
+// multiplies per point that the decision does not need.  With n2 = nr^2, K = R^2 + eps^2, H = 2 R eps:
+//     |nr - R| < eps  <=>  (R - eps)^2 < n2 < (R + eps)^2  <=>  |n2 - K| < H                       (needs R - eps > 0)
+//     s / nr > c      <=>  s > 0 and s^2 > c^2 n2           <=>  v := s |s| - c^2 n2 > 0          (needs c > 0, nr > 0)
+// and the kernel computes, both scaled like the plane's (widths W2 = 2 m2, Wv = 2 mv),
+//     ua = (|n2 - K| - (H - m2)) / W2,      ub = (mv - v) / Wv = 1/2 + (c^2 n2 - sgn qn |qn|) / Wv,       u = max(ua, ub).
+// Margins, first order x S (RH_CLS_SAFETY; tripled on a Float32 cloud).  mD, the margin of the older form on nr itself
+// (S (sqrt(3) e + 7 u (R + eps))), only places two radii: nrmax = R + eps + 3 mD, nrmin = R - eps - 3 mD.
+//   Which points count.  A point with nr > nrmax has ua > 1: |q^| >= nr - sqrt(3) e >= (R + eps) + 2.5 mD (sqrt(3) e <= mD / S),
+//   so |q^|^2 >= (K + H) + 5 mD (R + eps) + 6.25 mD^2, while m2 (below) <= S (2 (R + eps) sqrt(3) e + 20 u (R + eps)^2) + 6.5 mD^2:
+//   what is left, S (3 sqrt(3) e (R + eps) + 15 u (R + eps)^2) - mD^2 / 4 >= 2 mD (R + eps) >= 28 u (R + eps)^2 (R + eps > 3 mD),
+//   holds the roundings of n2^, of the subtraction and of the fma (~7 u (R + eps)^2) four times, and |q^|^2 (1 - 3.01 u) grows
+//   with nr.  Such a point is truly outside, so u > 1 is right whatever ub is.  Every bound below is therefore needed for
+//   nr <= nrmax only, where |q^| <= nq = nrmax + sqrt(3) e.
+//   n2:  |q^|^2 - n2 = 2 q . dq + |dq|^2 with |dq| <= sqrt(3) e; the three roundings of the sum of squares (non-negative terms)
+//        3.01 u nq^2; K's conversion, the subtraction, the scaled constants and the fma, near the band where |n2 - K| ~ H <= K:
+//        below 6 u K.       dn2 = 2 nrmax sqrt(3) e + 3 e^2 + 4 u nq^2 + 6 u K,        m2 = S dn2.
+//   qn:  the conversion of np and of q (3 Nm e + u Nm |q^|_1) and three roundings of partial sums below Nm |q^|_1 <= Nm sqrt(3) nq:
+//                           ds = 3 Nm e + 5 u Nm sqrt(3) nq.
+//   v:   |s^ |s^| - s |s|| <= 2 |s| ds + ds^2 (x |x| has slope 2 |x|); c^2 dn2 for n2; the product, the two scaled constants and
+//        the two fma: 2 u s^2 + 3 u c^2 n2.  Only |s| <= c nr + ds has to be covered:
+//          - "surely in" (v^ > mv) of a point the test rejects (s <= c nr): for s^ <= 0 both addends of ub are >= 0 whatever the
+//            roundings (they are relative, signs are exact) and ub >= 1/2; else -ds <= s <= c nr;
+//          - "surely out" (v^ < -mv) of a point the test accepts (s > c nr): the shortfall error(s) - v(s) has the derivative
+//            2 ds + 4 u s - 2 s < 0 for s > 1.01 ds, so its largest value over s >= c nr is taken at s = c nr (or below c nr + ds),
+//            where v = 0.
+//                           mv = S (2 (c nrmax + ds) ds + ds^2 + c^2 dn2 + 8 u c^2 nq^2).
+//        With sqrt(3) Nm nrmax (all a normal can give) in place of c nrmax + ds the undecided points rise by a third (tools/proto/root_free.py).
+//   Float32 cloud: the exact chain's error in nr and in s / nr reaches n2 and v through the factors 2 nr and 2 c nr^2, the very
+//   factors that carry the classifier's own e and u terms into dn2 and ds above: two more parts of the same bounds, as everywhere.
+// Guards (any failure: exact-only).  eps >= 0, c > 0, nrmin > 0.  A point whose ua can be <= 1 has n2^ >= n2min =
+// (R - eps)^2 - 2 m2; n2min > 0 makes the point ON the centre / axis (n2 = 0) surely out.  A disabled point is staged as zeros:
+// qn = 0 and ub = 1/2 + c^2 n2^ / Wv, which exceeds 1 -- surely out, not merely undecided -- iff c^2 n2^ > mv: c^2 n2min >
+// 1.001 mv.  No product may overflow (inf - inf = NaN, and the books read the sign bit of u): every scaled constant x the
+// largest value of its operand on this point set (n2 <= 3.1 T^2 (1 + |a|_inf |a|_1)^2, qn^2 <= 3 Nm^2 n2) stays below 2^120.
+
 // P: the binary64 record of the candidate (rh_prep, kernels.hip prep_one, with prep_derived); eps, cosa: the kind's
 // thresholds; M, Nm: max |coordinate| / max |normal component| of the point set.  o: classifier record; box: the culling
 // record's fields go to box[f * bstride] (f < RH_BOX_FIELDS).
-// dbg4 (audit): the unscaled thresholds and widths behind a scaled record: cN_hi, wN, eD_lo, wD
+// dbg4 (audit): the unscaled thresholds and widths behind a scaled record: cN_hi, wN, eD_lo, wD (plane, cone); the margins and
+// widths of the squared form m2, W2, mv, Wv (sphere, cylinder)
 __host__ __device__ inline void cls_make(const rh_prep &P, int kind, double eps, double cosa, double M, double Nm, rh_cls &o,
                                          float *box, int64_t bstride, double *dbg4 = nullptr, bool f32cloud = false, double Ln = 0.0)
 {
@@ -310,32 +348,38 @@ __host__ __device__ inline void cls_make(const rh_prep &P, int kind, double eps,
             lipk = fmax(1.0, fabs(P.f[9] - 1.0));   // |1 - |a|^2| = |k - 1| (prep_derived)
         }
         const double s3 = 1.7320508075688774;
-        const double mD = S * (s3 * e + 7.0 * u * (fabs(R) + fabs(eps))) + 1e-30;   // (nr = n2 * rsq(n2): 4.5 u; R, eps and the scaled constant: 2 u)
-        // a point the distance half may accept (|nr32 - R| < eps + wD / 2, wD < 4 mD) lies at least this far from the
-        // centre / axis
-        const double nrmin = R - eps - 3.0 * mD;
-        // margin of the normal half as a margin on cos(alpha): |L32 - L| / nr.  Without a positive lower bound on nr (the
-        // centre lies inside the band) or with a margin that is not small the candidate is exact-only.
-        double mN = nrmin > 0.0 ? S * ((3.0 * Nm + s3 * (fabs(cosa) + 0.25)) * e / nrmin + (8.7 * Nm + 6.0 * (fabs(cosa) + 0.25)) * u) + 1e-30
-                                : __builtin_nan("");
-        if (!(mN <= 0.25)) mN = __builtin_nan("");
-        // scaled like the plane record: ua = (|nr - R| - eD_lo) / wD, ub = (cN_hi - sgn (q . np) / nr) / wN, u = max(ua, ub);
-        // a point whose distance half fails surely has ua > 1 whatever ub is
-        ok = ok && cls_fin(mD) && cls_fin(mN) && (sgn == 1.0 || sgn == -1.0) && mD < 1e30;
+        // the root-free form ("Round kinds without a square root" above).  mD, the margin of the older form on nr itself, only
+        // places the two radii between which a point's ua can be <= 1
+        const double mD = S * (s3 * e + 7.0 * u * (fabs(R) + fabs(eps))) + 1e-30;
+        const double nrmax = R + eps + 3.0 * mD, nrmin = R - eps - 3.0 * mD;
+        const double nq = nrmax + s3 * e;                        // |q^| where nr <= nrmax
+        const double K = R * R + eps * eps, H = 2.0 * R * eps, ca2 = cosa * cosa;
+        const double dn2 = 2.0 * nrmax * s3 * e + 3.0 * e * e + 4.0 * u * nq * nq + 6.0 * u * K;
+        const double m2 = S * dn2 + 1e-30;
+        const double ds = 3.0 * Nm * e + 5.0 * u * Nm * s3 * nq;
+        const double mv = S * (2.0 * (fabs(cosa) * nrmax + ds) * ds + ds * ds + ca2 * dn2 + 8.0 * u * ca2 * nq * nq) + 1e-30;
+        // a point whose ua can be <= 1 has n2 (true and computed) above this
+        const double n2min = (R - eps) * (R - eps) - 2.0 * m2;
+        ok = ok && cls_fin(m2) && cls_fin(mv) && (sgn == 1.0 || sgn == -1.0) && m2 < 1e30 && mv < 1e30;
+        // the equivalences need R - eps > 0 and cos(alpha) > 0; a disabled point (staged as zeros: qn = 0, ub = (cos^2 n2 + mv) / Wv)
+        // must come out SURELY out wherever its ua does not say so already
+        ok = ok && eps >= 0.0 && cosa > 0.0 && nrmin > 0.0 && n2min > 0.0 && ca2 * n2min > 1.001 * mv;
         // (constant indices only: a run-time index would move the record to scratch memory)
-        if (sph) { o.f[0] = (float)P.f[0]; o.f[1] = (float)P.f[1]; o.f[2] = (float)P.f[2]; o.f[3] = (float)R; }
-        else { o.f[0] = (float)P.f[0]; o.f[1] = (float)P.f[1]; o.f[2] = (float)P.f[2]; o.f[3] = (float)P.f[3]; o.f[4] = (float)P.f[4]; o.f[5] = (float)P.f[5]; o.f[6] = (float)R; }
+        if (sph) { o.f[0] = (float)P.f[0]; o.f[1] = (float)P.f[1]; o.f[2] = (float)P.f[2]; }
+        else { o.f[0] = (float)P.f[0]; o.f[1] = (float)P.f[1]; o.f[2] = (float)P.f[2]; o.f[3] = (float)P.f[3]; o.f[4] = (float)P.f[4]; o.f[5] = (float)P.f[5]; }
         if (ok) {
-            const double mN2 = mN + 8.0 * u * Nm;   // + the rsq / multiply in place of the comparison against c * nr
-            const double wD = 2.0 * mD, wN = 2.0 * mN2;
-            const double eDlo = eps - 0.5 * wD, cNhi = cosa + 0.5 * wN;
-            ok = cosa - 0.5 * wN > 0.0;   // a zero normal (a disabled point) must fail the angle test surely
-            const double iN = 1.0 / wN, iD = 1.0 / wD;
-            const float s0 = (float)iD, s1 = (float)(-eDlo * iD), s2 = (float)(-sgn * iN), s3f = (float)(cNhi * iN);
-            if (dbg4 != nullptr) { dbg4[0] = cNhi; dbg4[1] = wN; dbg4[2] = eDlo; dbg4[3] = wD; }
-            if (sph) { o.f[4] = s0; o.f[5] = s1; o.f[6] = s2; o.f[7] = s3f; }
-            else { o.f[7] = s0; o.f[8] = s1; o.f[9] = s2; o.f[10] = s3f; }
-            ok = ok && fabs((double)s0) < 1e30 && fabs((double)s1) < 1e30 && fabs((double)s2) < 1e30 && fabs((double)s3f) < 1e30;
+            const double W2 = 2.0 * m2, Wv = 2.0 * mv;
+            const double i2 = 1.0 / W2, iv = 1.0 / Wv;
+            const float s0 = (float)K, s1 = (float)i2, s2 = (float)(-(H - m2) * i2), s3f = (float)(-sgn * iv), s4 = (float)(ca2 * iv);
+            if (dbg4 != nullptr) { dbg4[0] = m2; dbg4[1] = W2; dbg4[2] = mv; dbg4[3] = Wv; }
+            if (sph) { o.f[3] = s0; o.f[4] = s1; o.f[5] = s2; o.f[6] = s3f; o.f[7] = s4; }
+            else { o.f[6] = s0; o.f[7] = s1; o.f[8] = s2; o.f[9] = s3f; o.f[10] = s4; }
+            // no product of the chain may overflow (inf - inf = NaN, and the books read the sign bit of u): every scaled constant x
+            // the largest value its operand takes on this point set stays below 2^120
+            const double big = 1.329227995784916e36;
+            const double n2max = 3.1 * T * T * ((1.0 + ai * a1) * (1.0 + ai * a1)), qn2max = 3.0 * Nm * Nm * n2max;
+            ok = ok && fabs((double)s0) < 1e30 && fabs((double)s1) < 1e30 && fabs((double)s2) < 1e30 && fabs((double)s3f) < 1e30 && fabs((double)s4) < 1e30;
+            ok = ok && (n2max + K) * i2 < big && qn2max * iv < big && n2max * ca2 * iv < big;
         }
         if (fin && axis_ok && (sph || a1 > 0.0) && cls_fin(eps) && cls_fin(M)) {
             // box: |p - o| (sphere) or the distance from the axis (cylinder, at the centre of the box +- Lipschitz) against
@@ -543,9 +587,11 @@ static __device__ __forceinline__ float cls_plane_u(const rh_cls &C, float x, fl
     return fmaxf(a, b);
 }
 
-// ---- sphere / cylinder: the same u = max(ua, ub) from the scaled record
+// ---- sphere / cylinder: the same u = max(ua, ub) from the scaled record, in the squared quantities n2 = |q|^2 and qn |qn|
+// ("Round kinds without a square root" above).  Host and device: the kernel's point loops, its second pass, the audits and
+// rh_dbg_cls_round run this one statement.
 template <int KIND>
-static __device__ __forceinline__ void cls_round_ab(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz, float &ua, float &ub)
+static __host__ __device__ __forceinline__ void cls_round_ab(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz, float &ua, float &ub)
 {
     float qx, qy, qz;
     constexpr int b = KIND == RH_SPHERE ? 3 : 6;
@@ -556,14 +602,11 @@ static __device__ __forceinline__ void cls_round_ab(const rh_cls &C, float x, fl
         const float sd = __builtin_fmaf(C.f[2], tz, __builtin_fmaf(C.f[1], ty, C.f[0] * tx));
         qx = __builtin_fmaf(-C.f[0], sd, tx); qy = __builtin_fmaf(-C.f[1], sd, ty); qz = __builtin_fmaf(-C.f[2], sd, tz);
     }
-    // (+ 1e-37: a point ON the centre / axis gives nr = 0 and a zero cosine -- surely out, as the exact test's NaN says --
-    // instead of 0 x inf = NaN, whose sign bit the books below would read; any other n2 absorbs it unchanged)
-    const float n2 = __builtin_fmaf(qz, qz, __builtin_fmaf(qy, qy, __builtin_fmaf(qx, qx, 1e-37f)));
-    const float inr = __builtin_amdgcn_rsqf(n2);
-    const float nr = n2 * inr;
-    const float dt = __builtin_fmaf(qz, nz, __builtin_fmaf(qy, ny, qx * nx)) * inr;
-    ua = __builtin_fmaf(__builtin_fabsf(nr - C.f[b]), C.f[b + 1], C.f[b + 2]);
-    ub = __builtin_fmaf(dt, C.f[b + 3], C.f[b + 4]);
+    // (nothing is divided: a point ON the centre / axis has n2 = 0, and ua > 1 says surely out as the exact test's NaN does)
+    const float n2 = __builtin_fmaf(qz, qz, __builtin_fmaf(qy, qy, qx * qx));
+    const float qn = __builtin_fmaf(qz, nz, __builtin_fmaf(qy, ny, qx * nx));
+    ua = __builtin_fmaf(__builtin_fabsf(n2 - C.f[b]), C.f[b + 1], C.f[b + 2]);
+    ub = __builtin_fmaf(qn * __builtin_fabsf(qn), C.f[b + 3], __builtin_fmaf(n2, C.f[b + 4], 0.5f));   // (mv / Wv = 1/2: no field)
 }
 template <int KIND>
 static __device__ __forceinline__ float cls_round_u(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz)
