@@ -3,7 +3,8 @@
 word / tile boundaries, coordinate scales 1 .. 1e4, NaN / inf points, random enabled patterns), thresholds from tiny to
 huge, shapes from jittered ground truth to degenerate -- with the culled scan (korder.hip: Morton order, box tests)
 forced on clouds of every size, or the plain scan, and on Float32 clouds.  Run on a GPU box:
-python tools/fuzz_refit.py [n_cases] [seed]; a fixed-seed slice runs in tests/test_fuzz_gpu.py."""
+python tools/fuzz_refit.py [n_cases] [seed] [shift]; a fixed-seed slice runs in tests/test_fuzz_gpu.py.  shift: clouds moved away
+from the origin (fuzz_score.shift_vector)."""
 import ctypes as C
 import os
 import sys
@@ -15,10 +16,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ransac_jl_amd as R
 from ransac_jl_amd import _lib as L, synth
 from oracle import oracle as orc
-from fuzz_score import KMAP, rand_shape
+from fuzz_score import KMAP, apply_shift, rand_shape, shift_arg, shift_vector
 
 
-def one(case, rng, f32=False):
+def one(case, rng, f32=False, shift=None):
     scale = float(rng.choice([1.0, 100.0, 100.0, 1e4]))
     n = int(rng.choice([1, 63, 64, 65, 700, 4096, 8193, 20_000, 65_536, 150_001]))
     names = list(rng.choice(list(KMAP), size=int(rng.integers(1, 6))))
@@ -28,6 +29,9 @@ def one(case, rng, f32=False):
         for k in ("point", "center", "apex"):
             if k in t: t[k] = np.asarray(t[k]) * (scale / 100.0)
         if "radius" in t: t["radius"] = t["radius"] * (scale / 100.0)
+    vec = shift_vector(case, shift)
+    xyz = apply_shift(xyz, truth, vec)
+    origin = 0.0 if vec is None else vec
     bad_pts = int(rng.choice([0, 0, 1, 5]))
     for _ in range(min(bad_pts, n)):          # points no shape can hold: they must neither match nor hide a group
         xyz[int(rng.integers(0, n)), int(rng.integers(0, 3))] = float(rng.choice([np.nan, np.inf, -np.inf]))
@@ -55,7 +59,7 @@ def one(case, rng, f32=False):
     op = orc.Params.from_buffer_copy(bytes(cp))
     ok, tot = True, 0
     for q in range(6):
-        s = rand_shape(rng, truth, scale)
+        s = rand_shape(rng, truth, scale, origin)
         if f32:
             R.lib().rh_shape_finalize_f32(C.byref(s))
         got = R.refit(s, pc, cp).inpoints
@@ -66,17 +70,18 @@ def one(case, rng, f32=False):
             R.invalidate_indexes(pc, exp)
             oc.invalidate(exp)
     ok = ok and np.array_equal(pc.enabled_chunks(), oc.get_enabled())
-    return ok, "n=%d scale=%g path=%s f32=%d bad=%d p_en=%g inliers=%d" % (n, scale, path, f32, bad_pts, p_en, tot)
+    return ok, "n=%d scale=%g%s path=%s f32=%d bad=%d p_en=%g inliers=%d" % (
+        n, scale, "" if vec is None else " shift=(%g,%g,%g)" % tuple(vec), path, f32, bad_pts, p_en, tot)
 
 
 def main():
     ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     rng = np.random.default_rng(seed)
-    bad = 0
+    bad, shift = 0, shift_arg(sys.argv)
     for case in range(ncases):
         for f32 in (False, True):
-            ok, desc = one(case, rng, f32=f32)
+            ok, desc = one(case, rng, f32=f32, shift=shift)
             if not ok:
                 bad += 1
                 print("MISMATCH", case, desc, flush=True)

@@ -6,7 +6,8 @@ arbitrary / degenerate / far-away-point shapes (tools/fuzz_score.py's generator)
   (ii)  points the binary32 classifier calls surely-in that the exact test rejects,
   (iii) points it calls surely-out that the exact test accepts,
   (iv)  candidates whose classifier would count the all-zero point a disabled point is staged as
-must all be 0.  python tools/fuzz_sound.py [ncases] [seed]   (F32=1: Float32 clouds)"""
+must all be 0.  python tools/fuzz_sound.py [ncases] [seed] [shift]   (F32=1: Float32 clouds; shift: clouds moved away from
+the origin, fuzz_score.shift_vector)"""
 import os, sys, time
 if __name__ == "__main__":
     os.environ.setdefault("RH_LIB_VARIANT", "diag")   # the A/B switches / rh_dbg_* audits live in the diag build (libransac_hip_diag.so)
@@ -24,7 +25,7 @@ FIELDS = ("pairs", "pairs_skipped", "V_skipped_with_inlier", "points", "sure_in"
 VIOL = (2, 6, 7, 9)
 
 
-def one(case, rng, f32=False):
+def one(case, rng, f32=False, shift=None):
     scale = float(rng.choice([1.0, 100.0, 100.0, 1e4, 1e6]))
     r = int(rng.choice([1, 2, 3]))
     n = int(rng.choice([8192, 8193, 20_000, 65_536, 150_001])) * r
@@ -35,6 +36,9 @@ def one(case, rng, f32=False):
         for k in ("point", "center", "apex"):
             if k in t: t[k] = np.asarray(t[k]) * (scale / 100.0)
         if "radius" in t: t["radius"] = t["radius"] * (scale / 100.0)
+    vec = fuzz_score.shift_vector(case, shift)
+    xyz = fuzz_score.apply_shift(xyz, truth, vec)
+    origin = 0.0 if vec is None else vec
     subs = synth.make_subsets(n, r, seed=case)
     if f32:
         xyz, nrm = xyz.astype(np.float32), nrm.astype(np.float32)
@@ -47,7 +51,7 @@ def one(case, rng, f32=False):
         params[k]["α"] = float(np.radians(rng.choice([0.5, 5.0, 30.0, 89.0, 120.0])))
     cp = R.params_to_c(params, score_mode=L.SCORE_F64)
     b = int(rng.choice([64, 128, 300]))
-    arr = (L.Shape * b)(*[fuzz_score.rand_shape(rng, truth, scale) for _ in range(b)])
+    arr = (L.Shape * b)(*[fuzz_score.rand_shape(rng, truth, scale, origin) for _ in range(b)])
     if f32:
         for i in range(b):
             R.lib().rh_shape_finalize_f32(C.byref(arr[i]))
@@ -57,7 +61,8 @@ def one(case, rng, f32=False):
     out = out[:40].reshape(4, 10).astype(np.int64)
     ok = int(out[:, VIOL].sum()) == 0 and int(st_viol.sum()) == 0
     ST_TOT[0] += st_skipped; ST_TOT[1] += st_viol
-    return ok, "n=%d r=%d scale=%g b=%d f32=%d viol=%s st_viol=%s" % (n, r, scale, b, f32, out[:, VIOL].tolist(), st_viol.tolist()), out
+    return ok, "n=%d r=%d scale=%g%s b=%d f32=%d viol=%s st_viol=%s" % (
+        n, r, scale, "" if vec is None else " shift=(%g,%g,%g)" % tuple(vec), b, f32, out[:, VIOL].tolist(), st_viol.tolist()), out
 
 
 ST_TOT = [np.zeros(4, dtype=np.int64), np.zeros(4, dtype=np.int64)]
@@ -66,11 +71,11 @@ ST_TOT = [np.zeros(4, dtype=np.int64), np.zeros(4, dtype=np.int64)]
 def main():
     ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 17)
-    f32 = bool(os.environ.get("F32"))
+    f32, shift = bool(os.environ.get("F32")), fuzz_score.shift_arg(sys.argv)
     tot = np.zeros((4, 10), dtype=np.int64)
     bad, t0 = 0, time.time()
     for case in range(ncases):
-        ok, desc, out = one(case, rng, f32=f32)
+        ok, desc, out = one(case, rng, f32=f32, shift=shift)
         tot += out
         print("%s case %3d  %s" % ("ok  " if ok else "FAIL", case, desc), flush=True)
         bad += not ok
