@@ -73,6 +73,15 @@ int rh_dbg_cls_round(const rh_shape *shape, const rh_params *p, double M, double
  * disagreements over `queries` random queries.  Needs no GPU. */
 int rh_dbg_oct_search_selftest(int64_t n, uint64_t seed, int64_t queries, int64_t *mismatches);
 
+/* The protocol of the enabled bits (csrc/enabled_state.h) on its own, host code only: nseq sequences of len events each,
+ * every sequence on a fresh state; answers[q * len + t] = what the state's queries say after event t of sequence q.
+ * Events: 0 / 1 bits_replaced(mirror copied: no / yes), 2 / 3 bits_cleared_by_list(mirror updated: no / yes), 4 .. 7
+ * scan_started(culled = bit 1, apply = bit 0 of event - 4), 8 / 9 scan_folded(has blocks: yes / no), 10 scratch_taken,
+ * 11 directory_built, 12 list_built, 13 records_built, 14 mirror_built, 15 / 16 long_window(very long: no / yes), 17 nothing
+ * (scoring, reads).  Answer bits: 1 has_directory, 2 has_list, 4 has_records, 8 has_mirror, 16 has_block_sums,
+ * 32 scan_left_sums, 64 what long_window returned (events 15 / 16), bits 8 and up long_windows().  Needs no GPU. */
+int rh_dbg_enabled_events(const uint8_t *events, int64_t nseq, int32_t len, uint16_t *answers);
+
 /* Event counters of the culled score kernel's launches on cloud c (csrc/score4.hip, S4_STAT: chunk visits, box-tested
  * candidates, surviving pairs, batches, pairs of the second pass, undecided points, ring drains, ... per kind; blocks and
  * stagings): what tools/isa_account.py multiplies with the static instruction histogram of the kernel's regions.

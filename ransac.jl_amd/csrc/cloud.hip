@@ -154,27 +154,6 @@ static void cloud_free(rh_cloud *c)
     delete c;   // (the buffers go with it: every stream that used them has been waited for above)
 }
 
-static int set_all_enabled(rh_cloud *c)
-{
-    if (c->nwords > 0) {
-        RH_HIP(hipMemsetAsync(c->enabled, 0xFF, sizeof(uint64_t) * (size_t)c->nwords, c->stream));
-        if (c->n % 64) {
-            const uint64_t last = (~0ULL) >> (64 - c->n % 64);
-            RH_HIP(hipMemcpyAsync(c->enabled + (c->nwords - 1), &last, sizeof last, hipMemcpyHostToDevice, c->stream));
-            RH_HIP(hipStreamSynchronize(c->stream));
-        }
-        if (c->k_built) {   // the same n bits in Morton order
-            RH_HIP(hipMemcpyAsync(c->oct_men, c->enabled, sizeof(uint64_t) * (size_t)c->nwords, hipMemcpyDeviceToDevice, c->stream));
-            c->k_men_valid = true;
-        }
-    }
-    RH_TRY(rhk_rebuild_sub_enabled(c, true));
-    c->select_valid = false;
-    c->en_sums_valid = false;
-    c->n_dis = 0;
-    return RH_OK;
-}
-
 // bounding cube of the cloud like the reference's octree (findAABB: src/utilities.jl:125-136; the cube's edge is the
 // largest extent) and the largest finite |coordinate|
 static void cloud_aabb(const double *xyz, int64_t n, double lo[3], double *size_out, double *mag_out)
@@ -361,21 +340,14 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
         if (e == RH_SCORE_PATH_BRUTE) c->use_groups = false;
         if (e == RH_SCORE_PATH_GROUPS) c->use_groups = s > 0;
     }
-    CK(c->enabled.alloc(c->nwords));
-    CK(c->sub_enabled.alloc(c->swords));
-    CK(c->d_ndis.alloc(1));
+    CK(rhk_enabled_alloc(c));
     CK(c->refit_mask.alloc(c->nwords));
-    CK(c->block_sums.alloc(std::max<int64_t>(c->nblocks, (c->swords + RH_WORDS_PER_BLOCK - 1) / RH_WORDS_PER_BLOCK) + 2));
-    CK(c->en_block_sums.alloc(c->nblocks + 2));
-    CK(c->word_prefix.alloc(c->nwords + 1));
     CK(c->idx_out.alloc(n));
-    CK(c->d_total.alloc(1));
     CK(c->d_nk.alloc(4));
     CK(c->ws[0].d_nk2.alloc(8));
     CKH(hipMemsetAsync(c->full, 0, sizeof(double) * 6 * (size_t)c->n_pad, c->stream));
     CKH(hipMemsetAsync(c->sub, 0, sizeof(double) * 6 * (size_t)c->s_pad, c->stream));
     CKH(hipMemsetAsync(c->dis, 0, sizeof(double) * 6 * (size_t)c->dis_stride, c->stream));
-    CKH(hipMemsetAsync(c->d_total, 0, sizeof(int32_t), c->stream));
     stamp("streams, allocations, memsets");
 
     if (n > 0) {
@@ -544,7 +516,7 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
         }
     }
     stamp("subset order, gather, boxes");
-    CK(set_all_enabled(c));
+    CK(rhk_enabled_replace(c, nullptr));
     CKH(hipStreamSynchronize(c->stream));
     stamp("enabled bits");
 #undef CK
@@ -654,20 +626,7 @@ extern "C" int rh_cloud_set_enabled(rh_cloud *c, const uint64_t *chunks, int64_t
         rh_set_error("rh_cloud_set_enabled: nchunks=%lld, expected %lld", (long long)nchunks, (long long)c->nwords);
         return RH_E_INVALID;
     }
-    if (c->nwords > 0) {
-        c->k_men_valid = false;
-        RH_HIP(hipMemcpyAsync(c->enabled, chunks, sizeof(uint64_t) * (size_t)nchunks, hipMemcpyHostToDevice, c->stream));
-        if (c->n % 64) {   // BitVector keeps the unused tail bits zero; enforce it
-            const uint64_t last = chunks[nchunks - 1] & ((~0ULL) >> (64 - c->n % 64));
-            RH_HIP(hipMemcpyAsync(c->enabled + (nchunks - 1), &last, sizeof last, hipMemcpyHostToDevice, c->stream));
-        }
-        RH_HIP(hipStreamSynchronize(c->stream));
-    }
-    RH_TRY(rhk_rebuild_sub_enabled(c, true));
-    RH_HIP(hipStreamSynchronize(c->stream));
-    c->select_valid = false;
-    c->en_sums_valid = false;
-    return RH_OK;
+    return rhk_enabled_replace(c, chunks);   // (null only with an empty cloud, where "all ones" is the same nothing)
 }
 
 extern "C" int rh_cloud_get_enabled(rh_cloud *c, uint64_t *chunks, int64_t nchunks)
@@ -687,7 +646,7 @@ extern "C" int rh_cloud_get_enabled(rh_cloud *c, uint64_t *chunks, int64_t nchun
 extern "C" int rh_cloud_enable_all(rh_cloud *c)
 {
     RH_TRY(enter(c));
-    RH_TRY(set_all_enabled(c));
+    RH_TRY(rhk_enabled_replace(c, nullptr));
     RH_HIP(hipStreamSynchronize(c->stream));
     return RH_OK;
 }
@@ -1057,25 +1016,10 @@ extern "C" int rh_refit(rh_cloud *c, const rh_shape *shape, const rh_params *p, 
     *n_out = 0;
     rh_prep P;
     rh_prep_host(*shape, &P);
-    c->select_valid = false;   // block_sums / d_total are shared with the select directory
     RH_HIP(hipEventRecord(c->evk[0], c->stream));
     RH_TRY(rhk_refit_mask(c, P, shape->kind, p->eps[shape->kind], p->cos_alpha[shape->kind]));
     RH_HIP(hipEventRecord(c->evk[1], c->stream));
-    RH_TRY(rhk_compact_mask(c, c->refit_mask, c->nwords, c->idx_out, c->n, c->d_total));
-    RH_HIP(hipEventRecord(c->evk[2], c->stream));
-    int32_t total = 0;
-    RH_HIP(hipMemcpyAsync(&total, c->d_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
-    RH_HIP(hipStreamSynchronize(c->stream));
-    *n_out = total;
-    if (total > cap) {
-        rh_set_error("rh_refit: %d inliers, capacity %lld", total, (long long)cap);
-        return RH_E_CAPACITY;
-    }
-    if (total > 0) {
-        RH_HIP(hipMemcpyAsync(idx_out, c->idx_out, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-        RH_HIP(hipStreamSynchronize(c->stream));
-    }
-    return RH_OK;
+    return rhk_refit_total(c, "rh_refit", idx_out, cap, n_out, c->evk[2]);
 }
 
 extern "C" int rh_last_refit_ms(rh_cloud *c, float *ms_scan, float *ms_compact)
@@ -1102,11 +1046,7 @@ extern "C" int rh_invalidate(rh_cloud *c, const int64_t *idx, int64_t n)
         return RH_OK;
     }
     RH_HIP(hipMemcpyAsync(c->idx_out, idx, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    RH_TRY(rhk_invalidate_idx(c, c->idx_out, n));
-    RH_TRY(rhk_rebuild_sub_enabled(c, false));
-    RH_HIP(hipStreamSynchronize(c->stream));
-    c->select_valid = false;
-    return RH_OK;
+    return rhk_enabled_clear_list(c, c->idx_out, n);
 }
 
 extern "C" int rh_select_enabled(rh_cloud *c, const int64_t *ranks, int32_t k, int64_t *idx_out)
@@ -1117,7 +1057,7 @@ extern "C" int rh_select_enabled(rh_cloud *c, const int64_t *ranks, int32_t k, i
     if (c->nwords == 0) { for (int i = 0; i < k; i++) idx_out[i] = 0; return RH_OK; }
     if (2 * (int64_t)k > c->d_ranks.count()) RH_TRY(c->d_ranks.grow(c->stream, 2 * (int64_t)k));   // ranks in the first half, indices in the second
     const int64_t ranks_cap = c->d_ranks.count() / 2;
-    if (!c->select_valid) RH_TRY(rhk_build_select(c));
+    RH_TRY(rhk_ensure_select(c));
     if (k <= 1024) {
         // the per-sample call of the reference's loop (a couple of ranks): the kernel reads the ranks from the pinned
         // block and writes the indices back into it -- one launch and one wait, no transfer operation
@@ -1143,10 +1083,8 @@ extern "C" int rh_sample_sets(rh_cloud *c, int32_t drawN, rh_rng *rng, int32_t k
     if (!rng || k < 0 || drawN < 2 || drawN > 16 || (k > 0 && (!idx_out || !ok_out))) { rh_set_error("rh_sample_sets: bad arguments (drawN 2..16)"); return RH_E_INVALID; }
     if (k == 0) return RH_OK;
     if (c->n == 0) { rh_set_error("rh_sample_sets: the cloud is empty"); return RH_E_INVALID; }
-    if (!c->select_valid) RH_TRY(rhk_build_select(c));
     int32_t count = 0;
-    RH_HIP(hipMemcpyAsync(&count, c->d_total, sizeof count, hipMemcpyDeviceToHost, c->stream));
-    RH_HIP(hipStreamSynchronize(c->stream));
+    RH_TRY(rhk_enabled_total(c, &count));
     if (count <= 0) { rh_set_error("rh_sample_sets: no enabled point (the reference would draw for ever, fitting.jl:393)"); return RH_E_INVALID; }
     const int W = drawN + 2;
     constexpr int64_t L_MAX = 1 << 20;

@@ -265,28 +265,15 @@ extern "C" int rh_refit_component(rh_cloud *c, const rh_shape *shape, const rh_p
     RH_TRY(rh_component_check_beta("rh_refit_component", beta));
     rh_prep P;
     rh_prep_host(*shape, &P);
-    c->select_valid = false;   // block_sums / d_total are shared with the select directory
     RH_TRY(rhk_refit_mask(c, P, shape->kind, p->eps[shape->kind], p->cos_alpha[shape->kind]));
     int64_t n_refit = 0, ncomp = 0;
     RH_TRY(rhk_component_filter(c, beta, conn26, &n_refit));
     if (n_refit_out) *n_refit_out = n_refit;
     if (n_refit == 0) return RH_OK;
-    RH_TRY(rhk_compact_mask(c, c->refit_mask, c->nwords, c->idx_out, c->n, c->d_total));
-    int32_t total = 0;
-    RH_HIP(hipMemcpyAsync(&total, c->d_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
-    RH_TRY(rhk_component_stats(c, &ncomp));
-    RH_HIP(hipStreamSynchronize(c->stream));
-    *n_out = total;
+    RH_TRY(rhk_component_stats(c, &ncomp));   // (queued in front of the compaction, read behind its wait)
+    const int rc = rhk_refit_total(c, "rh_refit_component", idx_out, cap, n_out);
     if (n_components_out) *n_components_out = (int32_t)ncomp;
-    if (total > cap) {
-        rh_set_error("rh_refit_component: %d points in the largest component, capacity %lld", total, (long long)cap);
-        return RH_E_CAPACITY;
-    }
-    if (total > 0) {
-        RH_HIP(hipMemcpyAsync(idx_out, c->idx_out, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-        RH_HIP(hipStreamSynchronize(c->stream));
-    }
-    return RH_OK;
+    return rc;
 }
 
 extern "C" int rh_cloud_set_component_filter(rh_cloud *c, double beta, int32_t conn26)

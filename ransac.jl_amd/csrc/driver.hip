@@ -93,12 +93,7 @@ int Driver::init()
     if (!arena) { rh_set_error("rh_ransac: cannot pin %lld bytes for the index lists", (long long)(8 * arena_cap)); return RH_E_NOMEM; }
     arena_used = 0;
     // the disabled list must describe the cloud as it is now (points disabled before the call)
-    RUN(rhk_rebuild_sub_enabled(c, true));
-    int32_t ndis = 0;
-    RUNH(hipMemcpyAsync(&ndis, c->d_ndis, sizeof ndis, hipMemcpyDeviceToHost, c->stream));
-    RUNH(hipStreamSynchronize(c->stream));
-    c->n_dis = ndis;
-    c->select_valid = false;
+    RUN(rhk_enabled_resync(c));
     if (!st.d_nk) RUN(st.d_nk.alloc(8));
     if (!st.live) {
         RUN(st.live.alloc(LIVE_MAX));
@@ -448,7 +443,7 @@ static int ransac_impl(rh_cloud *c, const double *xyz, const double *nrm, const 
     out->arena = d.arena;   // ownership of the index lists moved to the result
     d.arena = nullptr;
     d.clean = true;
-    c->select_valid = false;
+    rhk_enabled_run_ended(c);
     out->seconds = now_s() - t_start;
     out->seconds_to_last_extraction = d.t_last_extraction > 0 ? d.t_last_extraction - t_start : 0.0;
     out->seconds_score = d.t_score;

@@ -182,7 +182,7 @@ int Driver::maybe_extract(int64_t k, bool *did)
     int32_t *h_nk = h_scr + 16, *h_counts = h_scr + 32, *h_lists = h_scr + 32 + sum_n;
     const int64_t ndis_old = c->n_dis;
     // component filter set (rh_cloud_set_component_filter): the scan leaves the bits alone (apply = false: no Morton-order
-    // bits cleared on the way, no block sums left behind -- rhk_compact_refit_apply then regathers / recounts as after a plain
+    // bits cleared on the way, no block sums left behind -- rhk_enabled_apply_refit then regathers / recounts as after a plain
     // scan), the mask shrinks to its largest connected component, and everything below extracts just that
     const bool filtered = c->comp_beta > 0;
     RUN(rhk_refit_mask(c, P, bestshape.kind, p->eps[bestshape.kind], p->cos_alpha[bestshape.kind], !filtered));
@@ -193,8 +193,7 @@ int Driver::maybe_extract(int64_t k, bool *did)
     }
     // ... with invalidate_indexes! (fitting.jl:197-202) folded into the compaction as enabled &= ~mask;
     // then subset bits + disabled list
-    RUN(rhk_compact_refit_apply(c));
-    RUN(rhk_rebuild_sub_enabled(c, false));
+    RUN(rhk_enabled_apply_refit(c));
     if (fast) {
         rh_live_args A;
         A.f32 = c->f32 ? 1 : 0;
@@ -215,12 +214,12 @@ int Driver::maybe_extract(int64_t k, bool *did)
         if (sum_n > 0) RUN(rhk_liveness_small(c, lo, std::min<int64_t>(c->s - lo, span), A, st.live));
         RUN(rhk_pack_live(c, st.live, (int32_t)sum_n, h_counts, h_scr));
     } else {
-        RUN(rhk_fetch2_i32(c, c->d_total, c->d_ndis, h_scr));
+        RUN(rhk_fetch2_i32(c, rhk_fold_total(c), c->d_ndis, h_scr));
     }
     RUNH(hipEventRecord(c->ev_sync, c->stream));
     // the next window needs the select directory of the new bits: its two launches run while the host wakes up
-    if (!host_sampling && !octree) RUN(rhk_build_select(c));
-    if (octree) RUN(rhk_oct_clear_mask(c, c->refit_mask));   // (its prefix pass reuses d_total: after the read-back)
+    if (!host_sampling && !octree) RUN(rhk_ensure_select(c));
+    if (octree) RUN(rhk_oct_sync_enabled(c));   // (its prefix pass takes the scratch total: after the read-back)
     RUNH(hipEventSynchronize(c->ev_sync));
     const int32_t total = h_scr[0], ndis_new = h_scr[1];
     rh_extracted ex;

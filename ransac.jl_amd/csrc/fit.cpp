@@ -339,4 +339,35 @@ extern "C" int rh_dbg_oct_search_selftest(int64_t n, uint64_t seed, int64_t quer
     *mismatches = bad;
     return RH_OK;
 }
+
+// ---- the protocol of the enabled bits (enabled_state.h) on its own: ransac_hip_diag.h ------------------------------------
+extern "C" int rh_dbg_enabled_events(const uint8_t *events, int64_t nseq, int32_t len, uint16_t *answers)
+{
+    if (nseq < 0 || len < 0 || (nseq * len > 0 && (!events || !answers))) { rh_set_error("rh_dbg_enabled_events: bad arguments"); return RH_E_INVALID; }
+    for (int64_t q = 0; q < nseq; q++) {
+        rh_enabled_state st;
+        for (int32_t t = 0; t < len; t++) {
+            const int64_t at = q * len + t;
+            const int e = events[at];
+            bool want = false;
+            switch (e) {
+            case 0: case 1: st.bits_replaced(e == 1); break;
+            case 2: case 3: st.bits_cleared_by_list(e == 3); break;
+            case 4: case 5: case 6: case 7: st.scan_started((e - 4) >> 1, (e - 4) & 1); break;
+            case 8: case 9: st.scan_folded(e == 8); break;
+            case 10: st.scratch_taken(); break;
+            case 11: st.directory_built(); break;
+            case 12: st.list_built(); break;
+            case 13: st.records_built(); break;
+            case 14: st.mirror_built(); break;
+            case 15: case 16: want = st.long_window(e == 16); break;
+            case 17: break;   // scoring, reads: nothing to report
+            default: rh_set_error("rh_dbg_enabled_events: unknown event %d", e); return RH_E_INVALID;
+            }
+            answers[at] = (uint16_t)((st.has_directory() ? 1 : 0) | (st.has_list() ? 2 : 0) | (st.has_records() ? 4 : 0) | (st.has_mirror() ? 8 : 0) |
+                                     (st.has_block_sums() ? 16 : 0) | (st.scan_left_sums() ? 32 : 0) | (want ? 64 : 0) | (st.long_windows() << 8));
+        }
+    }
+    return RH_OK;
+}
 #endif   // RH_DIAG

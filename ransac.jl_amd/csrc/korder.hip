@@ -241,15 +241,6 @@ int rhk_f32_build(rh_cloud *c)
     return RH_OK;
 }
 
-// the Morton-order enabled bits follow `enabled` lazily: whoever rewrites `enabled` wholesale clears k_men_valid
-int rhk_korder_sync_enabled(rh_cloud *c)
-{
-    if (!c->k_built || c->k_men_valid) return RH_OK;
-    RH_TRY(rhk_oct_gather_enabled(c));
-    c->k_men_valid = true;
-    return RH_OK;
-}
-
 // which scan a refit takes: the culled one from RH_KREFIT_MIN points on (below it the whole cloud is a few
 // microseconds of streaming and two launches cost more); RH_REFIT_PATH=scan|culled forces one (tests, A/B)
 bool rhk_refit_is_culled(const rh_cloud *c)
@@ -287,7 +278,7 @@ static int launch_refitk(rh_cloud *c, const T *pts, const PREP &PX, const rh_pre
         hipLaunchKernelGGL((refitk_groups_kernel<K, T, PREP>), g2, blk, 0, c->stream, pts, c->n_pad, c->n, c->oct_perm,  \
                            c->oct_men, ap, PX, eps, cosa, c->klist, c->kctr, c->kflag);                                      \
         hipLaunchKernelGGL(refitk_flags_kernel, dim3((unsigned)c->nblocks), blk, 0, c->stream, c->kflag, ng, c->refit_mask,  \
-                           c->kctr, c->block_sums);                                                                          \
+                           c->kctr, rhk_take_scan_scratch(c).sums);                                                          \
     } while (0)
     switch (kind) {
     case RH_PLANE: RH_K(RH_PLANE); break;

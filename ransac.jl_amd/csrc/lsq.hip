@@ -211,20 +211,12 @@ extern "C" int rh_refit_lsq(rh_cloud *c, const rh_shape *shape, const rh_params 
     // selection: compatible points within 3 eps (Schnabel et al. 2007, sec. 4.4)
     rh_prep P0;
     rh_prep_host(*shape, &P0);
-    c->select_valid = false;
     RH_TRY(rhk_refit_mask(c, P0, kind, 3.0 * p->eps[kind], p->cos_alpha[kind]));
-
     int64_t cnt = 0;
-    {
-        RH_TRY(rhk_compact_mask(c, c->refit_mask, c->nwords, nullptr, 0, c->d_total));
-        int32_t total = 0;
-        RH_HIP(hipMemcpyAsync(&total, c->d_total, sizeof total, hipMemcpyDeviceToHost, c->stream));
-        RH_HIP(hipStreamSynchronize(c->stream));
-        cnt = total;
-        if (cnt < 8) {
-            rh_set_error("rh_refit_lsq: only %lld compatible points within 3 eps of the shape", (long long)cnt);
-            return RH_E_INVALID;
-        }
+    RH_TRY(rhk_refit_total(c, nullptr, nullptr, 0, &cnt));
+    if (cnt < 8) {
+        rh_set_error("rh_refit_lsq: only %lld compatible points within 3 eps of the shape", (long long)cnt);
+        return RH_E_INVALID;
     }
     const int nblocks = 512;
     rh_dev<double> d_part, d_out;

@@ -8,6 +8,7 @@
 
 #include "ransac_hip.h"
 #include "dev_buf.h"
+#include "enabled_state.h"
 
 // ---- error plumbing -------------------------------------------------------
 void rh_set_error(const char *fmt, ...);
@@ -276,18 +277,9 @@ struct rh_cloud {
     rh_dev<double> set_ws;             // sampler -> fitter hand-over: gathered minimal sets, [drawN * 6][sets]
     rh_dev<int32_t> set_level;         // per set: octree level it was drawn from, 0 = no set
     int64_t set_ws_sets = 0;
-    rh_dev<double> crec;               // 64-byte records (8 doubles each) of the ENABLED points in rank order (long sampling windows)
-    bool crec_valid = false;           // cleared whenever the select list is rebuilt
-    int very_long_windows = 0;         // windows of >= 2^19 sets sampled since the select directory was last built
-    rh_dev<int32_t> sel_list;          // sel_list[r] = 0-based index of the (r+1)-th enabled point (valid with sel_valid)
-    bool sel_valid = false;            // built on demand by rhk_build_sel_list, dropped with the select directory
     rh_dev<double> rec;                // the same points as 64-byte records (x y z nx ny nz 0 0): one line per random gather
     rh_dev<double> sub;                // subset 1, subset order
-    rh_dev<double> dis;                // disabled subset-1 points (append-only), capacity s_pad + tile
-    int64_t dis_stride = 0;
     rh_dev<int32_t> sub_idx0;          // [s] 0-based original index of subset position j
-    rh_dev<uint64_t> enabled;          // [nwords]  pc.isenabled chunks
-    rh_dev<uint64_t> sub_enabled;      // [swords]  enabled bits gathered into subset order
     rh_dev<int32_t> sub_perm;          // [s] internal (k-d leaf order) position -> subset position j
     rh_dev<double> gb;                 // 7 planes x ng_pad: box centre cx cy cz, half extents hx hy hz, radius hr
     int64_t ngroups = 0, ng_pad = 0;   // 64-point groups of the subset (internal order)
@@ -304,15 +296,28 @@ struct rh_cloud {
     rh_dev<uint32_t> stm32;            // ... of the super-tiles: the OR of their 16 groups' masks, 4 words each
     double nrm_len = 0;                // largest finite normal length over the subset (0: not known), made with the masks
     rh_dev<double> dis_gb;             // boxes of the dis segment in use (7 x ng_pad)
+
+    // The enabled bits and what follows them: `en` says which derived structure matches the bits (enabled_state.h, DESIGN.md
+    // section 3).  Only enabled.hip writes `enabled` and names block_sums / d_total.
+    rh_enabled_state en;
+    rh_dev<uint64_t> enabled;          // [nwords]  pc.isenabled chunks
+    rh_dev<uint64_t> sub_enabled;      // [swords]  enabled bits gathered into subset order
+    rh_dev<double> dis;                // disabled subset-1 points (append-only), capacity s_pad + tile
+    int64_t dis_stride = 0;
     rh_dev<int32_t> d_ndis;            // device counter: entries in dis
-    int64_t n_dis = 0;                 // host mirror
+    int64_t n_dis = 0;                 // host mirror: exact outside a run; inside rh_ransac as of the last extraction's read-back
+    rh_dev<uint64_t> oct_men;          // [nwords] the Morton-order mirror of the bits (en.has_mirror; else regathered on its next use)
+    rh_dev<int32_t> oct_prefix;        // [nwords + 1] its popcount prefix (rhk_oct_sync_enabled)
+    rh_dev<int32_t> en_block_sums;     // [nblocks + 1] popcounts of the enabled words per block (en.has_block_sums), scanned in place by the directory
+    rh_dev<int32_t> word_prefix;       // [nwords + 1] the select directory: exclusive prefix of popcount(enabled); its total is d_total (en.has_directory)
+    rh_dev<int32_t> sel_list;          // sel_list[r] = 0-based index of the (r+1)-th enabled point (en.has_list; built on demand)
+    rh_dev<double> crec;               // 64-byte records (8 doubles each) of the ENABLED points in rank order (en.has_records; long sampling windows)
+    rh_dev<int32_t> block_sums;        // [nblocks + 1] the scan scratch, lent out by rhk_take_scan_scratch ...
+    rh_dev<int32_t> d_total;           // ... and its scalar: the directory's total until somebody else takes it
 
     // The cloud in Morton order (korder.hip), built on the device with the cloud: the order of the linear octree of
     // octree_sampling = 1 and of the culled refit scan.
     bool k_built = false;
-    bool k_men_valid = false;          // oct_men mirrors `enabled` (else it is regathered on the next use)
-    bool k_applied = false;            // the refit scan in flight has already cleared its inliers in oct_men
-    bool k_sums_ready = false;         // ... and left the per-block popcounts of refit_mask in block_sums
     double k_lo[3] = { 0, 0, 0 }, k_size = 1;   // bounding cube of the cloud (findAABB, utilities.jl:125-136)
     double k_mag = 0;                  // max |coordinate| over the cloud (rounding slack of the box tests)
     rh_dev<double> fullk;              // 6 planes x n_pad, Morton order
@@ -327,8 +332,6 @@ struct rh_cloud {
     rh_dev<uint64_t> oct_code;         // [n] sorted Morton codes (device)
     rh_dev<int32_t> oct_perm;          // [n] Morton position -> original index0
     rh_dev<int32_t> oct_pos;           // [n] original index0 -> Morton position
-    rh_dev<uint64_t> oct_men;          // [nwords] enabled bits in Morton order
-    rh_dev<int32_t> oct_prefix;        // [nwords + 1]
     rh_dev<rh_oct_state> oct_state;    // chained octree windows: the window's state,
     rh_dev<float> dis_gb32;            // binary32 twins of dis_gb
     rh_dev<unsigned long long> s4_stats;   // diag build: event counters of the score launches (rh_dbg_s4_stats), 128 x u64 on the device
@@ -343,15 +346,9 @@ struct rh_cloud {
     std::vector<uint64_t> h_oct_code;  // host twins (host-side sampling, enabled mirror)
     std::vector<int32_t> h_oct_perm, h_oct_pos;
 
-    // refit / select workspaces
+    // refit workspaces
     rh_dev<uint64_t> refit_mask;       // [nwords]
-    rh_dev<int32_t> block_sums;        // [nblocks + 1]
-    rh_dev<int32_t> en_block_sums;     // [nblocks + 1] popcounts of the enabled words per block (select directory)
-    bool en_sums_valid = false;        // left behind by rhk_compact_refit_apply for the next rhk_build_select
-    rh_dev<int32_t> word_prefix;       // [nwords + 1] exclusive prefix of popcount(enabled) (select)
-    bool select_valid = false;
     rh_dev<int64_t> idx_out;           // [n] compacted indices
-    rh_dev<int32_t> d_total;           // scalar
 
     // largest-connected-component filter of a refit set (component.hip): the setting rh_ransac's extractions read
     // (rh_cloud_set_component_filter; 0: off) and the workspace, grown on demand and kept between calls
@@ -489,34 +486,22 @@ int rhk_score_kind_dis(rh_cloud *c, int kind, int64_t first, int64_t cnt, const 
 int rhk_group_bounds(rh_cloud *c);
 int rhk_unpermute_masks(rh_cloud *c, const uint64_t *d_in, int32_t b, uint64_t *d_out);
 // refit_mask = the shape's inliers among the enabled points (original order), by the cloud's element type; `apply`: the
-// caller follows up with rhk_compact_refit_apply, so a culled scan may clear the Morton-order enabled bits on the way
+// caller follows up with rhk_enabled_apply_refit, so a culled scan may clear the Morton-order enabled bits on the way
 int rhk_refit_mask(rh_cloud *c, const rh_prep &P, int kind, double eps, double cosa, bool apply = false);
 // korder.hip
 int rhk_korder_build(rh_cloud *c, const double *d_xyz, const double *d_nrm, const double lo[3], double size, double mag);
 int rhk_f32_build(rh_cloud *c);   // full32, sub32 (the caller's allocations) and fullk32 of a Float32 cloud
-int rhk_korder_sync_enabled(rh_cloud *c);
 bool rhk_refit_is_culled(const rh_cloud *c);
 int rhk_refitk_mask(rh_cloud *c, const rh_prep &P, int kind, double eps, double cosa, bool apply);
 int rhk_group_bounds_of(rh_cloud *c, const double *pts, int64_t stride, int64_t count, int64_t ngroups, double *gb, int64_t gstride);
 int rhk_oct_build_tab(rh_cloud *c);                                     // the sampler's cell directory (needs oct_depth)
-int rhk_oct_gather_enabled(rh_cloud *c);                                // oct_men = enabled in Morton order
-int rhk_compact_mask(rh_cloud *c, const uint64_t *mask, int64_t nwords, int64_t *idx_out, int64_t cap,
-                     int32_t *d_total);
 // component.hip: refit_mask &= the largest connected component of its points on the voxel grid of size beta (one wait for
 // the stream: |I| sizes the table); the number of components follows in stream order
 int rhk_component_filter(rh_cloud *c, double beta, int conn26, int64_t *n_refit_out);
 int rhk_component_stats(rh_cloud *c, int64_t *h_ncomp);
-int rhk_invalidate_idx(rh_cloud *c, const int64_t *d_idx, int64_t n);
-int rhk_rebuild_sub_enabled(rh_cloud *c, bool reset_list);
-int rhk_compact_refit_apply(rh_cloud *c);
-int rhk_build_sel_list(rh_cloud *c);
 int rhk_liveness_small(rh_cloud *c, int64_t lo, int64_t span, const rh_live_args &A, int32_t *d_flags);   // flags must be zero on entry
 int rhk_pack_live(rh_cloud *c, int32_t *d_flags, int32_t n_flags, int32_t *h_flags, int32_t *h_scalars);
-int rhk_build_select(rh_cloud *c);
-int rhk_select(rh_cloud *c, const int64_t *d_ranks, int32_t k, int64_t *d_out);
-int rhk_count_enabled(rh_cloud *c, int64_t *out);
 uint64_t rh_rng_next_raw(rh_rng *r);   // fit.cpp: the next raw 64-bit draw (an injected stream first)
-int rhk_sample_sets_seq(rh_cloud *c, const uint64_t *d_raw, int32_t L, int32_t drawN, int64_t *d_rec);   // rh_sample_sets
 int rhk_iota(rh_cloud *c, int32_t *d, int32_t n, int32_t base);
 int rhk_gather_prep(rh_cloud *c, const rh_prep *src, const int32_t *d_idx, int32_t n, rh_prep *dst);
 // removeinvalidshapes! (fitting.jl:209-221) on a device-managed store (driver.hip, chained octree windows): the store's
@@ -544,7 +529,27 @@ int rhk_store_compact(rh_cloud *c, const rh_store_plan &P, int32_t *d_work, int3
                       int32_t *d_dead, rh_store_best *d_best);
 
 int rhk_compact_generic(hipStream_t stream, const uint64_t *mask, int64_t nwords, int32_t *ws_block_sums,
-                        int64_t *idx_out, int64_t cap, int32_t *d_total);
+                        int64_t *idx_out, int64_t cap, int32_t *d_total, int32_t *word_prefix_out = nullptr);
+
+// ---- the enabled bits and what follows them (enabled.hip; the protocol: enabled_state.h) -------
+int rhk_enabled_alloc(rh_cloud *c);
+int rhk_enabled_replace(rh_cloud *c, const uint64_t *chunks);           // every word from the host's chunks (null: all ones)
+int rhk_enabled_clear_list(rh_cloud *c, const int64_t *d_idx, int64_t n);   // invalidate_indexes! of a device list; waits
+int rhk_enabled_apply_refit(rh_cloud *c);                               // idx_out = list of refit_mask, enabled &= ~refit_mask
+int rhk_enabled_resync(rh_cloud *c);                                    // start of rh_ransac: the disabled list from scratch
+void rhk_enabled_run_ended(rh_cloud *c);
+const int32_t *rhk_fold_total(const rh_cloud *c);                       // (device) the list length of the last apply_refit
+struct rh_scan_scratch { int32_t *sums, *total; };
+rh_scan_scratch rhk_take_scan_scratch(rh_cloud *c);                     // block_sums / d_total lent to a scan that is not the directory's: reports "scratch taken"
+int rhk_refit_total(rh_cloud *c, const char *who, int64_t *host_out, int64_t cap, int64_t *total_out, hipEvent_t ev = nullptr);
+int rhk_ensure_select(rh_cloud *c);                                     // the select directory, built unless c->en has it
+int rhk_build_sel_list(rh_cloud *c);
+int rhk_enabled_total(rh_cloud *c, int32_t *count);
+int rhk_select(rh_cloud *c, const int64_t *d_ranks, int32_t k, int64_t *d_out);   // (this and the next: the directory must be built)
+int rhk_sample_sets_seq(rh_cloud *c, const uint64_t *d_raw, int32_t L, int32_t drawN, int64_t *d_rec);   // rh_sample_sets
+int rhk_count_enabled(rh_cloud *c, int64_t *out);
+int rhk_korder_sync_enabled(rh_cloud *c);                               // oct_men = enabled in Morton order, unless it is already
+int rhk_oct_sync_enabled(rh_cloud *c);                                  // ... and oct_prefix
 
 // device-side sampling + fitting (sampler.hip)
 struct rh_cand_entry {
@@ -605,9 +610,6 @@ int rhk_oct_advance(rh_cloud *c, const rh_params *prm, rh_oct_state *ost, const 
 int rhk_pack_window(rh_cloud *c, void *d_status, int32_t n_iters, const rh_cand_entry *d_entries, const int32_t *d_counts,
                     int32_t head_cap, void *h_status, void *h_entries, int32_t *h_counts);
 int rh_octree_ensure(rh_cloud *c, const double *xyz, int max_depth);   // cloud.hip
-int rhk_oct_sync_enabled(rh_cloud *c);                                  // men = permuted enabled; prefix
-int rhk_oct_clear_mask(rh_cloud *c, const uint64_t *mask);             // clear the bits of an original-order mask
-int rhk_word_prefix(rh_cloud *c, const uint64_t *words, int64_t nwords, int32_t *prefix_out);
 
 int32_t rh_spread_multiplier(int32_t b);   // t -> (t * m) mod b: a permutation of the batch that separates neighbours
 

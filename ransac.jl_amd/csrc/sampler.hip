@@ -800,7 +800,7 @@ int rhk_sample_fit(rh_cloud *c, const rh_params *prm, uint64_t seed, int64_t k0,
     int32_t *d_count = (int32_t *)d_status, *d_gave_up = d_count + 1;
     unsigned long long *d_draws = (unsigned long long *)((char *)d_status + 8) + it0;
     if (prm->drawN > RH_MAX_DRAWN) { rh_set_error("device sampler supports drawN <= %d", RH_MAX_DRAWN); return RH_E_INVALID; }
-    if (!c->select_valid) RH_TRY(rhk_build_select(c));
+    RH_TRY(rhk_ensure_select(c));
     // (the block is a multiple of 64 bytes: one aligned fill; the driver's windows keep it zero themselves)
     if (!status_is_zero) RH_HIP(hipMemsetAsync(d_status, 0, (size_t)((8 + 8 * (int64_t)n_iters + 63) / 64 * 64), c->stream));
     SetShard sh;
@@ -830,15 +830,14 @@ int rhk_sample_fit(rh_cloud *c, const rh_params *prm, uint64_t seed, int64_t k0,
     if (long_window) {
         RH_TRY(rhk_build_sel_list(c));
         // the compact records cost a gather of the whole enabled cloud (0.12-0.33 ms at 10M points, 0.8 ms at
-        // 50M): only for windows 8 x longer still, and only from the second such window on the same enabled bits
-        // -- one that follows an extraction directly is usually cut short by the next one
-        if (total >= 8 * long_sets) c->very_long_windows++;
-        if (!no_crec && (c->crec_valid || (total >= 8 * long_sets && c->very_long_windows >= 2))) {
-            if (!c->crec_valid) {
+        // 50M): only for windows 8 x longer still, and only when c->en says so (rh_enabled_state::long_window)
+        const bool want_crec = c->en.long_window(total >= 8 * long_sets);
+        if (!no_crec && want_crec) {
+            if (!c->en.has_records()) {
                 if (c->crec.count() < 8 * (int64_t)n_enabled) RH_TRY(c->crec.alloc(8 * (int64_t)n_enabled));
                 hipLaunchKernelGGL(compact_records_kernel, dim3((unsigned)(((int64_t)n_enabled + 255) / 256)), dim3(256), 0,
                                    c->stream, c->rec, c->sel_list, (int64_t)n_enabled, c->crec);
-                c->crec_valid = true;
+                c->en.records_built();
             }
             crec = c->crec;
         }
@@ -848,7 +847,7 @@ int rhk_sample_fit(rh_cloud *c, const rh_params *prm, uint64_t seed, int64_t k0,
     en.prefix = c->word_prefix;
     en.nwords = c->nwords;
     en.total = n_enabled;
-    en.sel = c->sel_valid ? c->sel_list : nullptr;
+    en.sel = c->en.has_list() ? c->sel_list : nullptr;
     rhfit::OctView oc;
     oc.code = c->oct_code; oc.perm = c->oct_perm; oc.pos = c->oct_pos; oc.men = c->oct_men; oc.prefix = c->oct_prefix;
     oc.n = c->n; oc.nwords = c->nwords; oc.depth = c->oct_depth;
@@ -927,10 +926,8 @@ extern "C" int rh_dbg_sample_fit(rh_cloud *c, const rh_params *p, uint64_t seed,
     *n_out = 0;
     RH_TRY(rh_cloud_join(c));
     if (c->n == 0) { rh_set_error("rh_dbg_sample_fit: the cloud is empty"); return RH_E_INVALID; }
-    if (!c->select_valid) RH_TRY(rhk_build_select(c));
     int32_t count = 0;
-    RH_HIP(hipMemcpyAsync(&count, c->d_total, sizeof count, hipMemcpyDeviceToHost, c->stream));
-    RH_HIP(hipStreamSynchronize(c->stream));
+    RH_TRY(rhk_enabled_total(c, &count));
     if (count <= 0) { rh_set_error("rh_dbg_sample_fit: no enabled point"); return RH_E_INVALID; }
     const double *d_P = nullptr;
     if (P != nullptr) {

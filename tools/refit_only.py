@@ -18,6 +18,7 @@ types = [R.FittedPlane, R.FittedSphere, R.FittedCylinder]
 n, seed, scanner = 10_000_000, 3, None
 if wl == "cfg5":
     prim += ["cone"] * 8; types += [R.FittedCone]; n, seed, scanner = 50_000_000, 5, [synth.BOX / 2] * 3
+n = int(os.environ.get("POINTS", n))   # (POINTS=1000000: the same scene at 1M points)
 xyz, nrm, truth = synth.make_cloud(n, prim, 0.30, seed=seed, scanner=scanner)
 subs = synth.make_subsets(n, 32, seed=seed)
 f32 = bool(os.environ.get("F32"))
