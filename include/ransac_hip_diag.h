@@ -66,6 +66,26 @@ int rh_dbg_cylbox(const rh_shape *shape, const rh_params *p, double M, double Nm
  * component| of the point set the margins are made for; f32: a Float32 cloud's margins.  Needs no GPU. */
 int rh_dbg_cls_round(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
                      const double *nrm, float *ua_out, float *ub_out, float *rec_out /* [16] */, double *dbg4_out /* [4] */);
+/* The box test of a cone candidate as the score kernel's stage 1 runs it, on the host (csrc/score4_device.h: cls_make on the
+ * host's record, box_to_f32, cone_box_skip32 -- the very code of the kernel).  boxes[6 i ..]: centre and half extents of the n
+ * binary64 boxes; skip_out[i]: 1 = the box is skipped for the candidate; fields_out (may be NULL): the RH_BOX_FIELDS = 11 fields
+ * of the culling record (0-2 apex, 3-5 unit axis, 6 k = tan(opang / 2), 7 1 / cn, 8 (eps + slack) / cn, 9 beta and 10 alpha of
+ * the axis guard; NaN: never skip).  M, Nm, f32: as for rh_dbg_cylbox.  Needs no GPU. */
+int rh_dbg_conebox(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, const double *boxes, int64_t n,
+                   uint8_t *skip_out, float *fields_out /* [11] */);
+/* The classifier of a cone candidate as the score kernel runs it (csrc/score4_device.h: cls_make on the host's record, then the
+ * kernel's own cls_cone_ab -- device code: its rho goes through the hardware's reciprocal root -- in a kernel of its own on
+ * `device`, on the n points xyz[3 i ..] with normals nrm[3 i ..], converted to binary32 as the kernel's staging converts them).
+ * ua_out[i], ub_out[i]: the scaled values of the distance and the normal half; near_out[i]: 1 = the point lies inside the axis
+ * guard (n2 <= alpha |w|^2 + beta, or a NaN), where the kernel takes u = 1/2 -- undecided -- whatever ua and ub are (elsewhere
+ * u = max of the two: u < 0 surely an inlier, u > 1 surely not, else undecided).  rec_out: the 16 fields of the classifier
+ * record (field 15 NaN: the candidate is exact-only and the kernel reads none of the three); dbg4_out: 0, wL, eD_lo, wD -- the
+ * width of the normal half (infinite on a Float32 cloud, which never decides it), the lower threshold and the width of the
+ * distance half (zeros for a candidate without a record).  M, Nm, f32: as for rh_dbg_cls_round.  Synchronous; with n = 0 only
+ * the record and its widths are made, on the host: no GPU is touched. */
+int rh_dbg_cls_cone(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
+                    const double *nrm, int device, float *ua_out, float *ub_out, uint8_t *near_out, float *rec_out /* [16] */,
+                    double *dbg4_out /* [4] */);
 /* The device's octree sampler finds a point's cell and the r-th enabled point of a cell with a cell directory and
  * bracketed 8-ary searches (csrc/fit_shared.h: cell_bounds_code, lower_bound_in, select_in, select_in_many, select_bit)
  * where the host form uses plain binary searches.  Host-only self-check of those routines against the plain ones on a

@@ -291,6 +291,9 @@ DIAG_SIGNATURES = {
     "rh_dbg_cylbox": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_int, _dp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     "rh_dbg_cls_round": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), _dp]),
+    "rh_dbg_conebox": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_int, _dp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
+    "rh_dbg_cls_cone": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.c_int, C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_float), _dp]),
     "rh_dbg_oct_search_selftest": (C.c_int, [C.c_int64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]),
     "rh_dbg_enabled_events": (C.c_int, [_u8p, C.c_int64, C.c_int32, C.POINTER(C.c_uint16)]),
     "rh_dbg_s4_stats": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64)]),

@@ -809,6 +809,23 @@ cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, cons
     }
 }
 
+// ---- the cone's classifier on points of the caller's choice (rh_dbg_cls_cone): cls_cone_ab is device code -- its rho goes
+// through the hardware's reciprocal root --, so what it says of a point can only be asked here.  pts: 6 rows of n binary32
+// values (x y z nx ny nz), converted on the host the way the staging converts them.
+__global__ void __launch_bounds__(256)
+cls_cone_dbg_kernel(const rh_cls C, const float *__restrict__ pts, int64_t n, float *__restrict__ ua, float *__restrict__ ub,
+                    uint8_t *__restrict__ near_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float a, b;
+    bool near_axis;
+    cls_cone_ab(C, pts[i], pts[n + i], pts[2 * n + i], pts[3 * n + i], pts[4 * n + i], pts[5 * n + i], a, b, near_axis);
+    ua[i] = a;
+    ub[i] = b;
+    near_out[i] = near_axis ? 1 : 0;
+}
+
 #endif   // RH_DIAG
 
 // ---- masks -> subset order, from the entry lists the score kernel left (round 4; round 3 wrote the words into sparse
@@ -1556,6 +1573,77 @@ extern "C" int rh_dbg_cls_round(const rh_shape *shape, const rh_params *p, doubl
         if (shape->kind == RH_SPHERE) cls_round_ab<RH_SPHERE>(C, x, y, z, nx, ny, nz, ua_out[i], ub_out[i]);
         else cls_round_ab<RH_CYLINDER>(C, x, y, z, nx, ny, nz, ua_out[i], ub_out[i]);
     }
+    return RH_OK;
+}
+
+// the cone's box test as the host runs it: the culling record cls_make builds for the shape (fields_out[RH_BOX_FIELDS]), and for
+// each of the n binary64 boxes (centre, half extents: boxes[6 i ..]), converted by box_to_f32 like a group's, the decision of
+// the kernel's own function.  Host only: needs no GPU.
+extern "C" int rh_dbg_conebox(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, const double *boxes, int64_t n,
+                              uint8_t *skip_out, float *fields_out)
+{
+    if (shape == nullptr || p == nullptr || n < 0 || (n > 0 && (boxes == nullptr || skip_out == nullptr))) {
+        rh_set_error("rh_dbg_conebox: bad arguments");
+        return RH_E_INVALID;
+    }
+    if (shape->kind != RH_CONE) { rh_set_error("rh_dbg_conebox: cones only"); return RH_E_INVALID; }
+    rh_prep P;
+    rh_prep_host(*shape, &P);
+    rh_cls C;
+    float box[RH_BOX_FIELDS];
+    cls_make(P, RH_CONE, p->eps[RH_CONE], p->cos_alpha[RH_CONE], M, Nm, C, box, 1, nullptr, f32 != 0);
+    if (fields_out != nullptr)
+        for (int k = 0; k < RH_BOX_FIELDS; k++) fields_out[k] = box[k];
+    for (int64_t i = 0; i < n; i++) {
+        float o[8];
+        box_to_f32(boxes + 6 * i, boxes + 6 * i + 3, o);
+        rh_box32 G;
+        G.cx = o[0]; G.cy = o[1]; G.cz = o[2]; G.hx = o[3]; G.hy = o[4]; G.hz = o[5]; G.hr = o[6];
+        skip_out[i] = cone_box_skip32(box, G) ? 1 : 0;
+    }
+    return RH_OK;
+}
+
+// the classifier of a cone candidate: the record cls_make builds for the shape on the host, its thresholds and widths (dbg4:
+// 0, wL, eD_lo, wD) and the kernel's own cls_cone_ab on n points, on the device (cls_cone_dbg_kernel).  Synchronous.
+extern "C" int rh_dbg_cls_cone(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
+                               const double *nrm, int device, float *ua_out, float *ub_out, uint8_t *near_out, float *rec_out, double *dbg4_out)
+{
+    if (shape == nullptr || p == nullptr || n < 0 || n > (int64_t)1 << 24 ||
+        (n > 0 && (xyz == nullptr || nrm == nullptr || ua_out == nullptr || ub_out == nullptr || near_out == nullptr))) {
+        rh_set_error("rh_dbg_cls_cone: bad arguments");
+        return RH_E_INVALID;
+    }
+    if (shape->kind != RH_CONE) { rh_set_error("rh_dbg_cls_cone: cones only"); return RH_E_INVALID; }
+    rh_prep P;
+    rh_prep_host(*shape, &P);
+    rh_cls C;
+    double d4[4] = { 0, 0, 0, 0 };
+    cls_make(P, RH_CONE, p->eps[RH_CONE], p->cos_alpha[RH_CONE], M, Nm, C, nullptr, 0, d4, f32 != 0);
+    if (rec_out != nullptr)
+        for (int k = 0; k < 16; k++) rec_out[k] = C.f[k];
+    if (dbg4_out != nullptr)
+        for (int k = 0; k < 4; k++) dbg4_out[k] = d4[k];
+    if (n == 0) return RH_OK;
+    std::vector<float> h((size_t)n * 6);
+    for (int64_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) {
+            h[(size_t)(k * n + i)] = (float)xyz[3 * i + k];
+            h[(size_t)((3 + k) * n + i)] = (float)nrm[3 * i + k];
+        }
+    RH_HIP(hipSetDevice(device));
+    rh_dev<float> d_p, d_a, d_b;
+    rh_dev<uint8_t> d_n;
+    RH_TRY(d_p.alloc(n * 6));
+    RH_TRY(d_a.alloc(n));
+    RH_TRY(d_b.alloc(n));
+    RH_TRY(d_n.alloc(n));
+    RH_HIP(hipMemcpy(d_p, h.data(), sizeof(float) * (size_t)n * 6, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(cls_cone_dbg_kernel, dim3((unsigned)cdiv4(n, 256)), dim3(256), 0, 0, C, (const float *)d_p, n, (float *)d_a, (float *)d_b, (uint8_t *)d_n);
+    RH_HIP(hipGetLastError());
+    RH_HIP(hipMemcpy(ua_out, d_a, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    RH_HIP(hipMemcpy(ub_out, d_b, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    RH_HIP(hipMemcpy(near_out, d_n, (size_t)n, hipMemcpyDeviceToHost));
     return RH_OK;
 }
 

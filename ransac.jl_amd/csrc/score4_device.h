@@ -530,6 +530,24 @@ static __host__ __device__ __forceinline__ bool cyl_box_skip32(const float (&B)[
     return skip;
 }
 
+// the cone's decision, host and device (rh_dbg_conebox runs this very code): "surely outside the widened band", positive
+// comparisons only.  The closed form at the centre of the box (h, rho2 against the band k h +- e, e widened by the half
+// diagonal); a centre inside the axis guard (rho2 <= alpha |t|^2 + beta) is never skipped; on the far nappe the whole band lies
+// below rho = 0 (hi <= 0), and the inner clause needs a band that starts above the axis (lo > 0).
+static __host__ __device__ __forceinline__ bool cone_box_skip32(const float (&B)[RH_BOX_FIELDS], const rh_box32 &G)
+{
+    const float tx = G.cx - B[0], ty = G.cy - B[1], tz = G.cz - B[2];
+    const float tt = __builtin_fmaf(tz, tz, __builtin_fmaf(ty, ty, tx * tx));
+    const float h = __builtin_fmaf(tz, B[5], __builtin_fmaf(ty, B[4], tx * B[3]));
+    const float rho2 = __builtin_fmaf(-h, h, tt);
+    const float s2 = __builtin_fmaf(B[10], tt, B[9]);
+    const float e = __builtin_fmaf(G.hr, B[7], B[8]) * 1.000001f;
+    const float uu = B[6] * h;
+    const float lo = uu - e, hi = uu + e;
+    const float hi2 = __builtin_fmaf(hi, hi, s2), lo2 = __builtin_fmaf(lo, lo, -s2);
+    return (rho2 > s2) & ((hi <= 0.0f) | (rho2 > hi2) | ((lo > 0.0f) & (rho2 < lo2)));
+}
+
 template <int KIND>
 static __device__ __forceinline__ bool box_skip32(const float (&B)[RH_BOX_FIELDS], const rh_box32 &G)
 {
@@ -547,17 +565,7 @@ static __device__ __forceinline__ bool box_skip32(const float (&B)[RH_BOX_FIELDS
         return (dmin2 * 0.999999f > B[3]) | (dmax2 < B[4]);
     }
     if (KIND == RH_CYLINDER) return cyl_box_skip32<true>(B, G);
-    // cone: "surely outside the widened band", positive comparisons only
-    const float tx = G.cx - B[0], ty = G.cy - B[1], tz = G.cz - B[2];
-    const float tt = __builtin_fmaf(tz, tz, __builtin_fmaf(ty, ty, tx * tx));
-    const float h = __builtin_fmaf(tz, B[5], __builtin_fmaf(ty, B[4], tx * B[3]));
-    const float rho2 = __builtin_fmaf(-h, h, tt);
-    const float s2 = __builtin_fmaf(B[10], tt, B[9]);
-    const float e = __builtin_fmaf(G.hr, B[7], B[8]) * 1.000001f;
-    const float uu = B[6] * h;
-    const float lo = uu - e, hi = uu + e;
-    const float hi2 = __builtin_fmaf(hi, hi, s2), lo2 = __builtin_fmaf(lo, lo, -s2);
-    return (rho2 > s2) & ((hi <= 0.0f) | (rho2 > hi2) | ((lo > 0.0f) & (rho2 < lo2)));
+    return cone_box_skip32(B, G);
 }
 
 // ---- The classifier's value of a (candidate, point) pair: u = max(ua, ub), the scaled "outsideness" of the two tests --
