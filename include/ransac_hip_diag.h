@@ -66,6 +66,19 @@ int rh_dbg_cylbox(const rh_shape *shape, const rh_params *p, double M, double Nm
  * component| of the point set the margins are made for; f32: a Float32 cloud's margins.  Needs no GPU. */
 int rh_dbg_cls_round(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
                      const double *nrm, float *ua_out, float *ub_out, float *rec_out /* [16] */, double *dbg4_out /* [4] */);
+/* The two-bit books of the score kernel's point loops (csrc/score4_device.h, "Two-bit books") as the host runs them, through the
+ * very functions of the kernel.  u2[64 s ..]: the 64 values u' = 2 u of sequence s in point order.  sure_count_out[s]: points
+ * with the sign bit set; sure_word_out[s] / und_word_out[s]: bit p = point p is surely in / undecided (sign clear and u' < 2,
+ * i.e. bit 30 clear; a NaN with a clear sign is "out"); any_und_out[s]: 1 = some point is undecided.  Needs no GPU. */
+int rh_dbg_books2(const float *u2, int64_t nseq, int32_t *sure_count_out, uint64_t *sure_word_out, uint64_t *und_word_out,
+                  uint8_t *any_und_out);
+/* u and u' of a plane, sphere or cylinder candidate on the n points xyz[3 i ..] with normals nrm[3 i ..] (converted to binary32
+ * as the kernel's staging converts them), on the host: u_out[i] = max(ua, ub) from the record cls_make builds, by the functions
+ * the audits use; u2_out[i] = what the kernel's point loops compute, from that record doubled in registers (cls_double) with
+ * the inline 1/2 of the round kinds as 1.  bits(u2) == bits(2 u) away from the subnormal range.  rec_out (may be NULL): the
+ * 16 fields of the undoubled record.  M, Nm, f32: as for rh_dbg_cls_round.  Needs no GPU. */
+int rh_dbg_cls_u2(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
+                  const double *nrm, float *u_out, float *u2_out, float *rec_out /* [16] or NULL */);
 /* The box test of a cone candidate as the score kernel's stage 1 runs it, on the host (csrc/score4_device.h: cls_make on the
  * host's record, box_to_f32, cone_box_skip32 -- the very code of the kernel).  boxes[6 i ..]: centre and half extents of the n
  * binary64 boxes; skip_out[i]: 1 = the box is skipped for the candidate; fields_out (may be NULL): the RH_BOX_FIELDS = 11 fields

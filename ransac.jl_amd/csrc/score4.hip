@@ -13,12 +13,15 @@
 //    instruction, padded apart in the banks) with its candidate's record and its counters in vector registers: no
 //    scalar instruction in the loop but its control, no ballot, no reduction, no divergence.
 //  * The per-point work is the two-sided binary32 classifier of score4_device.h on a binary32 tile (24 B per point):
-//    u = max(ua, ub) per point with sure <=> u < 0 and maybe <=> u <= 1 (plane; sphere and cylinder in the squared
-//    quantities |q|^2 and qn |qn|: no root, no division).  A pair whose "sure" and "maybe" counts differ -- some point
-//    lies within the rounding margin of a threshold -- is redone as a whole by
-//    the reference's binary64 test (score_device.h, unchanged; lane = point, the points from global memory).  Cones
-//    are classified the same way (the closed form of project2cone's frame, score4_device.h); their undecided POINTS go
-//    through a per-wave ring to the exact test one by one (a redo of the whole group costs 247 binary64 instructions).
+//    u = max(ua, ub) per point with sure <=> u < 0 and undecided <=> 0 <= u < 1 (plane; sphere and cylinder in the squared
+//    quantities |q|^2 and qn |qn|: no root, no division).  The point loops evaluate u' = 2 u from the record doubled in
+//    registers, so that both verdicts are the top two bits of u' and one v_alignbit_b32 per point keeps the pair's books
+//    (score4_device.h, "Two-bit books").  The undecided POINTS of a pair -- those within the rounding margin of a
+//    threshold -- are read off the owning lane's books and go through a per-wave ring to the reference's binary64 test
+//    (score_device.h, unchanged; lane = ring entry, the points from global memory) one by one, whatever pair they belong
+//    to; the classifier is never evaluated twice.  Cones are classified the same way (the closed form of project2cone's
+//    frame, score4_device.h) with a "sure" and an "undecided" word per pair (a redo of a whole group would cost 247
+//    binary64 instructions).
 //  * A block's waves never wait for each other between staging and the end of a kind: each walks its own chunks
 //    (culling records prefetched one chunk ahead); only the partial last batches of the waves are merged.
 //
@@ -111,7 +114,8 @@ struct S4AllArgs {
 // ---- event counters (diag build only; tools/isa_account.py multiplies them with the static instruction histogram of the
 // kernel's regions): one add per WAVE-level event.  Per kind k at 24 k + ...: 0 segments entered, 1..4 chunk visits of the
 // wave's 1st..4th chunk, 5 candidates box-tested, 6 chunk visits without a survivor, 7 surviving pairs, 8 batches, 9 pairs
-// taken by the second (lane = point) pass, 10 undecided points queued for the exact test, 11 full ring drains, 12 final drains,
+// with an undecided point (the wave-uniform loop that queues them: the "second pass" of the tools), 10 undecided points
+// queued for the exact test, 11 full ring drains, 12 final drains,
 // 13 points the exact test accepted, 14 pairs with a count > 0, 15 cone: compaction rounds.  Global at 96 + ...: 0 waves of
 // blocks with a tile, 1 stagings (per wave), 2 re-used stagings, 3 waves whose tile has no enabled point.
 #ifdef RH_DIAG
@@ -204,64 +208,51 @@ score4_batch(S4Shared<R, MASK, LIST> &sh, const int wv, const int lane, const in
 #pragma unroll
         for (int f = 0; f < NF; f++) C.f[f] = rec->f[f];
         const bool exact_only = weird || is_nan_bits(rec->f[RH_CLS_FLAG]);
-        // The books of the pair over its 64 points (score4_device.h, cls_plane_u): the sign bit of a point's u -- surely an
-        // inlier -- is shifted into the pair's word from the right (un-reversed afterwards), and the unsigned minimum of the
-        // u's bit patterns ends <= bits(1.0f) iff some point was undecided.  No compare, no carry chain: v_alignbit_b32 +
-        // half a v_min3_u32 per point.
-        uint32_t wlo = 0, whi = 0, umin = 0xffffffffu;
-        auto point_u = [&](int j) {
-            const rh_f32x4 a = rowa[j];
-            const rh_f32x2 b = rowb[j];
-            const float u = KIND == RH_PLANE ? cls_plane_u(C, a.x, a.y, a.z, a.w, b.x, b.y)
-                                             : cls_round_u<KIND == RH_PLANE ? RH_SPHERE : KIND>(C, a.x, a.y, a.z, a.w, b.x, b.y);
-            const uint32_t ub = __builtin_bit_cast(uint32_t, u);
-            umin = umin < ub ? umin : ub;
-            return ub;
-        };
+        // The books of the pair over its 64 points (score4_device.h, "Two-bit books"): the record is doubled in registers, so a
+        // point's verdict sits in the top two bits of its u' = 2 u -- sign: surely an inlier; neither bit: undecided -- and ONE
+        // v_alignbit_b32 per point shifts both into the pair's books, 16 points per word.  No compare, no carry chain, no
+        // running minimum; four loops over consecutive points, so that the LDS reads keep their pairing.
+        cls_double<KIND>(C);
+        uint32_t w[4] = { 0u, 0u, 0u, 0u };
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
 #pragma unroll 8
-        for (int j = 0; j < 32; j++) wlo = __builtin_amdgcn_alignbit(wlo, point_u(j), 31);
-#pragma unroll 8
-        for (int j = 32; j < 64; j++) whi = __builtin_amdgcn_alignbit(whi, point_u(j), 31);
-        if (MASK) { wlo = __brev(wlo); whi = __brev(whi); }
-        const int cs = __popc(wlo) + __popc(whi);
-        // (u = 1 exactly -- surely outside by the margins -- counts as undecided too: the redo is exact either way; a NaN u
-        // can only come from a non-finite record or point, and those never get here: exact_only, weird)
-        const bool amb = act && (umin <= 0x3f800000u || exact_only);
-        total = (act && !amb) ? cs : 0;
-        word = (act && !amb) ? (((uint64_t)whi << 32) | wlo) : 0ULL;
-        // Pairs with an undecided point (a percent of them): the classifier once more with lane = POINT (the candidate's record
-        // through scalar loads, the points from LDS), which says WHICH points are undecided -- only those take the exact test,
-        // 64 at a time through the ring, whatever pair they belong to.  (Round 3 ran the exact test on the whole group of every
-        // such pair: 40 binary64 instructions per wave and pair, a tenth of the launch's issue cycles.)
+            for (int j = 0; j < 16; j++) {
+                const rh_f32x4 a = rowa[16 * q + j];
+                const rh_f32x2 b = rowb[16 * q + j];
+                w[q] = books2_push(w[q], cls_u2<KIND>(C, a.x, a.y, a.z, a.w, b.x, b.y));
+            }
+        }
+        // (a disabled or out-of-range point is staged as zeros and surely out by cls_make's guards: no mask by the group's
+        // enabled word here.  u' = 2 exactly -- u = 1, surely outside by the margins -- is out; a NaN u' can only come from a
+        // non-finite record or point, and those pairs ignore their books: exact_only, weird)
+        const bool amb = act && (exact_only || books2_any_undecided(w));
+        total = (act && !exact_only) ? books2_sure_count(w) : 0;
+        if (MASK) word = (act && !exact_only) ? books2_sure64(w) : 0ULL;
+        // Pairs with an undecided point (a percent of them): the owning lane's books say WHICH points are undecided; a
+        // wave-uniform loop over those pairs puts them on the ring with lane = point -- two v_readlane of the owner's word, a
+        // rank, a store; no record, no point and no classifier a second time -- and only they take the exact test, 64 at a
+        // time, whatever pair they belong to.  (Until round 12 the loop evaluated the classifier again with lane = point to
+        // find them: 36-48 vector and 53-56 scalar instructions per pair behind a scalar-load round trip.  Round 3 ran the
+        // exact test on the whole group of every such pair: 40 binary64 instructions per wave and pair.)
         uint64_t redo = WB(amb);
         S4_STAT(stats, 24 * KIND + 9, __popcll(redo));
         if (redo != 0) {
+            const uint64_t lg = sh.len[g];
+            const uint64_t und = exact_only ? lg : (books2_und64(w) & lg);   // (exact-only: every enabled point; read of the amb lanes only)
+            const uint32_t undlo = (uint32_t)und, undhi = (uint32_t)(und >> 32);
             sh.cntb[wv][lane] = 0;
             if (MASK) sh.maskb[wv][lane] = 0ULL;
             while (redo != 0) {
                 const int k = __builtin_ctzll(redo);
                 redo &= redo - 1;
-                const uint32_t ek = __builtin_amdgcn_readlane(e, k);
-                const int g2 = (int)(ek & S4_GM);
-                const int ci2 = LIST ? __builtin_amdgcn_readfirstlane((int)sh.ctab[ek >> S4_GB]) : cbase + (int)(ek >> S4_GB);
-                const RH4_CONST_AS rh_cls *rk = (const RH4_CONST_AS rh_cls *)(uintptr_t)&cls[ci2];   // (wave-uniform: scalar loads)
-                rh_cls Ck;
-#pragma unroll
-                for (int f = 0; f < NF; f++) Ck.f[f] = rk->f[f];
-                const bool xo = weird || is_nan_bits(rk->f[RH_CLS_FLAG]);
-                const rh_f32x4 a = sh.pa[g2][lane];
-                const rh_f32x2 b = sh.pb[g2][lane];
-                const float u = KIND == RH_PLANE ? cls_plane_u(Ck, a.x, a.y, a.z, a.w, b.x, b.y)
-                                                 : cls_round_u<KIND == RH_PLANE ? RH_SPHERE : KIND>(Ck, a.x, a.y, a.z, a.w, b.x, b.y);
-                const uint64_t lg = sh.len[g2];
-                const uint64_t sure = xo ? 0ULL : (WB(cls_sure(u)) & lg);
-                const uint64_t und = xo ? lg : (WB(cls_undecided(u)) & lg);   // (exact-only: every enabled point)
-                if (lane == k) { total = __popcll(sure); word = sure; }
-                const bool has = (und >> lane) & 1ULL;
-                const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(und >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)und, 0));
+                const uint32_t ulo = __builtin_amdgcn_readlane(undlo, k), uhi = __builtin_amdgcn_readlane(undhi, k);
+                const uint64_t uk = ((uint64_t)uhi << 32) | ulo;
+                const bool has = (uk >> lane) & 1ULL;
+                const int rank = __builtin_amdgcn_mbcnt_hi(uhi, __builtin_amdgcn_mbcnt_lo(ulo, 0));
                 if (has) sh.qb[wv][(qbh + qbn + rank) & 127] = (uint16_t)((k << 6) | lane);
-                qbn += __popcll(und);
-                S4_STAT(stats, 24 * KIND + 10, __popcll(und));
+                qbn += __popcll(uk);
+                S4_STAT(stats, 24 * KIND + 10, __popcll(uk));
                 if (qbn >= 64) drain_b(64);
             }
             if (qbn > 0) drain_b(qbn);
@@ -1572,6 +1563,60 @@ extern "C" int rh_dbg_cls_round(const rh_shape *shape, const rh_params *p, doubl
         const float nx = (float)nrm[3 * i], ny = (float)nrm[3 * i + 1], nz = (float)nrm[3 * i + 2];
         if (shape->kind == RH_SPHERE) cls_round_ab<RH_SPHERE>(C, x, y, z, nx, ny, nz, ua_out[i], ub_out[i]);
         else cls_round_ab<RH_CYLINDER>(C, x, y, z, nx, ny, nz, ua_out[i], ub_out[i]);
+    }
+    return RH_OK;
+}
+
+// the two-bit books of the score kernel's point loops as the host runs them (score4_device.h, "Two-bit books": books2_push and
+// the four read-outs, the very statements of score4_batch): nseq sequences of 64 values u' each, pushed in point order.  Host
+// only: needs no GPU.
+extern "C" int rh_dbg_books2(const float *u2, int64_t nseq, int32_t *sure_count_out, uint64_t *sure_word_out, uint64_t *und_word_out,
+                             uint8_t *any_und_out)
+{
+    if (nseq < 0 || (nseq > 0 && (u2 == nullptr || sure_count_out == nullptr || sure_word_out == nullptr || und_word_out == nullptr || any_und_out == nullptr))) {
+        rh_set_error("rh_dbg_books2: bad arguments");
+        return RH_E_INVALID;
+    }
+    for (int64_t s = 0; s < nseq; s++) {
+        uint32_t w[4] = { 0u, 0u, 0u, 0u };
+        for (int q = 0; q < 4; q++)
+            for (int j = 0; j < 16; j++) w[q] = books2_push(w[q], u2[64 * s + 16 * q + j]);
+        sure_count_out[s] = books2_sure_count(w);
+        sure_word_out[s] = books2_sure64(w);
+        und_word_out[s] = books2_und64(w);
+        any_und_out[s] = books2_any_undecided(w) ? 1 : 0;
+    }
+    return RH_OK;
+}
+
+// u and u' of a plane, sphere or cylinder candidate on n points, on the host: u = max(ua, ub) by the functions every other caller
+// uses on the record cls_make builds, u' by the point loops' own path -- that record doubled by cls_double, then cls_u2.  Host
+// only: needs no GPU.
+extern "C" int rh_dbg_cls_u2(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
+                             const double *nrm, float *u_out, float *u2_out, float *rec_out)
+{
+    if (shape == nullptr || p == nullptr || n < 0 || (n > 0 && (xyz == nullptr || nrm == nullptr || u_out == nullptr || u2_out == nullptr))) {
+        rh_set_error("rh_dbg_cls_u2: bad arguments");
+        return RH_E_INVALID;
+    }
+    const int kind = shape->kind;
+    if (kind != RH_PLANE && kind != RH_SPHERE && kind != RH_CYLINDER) { rh_set_error("rh_dbg_cls_u2: planes, spheres and cylinders only"); return RH_E_INVALID; }
+    rh_prep P;
+    rh_prep_host(*shape, &P);
+    rh_cls C;
+    cls_make(P, kind, p->eps[kind], p->cos_alpha[kind], M, Nm, C, nullptr, 0, nullptr, f32 != 0);
+    if (rec_out != nullptr)
+        for (int k = 0; k < 16; k++) rec_out[k] = C.f[k];
+    rh_cls D = C;
+    if (kind == RH_PLANE) cls_double<RH_PLANE>(D);
+    else if (kind == RH_SPHERE) cls_double<RH_SPHERE>(D);
+    else cls_double<RH_CYLINDER>(D);
+    for (int64_t i = 0; i < n; i++) {
+        const float x = (float)xyz[3 * i], y = (float)xyz[3 * i + 1], z = (float)xyz[3 * i + 2];
+        const float nx = (float)nrm[3 * i], ny = (float)nrm[3 * i + 1], nz = (float)nrm[3 * i + 2];
+        if (kind == RH_PLANE) { u_out[i] = cls_plane_u(C, x, y, z, nx, ny, nz); u2_out[i] = cls_u2<RH_PLANE>(D, x, y, z, nx, ny, nz); }
+        else if (kind == RH_SPHERE) { u_out[i] = cls_round_u<RH_SPHERE>(C, x, y, z, nx, ny, nz); u2_out[i] = cls_u2<RH_SPHERE>(D, x, y, z, nx, ny, nz); }
+        else { u_out[i] = cls_round_u<RH_CYLINDER>(C, x, y, z, nx, ny, nz); u2_out[i] = cls_u2<RH_CYLINDER>(D, x, y, z, nx, ny, nz); }
     }
     return RH_OK;
 }

@@ -39,7 +39,9 @@
 //
 // The records are SCALED: with wN, wD = 2 x margin, the kernel computes ua = (cN_hi - dn) / wN and ub = (|d| - eD_lo) / wD
 // directly (the scaling is folded into the coefficients before they are rounded to binary32), so that with u = max(ua, ub)
-//     sure <=> u < 0,   maybe <=> u <= 1                        (read off the bit pattern of u: cls_plane_u below).
+//     sure <=> u < 0,   maybe <=> u <= 1                        (read off the bit pattern of u: cls_plane_u below; the score
+//                                                                kernel's point loops read both off the top two bits of 2 u and
+//                                                                take u = 1 for "out": "Two-bit books" below).
 //
 // Guards.  Non-finite or huge inputs would make binary32 overflow where binary64 does not, so a candidate is marked
 // EXACT-ONLY (field RH_CLS_FLAG = NaN) unless all its parameters are finite and below 2^20 (cylinder axis components
@@ -574,21 +576,22 @@ static __device__ __forceinline__ bool box_skip32(const float (&B)[RH_BOX_FIELDS
 //     u < 0  (sign bit set)   both tests pass by more than their margins: SURELY an inlier
 //     0 <= u <= 1             some test is within its margin and none fails surely: UNDECIDED -> the exact test
 //     u > 1                   some test fails by more than its margin: surely not
-// so that the 64-point loop of the score kernel (score4.hip) keeps the books with two instructions per point and no
-// compare: the sign bit of u is shifted into the pair's inlier word (v_alignbit_b32), and a running UNSIGNED minimum over
-// the bit patterns of the u (v_min3_u32, two points per instruction) ends <= bits(1.0f) iff some point was undecided --
-// non-negative floats order like their bit patterns and every negative one lies above them.  (Measured on this GPU,
-// tools/ubench/count_seq.hip: v_cmp / v_cndmask / v_addc / v_min_f32 hold the issue port 4.2 cycles each, fma / add / mul
-// 2.3-2.9; round 3's t = min(a, b) with `count += t > 1/2` and a running minimum of |t| cost 14.6 cycles per point beside the
-// arithmetic, this form 10.5.)  u = -0 counts as surely-in: it stands for a test passed by exactly its margin, and the
-// margins carry a factor RH_CLS_SAFETY over the first-order bound.
-static __device__ __forceinline__ void cls_plane_ab(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz, float &ua, float &ub)
+// so that the 64-point loops of the score kernel (score4.hip) keep the books with ONE instruction per point and no compare:
+// they evaluate u' = 2 u, whose top two bits hold the verdict, and shift both into the pair's books with a v_alignbit_b32
+// ("Two-bit books" at the end of this file).  Rounds 4 to 11 shifted the sign bit of u alone and kept a running UNSIGNED
+// minimum over the bit patterns of the u beside it (v_min3_u32, two points per instruction), which ended <= bits(1.0f) iff
+// SOME point was undecided -- and a second evaluation of the classifier, lane = point, then had to find out which.
+// (Measured on this GPU, tools/ubench/count_seq.hip: v_cmp / v_cndmask / v_addc / v_min_f32 hold the issue port 4.2 cycles
+// each, fma / add / mul 2.3-2.9; round 3's t = min(a, b) with `count += t > 1/2` and a running minimum of |t| cost 14.6
+// cycles per point beside the arithmetic, the form with the minimum 10.5.)  u = -0 counts as surely-in: it stands for a test
+// passed by exactly its margin, and the margins carry a factor RH_CLS_SAFETY over the first-order bound.
+static __host__ __device__ __forceinline__ void cls_plane_ab(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz, float &ua, float &ub)
 {
     ua = __builtin_fmaf(C.f[2], nz, __builtin_fmaf(C.f[1], ny, __builtin_fmaf(C.f[0], nx, C.f[3])));
     const float d = __builtin_fmaf(C.f[6], z, __builtin_fmaf(C.f[5], y, __builtin_fmaf(C.f[4], x, C.f[7])));
     ub = __builtin_fabsf(d) - C.f[8];
 }
-static __device__ __forceinline__ float cls_plane_u(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz)
+static __host__ __device__ __forceinline__ float cls_plane_u(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz)
 {
     float a, b;
     cls_plane_ab(C, x, y, z, nx, ny, nz, a, b);
@@ -596,10 +599,11 @@ static __device__ __forceinline__ float cls_plane_u(const rh_cls &C, float x, fl
 }
 
 // ---- sphere / cylinder: the same u = max(ua, ub) from the scaled record, in the squared quantities n2 = |q|^2 and qn |qn|
-// ("Round kinds without a square root" above).  Host and device: the kernel's point loops, its second pass, the audits and
-// rh_dbg_cls_round run this one statement.
+// ("Round kinds without a square root" above).  Host and device: the kernel's point loops (with a doubled record and
+// half = 1: cls_u2), the audits, rh_dbg_cls_round and rh_dbg_cls_u2 run this one statement.
 template <int KIND>
-static __host__ __device__ __forceinline__ void cls_round_ab(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz, float &ua, float &ub)
+static __host__ __device__ __forceinline__ void cls_round_ab(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz, float &ua, float &ub,
+                                                            const float half = 0.5f)
 {
     float qx, qy, qz;
     constexpr int b = KIND == RH_SPHERE ? 3 : 6;
@@ -614,13 +618,13 @@ static __host__ __device__ __forceinline__ void cls_round_ab(const rh_cls &C, fl
     const float n2 = __builtin_fmaf(qz, qz, __builtin_fmaf(qy, qy, qx * qx));
     const float qn = __builtin_fmaf(qz, nz, __builtin_fmaf(qy, ny, qx * nx));
     ua = __builtin_fmaf(__builtin_fabsf(n2 - C.f[b]), C.f[b + 1], C.f[b + 2]);
-    ub = __builtin_fmaf(qn * __builtin_fabsf(qn), C.f[b + 3], __builtin_fmaf(n2, C.f[b + 4], 0.5f));   // (mv / Wv = 1/2: no field)
+    ub = __builtin_fmaf(qn * __builtin_fabsf(qn), C.f[b + 3], __builtin_fmaf(n2, C.f[b + 4], half));   // (mv / Wv = 1/2: no field; 1 with a doubled record, cls_double)
 }
 template <int KIND>
-static __device__ __forceinline__ float cls_round_u(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz)
+static __host__ __device__ __forceinline__ float cls_round_u(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz, const float half = 0.5f)
 {
     float a, b;
-    cls_round_ab<KIND>(C, x, y, z, nx, ny, nz, a, b);
+    cls_round_ab<KIND>(C, x, y, z, nx, ny, nz, a, b, half);
     return fmaxf(a, b);
 }
 
@@ -658,6 +662,79 @@ static __device__ __forceinline__ float cls_cone_u(const rh_cls &C, float x, flo
 // what the books say of a u (score kernel, audits)
 static __device__ __forceinline__ bool cls_sure(float u) { return (__builtin_bit_cast(uint32_t, u) >> 31) != 0; }
 static __device__ __forceinline__ bool cls_undecided(float u) { return __builtin_bit_cast(uint32_t, u) <= 0x3f800000u; }   // 0 <= u <= 1
+
+// ---- Two-bit books (plane, sphere, cylinder: the point loops of score4_batch).  The kernel evaluates u' = 2 u: the record
+// fields that enter u linearly are doubled in registers once per batch (cls_double; the records in memory, the audits and
+// every other caller keep u) and the inline 1/2 of cls_round_ab becomes 1.  Doubling commutes with every rounding of the
+// chain (powers of two; below the normal range a partial result may differ in its last place, 2^-149 of a quantity whose
+// margin is of order 1, and a subnormal u' keeps its sign, which is all the books read of it; overflow: cls_make keeps every
+// product below 2^120).  The verdict is then in the TOP TWO BITS of u':
+//     sign set                    u' < 0 (or -0)          surely an inlier
+//     sign clear, bit 30 clear    0 <= u' < 2             undecided -> the exact test
+//     sign clear, bit 30 set      u' >= 2                 surely out (u = 1 exactly too: the margins say so; a NaN with a
+//                                                         clear sign as well -- none arrives: exact-only pairs ignore the books)
+// One v_alignbit_b32(w, bits(u'), 30) per point shifts both bits into a word from the right: 16 points per word, four words
+// per pair, and no running minimum beside them.  Layout: word q holds the points 16 q .. 16 q + 15 in push order; after its
+// 16 pushes point 16 q + j has its sign bit at bit 31 - 2 j and its bit 30 at bit 30 - 2 j (the first point on top).
+// Host and device run these very statements (rh_dbg_books2).
+template <int KIND>
+static __host__ __device__ __forceinline__ void cls_double(rh_cls &C)
+{
+    constexpr int lo = KIND == RH_PLANE ? 0 : (KIND == RH_SPHERE ? 4 : 7), hi = KIND == RH_PLANE ? 9 : (KIND == RH_SPHERE ? 8 : 11);
+#pragma unroll
+    for (int f = lo; f < hi; f++) C.f[f] = C.f[f] + C.f[f];
+}
+// u' of a point by the doubled record (C: after cls_double<KIND>)
+template <int KIND>
+static __host__ __device__ __forceinline__ float cls_u2(const rh_cls &C, float x, float y, float z, float nx, float ny, float nz)
+{
+    if (KIND == RH_PLANE) return cls_plane_u(C, x, y, z, nx, ny, nz);
+    return cls_round_u<KIND == RH_PLANE ? RH_SPHERE : KIND>(C, x, y, z, nx, ny, nz, 1.0f);
+}
+static __host__ __device__ __forceinline__ uint32_t books2_push(uint32_t w, float u2)
+{
+    const uint32_t b = __builtin_bit_cast(uint32_t, u2);
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_alignbit(w, b, 30);
+#else
+    return (w << 2) | (b >> 30);
+#endif
+}
+constexpr uint32_t RH_BOOKS2_SIGN = 0xAAAAAAAAu;   // the sign bits of a word's 16 points
+// points surely in, over the pair's four words
+static __host__ __device__ __forceinline__ int books2_sure_count(const uint32_t (&w)[4])
+{
+    return (__builtin_popcount(w[0] & RH_BOOKS2_SIGN) + __builtin_popcount(w[1] & RH_BOOKS2_SIGN)) +
+           (__builtin_popcount(w[2] & RH_BOOKS2_SIGN) + __builtin_popcount(w[3] & RH_BOOKS2_SIGN));
+}
+// a word's undecided points, at their sign bits' places: both bits clear
+static __host__ __device__ __forceinline__ uint32_t books2_und_bits(uint32_t w) { return ~(w | (w << 1)) & RH_BOOKS2_SIGN; }
+static __host__ __device__ __forceinline__ bool books2_any_undecided(const uint32_t (&w)[4])
+{
+    return (((books2_und_bits(w[0]) | books2_und_bits(w[1])) | books2_und_bits(w[2])) | books2_und_bits(w[3])) != 0u;
+}
+// the 16 sign-place bits of a word (x & RH_BOOKS2_SIGN == x) in point order: point j of the word at bit j
+static __host__ __device__ __forceinline__ uint32_t books2_compress(uint32_t x)
+{
+    x = __builtin_bitreverse32(x);                 // point j at bit 2 j
+    x = (x | (x >> 1)) & 0x33333333u;
+    x = (x | (x >> 2)) & 0x0f0f0f0fu;
+    x = (x | (x >> 4)) & 0x00ff00ffu;
+    return (x | (x >> 8)) & 0x0000ffffu;
+}
+// the pair's undecided / surely-in points as 64-bit words in point order (bit p = point p of the group)
+static __host__ __device__ __forceinline__ uint64_t books2_und64(const uint32_t (&w)[4])
+{
+    const uint32_t lo = books2_compress(books2_und_bits(w[0])) | (books2_compress(books2_und_bits(w[1])) << 16);
+    const uint32_t hi = books2_compress(books2_und_bits(w[2])) | (books2_compress(books2_und_bits(w[3])) << 16);
+    return ((uint64_t)hi << 32) | lo;
+}
+static __host__ __device__ __forceinline__ uint64_t books2_sure64(const uint32_t (&w)[4])
+{
+    const uint32_t lo = books2_compress(w[0] & RH_BOOKS2_SIGN) | (books2_compress(w[1] & RH_BOOKS2_SIGN) << 16);
+    const uint32_t hi = books2_compress(w[2] & RH_BOOKS2_SIGN) | (books2_compress(w[3] & RH_BOOKS2_SIGN) << 16);
+    return ((uint64_t)hi << 32) | lo;
+}
 #endif   // __HIPCC__
 
 }  // namespace rh4

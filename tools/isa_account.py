@@ -5,8 +5,8 @@
                                                                       x (how often the region runs in one launch)
 
 The static side is the gfx950 ISA hipcc emits for the product flags (no GPU needed): the kernel is cut into basic blocks,
-LLVM's own loop annotations give the loop tree (per kind body: the batch loop with its two point loops and the second-pass /
-compaction loop), and every instruction gets a price by OPCODE -- two columns: MI355X_MICROARCH.md's rates and the rates
+LLVM's own loop annotations give the loop tree (per kind body: the batch loop with its point loops -- four of 16 points, the cone two of 32:
+n_point_loops -- and the undecided-pair / compaction loop), and every instruction gets a price by OPCODE -- two columns: MI355X_MICROARCH.md's rates and the rates
 measured on this GPU (tools/ubench/valu_rates.hip, count_seq.hip).  The dynamic side is the diag build's event counters of
 one launch (tools/s4_stats.py -> s4_stats_<WL>.json: chunk visits, batches, second-pass pairs, ring drains per kind).  The
 result is checked against the hardware's own per-class instruction counters of the same launch (profiles/rN/pmc_sq_counters*.json)
@@ -184,10 +184,16 @@ def has_f64(b):
     return any(op.endswith("_f64") or "_f64_" in op for op in b.ins)
 
 
+def n_point_loops(kind):
+    """point loops of a kind's batch body and the points each covers: plane, sphere and cylinder keep two-bit books, 16 points to
+    a word and a loop per word (score4_device.h, "Two-bit books"); the cone two words of 32 points, a loop each"""
+    return (2, 32) if kind == "cone" else (4, 16)
+
+
 def regions(blocks, rows):
     """region name -> list of blocks.  Per kind body k (in the kernel's order): pre (everything between the previous body's batch
     loop and this one: staging + the unrolled chunk visits of stage 1), batch (the batch loop outside its inner loops), pl (the
-    two point loops), p2 (the third inner loop: second pass, or the cone's compaction rounds), drain_in (its blocks with binary64
+    point loops), p2 (the inner loop behind them: the pairs with an undecided point, or the cone's compaction rounds), drain_in (its blocks with binary64
     arithmetic: a full ring drained inside the loop), drain_end (binary64 blocks behind it: the final drain), p2_tail (the
     other blocks that only run for batches with an undecided point)."""
     l1_heads = [b.l1 for b in blocks if b.is_l1_header]
@@ -210,7 +216,7 @@ def regions(blocks, rows):
         if b.l2 is None:
             # behind the third inner loop? (textual order: blocks of the batch loop after the last inner header)
             reg["batch_%s" % k].append(b)
-        elif b.l2 in l2s[:2]:
+        elif b.l2 in l2s[:n_point_loops(k)[0]]:
             reg["pl_%s" % k].append(b)
         else:
             reg[("drain_in_%s" if has_f64(b) else "p2_%s") % k].append(b)
@@ -235,13 +241,14 @@ def regions(blocks, rows):
         third_seen = False
         order = [b for b in blocks if b.l1 is not None and kind_of[b.l1] == k]
         l2s = [x.l2 for x in order if x.is_l2_header]
+        npl = n_point_loops(k)[0]     # (the "third" loop: the one behind the point loops)
         for b in order:
-            if b.l2 is not None and len(l2s) >= 3 and b.l2 == l2s[2]:
+            if b.l2 is not None and len(l2s) > npl and b.l2 == l2s[npl]:
                 third_seen = True
         after_third = False
         for b in reg["batch_%s" % k]:
             idx = order.index(b)
-            after_third = any(x.l2 is not None and len(l2s) >= 3 and x.l2 == l2s[2] for x in order[:idx])
+            after_third = any(x.l2 is not None and len(l2s) > npl and x.l2 == l2s[npl] for x in order[:idx])
             if after_third and has_f64(b):
                 reg["drain_end_%s" % k].append(b)
             else:
@@ -297,7 +304,8 @@ def account(isa, stats, rows, lists=False):
         cnt = info["count"]
         if name.startswith("pl_"):
             k = name[3:]
-            # the two point loops cover 32 points each; a body of U points runs 32 / U times per loop and batch
+            # a point loop covers 16 points (two-bit books: one alignbit per point) or 32 (cone: two alignbits per point); a body
+            # of U points runs 16 / U resp. 32 / U times per loop and batch
             per_loop = []
             l2s = sorted({b.l2 for b in blks})
             total = Counter()
@@ -305,7 +313,7 @@ def account(isa, stats, rows, lists=False):
                 hb = hist([b for b in blks if b.l2 == l2])
                 nbits = sum(v for o, v in hb.items() if o.startswith("v_alignbit"))
                 u = max(1, nbits // (2 if k == "cone" else 1))
-                iters = 32.0 / u
+                iters = float(n_point_loops(k)[1]) / u
                 per_loop.append({"loop": l2, "instructions_per_iteration": sum(hb.values()), "points_per_iteration": u})
                 for o, v in hb.items():
                     total[o] += v * iters
