@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 121
+#define RH_VERSION 122
 
 enum {
     RH_OK = 0,
@@ -955,6 +955,12 @@ int rh_register_f32(const float *ref_xyz_aos, const float *ref_nrm_aos_or_null, 
  *                 when no point of the group has its normal in one of the 96 direction cells the candidate can accept (masks
  *                 per 64-point group, made once when the cloud is created).  Counts and masks do not depend on it.  Read on
  *                 every launch.
+ *   "plane_order" 0 (default: by size, from 256 tiles of 256 subset points on) / 1 (whenever possible) / 2 (never) --
+ *                 counts-only launches of the culled score kernel on subset 1 walk their PLANE
+ *                 candidates over a second internal order of the subset: inside every node of the position tree with at most
+ *                 1024 points the same points, ordered by a k-d tree on their normals, so that a group's normal-cell mask
+ *                 holds fewer cells and fewer (plane, group) pairs survive (made once when the cloud is created; about 52
+ *                 bytes per subset point).  Counts do not depend on it; launches that write masks never take it.  Read on every launch.
  *   "batches_in_flight"  1 (default) .. 4 -- with F > 1, rh_score_batch_dev calls take turns on the cloud's
  *                 stream and F - 1 more with workspaces of their own, so one batch's prepare + score launches start while
  *                 the previous batches' launches drain.  The caller keeps F count (and mask) buffers and gives call k of a

@@ -49,6 +49,16 @@ int rh_dbg_nsig(const rh_shape *shape, const rh_params *p, double M, double Nm, 
 /* The binary64 boxes of the 64-point groups of subset 1 in the library's own (k-d leaf) order: out[6 g ..] = centre and half
  * extents of group g; *ngroups_out: their number (out = NULL or cap < that number: only the number is returned). */
 int rh_dbg_group_boxes(rh_cloud *c, double *out, int64_t cap, int64_t *ngroups_out);
+/* The plane order of subset 1 (csrc/kdorder.hip: inside every node of the position k-d tree with at most 1024 points the same
+ * points, ordered by a k-d tree on their normals; what plane candidates of counts-only score launches walk) as the cloud holds it.
+ * The nodes: a node of cnt > 1024 points gives its left child ((cnt / 64 + 1) / 2) * 64 of them, from [0, s) down.
+ * info_out[4]: s, the number of 64-point groups, the number of super-tiles, 1 if the cloud has a plane order (else nothing more
+ * is written).  Every other pointer may be NULL.  sub_out / pl_out [6 s]: the subset in leaf order / in plane order, planes
+ * x y z nx ny nz, s apart; src_out [s]: plane-order position i holds the point of leaf-order position src_out[i];
+ * gb32_out [8 groups]: the plane-order groups' binary32 boxes (cx cy cz hx hy hz hr 0); gm32_out [4 groups]: their normal-cell
+ * masks; en_out [2 ceil(s / 64)]: the enabled words in leaf order, then in plane order.  Synchronous. */
+int rh_dbg_plane_order(rh_cloud *c, int64_t *info_out /* [4] */, double *sub_out, double *pl_out, int32_t *src_out, float *gb32_out,
+                       uint32_t *gm32_out, uint64_t *en_out);
 /* The box test of a cylinder candidate as the score kernel's stage 1 runs it, on the host (csrc/score4_device.h: cls_make on the
  * host's record, box_to_f32, cyl_box_skip32 -- the very code of the kernel).  boxes[6 i ..]: centre and half extents of the n
  * binary64 boxes; skip_out[i]: 1 = the box is skipped for the candidate; ball_out[i]: the same by the two clauses alone that

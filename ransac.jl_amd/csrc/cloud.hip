@@ -516,6 +516,10 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
         }
     }
     stamp("subset order, gather, boxes");
+    // the second internal order of subset 1, for the plane candidates of the culled score kernel (kdorder.hip); the enabled
+    // words below are gathered into it too
+    if (n > 0 && s > 0) CK(rhk_plane_order_build(c));
+    stamp("plane order");
     CK(rhk_enabled_replace(c, nullptr));
     CKH(hipStreamSynchronize(c->stream));
     stamp("enabled bits");

@@ -363,7 +363,10 @@ static int rebuild_sub_enabled(rh_cloud *c, bool reset_list)
                        c->enabled, c->sub_idx0, c->s, c->swords, c->sub_enabled, reset_list ? 1 : 0, c->sub, c->s_pad,
                        c->dis, c->dis_stride, c->d_ndis);
     RH_HIP(hipGetLastError());
-    return RH_OK;
+    // The plane-order twin of the words follows at once, on the same stream: whoever is ordered behind sub_enabled is ordered
+    // behind it.  (Not lazily at the first plane launch: that launch may sit on a batch slot's stream, and the other slots
+    // are ordered behind the cloud's stream only.)
+    return rhk_plane_enabled_sync(c);
 }
 
 static int read_ndis(rh_cloud *c)   // n_dis = the list's length as the device has it (waits for the stream)

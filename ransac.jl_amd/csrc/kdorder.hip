@@ -21,6 +21,9 @@
 #include <hipcub/hipcub.hpp>
 
 #include "rh_internal.h"
+#ifdef RH_DIAG
+#include "ransac_hip_diag.h"
+#endif
 
 namespace {
 
@@ -165,6 +168,129 @@ __global__ void kd_finish_kernel(const int32_t *__restrict__ ord, const int32_t 
 }
 
 struct KdNode { int32_t lo, hi; };
+
+// ---- the plane order of subset 1 (score4.hip walks it with plane candidates).  The position tree is
+// stopped at its nodes of at most PO_ST = 1024 points (whole groups: every split is at a multiple of 64; 576 .. 640 points at
+// cfg3 -- NOT the runs of 1024 consecutive points that the candidate lists call super-tiles: those straddle the tree's nodes,
+// their points lie further apart, and cutting them by normals leaves boxes half as large again: tools/proto/plane_order_proto.py).
+// Inside every such node the SAME points, ordered by a k-d tree on their NORMALS: widest axis of the node's finite normals,
+// median split, the left child a multiple of 64 like the position tree's, down to 64-point groups (four levels).  A node is
+// small enough for one block: the normals in LDS, per level the nodes' boxes by atomics and one bitonic sort of 1024 keys
+//     node << 42 | ordered binary32 pattern of the normal along the node's axis << 10 | leaf-order position in the block.
+// The keys are distinct, so the order is a function of the normals alone: no ties, no dependence on the schedule.  A NaN
+// component sorts last, an axis without a finite value is never the widest; where such a point lands is of no consequence
+// (every grouping of the points gives the same counts).  Positions behind the block's end take the last node number and keep
+// their place.
+constexpr int PO_ST = 1024;
+constexpr int PO_THREADS = 512;
+
+__global__ void __launch_bounds__(PO_THREADS)
+plane_order_kernel(const double *__restrict__ sub, int64_t stride, const int32_t *__restrict__ blk_lo, int32_t *__restrict__ src)
+{
+    __shared__ float nv[3][PO_ST];
+    __shared__ uint64_t key[PO_ST];
+    __shared__ uint16_t ord[PO_ST];     // position in the plane order -> leaf-order position, both inside the block
+    __shared__ uint32_t box[16][6];
+    __shared__ int nlo[2][18];          // node starts of the level (alternating rows), closed by the point count
+    __shared__ int nnode[2];
+    const int tid = threadIdx.x;
+    const int64_t base = blk_lo[blockIdx.x];
+    const int cnt = (int)(blk_lo[blockIdx.x + 1] - base);   // (1 .. PO_ST: rhk_plane_order_build)
+    for (int i = tid; i < PO_ST; i += PO_THREADS) {
+        const bool in = i < cnt;
+#pragma unroll
+        for (int k = 0; k < 3; k++) nv[k][i] = in ? (float)sub[(3 + k) * stride + base + i] : 0.0f;
+        ord[i] = (uint16_t)i;
+    }
+    if (tid == 0) { nlo[0][0] = 0; nlo[0][1] = cnt; nnode[0] = 1; }
+    __syncthreads();
+    for (int level = 0; level < 4; level++) {
+        const int *lo = nlo[level & 1];
+        const int nn = nnode[level & 1];
+        for (int t = tid; t < 16 * 6; t += PO_THREADS) box[t / 6][t % 6] = (t % 6) < 3 ? 0xffffffffu : 0u;
+        __syncthreads();
+        auto node_of = [&](int i) { int nd = 0; for (int k = 1; k < nn; k++) nd += lo[k] <= i ? 1 : 0; return nd; };
+        for (int i = tid; i < cnt; i += PO_THREADS) {
+            const int nd = node_of(i);
+            if (lo[nd + 1] - lo[nd] <= 64) continue;
+            const int j = ord[i];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const float v = nv[k][j];
+                if (v - v == 0.0f) { atomicMin(&box[nd][k], ord32(v)); atomicMax(&box[nd][3 + k], ord32(v)); }
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < PO_ST; i += PO_THREADS) {
+            const int j = ord[i];
+            int nd = 31;
+            uint32_t sk = (uint32_t)i;   // a finished node, the padding: the position itself
+            if (i < cnt) {
+                nd = node_of(i);
+                if (lo[nd + 1] - lo[nd] > 64) {
+                    int ax = 0;
+                    float best = -2.0f;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        const uint32_t bl = box[nd][k], bh = box[nd][3 + k];
+                        const float e = bl <= bh ? unord32(bh) - unord32(bl) : -1.0f;
+                        if (e > best) { best = e; ax = k; }
+                    }
+                    sk = ord32(nv[ax][j]);
+                }
+            }
+            key[i] = ((uint64_t)nd << 42) | ((uint64_t)sk << 10) | (uint64_t)j;
+        }
+        __syncthreads();
+        for (int k = 2; k <= PO_ST; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), p = i | j;
+                const uint64_t a = key[i], b = key[p];
+                if ((a > b) == ((i & k) == 0)) { key[i] = b; key[p] = a; }
+                __syncthreads();
+            }
+        for (int i = tid; i < PO_ST; i += PO_THREADS) ord[i] = (uint16_t)(key[i] & 1023u);
+        if (tid == 0) {   // the next level's nodes: the children of those that split
+            int *nx = nlo[(level + 1) & 1];
+            int m = 0;
+            for (int q = 0; q < nn; q++) {
+                const int c0 = lo[q + 1] - lo[q];
+                nx[m++] = lo[q];
+                if (c0 > 64) nx[m++] = lo[q] + ((c0 / 64 + 1) / 2) * 64;
+            }
+            nx[m] = cnt;
+            nnode[(level + 1) & 1] = m;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < cnt; i += PO_THREADS) src[base + i] = (int32_t)base + ord[i];
+}
+
+// pl_sub = sub read through the table, plane by plane (positions from s on stay zero)
+__global__ void __launch_bounds__(256)
+plane_gather_kernel(const double *__restrict__ sub, int64_t stride, int64_t s, const int32_t *__restrict__ src, double *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= s) return;
+    const int64_t j = src[i];
+#pragma unroll
+    for (int k = 0; k < 6; k++) out[k * stride + i] = sub[k * stride + j];
+}
+
+// the enabled words in plane order: a wave per word, lane = point, the bit of the point's leaf-order position, one ballot
+__global__ void __launch_bounds__(256)
+plane_enabled_kernel(const uint64_t *__restrict__ sub_enabled, int64_t s, int64_t swords, const int32_t *__restrict__ src,
+                     uint64_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bit = false;
+    if (i < s) {
+        const int64_t j = src[i];
+        bit = (sub_enabled[j >> 6] >> (j & 63)) & 1ULL;
+    }
+    const uint64_t w = __builtin_amdgcn_ballot_w64(bit);
+    if ((threadIdx.x & 63) == 0 && (i >> 6) < swords) out[i >> 6] = w;
+}
 
 // ---- findAABB (utilities.jl:125-136) of the uploaded cloud: per axis the smallest and the largest value that is not a NaN
 // (infinities count, like in the host loop this replaces), and the largest finite magnitude.  Doubles as ordered 64-bit
@@ -325,3 +451,80 @@ int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const in
     c->nrm_mag = __builtin_bit_cast(double, h_mags[1]);
     return RH_OK;
 }
+
+// The plane order of subset 1, once per cloud, behind the leaf order, the gather of c->sub and the groups' boxes: the table, the
+// plane-order copy of the points, then the binary32 boxes and normal-cell masks of its groups and super-tiles (rhk_plane_boxes).
+// Only for clouds the culled score kernel runs on; about 52 bytes per subset point.
+int rhk_plane_order_build(rh_cloud *c)
+{
+    if (!c->use_groups || c->s <= 0 || c->nst <= 0) return RH_OK;
+    if (c->s > (int64_t)0x7fffffff) { rh_set_error("rhk_plane_order_build: subset of %lld points", (long long)c->s); return RH_E_INVALID; }
+    // the blocks: the nodes of the position tree (its shape depends on the point count alone: rhk_kd_order) with <= PO_ST points
+    std::vector<int32_t> lo;
+    {
+        std::vector<KdNode> stack(1, KdNode{ 0, (int32_t)c->s });
+        while (!stack.empty()) {
+            const KdNode nd = stack.back();
+            stack.pop_back();
+            const int32_t cnt = nd.hi - nd.lo;
+            if (cnt <= PO_ST) { lo.push_back(nd.lo); continue; }
+            const int32_t nl = ((cnt / 64 + 1) / 2) * 64;
+            stack.push_back(KdNode{ nd.lo + nl, nd.hi });   // (the left child on top: the nodes come out in position order)
+            stack.push_back(KdNode{ nd.lo, nd.lo + nl });
+        }
+        lo.push_back((int32_t)c->s);
+    }
+    const int64_t nblk = (int64_t)lo.size() - 1;
+    rh_dev<int32_t> d_lo;   // (lives until rhk_plane_boxes has waited for the stream)
+    RH_TRY(d_lo.alloc((int64_t)lo.size()));
+    RH_HIP(hipMemcpyAsync(d_lo, lo.data(), sizeof(int32_t) * lo.size(), hipMemcpyHostToDevice, c->stream));
+    RH_TRY(c->pl_sub.alloc(6 * c->s_pad));
+    RH_TRY(c->pl_src.alloc(c->s_pad));
+    RH_TRY(c->pl_st32.alloc(8 * c->nst));
+    RH_TRY(c->pl_stm32.alloc(4 * c->nst));
+    RH_TRY(c->pl_gb32.alloc(8 * c->ng_pad));
+    RH_TRY(c->pl_gm32.alloc(4 * c->ng_pad));
+    RH_TRY(c->pl_enabled.alloc(c->swords));
+    RH_HIP(hipMemsetAsync(c->pl_sub, 0, sizeof(double) * 6 * (size_t)c->s_pad, c->stream));
+    RH_HIP(hipMemsetAsync(c->pl_src, 0, sizeof(int32_t) * (size_t)c->s_pad, c->stream));
+    hipLaunchKernelGGL(plane_order_kernel, dim3((unsigned)nblk), dim3(PO_THREADS), 0, c->stream, c->sub, c->s_pad, d_lo.get(), c->pl_src.get());
+    hipLaunchKernelGGL(plane_gather_kernel, dim3(cdivq(c->s, 256)), dim3(256), 0, c->stream, c->sub, c->s_pad, c->s, c->pl_src.get(), c->pl_sub.get());
+    RH_HIP(hipGetLastError());
+    return rhk_plane_boxes(c);
+}
+
+int rhk_plane_enabled_sync(rh_cloud *c)
+{
+    if (c->pl_enabled == nullptr || c->s <= 0) return RH_OK;
+    hipLaunchKernelGGL(plane_enabled_kernel, dim3(cdivq(c->swords * 64, 256)), dim3(256), 0, c->stream, c->sub_enabled, c->s, c->swords,
+                       c->pl_src.get(), c->pl_enabled.get());
+    RH_HIP(hipGetLastError());
+    return RH_OK;
+}
+
+#ifdef RH_DIAG
+// diagnostics (tests): the plane order as the cloud holds it, next to the leaf order it was made from (ransac_hip_diag.h)
+extern "C" int rh_dbg_plane_order(rh_cloud *c, int64_t *info_out, double *sub_out, double *pl_out, int32_t *src_out, float *gb32_out,
+                                  uint32_t *gm32_out, uint64_t *en_out)
+{
+    if (c == nullptr || info_out == nullptr) { rh_set_error("rh_dbg_plane_order: bad arguments"); return RH_E_INVALID; }
+    const bool has = c->pl_sub != nullptr;
+    info_out[0] = c->s; info_out[1] = c->ngroups; info_out[2] = c->nst; info_out[3] = has ? 1 : 0;
+    if (!has || c->s <= 0) return RH_OK;
+    RH_HIP(hipSetDevice(c->device));
+    const size_t s = (size_t)c->s;
+    for (int k = 0; k < 6; k++) {
+        if (sub_out != nullptr) RH_HIP(hipMemcpyAsync(sub_out + k * s, c->sub + k * c->s_pad, sizeof(double) * s, hipMemcpyDeviceToHost, c->stream));
+        if (pl_out != nullptr) RH_HIP(hipMemcpyAsync(pl_out + k * s, c->pl_sub + k * c->s_pad, sizeof(double) * s, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (src_out != nullptr) RH_HIP(hipMemcpyAsync(src_out, c->pl_src, sizeof(int32_t) * s, hipMemcpyDeviceToHost, c->stream));
+    if (gb32_out != nullptr) RH_HIP(hipMemcpyAsync(gb32_out, c->pl_gb32, sizeof(float) * 8 * (size_t)c->ngroups, hipMemcpyDeviceToHost, c->stream));
+    if (gm32_out != nullptr) RH_HIP(hipMemcpyAsync(gm32_out, c->pl_gm32, sizeof(uint32_t) * 4 * (size_t)c->ngroups, hipMemcpyDeviceToHost, c->stream));
+    if (en_out != nullptr) {
+        RH_HIP(hipMemcpyAsync(en_out, c->sub_enabled, sizeof(uint64_t) * (size_t)c->swords, hipMemcpyDeviceToHost, c->stream));
+        RH_HIP(hipMemcpyAsync(en_out + c->swords, c->pl_enabled, sizeof(uint64_t) * (size_t)c->swords, hipMemcpyDeviceToHost, c->stream));
+    }
+    RH_HIP(hipStreamSynchronize(c->stream));
+    return RH_OK;
+}
+#endif

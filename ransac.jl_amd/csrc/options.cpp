@@ -42,6 +42,7 @@ const OptDef kDefs[] = {
     RH_O(RH_OPT_BATCHES_IN_FLIGHT, "batches_in_flight", "RH_BATCHES_IN_FLIGHT", T_INT),
     RH_O(RH_OPT_ST_LIST_MB, "st_list_mb", "RH_ST_LIST_MB", T_INT),
     RH_O(RH_OPT_NSIG, "nsig", "RH_NSIG", T_INT),
+    RH_O(RH_OPT_PLANE_ORDER, "plane_order", "RH_PLANE_ORDER", T_INT),
 #ifdef RH_DIAG
     RH_O(RH_OPT_CREATE_PROF, "create_prof", "RH_CREATE_PROF", T_FLAG),
     RH_O(RH_OPT_AABB_HOST, "aabb_host", "RH_AABB_HOST", T_FLAG),
@@ -154,6 +155,7 @@ extern "C" int rh_set_option(rh_cloud *c, const char *key, int64_t value)
         case RH_OPT_BATCHES_IN_FLIGHT: ok = value >= 0 && value <= RH_MAX_IN_FLIGHT; break;
         case RH_OPT_ST_LIST_MB: ok = value >= 0 && value <= (1 << 20); break;
         case RH_OPT_NSIG: ok = value == 0 || value == 2; break;
+        case RH_OPT_PLANE_ORDER: ok = value >= 0 && value <= 2; break;
         default: break;
         }
         if (!ok) { rh_set_error("rh_set_option: value %lld is not valid for '%s'", (long long)value, key); return RH_E_INVALID; }

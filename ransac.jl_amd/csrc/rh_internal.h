@@ -41,6 +41,7 @@ enum rh_opt_id {
     RH_OPT_BATCHES_IN_FLIGHT,
     RH_OPT_ST_LIST_MB,
     RH_OPT_NSIG,
+    RH_OPT_PLANE_ORDER,
     RH_OPT_N_PRODUCT,
     // A/B switches and diagnostics: alive in the diag build only (in the product build they read as unset)
     RH_OPT_CREATE_PROF = RH_OPT_N_PRODUCT, RH_OPT_AABB_HOST, RH_OPT_SUB_ORDER, RH_OPT_KD_HOST, RH_OPT_NO_SPREAD, RH_OPT_OCT_CHAIN_W,
@@ -295,6 +296,17 @@ struct rh_cloud {
     rh_dev<uint32_t> gm32;             // normal-cell masks of the groups (score4_device.h, nsig_cell): 96 bits in 4 words each, over ALL points of the group -- never rebuilt
     rh_dev<uint32_t> stm32;            // ... of the super-tiles: the OR of their 16 groups' masks, 4 words each
     double nrm_len = 0;                // largest finite normal length over the subset (0: not known), made with the masks
+    // The plane order (kdorder.hip): a second internal order of subset 1 that the plane segments of
+    // counts-only score launches walk -- inside every node of the position tree with at most 1024 points the same points,
+    // ordered by a k-d tree on their NORMALS down to 64-point groups.  Null: the cloud has none (no culled path), planes walk
+    // the leaf order.
+    rh_dev<double> pl_sub;             // 6 planes x s_pad: subset 1 in plane order
+    rh_dev<int32_t> pl_src;            // [s_pad] plane-order position i holds the point of leaf-order position pl_src[i]
+    rh_dev<float> pl_gb32;             // binary32 boxes of the plane-order groups, 8 floats each (like gb32)
+    rh_dev<uint32_t> pl_gm32;          // normal-cell masks of the plane-order groups, 4 words each (like gm32)
+    rh_dev<float> pl_st32;             // boxes of the plane order's super-tiles (16 consecutive groups of ITS order: what the plane lists are cut by), like st32
+    rh_dev<uint32_t> pl_stm32;         // ... and their normal-cell masks, like stm32
+    rh_dev<uint64_t> pl_enabled;       // [swords] sub_enabled gathered into plane order: rewritten behind every change of sub_enabled, on its stream
     rh_dev<double> dis_gb;             // boxes of the dis segment in use (7 x ng_pad)
 
     // The enabled bits and what follows them: `en` says which derived structure matches the bits (enabled_state.h, DESIGN.md
@@ -481,6 +493,9 @@ int rhk_store_cls(rh_cloud *c, const rh_prep *const prep[4], const int32_t n[4],
 int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, rh_score_job job);   // the same over dis[first, first + cnt): fills in job.points
 int rhk_cloud_aabb(rh_cloud *c, const double *d_xyz, int64_t n, double lo[3], double hi[3], bool has[3], double *mag);   // kdorder.hip
 int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const int32_t *d_idx0);   // kdorder.hip: subset 1's k-d leaf order on the device
+int rhk_plane_order_build(rh_cloud *c);     // kdorder.hip: the plane order of subset 1 from c->sub (pl_sub, pl_src, then rhk_plane_boxes)
+int rhk_plane_enabled_sync(rh_cloud *c);    // kdorder.hip: pl_enabled from sub_enabled, on the cloud's stream (no plane order: nothing)
+int rhk_plane_boxes(rh_cloud *c);           // score4.hip: pl_gb32 / pl_gm32 / pl_st32 / pl_stm32 from pl_sub
 int rhk_score_kind_dis(rh_cloud *c, int kind, int64_t first, int64_t cnt, const rh_prep *d_prep, const int32_t *d_orig,
                        const int32_t *d_nk, int32_t nk_bound, double eps, double cosa, int32_t *d_counts);
 int rhk_group_bounds(rh_cloud *c);

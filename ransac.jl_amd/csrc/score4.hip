@@ -88,6 +88,13 @@ struct S4KindArgs {
     const int32_t *orig, *nk;
     const uint64_t *en;
     double eps, cosa;
+    // the kind's point set (planes may walk the cloud's plane order while the other kinds walk the k-d leaf order: same
+    // points tile by super-tile, another grouping): six planes `stride` apart, the groups' binary32 boxes (8 floats each) and
+    // their normal-cell masks (4 words each; null: no pair is ruled out by its normals); `en` is in the set's order
+    const double *pts;
+    int64_t stride;
+    const float *gb32;
+    const uint32_t *gm32;
 };
 struct S4AllArgs {
     const int32_t *stop;   // chained octree windows: non-zero = the window has ended, nothing to score (else null)
@@ -95,8 +102,6 @@ struct S4AllArgs {
     int rows;              // sized launch: > 0 = a one-dimensional grid of (tiles padded to 8) x rows blocks in XCD order (score4_kernel)
     S4KindArgs k[4];
     int64_t ntiles, bstride, ngroups;
-    const float *gb32;      // binary32 boxes of the groups, 8 floats each
-    const uint32_t *gm32;   // normal-cell masks of the groups, 4 words each (score4_device.h); null: no pair is ruled out by its normals
     // masks wanted: per candidate (as the caller numbers it) a LIST of its non-zero inlier words in internal (k-d leaf)
     // order -- entries of 16 bytes (word number, word), mstride of them per row at most; occ = one int32 cursor per row
     // (zero on entry)
@@ -510,7 +515,7 @@ template <int R, bool MASK, bool F32, bool TAIL = false, bool LIST = false>
 #define RH_S4_MINBLK 7
 #endif
 __global__ void __launch_bounds__(64 * S4_W, (F32 && !(LIST && R == 16)) ? 8 : RH_S4_MINBLK)   // (the Float32 instantiations: 8 / 64 registers, 0.0916 -> see experiments.txt; LIST rows of 16: 20.8 KB of LDS, seven blocks)
-score4_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const S4AllArgs A, int32_t *__restrict__ counts, int dbg_arg)
+score4_kernel(int64_t s, const S4AllArgs A, int32_t *__restrict__ counts, int dbg_arg)
 {
 #ifdef RH_DIAG
     const int dbg = dbg_arg;   // diag build: 1 = no pair survives stage 1 (the skeleton alone), 2 = every pair does
@@ -542,15 +547,18 @@ score4_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const S
     bool ran = false, weird = false;
     unsigned live = 0;
     const uint64_t *staged_en = nullptr;
+    const double *staged_pts = nullptr;
     (void)staged_en;
+    (void)staged_pts;
 #define RH_S4_BODY(K)                                                                                                  \
     {                                                                                                                  \
         const int slo = max(lo, base) - base, shi = min(hi, base + nch[K]) - base;                                     \
         if (slo < shi) {                                                                                               \
             if (ran) __syncthreads();   /* the previous segment's waves are done with the tile and the list */        \
-            if (!ran || A.k[K].en != staged_en) {                                                                      \
-                s4_stage(sh, pts, stride, s, A.k[K].en, g0 * 64, A.gb32, A.gm32, A.ngroups);                                   \
+            if (!ran || A.k[K].en != staged_en || A.k[K].pts != staged_pts) {   /* (another point set: its own boxes and masks too) */ \
+                s4_stage(sh, A.k[K].pts, A.k[K].stride, s, A.k[K].en, g0 * 64, A.k[K].gb32, A.k[K].gm32, A.ngroups);   \
                 staged_en = A.k[K].en;                                                                                 \
+                staged_pts = A.k[K].pts;                                                                               \
                 S4_STAT(A.stats, 96 + 1, 1);                                                                           \
             } else { S4_STAT(A.stats, 96 + 2, 1); if (threadIdx.x == 0) { sh.npairs = 0; sh.next_batch = 0; } }   /* same tile, same enabled words */   \
             __syncthreads();                                                                                           \
@@ -558,7 +566,7 @@ score4_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const S
             for (int g = 0; g < S4_TG; g++) live |= sh.len[g] != 0 ? (1u << g) : 0u;                                   \
             live = __builtin_amdgcn_readfirstlane(live);                                                               \
             { int ww = 0; for (int g = 0; g < S4_TG; g++) ww |= sh.weirdw[g]; weird = __builtin_amdgcn_readfirstlane(ww) != 0; }  \
-            if (live != 0) score4_segment<K, R, MASK, F32, LIST>(sh, A.k[K], LIST ? A.stcount + (st4 + K) : A.k[K].nk, LIST ? A.stlist + (st4 + K) * A.stcap : nullptr, A.bstride, slo, shi, pts, stride, g0, live, weird, counts, dbg, A.masks, A.occ, A.mstride, A.stats); \
+            if (live != 0) score4_segment<K, R, MASK, F32, LIST>(sh, A.k[K], LIST ? A.stcount + (st4 + K) : A.k[K].nk, LIST ? A.stlist + (st4 + K) * A.stcap : nullptr, A.bstride, slo, shi, A.k[K].pts, A.k[K].stride, g0, live, weird, counts, dbg, A.masks, A.occ, A.mstride, A.stats); \
             else S4_STAT(A.stats, 96 + 3, 1);                                                                         \
             ran = true;                                                                                                \
         }                                                                                                              \
@@ -765,7 +773,7 @@ static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4S
 
 __global__ void __launch_bounds__(64)
 cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const float *__restrict__ gb32, const float *__restrict__ st32, const float *__restrict__ tile32, const uint32_t *__restrict__ gm32, const uint32_t *__restrict__ stm32, const S4SoundCand *__restrict__ cands,
-                 int ncand, const S4SoundArgs A, unsigned long long *__restrict__ out)
+                 int ncand, const S4SoundArgs A, const int kinds, unsigned long long *__restrict__ out)   // kinds: bit k = candidates of kind k count
 {
     const int lane = threadIdx.x;
     const int64_t g = blockIdx.x;
@@ -790,6 +798,7 @@ cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, cons
     const rh_u32x4 gm = ((const rh_u32x4 *)gm32)[g], sm = ((const rh_u32x4 *)stm32)[g / S4_STG];
     for (int c = blockIdx.y; c < ncand; c += gridDim.y) {
         const S4SoundCand &Q = cands[c];
+        if (Q.kind < 0 || Q.kind > 3 || !((kinds >> Q.kind) & 1)) continue;
         switch (Q.kind) {
         case RH_PLANE: sound_one<RH_PLANE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
         case RH_SPHERE: sound_one<RH_SPHERE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
@@ -1035,8 +1044,8 @@ struct StCullArgs {
     const float *box[4];
     const int32_t *nk[4];
     int64_t bstride, stcap;
-    const float *st32;
-    const uint32_t *stm32;   // normal-cell masks of the super-tiles (the OR of their groups'), 4 words each; null: not looked at
+    const float *st32, *st32_plane;   // boxes of the super-tiles of the order the kind walks (planes: maybe the plane order's)
+    const uint32_t *stm32;   // normal-cell masks of the planes' super-tiles (the OR of their groups'), 4 words each; null: not looked at
     uint16_t *stlist;
     int32_t *stcount;
 };
@@ -1052,7 +1061,7 @@ static __device__ __forceinline__ void st_cull_kind(const StCullArgs &A, const i
     if (nk <= 0) { if (tid == 0) *cnt = 0; return; }
     rh_box32 G;
     {
-        const float *b = A.st32 + st * 8;
+        const float *b = (KIND == RH_PLANE ? A.st32_plane : A.st32) + st * 8;
         G.cx = b[0]; G.cy = b[1]; G.cz = b[2]; G.hx = b[3]; G.hy = b[4]; G.hz = b[5]; G.hr = b[6];
     }
     rh_u32x4 GM = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u };
@@ -1135,6 +1144,48 @@ int rhk_gb32_build(rh_cloud *c)
     return RH_OK;
 }
 
+// the same for the plane order (kdorder.hip): boxes and normal-cell masks of the 64-point groups of c->pl_sub and of its
+// super-tiles, by the kernels that make the leaf order's.  Once per cloud; waits for the stream (the binary64 boxes are a
+// temporary of the call).
+int rhk_plane_boxes(rh_cloud *c)
+{
+    if (c->pl_sub == nullptr || c->ngroups == 0) return RH_OK;
+    rh_dev<double> gb;
+    rh_dev<unsigned long long> d_len;
+    RH_TRY(gb.alloc(7 * c->ng_pad));
+    RH_TRY(d_len.alloc(1));
+    RH_HIP(hipMemsetAsync(gb, 0, sizeof(double) * 7 * (size_t)c->ng_pad, c->stream));
+    RH_HIP(hipMemsetAsync(d_len, 0, sizeof(unsigned long long), c->stream));
+    RH_HIP(hipMemsetAsync(c->pl_gb32, 0, sizeof(float) * 8 * (size_t)c->ng_pad, c->stream));
+    RH_HIP(hipMemsetAsync(c->pl_gm32, 0, sizeof(uint32_t) * 4 * (size_t)c->ng_pad, c->stream));
+    RH_TRY(rhk_group_bounds_of(c, c->pl_sub, c->s_pad, c->s, c->ngroups, gb, c->ng_pad));
+    hipLaunchKernelGGL(gb32_kernel, dim3(cdiv4(c->ngroups, 256)), dim3(256), 0, c->stream, gb, c->ng_pad, c->ngroups, c->pl_gb32);
+    hipLaunchKernelGGL(nsig_kernel, dim3(cdiv4(c->ngroups, 4)), dim3(256), 0, c->stream, c->pl_sub, c->s_pad, c->s, c->ngroups, c->pl_gm32, d_len);
+    // (16 consecutive groups of the plane order are another point set than 16 of the leaf order: boxes and masks of their own)
+    hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->nst, 64)), dim3(64), 0, c->stream, gb, c->ng_pad, c->ngroups, S4_STG, c->nst, c->pl_st32);
+    hipLaunchKernelGGL(nsig_st_kernel, dim3(cdiv4(c->nst, 64)), dim3(64), 0, c->stream, c->pl_gm32, c->ngroups, S4_STG, c->nst, c->pl_stm32);
+    RH_HIP(hipGetLastError());
+    RH_HIP(hipStreamSynchronize(c->stream));
+    return RH_OK;
+}
+
+// "plane_order" (read on every launch; 0 = by size, 1 = whenever the cloud has the order, 2 = never): do plane candidates walk
+// the plane order of subset 1?  By size: from RH_PLANE_ORDER_MIN_TILES tiles on.  The order removes plane pairs -- vector
+// instructions -- and pays where the launch is bound by their issue, not where a small grid's time is set by its heaviest block
+// and by launch latency (and a row with cylinders and planes stages its tile twice).  Measured (profiles/r13/experiments.txt,
+// section 7; three batches in flight, the order forced on against forced off in one process): cfg2's 123 tiles +0.2 % (inside the
+// sweep's range), cfg3's mix on 305 tiles -3.4 %, on 610 tiles -4.8 %, cfg3's 1221 tiles -3.5 %, cfg5's 6104 -2.6 %.  The rule sits
+// between the largest size without a gain and the smallest with one.
+#ifndef RH_PLANE_ORDER_MIN_TILES
+#define RH_PLANE_ORDER_MIN_TILES 256
+#endif
+static bool plane_order_wanted(const rh_cloud *c)
+{
+    if (c->pl_sub == nullptr) return false;
+    const int64_t opt = rh_opt_int(c, RH_OPT_PLANE_ORDER, 0);
+    return opt == 1 || (opt == 0 && (c->ngroups + S4_TG - 1) / S4_TG >= RH_PLANE_ORDER_MIN_TILES);
+}
+
 // the super-tile lists of the workspace's batch: [nst][4][cap] bin slots + [nst][4] counts
 static inline int64_t stlist_bytes(const rh_cloud *c, int64_t cap) { return (int64_t)sizeof(uint16_t) * c->nst * 4 * cap; }
 static int ensure_stlists(rh_cloud *c, rh_batch_ws &w, int64_t cap)
@@ -1169,18 +1220,33 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
         return RH_E_INTERNAL;
     }
     const int dbg = (int)rh_opt_int(c, RH_OPT_G2_DBG, 0);   // (diag build only -- 1: no pair survives stage 1, the skeleton alone: tools/region_counters.sh)
+    // "nsig" (read on every launch; 0 = on, 2 = off): plane pairs are also ruled out by the groups' normal-cell masks -- on subset 1,
+    // whose masks the cloud holds; any other point set is walked by its boxes alone.  Counts and masks do not depend on it.
+    const bool nsig_on = on_subset && c->gm32 != nullptr && rh_opt_int(c, RH_OPT_NSIG, 0) != 2;
     S4AllArgs A;
     for (int k = 0; k < 4; k++)
-        A.k[k] = { (const rh_cls *)B.cls[k], B.box[k], B.prep[k], B.orig[k], job.nk[k], job.en[k], job.eps[k], job.cosa[k] };
+        A.k[k] = { (const rh_cls *)B.cls[k], B.box[k], B.prep[k], B.orig[k], job.nk[k], job.en[k], job.eps[k], job.cosa[k],
+                   PS.pts, PS.stride, PS.gb32, nsig_on ? (const uint32_t *)c->gm32 : nullptr };
+    // "plane_order" (plane_order_wanted: by size, always, never): the plane candidates of a counts-only launch on subset 1 walk the
+    // cloud's plane order (kdorder.hip) -- the same points, inside every node of the position tree with at most 1024 points
+    // grouped by their normals, so that a group's normal-cell mask holds 8 cells instead of 18 (cfg3) and a third fewer (plane,
+    // group) pairs survive stage 1.  The culling rules are sound for ANY grouping of the points and a count is a sum over
+    // points: the counts are the same, bit for bit.  The plane lists of the launch (st_cull_kernel) are cut by the boxes and
+    // masks of the plane order's own super-tiles.  Mask launches keep the leaf order (their inlier words are numbered by it),
+    // and so do the diag build's skeleton modes.  The enabled words: the cloud's plane-order twin of sub_enabled, or none.
+    const bool plane_on = on_subset && d_masks_int == nullptr && dbg == 0 && plane_order_wanted(c) &&
+                          (job.en[RH_PLANE] == nullptr || job.en[RH_PLANE] == c->sub_enabled.get());
+    if (plane_on) {
+        S4KindArgs &P = A.k[RH_PLANE];
+        P.pts = c->pl_sub;
+        P.gb32 = c->pl_gb32;
+        if (nsig_on) P.gm32 = c->pl_gm32;
+        if (P.en != nullptr) P.en = c->pl_enabled;
+    }
     A.stop = job.stop;
     A.ntiles = ntiles;
     A.bstride = job.bstride;
     A.ngroups = PS.ngroups;
-    A.gb32 = PS.gb32;
-    // "nsig" (read on every launch; 0 = on, 2 = off): plane pairs are also ruled out by the groups' normal-cell masks -- on subset 1,
-    // whose masks the cloud holds; any other point set is walked by its boxes alone.  Counts and masks do not depend on it.
-    const bool nsig_on = on_subset && c->gm32 != nullptr && rh_opt_int(c, RH_OPT_NSIG, 0) != 2;
-    A.gm32 = nsig_on ? (const uint32_t *)c->gm32 : nullptr;
     A.masks = d_masks_int;
     A.occ = d_masks_int ? w.d_occ : nullptr;
     A.mstride = d_masks_int ? w.mstride4 : 0;
@@ -1229,7 +1295,8 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
     if (use_lists) {
         StCullArgs SA;
         for (int k = 0; k < 4; k++) { SA.box[k] = B.box[k]; SA.nk[k] = job.nk[k]; }
-        SA.bstride = job.bstride; SA.stcap = w.stlist_cap; SA.st32 = c->st32; SA.stm32 = nsig_on && c->stm32 != nullptr ? (const uint32_t *)c->stm32 : nullptr; SA.stlist = w.d_stlist; SA.stcount = w.d_stcount;
+        SA.bstride = job.bstride; SA.stcap = w.stlist_cap; SA.st32 = c->st32; SA.st32_plane = plane_on ? c->pl_st32 : c->st32;
+        SA.stm32 = nsig_on && c->stm32 != nullptr ? (const uint32_t *)(plane_on ? c->pl_stm32 : c->stm32) : nullptr; SA.stlist = w.d_stlist; SA.stcount = w.d_stcount;
         hipLaunchKernelGGL(st_cull_kernel, dim3((unsigned)c->nst, 4), dim3(256), 0, c->stream, SA);
         A.stlist = w.d_stlist; A.stcount = w.d_stcount; A.stcap = w.stlist_cap;
         if (job.ev_listed != nullptr) RH_HIP(hipEventRecord(job.ev_listed, c->stream));
@@ -1278,11 +1345,11 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
     auto launch_tail = [&](unsigned ny) {   // the TAIL instantiations (open-ended windows: R = 4 / 8, no masks) on a (tile, ny) grid
         const dim3 gt(tiles_x, ny);
         if (f32cloud) {
-            if (R == 4) hipLaunchKernelGGL((score4_kernel<4, false, true, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
-            else hipLaunchKernelGGL((score4_kernel<8, false, true, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
+            if (R == 4) hipLaunchKernelGGL((score4_kernel<4, false, true, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.s, A, d_counts, dbg);
+            else hipLaunchKernelGGL((score4_kernel<8, false, true, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.s, A, d_counts, dbg);
         } else {
-            if (R == 4) hipLaunchKernelGGL((score4_kernel<4, false, false, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
-            else hipLaunchKernelGGL((score4_kernel<8, false, false, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);
+            if (R == 4) hipLaunchKernelGGL((score4_kernel<4, false, false, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.s, A, d_counts, dbg);
+            else hipLaunchKernelGGL((score4_kernel<8, false, false, true>), gt, dim3(64 * S4_W), 0, c->stream, PS.s, A, d_counts, dbg);
         }
     };
     if (loop_max > 0 && d_masks_int == nullptr && nchunks <= loop_max) {
@@ -1292,8 +1359,8 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
     }
 #define RH_S4_LAUNCH(RR, MM, FF)                                                                                                              \
     do {                                                                                                                                      \
-        if (use_lists) hipLaunchKernelGGL((score4_kernel<RR, MM, FF, false, true>), grid, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg); \
-        else hipLaunchKernelGGL((score4_kernel<RR, MM, FF>), grid, dim3(64 * S4_W), 0, c->stream, PS.pts, PS.stride, PS.s, A, d_counts, dbg);  \
+        if (use_lists) hipLaunchKernelGGL((score4_kernel<RR, MM, FF, false, true>), grid, dim3(64 * S4_W), 0, c->stream, PS.s, A, d_counts, dbg); \
+        else hipLaunchKernelGGL((score4_kernel<RR, MM, FF>), grid, dim3(64 * S4_W), 0, c->stream, PS.s, A, d_counts, dbg);  \
     } while (0)
 #define RH_S4_LAUNCH_R(MM, FF)                                                                                         \
     do {                                                                                                               \
@@ -1436,8 +1503,25 @@ static int cls_soundness_run(rh_cloud *c, const rh_shape *shapes, int32_t b, con
     RH_TRY(d_o.alloc(72));
     RH_HIP(hipMemcpyAsync(d_c, h.data(), sizeof(S4SoundCand) * (size_t)b, hipMemcpyHostToDevice, c->stream));
     RH_HIP(hipMemsetAsync(d_o, 0, sizeof(unsigned long long) * 72, c->stream));
-    hipLaunchKernelGGL(cls_sound_kernel, dim3((unsigned)c->ngroups, (unsigned)std::min<int32_t>(b, 64)), dim3(64), 0, c->stream, c->sub, c->s_pad, c->s,
-                       c->gb32, c->st32, c->tile32, c->gm32, c->stm32, d_c, b, A, d_o);
+    // The census describes what the score kernel walks: with the plane order in use ("plane_order"), the plane candidates meet
+    // the plane-order groups -- their points, boxes and masks, those of the plane order's super-tiles, and the boxes of runs of
+    // S4_TG of them, made here -- and the other kinds the leaf order's.
+    const bool pl = plane_order_wanted(c);
+    const dim3 grid((unsigned)c->ngroups, (unsigned)std::min<int32_t>(b, 64));
+    hipLaunchKernelGGL(cls_sound_kernel, grid, dim3(64), 0, c->stream, c->sub, c->s_pad, c->s, c->gb32, c->st32, c->tile32, c->gm32, c->stm32, d_c, b, A,
+                       pl ? 0xe : 0xf, d_o);
+    rh_dev<double> pl_gb;
+    rh_dev<float> pl_tile32;
+    if (pl) {
+        RH_TRY(pl_gb.alloc(7 * c->ng_pad));
+        RH_TRY(pl_tile32.alloc(8 * std::max<int64_t>(1, c->ntile)));
+        RH_HIP(hipMemsetAsync(pl_gb, 0, sizeof(double) * 7 * (size_t)c->ng_pad, c->stream));
+        RH_TRY(rhk_group_bounds_of(c, c->pl_sub, c->s_pad, c->s, c->ngroups, pl_gb, c->ng_pad));
+        hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->ntile, 64)), dim3(64), 0, c->stream, pl_gb, c->ng_pad, c->ngroups, S4_TG, c->ntile, pl_tile32);
+        hipLaunchKernelGGL(cls_sound_kernel, grid, dim3(64), 0, c->stream, c->pl_sub, c->s_pad, c->s, c->pl_gb32, c->pl_st32, pl_tile32, c->pl_gm32, c->pl_stm32, d_c,
+                           b, A, 0x1, d_o);
+    }
+    RH_HIP(hipGetLastError());
     unsigned long long ho[72];
     RH_HIP(hipMemcpyAsync(ho, d_o, sizeof ho, hipMemcpyDeviceToHost, c->stream));
     RH_HIP(hipStreamSynchronize(c->stream));
