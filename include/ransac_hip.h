@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 122
+#define RH_VERSION 123
 
 enum {
     RH_OK = 0,
@@ -961,6 +961,13 @@ int rh_register_f32(const float *ref_xyz_aos, const float *ref_nrm_aos_or_null, 
  *                 1024 points the same points, ordered by a k-d tree on their normals, so that a group's normal-cell mask
  *                 holds fewer cells and fewer (plane, group) pairs survive (made once when the cloud is created; about 52
  *                 bytes per subset point).  Counts do not depend on it; launches that write masks never take it.  Read on every launch.
+ *   "kd_align"    0 (default: by size, from 1000 tiles of 256 subset points on) / 1 (always) / 2 (never) -- the shape of the
+ *                 position k-d tree whose 64-point leaves are the internal order of subset 1: aligned, a node of more than
+ *                 1024 points gives its left child a multiple of 1024 points, so that the runs of 1024 consecutive points
+ *                 that "st_cull" keeps candidate lists for (and the nodes "plane_order" sorts inside) are nodes of the tree,
+ *                 with tighter boxes and shorter lists.  Results do not depend on it.  Read when a cloud is created and
+ *                 fixed for its life, like "score_path": process-wide only; setting it on a cloud is RH_E_INVALID, and a
+ *                 process-wide change leaves the clouds that exist as they are.
  *   "batches_in_flight"  1 (default) .. 4 -- with F > 1, rh_score_batch_dev calls take turns on the cloud's
  *                 stream and F - 1 more with workspaces of their own, so one batch's prepare + score launches start while
  *                 the previous batches' launches drain.  The caller keeps F count (and mask) buffers and gives call k of a

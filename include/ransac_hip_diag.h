@@ -49,9 +49,21 @@ int rh_dbg_nsig(const rh_shape *shape, const rh_params *p, double M, double Nm, 
 /* The binary64 boxes of the 64-point groups of subset 1 in the library's own (k-d leaf) order: out[6 g ..] = centre and half
  * extents of group g; *ngroups_out: their number (out = NULL or cap < that number: only the number is returned). */
 int rh_dbg_group_boxes(rh_cloud *c, double *out, int64_t cap, int64_t *ngroups_out);
+/* The shape of the position k-d tree of a subset of s points (1 .. 2^31 - 1), as the library's one statement of it
+ * (kd_left_count, csrc/rh_internal.h) makes it for the device order, the host order and the plane order's blocks alike.
+ * aligned: 0 = a node of cnt > 64 points gives its left child ((cnt / 64 + 1) / 2) * 64 of them; 1 = a node of more than 1024
+ * points gives it ((ceil(cnt / 1024) + 1) / 2) * 1024 instead; -1 = what a cloud of s subset points created now would take
+ * (the process-wide "kd_align").  info_out[5]: the number of nodes of at most 1024 points (the first such node on every way
+ * down from [0, s)), of nodes of more than 1024 points, of leaves (nodes of at most 64 points; 0 unless leaves_out is given),
+ * the tree's height over its leaves (the levels the device order sorts), 1 if the shape is the aligned one.
+ * nodes_out [2 node_cap]: lo, hi of the nodes of at most 1024 points in position order; splits_out [3 split_cap]: lo, mid, hi of
+ * the larger nodes, parents first; leaves_out [2 leaf_cap]: lo, hi of the leaves in position order.  Each may be NULL; entries
+ * beyond a capacity are counted and not written.  Needs no GPU. */
+int rh_dbg_kd_shape(int64_t s, int aligned, int64_t *info_out /* [5] */, int64_t *nodes_out, int64_t node_cap, int64_t *splits_out,
+                    int64_t split_cap, int64_t *leaves_out, int64_t leaf_cap);
 /* The plane order of subset 1 (csrc/kdorder.hip: inside every node of the position k-d tree with at most 1024 points the same
  * points, ordered by a k-d tree on their normals; what plane candidates of counts-only score launches walk) as the cloud holds it.
- * The nodes: a node of cnt > 1024 points gives its left child ((cnt / 64 + 1) / 2) * 64 of them, from [0, s) down.
+ * The nodes: those of rh_dbg_kd_shape below, in the shape the cloud was created with ("kd_align").
  * info_out[4]: s, the number of 64-point groups, the number of super-tiles, 1 if the cloud has a plane order (else nothing more
  * is written).  Every other pointer may be NULL.  sub_out / pl_out [6 s]: the subset in leaf order / in plane order, planes
  * x y z nx ny nz, s apart; src_out [s]: plane-order position i holds the point of leaf-order position src_out[i];

@@ -288,6 +288,7 @@ DIAG_SIGNATURES = {
     "rh_dbg_cls_soundness_nsig": (C.c_int, [_vp, _sp, C.c_int32, _pp, C.POINTER(C.c_uint64)]),
     "rh_dbg_nsig": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint32), _dp, C.c_int64, _i32p]),
     "rh_dbg_group_boxes": (C.c_int, [_vp, _dp, C.c_int64, C.POINTER(C.c_int64)]),
+    "rh_dbg_kd_shape": (C.c_int, [C.c_int64, C.c_int, _i64p, _i64p, C.c_int64, _i64p, C.c_int64, _i64p, C.c_int64]),
     "rh_dbg_plane_order": (C.c_int, [_vp, _i64p, _dp, _dp, _i32p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), _u64p]),
     "rh_dbg_cylbox": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_int, _dp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),
     "rh_dbg_cls_round": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.POINTER(C.c_float), C.POINTER(C.c_float),

@@ -339,6 +339,8 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
         c->use_groups = s >= RH_G2_MIN_POINTS;
         if (e == RH_SCORE_PATH_BRUTE) c->use_groups = false;
         if (e == RH_SCORE_PATH_GROUPS) c->use_groups = s > 0;
+        // "kd_align", like the score path: the shape of the position tree of subset 1 is fixed here, for the life of the cloud
+        c->kd_aligned = kd_aligned_for(s, rh_opt_int(nullptr, RH_OPT_KD_ALIGN, 0));
     }
     CK(rhk_enabled_alloc(c));
     CK(c->refit_mask.alloc(c->nwords));
@@ -460,7 +462,7 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
                         const double e = bhi[k] - blo[k];
                         if (e > best) { best = e; ax = k; }
                     }
-                    const int64_t nl = ((cnt / 64 + 1) / 2) * 64;
+                    const int64_t nl = kd_left_count(cnt, c->kd_aligned);
                     std::nth_element(order.begin() + lo_i, order.begin() + lo_i + nl, order.begin() + hi_i,
                                      [&](int32_t a, int32_t b) {
                                          const double ka = key(a, ax), kb = key(b, ax);

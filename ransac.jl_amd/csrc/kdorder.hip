@@ -2,8 +2,8 @@
 // what gives the culled score kernel its compact groups (cloud.hip builds the same tree on host threads -- std::nth_element
 // recursion, 70 ms at 312 500 points, 300 ms at 1.56 M -- and keeps that form behind RH_KD_HOST=1 as the A/B).
 //
-// The tree's SHAPE depends on the point count alone (a node of cnt > 64 points gives its left child ((cnt / 64 + 1) / 2) * 64
-// of them), so the host lays the levels out and the device only orders: per level
+// The tree's SHAPE depends on the point count alone (a node of cnt > 64 points gives its left child kd_left_count(cnt, aligned)
+// of them: rh_internal.h), so the host lays the levels out and the device only orders: per level
 //   1. the bounding box of every node that still splits (finite coordinates only; wave-uniform fast path + atomics),
 //   2. a 64-bit key per position -- node number << 32 | the point's coordinate along the node's widest axis as an ordered
 //      32-bit pattern (binary32 of the coordinate: NaN last, like the host's comparator) -- positions of finished nodes
@@ -169,10 +169,31 @@ __global__ void kd_finish_kernel(const int32_t *__restrict__ ord, const int32_t 
 
 struct KdNode { int32_t lo, hi; };
 
+// The position tree of s points from [0, s) down (kd_left_count, rh_internal.h), depth first, the left child first: node(lo, hi, 0)
+// for every node of at most `most` points -- they come in position order and the walk does not descend below them --
+// node(lo, hi, mid) for every larger one, split at mid.
+template <class F>
+void kd_walk(int64_t s, bool aligned, int64_t most, F node)
+{
+    struct Range { int64_t lo, hi; };
+    std::vector<Range> stack(1, Range{ 0, s });
+    while (!stack.empty()) {
+        const Range nd = stack.back();
+        stack.pop_back();
+        const int64_t cnt = nd.hi - nd.lo;
+        if (cnt <= most) { node(nd.lo, nd.hi, (int64_t)0); continue; }
+        const int64_t mid = nd.lo + kd_left_count(cnt, aligned);
+        node(nd.lo, nd.hi, mid);
+        stack.push_back(Range{ mid, nd.hi });
+        stack.push_back(Range{ nd.lo, mid });
+    }
+}
+
 // ---- the plane order of subset 1 (score4.hip walks it with plane candidates).  The position tree is
-// stopped at its nodes of at most PO_ST = 1024 points (whole groups: every split is at a multiple of 64; 576 .. 640 points at
-// cfg3 -- NOT the runs of 1024 consecutive points that the candidate lists call super-tiles: those straddle the tree's nodes,
-// their points lie further apart, and cutting them by normals leaves boxes half as large again: tools/proto/plane_order_proto.py).
+// stopped at its nodes of at most PO_ST = 1024 points (whole groups: every split is at a multiple of 64).  With the tree's
+// aligned shape (kd_left_count, rh_internal.h: cfg3) those nodes ARE the runs of 1024 consecutive points that the candidate
+// lists call super-tiles; with today's shape they are not (576 .. 640 points at cfg3 then, and a run of 1024 straddles two or
+// three of them: cutting such a run by normals leaves boxes half as large again, tools/proto/plane_order_proto.py).
 // Inside every such node the SAME points, ordered by a k-d tree on their NORMALS: widest axis of the node's finite normals,
 // median split, the left child a multiple of 64 like the position tree's, down to 64-point groups (four levels).  A node is
 // small enough for one block: the normals in LDS, per level the nodes' boxes by atomics and one bitonic sort of 1024 keys
@@ -181,7 +202,7 @@ struct KdNode { int32_t lo, hi; };
 // component sorts last, an axis without a finite value is never the widest; where such a point lands is of no consequence
 // (every grouping of the points gives the same counts).  Positions behind the block's end take the last node number and keep
 // their place.
-constexpr int PO_ST = 1024;
+constexpr int PO_ST = (int)RH_KD_NODE;
 constexpr int PO_THREADS = 512;
 
 __global__ void __launch_bounds__(PO_THREADS)
@@ -256,7 +277,7 @@ plane_order_kernel(const double *__restrict__ sub, int64_t stride, const int32_t
             for (int q = 0; q < nn; q++) {
                 const int c0 = lo[q + 1] - lo[q];
                 nx[m++] = lo[q];
-                if (c0 > 64) nx[m++] = lo[q] + ((c0 / 64 + 1) / 2) * 64;
+                if (c0 > 64) nx[m++] = lo[q] + ((c0 / 64 + 1) / 2) * 64;   // (kd_left_count's rule for c0 <= 1024)
             }
             nx[m] = cnt;
             nnode[(level + 1) & 1] = m;
@@ -391,7 +412,7 @@ int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const in
             for (const KdNode &nd : cur) {
                 const int32_t cnt = nd.hi - nd.lo;
                 if (cnt <= 64) { nxt.push_back(nd); continue; }
-                const int32_t nl = ((cnt / 64 + 1) / 2) * 64;
+                const int32_t nl = (int32_t)kd_left_count(cnt, c->kd_aligned);
                 nxt.push_back(KdNode{ nd.lo, nd.lo + nl });
                 nxt.push_back(KdNode{ nd.lo + nl, nd.hi });
             }
@@ -461,19 +482,8 @@ int rhk_plane_order_build(rh_cloud *c)
     if (c->s > (int64_t)0x7fffffff) { rh_set_error("rhk_plane_order_build: subset of %lld points", (long long)c->s); return RH_E_INVALID; }
     // the blocks: the nodes of the position tree (its shape depends on the point count alone: rhk_kd_order) with <= PO_ST points
     std::vector<int32_t> lo;
-    {
-        std::vector<KdNode> stack(1, KdNode{ 0, (int32_t)c->s });
-        while (!stack.empty()) {
-            const KdNode nd = stack.back();
-            stack.pop_back();
-            const int32_t cnt = nd.hi - nd.lo;
-            if (cnt <= PO_ST) { lo.push_back(nd.lo); continue; }
-            const int32_t nl = ((cnt / 64 + 1) / 2) * 64;
-            stack.push_back(KdNode{ nd.lo + nl, nd.hi });   // (the left child on top: the nodes come out in position order)
-            stack.push_back(KdNode{ nd.lo, nd.lo + nl });
-        }
-        lo.push_back((int32_t)c->s);
-    }
+    kd_walk(c->s, c->kd_aligned, PO_ST, [&](int64_t a, int64_t, int64_t) { lo.push_back((int32_t)a); });
+    lo.push_back((int32_t)c->s);
     const int64_t nblk = (int64_t)lo.size() - 1;
     rh_dev<int32_t> d_lo;   // (lives until rhk_plane_boxes has waited for the stream)
     RH_TRY(d_lo.alloc((int64_t)lo.size()));
@@ -503,7 +513,44 @@ int rhk_plane_enabled_sync(rh_cloud *c)
 }
 
 #ifdef RH_DIAG
-// diagnostics (tests): the plane order as the cloud holds it, next to the leaf order it was made from (ransac_hip_diag.h)
+// diagnostics (tests): the shape of the position tree of s points as kd_left_count makes it (ransac_hip_diag.h); no GPU
+extern "C" int rh_dbg_kd_shape(int64_t s, int aligned, int64_t *info_out, int64_t *nodes_out, int64_t node_cap, int64_t *splits_out,
+                               int64_t split_cap, int64_t *leaves_out, int64_t leaf_cap)
+{
+    if (info_out == nullptr || s < 1 || s > (int64_t)0x7fffffff || aligned < -1 || aligned > 1) { rh_set_error("rh_dbg_kd_shape: bad arguments"); return RH_E_INVALID; }
+    const bool al = aligned < 0 ? kd_aligned_for(s, rh_opt_int(nullptr, RH_OPT_KD_ALIGN, 0)) : aligned != 0;
+    int64_t nn = 0, ns = 0, nl = 0;
+    kd_walk(s, al, RH_KD_NODE, [&](int64_t lo, int64_t hi, int64_t mid) {
+        if (mid == 0) {
+            if (nodes_out != nullptr && nn < node_cap) { nodes_out[2 * nn] = lo; nodes_out[2 * nn + 1] = hi; }
+            nn++;
+        } else {
+            if (splits_out != nullptr && ns < split_cap) { splits_out[3 * ns] = lo; splits_out[3 * ns + 1] = mid; splits_out[3 * ns + 2] = hi; }
+            ns++;
+        }
+    });
+    if (leaves_out != nullptr)
+        kd_walk(s, al, 64, [&](int64_t lo, int64_t hi, int64_t mid) {
+            if (mid != 0) return;
+            if (nl < leaf_cap) { leaves_out[2 * nl] = lo; leaves_out[2 * nl + 1] = hi; }
+            nl++;
+        });
+    // the levels rhk_kd_order would run: the tree's height over its 64-point leaves, by the distinct node sizes of every level
+    int64_t depth = 0;
+    for (std::vector<int64_t> cur(1, s); ; depth++) {
+        std::vector<int64_t> nxt;
+        for (int64_t cnt : cur)
+            if (cnt > 64) { const int64_t l = kd_left_count(cnt, al); nxt.push_back(l); nxt.push_back(cnt - l); }
+        if (nxt.empty()) break;
+        std::sort(nxt.begin(), nxt.end());
+        nxt.erase(std::unique(nxt.begin(), nxt.end()), nxt.end());
+        cur.swap(nxt);
+    }
+    info_out[0] = nn; info_out[1] = ns; info_out[2] = nl; info_out[3] = depth; info_out[4] = al ? 1 : 0;
+    return RH_OK;
+}
+
+// the plane order as the cloud holds it, next to the leaf order it was made from (ransac_hip_diag.h)
 extern "C" int rh_dbg_plane_order(rh_cloud *c, int64_t *info_out, double *sub_out, double *pl_out, int32_t *src_out, float *gb32_out,
                                   uint32_t *gm32_out, uint64_t *en_out)
 {

@@ -43,6 +43,7 @@ const OptDef kDefs[] = {
     RH_O(RH_OPT_ST_LIST_MB, "st_list_mb", "RH_ST_LIST_MB", T_INT),
     RH_O(RH_OPT_NSIG, "nsig", "RH_NSIG", T_INT),
     RH_O(RH_OPT_PLANE_ORDER, "plane_order", "RH_PLANE_ORDER", T_INT),
+    RH_O(RH_OPT_KD_ALIGN, "kd_align", "RH_KD_ALIGN", T_INT),
 #ifdef RH_DIAG
     RH_O(RH_OPT_CREATE_PROF, "create_prof", "RH_CREATE_PROF", T_FLAG),
     RH_O(RH_OPT_AABB_HOST, "aabb_host", "RH_AABB_HOST", T_FLAG),
@@ -156,12 +157,17 @@ extern "C" int rh_set_option(rh_cloud *c, const char *key, int64_t value)
         case RH_OPT_ST_LIST_MB: ok = value >= 0 && value <= (1 << 20); break;
         case RH_OPT_NSIG: ok = value == 0 || value == 2; break;
         case RH_OPT_PLANE_ORDER: ok = value >= 0 && value <= 2; break;
+        case RH_OPT_KD_ALIGN: ok = value >= 0 && value <= 2; break;
         default: break;
         }
         if (!ok) { rh_set_error("rh_set_option: value %lld is not valid for '%s'", (long long)value, key); return RH_E_INVALID; }
     }
     if (d->id == RH_OPT_SCORE_PATH && c != nullptr) {
         rh_set_error("rh_set_option: 'score_path' is fixed when a cloud is created (its point order depends on it): set it process-wide (cloud = NULL) before rh_cloud_create");
+        return RH_E_INVALID;
+    }
+    if (d->id == RH_OPT_KD_ALIGN && c != nullptr) {
+        rh_set_error("rh_set_option: 'kd_align' is fixed when a cloud is created (it shapes the cloud's internal point order): set it process-wide (cloud = NULL) before rh_cloud_create");
         return RH_E_INVALID;
     }
     if (c != nullptr) {

@@ -42,6 +42,7 @@ enum rh_opt_id {
     RH_OPT_ST_LIST_MB,
     RH_OPT_NSIG,
     RH_OPT_PLANE_ORDER,
+    RH_OPT_KD_ALIGN,
     RH_OPT_N_PRODUCT,
     // A/B switches and diagnostics: alive in the diag build only (in the product build they read as unset)
     RH_OPT_CREATE_PROF = RH_OPT_N_PRODUCT, RH_OPT_AABB_HOST, RH_OPT_SUB_ORDER, RH_OPT_KD_HOST, RH_OPT_NO_SPREAD, RH_OPT_OCT_CHAIN_W,
@@ -167,6 +168,28 @@ constexpr int RH_WORDS_PER_BLOCK = 1024;                 // scan granularity (64
 constexpr int RH_G2_TG = 4;                              // 64-point groups per LDS tile of the culled score kernel
 constexpr int RH_G2_TILE = RH_G2_TG * 64;
 constexpr int64_t RH_G2_MIN_POINTS = 8192;               // below this the brute-force kernel is used
+// ---- the shape of the position k-d tree of subset 1 (kdorder.hip, cloud.hip).  The shape depends on the
+// point count alone, and this is its one statement: the device order, the host order (RH_KD_HOST) and the plane order's
+// blocks all split a node of cnt > 64 points where kd_left_count says.
+//   today's rule: the left child gets half of the node's whole 64-point groups, rounded up: every split is at a multiple of
+//     64, only the last group of the subset is partial;
+//   aligned: a node of more than RH_KD_NODE = 1024 points gives its left child half of its 1024-point runs, rounded up, so
+//     every node of at most 1024 points is exactly [1024 k, min(s, 1024 (k + 1))): the runs of 16 groups that the candidate
+//     lists call super-tiles ARE tree nodes, and the plane order's blocks are the super-tiles.  Below 1024 points today's rule.
+// Both children are non-empty for every cnt > 64 (aligned, cnt > 1024: m = ceil(cnt / 1024) >= 2 and (m + 1) / 2 <= m - 1).
+constexpr int64_t RH_KD_NODE = 1024;
+constexpr int64_t RH_KD_ALIGN_MIN_TILES = 1000;          // "kd_align" by size: subsets of this many 256-point tiles and more (the size from which list launches are taken with batches in flight)
+static inline int64_t kd_left_count(int64_t cnt, bool aligned)
+{
+    if (aligned && cnt > RH_KD_NODE) return (((cnt + RH_KD_NODE - 1) / RH_KD_NODE + 1) / 2) * RH_KD_NODE;
+    return ((cnt / 64 + 1) / 2) * 64;
+}
+// "kd_align" (0 = by size, 1 = always, 2 = never) for a subset of s points
+static inline bool kd_aligned_for(int64_t s, int64_t opt)
+{
+    const int64_t tiles = ((s + 63) / 64 + RH_G2_TG - 1) / RH_G2_TG;
+    return opt == 1 || (opt == 0 && tiles >= RH_KD_ALIGN_MIN_TILES);
+}
 constexpr int64_t RH_KREFIT_MIN = 1 << 21;               // clouds from this size on take the culled refit scan (korder.hip): 1M points 17 us culled against 13 us streaming, 10M 24 against 80
 
 // ---- the cloud --------------------------------------------------------------
@@ -288,6 +311,7 @@ struct rh_cloud {
     double coord_mag = 0;              // max |coordinate| over the subset (rounding slack of the bounds)
     double nrm_mag = 0;                // max |normal component| over the subset (margins of the binary32 classifier)
     bool use_groups = false;           // culled scoring path available (s large enough)
+    bool kd_aligned = false;           // the position tree of subset 1 has the aligned shape (kd_left_count; "kd_align" when the cloud was created)
     rh_dev<float> gb32;                // the same boxes in binary32, 8 floats per group (v4 score kernel: scalar loads)
     rh_dev<float> st32;                // boxes of the super-tiles (16 consecutive groups = 4 tiles of the k-d leaf order), 8 floats each
     int64_t nst = 0;

@@ -5,7 +5,9 @@ hit them alike.  Prints the median and the spread of the per-burst step time (HI
 that every build returns the same counts.
     python tools/ab_inproc.py variants/base.so ransac.jl_amd/libransac_hip.so        WL=cfg2|cfg3|cfg5  ROUNDS=12  STEPS=50
     MASKS=1: the step with the inlier masks written;  OPTS="s4_rows=8,..." applied to every build (rh_set_option);
-    lib.so@batches_in_flight=2@...: options of that entry's cloud alone (the same library may be listed more than once)"""
+    lib.so@batches_in_flight=2@...: options of that entry's cloud alone (the same library may be listed more than once);
+    lib.so@+kd_align=1: an option that is read when a cloud is created -- set process-wide around that entry's rh_cloud_create;
+    rh_cloud_create_ms of every entry's cloud is printed too"""
 import ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -53,9 +55,19 @@ def main():
             k, v = kv.split("=")
             assert lib.rh_set_option(None, k.encode(), int(v)) == 0, kv
         h = C.c_void_p()
+        at_create = [kv[1:].split("=") for kv in own if kv.startswith("+")]
+        for k, v in at_create:
+            assert lib.rh_set_option(None, k.encode(), int(v)) == 0, (k, v)
         rc = lib.rh_cloud_create(xyz.ctypes.data_as(dp), nrm.ctypes.data_as(dp), n, sub1.ctypes.data_as(i64p), S, 0, C.byref(h))
         assert rc == 0, (p, lib.rh_last_error())
+        for k, v in at_create:
+            assert lib.rh_set_option(None, k.encode(), L.OPTION_UNSET) == 0, k
+        ms4 = (C.c_double * 4)()
+        assert lib.rh_cloud_create_ms(h, ms4) == 0
+        print("rh_cloud_create_ms %s: total %.2f  subset order %.2f  before %.2f  after %.2f" % ("@".join([os.path.basename(p)] + own), *ms4), flush=True)
         for kv in own:
+            if kv.startswith("+"):
+                continue
             k, v = kv.split("=")
             assert lib.rh_set_option(h, k.encode(), int(v)) == 0, kv
         d_sh, d_cn, d_mk = C.c_void_p(), C.c_void_p(), C.c_void_p()
