@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 123
+#define RH_VERSION 124
 
 enum {
     RH_OK = 0,
@@ -931,6 +931,102 @@ int rh_register(const double *ref_xyz_aos, const double *ref_nrm_aos_or_null, in
 int rh_register_f32(const float *ref_xyz_aos, const float *ref_nrm_aos_or_null, int64_t n, const float *qry_xyz_aos, int64_t m,
                     const rh_register_params *p, const double *init_3x4_or_null, int device, double *transform_out_3x4,
                     rh_register_result *result_or_null, int32_t *n_valid_it_out_or_null, double *rms_it_out_or_null);
+
+/* ---- global registration without a start: point descriptors, feature matching, RANSAC over correspondences (no
+ *      counterpart in the reference, which works on one cloud) ----
+ * rh_register needs a start within its basin; these three calls produce one for two clouds that differ by an arbitrary
+ * rigid motion.  Everything is integers or one fixed sequence of IEEE binary64 operations (+, -, *, /, sqrt, floor; no
+ * contraction), so host, device and a numpy restatement give the same bytes.  Below
+ *     dot(x, y) = (x_0*y_0 + x_1*y_1) + x_2*y_2,   cross(a, b) = (a_1*b_2 - a_2*b_1, a_2*b_0 - a_0*b_2, a_0*b_1 - a_1*b_0).
+ *
+ * rh_describe: D_i, RH_DESC_DIM = 33 uint16 per point, from the points, their normals (required, used as given, not
+ * renormalised), k in 1 .. RH_KNN_MAX_K and radius (0 = none).
+ *  1. N(i) and count_i are the neighbour list and count of rh_knn for (k, radius).
+ *  2. PAIR FEATURES of (i, j), j in N(i); i is always the source (the pair is not reordered by the normals' angles):
+ *         d = p_j - p_i componentwise,  d2 = dot(d, d),  u = n_i,  s = n_j,
+ *         v = cross(u, d),  v2 = dot(v, v),  w = cross(u, v),  len = sqrt(d2),  vl = sqrt(v2),
+ *         f1 = dot(u, d) / len,   f2 = dot(v, s) / vl,   a = dot(w, s) / vl,   b = dot(u, s),
+ *         g = |a| + |b|,   r = b / g,   psi = a >= 0 ? 1.0 - r : 3.0 + r.
+ *     psi is a rational pseudo-angle in [0, 4) of the direction (b, a): monotone in the angle, no atan2.  The pair is
+ *     DEGENERATE and adds nothing when d2 == 0, v2 == 0, g == 0, or one of f1, f2, psi is NaN.
+ *  3. BINS, decided in binary64: bin(x) = t < 0 ? 0 : (t > 10 ? 10 : t) with t = floor(x);
+ *         b1 = bin((f1 + 1.0)*5.5),   b2 = bin((f2 + 1.0)*5.5),   b3 = bin(psi*2.75).
+ *     S_i, 33 counts, gets +1 at b1, at 11 + b2 and at 22 + b3 for every pair of i that is not degenerate.
+ *  4. D_i[c] = count_i*S_i[c] + the sum over j in N(i) of S_j[c]: integers, at most 2*63*63 = RH_DESC_MAX, so the order of
+ *     the sum does not show.
+ * In exact arithmetic D is invariant under a rigid motion of points and normals together; in floating point a value on
+ * a bin edge can move to the next bin.  desc_out: uint16 [n x 33]; count_out (optional): int32 [n], count_i.
+ * The _f32 entry widens coordinates and normals exactly.  The same bytes on every run.  RH_E_INVALID, before the device
+ * is touched: a null xyz / normals / desc_out, k outside 1 .. 63, radius negative or not finite, n < 1,
+ * n > (2^31 - 1) / 33; on the device: a coordinate or a normal that is not finite (nothing is written).
+ *
+ * rh_match_features: for every query row the reference row of smallest sum over c of (q_c - r_c)^2 -- an exact integer,
+ * at most 33 * 7938^2 < 2^31 -- ties to the smaller index.  idx_out: int32 [m], 1-based; dist_out (optional): uint32 [m],
+ * that sum.  flags = RH_MATCH_MUTUAL: the same search runs from the reference side (for every reference row its best
+ * query row, ties to the smaller index) and idx_out[j] = 0 where the best query of reference row idx_out[j] is not j;
+ * dist_out is not changed by it.  RH_E_INVALID, before the device is touched: a null ref / qry / idx_out, unknown flags,
+ * n or m outside 1 .. (2^31 - 1) / 80; on the device: a descriptor value above RH_DESC_MAX (nothing is written).
+ *
+ * rh_register_global: the motion x' = R x + t of the queries onto the reference that most of the c correspondences
+ * (q_corr_qry[i], r_corr_ref[i]), 1-based int32 indices, agree with; trials hypotheses from three correspondences each.
+ *  1. TRIPLES.  triples (int32 [trials x 3], 0-based into the correspondences) when given; otherwise rh_rng_seed(seed) and
+ *     trial t = 0, 1, .. takes three draws rh_rng_range(c) - 1 in order -- always three, whatever they are.
+ *  2. A trial (i0, i1, i2) is VALID when all of these hold:
+ *       the three indices are distinct;
+ *       for each edge (x, y) = (0, 1), (0, 2), (1, 2), with lq = dot(q_x - q_y, q_x - q_y) and lr likewise of r, ee =
+ *       edge_ratio*edge_ratio and mm = min_edge*min_edge:  lq >= ee*lr,  lr >= ee*lq,  lq >= mm;
+ *       the frames of (q_0, q_1, q_2) and of (r_0, r_1, r_2) exist.
+ *  3. FRAME of (x0, x1, x2):  h = x1 - x0,  hh = dot(h, h),  e1 = h / sqrt(hh) componentwise,  gv = cross(e1, x2 - x0),
+ *     g2 = dot(gv, gv); the frame exists when hh > 0 and g2 > 0;  e3 = gv / sqrt(g2),  e2 = cross(e3, e1).
+ *     F is the matrix with columns e1, e2, e3: F_k0 = e1_k, F_k1 = e2_k, F_k2 = e3_k.
+ *  4. TRANSFORM:  R_kl = (Fr_k0*Fq_l0 + Fr_k1*Fq_l1) + Fr_k2*Fq_l2;
+ *         cq = ((q_0 + q_1) + q_2) / 3.0 componentwise, cr likewise;
+ *         t_k = cr_k - ((R_k0*cq_0 + R_k1*cq_1) + R_k2*cq_2).
+ *  5. COUNT of a valid trial: the correspondences i with dot(z, z) <= tau*tau, where for q = q_corr_qry[i], r = r_corr_ref[i]
+ *         z_k = (((R_k0*q_0 + R_k1*q_1) + R_k2*q_2) + t_k) - r_k.
+ *     A trial that is not valid has count -1.
+ *  6. BEST: the largest count, ties to the smaller trial.
+ * transform_out: 3x4 row-major [R | t] of the best trial; the identity when no trial is valid.  result (optional): status
+ * RH_GLOB_OK or RH_GLOB_NO_TRIAL, best_trial (0-based) and best_count (both -1 with RH_GLOB_NO_TRIAL), n_valid_trials.
+ * counts_out (optional): int32 [trials].  The function returns RH_OK with either status.  The _f32 entry widens the
+ * coordinates exactly.  The array arguments of the three calls may be host or device pointers (hipMemcpyDefault); params,
+ * transform_out and result are host memory.  The same bytes on every run.
+ * RH_E_INVALID, before the device is touched: a null ref / qry / corr / params / transform_out, n or m outside the limits
+ * of rh_knn_query, c < 3 or c > (2^31 - 1) / 6, trials outside 1 .. RH_GLOBAL_MAX_TRIALS, tau not positive or not finite,
+ * edge_ratio outside (0, 1], min_edge negative or not finite; a given triple outside 0 .. c - 1; on the device: a
+ * coordinate that is not finite, a correspondence outside 1 .. m / 1 .. n (nothing is written). */
+#define RH_DESC_DIM 33
+#define RH_DESC_MAX 7938
+#define RH_MATCH_MUTUAL 1
+#define RH_GLOBAL_MAX_TRIALS (1 << 20)
+enum { RH_GLOB_OK = 0, RH_GLOB_NO_TRIAL = 1 };
+typedef struct {
+    int32_t trials;          /* 1 .. RH_GLOBAL_MAX_TRIALS */
+    int32_t reserved;
+    uint64_t seed;           /* of the draws; not read when triples are given */
+    double tau;              /* > 0: a correspondence agrees when its residual is at most tau */
+    double edge_ratio;       /* 0 < e <= 1: the shorter of a pair of edges is at least e times the longer */
+    double min_edge;         /* >= 0: every query edge of a triple is at least this long */
+} rh_global_params;
+typedef struct {
+    int32_t status;          /* RH_GLOB_* */
+    int32_t best_trial;      /* 0-based; -1: none */
+    int32_t best_count;
+    int32_t n_valid_trials;
+} rh_global_result;
+int rh_describe(const double *xyz_aos, const double *nrm_aos, int64_t n, int32_t k, double radius, int device,
+                uint16_t *desc_out, int32_t *count_out_or_null);
+int rh_describe_f32(const float *xyz_aos, const float *nrm_aos, int64_t n, int32_t k, double radius, int device,
+                    uint16_t *desc_out, int32_t *count_out_or_null);
+int rh_match_features(const uint16_t *ref_desc, int64_t n, const uint16_t *qry_desc, int64_t m, int32_t flags, int device,
+                      int32_t *idx_out, uint32_t *dist_out_or_null);
+int rh_register_global(const double *ref_xyz_aos, int64_t n, const double *qry_xyz_aos, int64_t m, const int32_t *corr_qry,
+                       const int32_t *corr_ref, int64_t c, const rh_global_params *p, const int32_t *triples_or_null, int device,
+                       double *transform_out_3x4, rh_global_result *result_or_null, int32_t *counts_out_or_null);
+int rh_register_global_f32(const float *ref_xyz_aos, int64_t n, const float *qry_xyz_aos, int64_t m, const int32_t *corr_qry,
+                           const int32_t *corr_ref, int64_t c, const rh_global_params *p, const int32_t *triples_or_null,
+                           int device, double *transform_out_3x4, rh_global_result *result_or_null,
+                           int32_t *counts_out_or_null);
 
 /* ---- tuning options ----
  * The library reads NO environment variable: what a caller may tune goes through this call, for one cloud or, with

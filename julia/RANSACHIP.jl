@@ -899,6 +899,116 @@ function register(reference::AbstractVector{SVector{3,T}}, queries::AbstractVect
                 n_valid_it = nv[1:it], rms_it = rms[1:it])
 end
 
+# ---- global registration without a start (rh_describe, rh_match_features, rh_register_global) ----
+const DESC_DIM = 33
+# typedef struct { int32_t trials, reserved; uint64_t seed; double tau, edge_ratio, min_edge; } rh_global_params;   (40 bytes)
+struct RhGlobalParams
+    trials::Cint
+    reserved::Cint
+    seed::UInt64
+    tau::Cdouble
+    edge_ratio::Cdouble
+    min_edge::Cdouble
+end
+# typedef struct { int32_t status, best_trial, best_count, n_valid_trials; } rh_global_result;   (16 bytes)
+struct RhGlobalResult
+    status::Cint
+    best_trial::Cint
+    best_count::Cint
+    n_valid_trials::Cint
+end
+const GLOB_STATUS = (:ok, :no_trial)
+
+"""
+    describe(vertices, normals; k = 32, radius = 0.0) -> (desc, count)
+
+An integer point-feature histogram per point (`rh_describe`, include/ransac_hip.h has the definition in full): `desc` is a
+33 x n `Matrix{UInt16}` (column `i` = the descriptor of point `i`, values 0 .. 7938), `count` the neighbours per point.
+The normals are used as given.
+"""
+function describe(vertices::AbstractVector{SVector{3,T}}, normals::AbstractVector{SVector{3,T}}; k::Integer = 32,
+                  radius::Real = 0.0, device::Integer = 0) where {T<:Union{Float32,Float64}}
+    vs = convert(Vector{SVector{3,T}}, vertices)
+    ns = convert(Vector{SVector{3,T}}, normals)
+    n = length(vs)
+    length(ns) == n || error("describe: $(length(ns)) normals for $n points")
+    desc = zeros(UInt16, DESC_DIM, n)
+    count = zeros(Int32, n)
+    GC.@preserve vs ns desc count begin
+        if T == Float32
+            check(ccall((:rh_describe_f32, LIB), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Int64, Int32, Cdouble, Cint, Ptr{UInt16}, Ptr{Int32}),
+                pointer(reinterpret(Float32, vs)), pointer(reinterpret(Float32, ns)), n, k, radius, device, desc, count))
+        else
+            check(ccall((:rh_describe, LIB), Cint, (Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int32, Cdouble, Cint, Ptr{UInt16}, Ptr{Int32}),
+                pointer(reinterpret(Float64, vs)), pointer(reinterpret(Float64, ns)), n, k, radius, device, desc, count))
+        end
+    end
+    return desc, count
+end
+
+"""
+    match_features(ref_desc, qry_desc; mutual = false) -> (idx, dist)
+
+For every column of `qry_desc` the column of `ref_desc` (both 33 x rows `Matrix{UInt16}`, as `describe` returns them) with
+the smallest sum of squared differences, ties to the smaller index (`rh_match_features`): `idx` 1-based `Int32`, `dist` the
+sums.  `mutual`: an entry is 0 unless the query is in turn the best query of its reference column.
+"""
+function match_features(ref_desc::Matrix{UInt16}, qry_desc::Matrix{UInt16}; mutual::Bool = false, device::Integer = 0)
+    size(ref_desc, 1) == DESC_DIM && size(qry_desc, 1) == DESC_DIM || error("match_features: descriptors are 33 x rows")
+    n, m = size(ref_desc, 2), size(qry_desc, 2)
+    idx = zeros(Int32, m)
+    dist = zeros(UInt32, m)
+    check(ccall((:rh_match_features, LIB), Cint, (Ptr{UInt16}, Int64, Ptr{UInt16}, Int64, Int32, Cint, Ptr{Int32}, Ptr{UInt32}),
+        ref_desc, n, qry_desc, m, mutual ? 1 : 0, device, idx, dist))
+    return idx, dist
+end
+
+"""
+    register_global(reference, queries, corr_qry, corr_ref; tau, trials = 20000, seed = 0, edge_ratio = 0.9, min_edge = 0.0,
+                    triples = nothing) -> (T, info)
+
+The rigid motion of `queries` onto `reference` that most of the correspondences `(corr_qry[i], corr_ref[i])` (1-based)
+agree with, by RANSAC over triples of them (`rh_register_global`, include/ransac_hip.h has the definition in full).
+`triples`: a 3 x trials `Matrix{Int32}`, 0-based into the correspondences, instead of the draws from `seed`.  `T` is a 4x4
+`Matrix{Float64}`, a start for `register`; `info` a named tuple `status` (`:ok`, `:no_trial`), `best_trial` (0-based),
+`best_count`, `n_valid_trials` and `counts`.  `tau`: about 1.5 point spacings.
+"""
+function register_global(reference::AbstractVector{SVector{3,T}}, queries::AbstractVector{SVector{3,T}},
+                         corr_qry::AbstractVector{<:Integer}, corr_ref::AbstractVector{<:Integer}; tau::Real, trials::Integer = 20000,
+                         seed::Integer = 0, edge_ratio::Real = 0.9, min_edge::Real = 0.0, triples = nothing,
+                         device::Integer = 0) where {T<:Union{Float32,Float64}}
+    rs = convert(Vector{SVector{3,T}}, reference)
+    qs = convert(Vector{SVector{3,T}}, queries)
+    cq = convert(Vector{Int32}, corr_qry)
+    cr = convert(Vector{Int32}, corr_ref)
+    length(cq) == length(cr) || error("register_global: $(length(cq)) query and $(length(cr)) reference indices")
+    tri = triples === nothing ? nothing : convert(Matrix{Int32}, triples)
+    tri === nothing || (size(tri, 1) == 3 || error("register_global: triples are 3 x trials"); trials = size(tri, 2))
+    p = RhGlobalParams(trials, 0, seed, tau, edge_ratio, min_edge)
+    out = zeros(Float64, 4, 3)                   # the library's row-major 3x4, read here column by column
+    counts = zeros(Int32, 1 <= trials <= (1 << 20) ? Int(trials) : 1)
+    res = Ref(RhGlobalResult(0, 0, 0, 0))
+    GC.@preserve rs qs cq cr tri out counts begin
+        if T == Float32
+            check(ccall((:rh_register_global_f32, LIB), Cint,
+                (Ptr{Cfloat}, Int64, Ptr{Cfloat}, Int64, Ptr{Int32}, Ptr{Int32}, Int64, Ref{RhGlobalParams}, Ptr{Int32}, Cint,
+                 Ptr{Cdouble}, Ref{RhGlobalResult}, Ptr{Int32}),
+                pointer(reinterpret(Float32, rs)), length(rs), pointer(reinterpret(Float32, qs)), length(qs), cq, cr, length(cq), p,
+                tri === nothing ? C_NULL : pointer(tri), device, out, res, counts))
+        else
+            check(ccall((:rh_register_global, LIB), Cint,
+                (Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ptr{Int32}, Ptr{Int32}, Int64, Ref{RhGlobalParams}, Ptr{Int32}, Cint,
+                 Ptr{Cdouble}, Ref{RhGlobalResult}, Ptr{Int32}),
+                pointer(reinterpret(Float64, rs)), length(rs), pointer(reinterpret(Float64, qs)), length(qs), cq, cr, length(cq), p,
+                tri === nothing ? C_NULL : pointer(tri), device, out, res, counts))
+        end
+    end
+    r = res[]
+    Tm = vcat(permutedims(out), [0.0 0.0 0.0 1.0])
+    return Tm, (status = GLOB_STATUS[r.status + 1], best_trial = Int(r.best_trial), best_count = Int(r.best_count),
+                n_valid_trials = Int(r.n_valid_trials), counts = counts)
+end
+
 _assign_shape(x::ExtractedShape) = toC(x.shape)
 _assign_shape(x::FittedShape) = toC(x)
 

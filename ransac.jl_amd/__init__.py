@@ -7,7 +7,7 @@ from .api import (DEFAULT_PARAMETERS, DEFAULT_SHAPE_DICT, ConfidenceInterval, E,
                   removeinvalidshapes, scorecandidates, setfloattype, findAABB, smallestdistance,
                   FittedCylinder, FittedPlane, FittedShape, FittedSphere, RANSACCloud, bitmapparameters,
                   defaultcommonparameters, defaultiterationparameters, defaultparameters,
-                  defaultshapeparameters, estimatenormals, orientnormals, knn, knn_query, cloud_distance, transfer_labels, register, transform_points, transform_normals, removeoutliers, estimatescore, fit, invalidate_indexes, largestconncomp,
+                  defaultshapeparameters, estimatenormals, orientnormals, knn, knn_query, cloud_distance, transfer_labels, register, describe, match_features, register_global, transform_points, transform_normals, removeoutliers, estimatescore, fit, invalidate_indexes, largestconncomp,
                   notsoconfident, params_to_c, prob, ransac, ransacparameters, MpGroup, refit, refit_component, refit_lsq, score_batch,
                   scorecandidate, select_enabled, sample_sets, fit_sets, shape_f32, shape_from_c, strt, buildoctree, octreedepth, findleaf,
                   getnthcell, iswithinrectangle, cell_enabled_points, shape_extents, OctreeCell, set_option, get_option, option,

@@ -121,7 +121,23 @@ class RegisterResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("n_valid", C.c_int64), ("rms", C.c_double)]
 
 
+class GlobalParams(C.Structure):
+    """rh_global_params (include/ransac_hip.h)"""
+    _fields_ = [("trials", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("tau", C.c_double),
+                ("edge_ratio", C.c_double), ("min_edge", C.c_double)]
+
+
+class GlobalResult(C.Structure):
+    """rh_global_result (include/ransac_hip.h)"""
+    _fields_ = [("status", C.c_int32), ("best_trial", C.c_int32), ("best_count", C.c_int32), ("n_valid_trials", C.c_int32)]
+
+
 KNN_MAX_K = 63
+DESC_DIM, DESC_MAX = 33, 7938
+MATCH_MUTUAL = 1
+GLOBAL_MAX_TRIALS = 1 << 20
+GLOB_OK, GLOB_NO_TRIAL = 0, 1
+GLOB_STATUS_NAMES = {GLOB_OK: "ok", GLOB_NO_TRIAL: "no_trial"}
 DIST_POINT, DIST_PLANE = 0, 1
 REG_CONVERGED, REG_MAX_ITER, REG_DEGENERATE, REG_TOO_FEW = 0, 1, 2, 3
 REG_STATUS_NAMES = {REG_CONVERGED: "converged", REG_MAX_ITER: "max_iter", REG_DEGENERATE: "degenerate", REG_TOO_FEW: "too_few"}
@@ -156,6 +172,8 @@ _i64p = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
 _u64p = C.POINTER(C.c_uint64)
 _u8p = C.POINTER(C.c_uint8)
+_u16p = C.POINTER(C.c_uint16)
+_u32p = C.POINTER(C.c_uint32)
 _sp, _pp, _vp = C.POINTER(Shape), C.POINTER(Params), C.c_void_p
 
 # every symbol include/ransac_hip.h declares: name -> (restype, argtypes)
@@ -267,6 +285,14 @@ SIGNATURES = {
                               C.POINTER(RegisterResult), _i32p, _dp]),
     "rh_register_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float), C.c_int64,
                                   C.POINTER(RegisterParams), _dp, C.c_int, _dp, C.POINTER(RegisterResult), _i32p, _dp]),
+    "rh_describe": (C.c_int, [_dp, _dp, C.c_int64, C.c_int32, C.c_double, C.c_int, _u16p, _i32p]),
+    "rh_describe_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_double, C.c_int, _u16p,
+                                  _i32p]),
+    "rh_match_features": (C.c_int, [_u16p, C.c_int64, _u16p, C.c_int64, C.c_int32, C.c_int, _i32p, _u32p]),
+    "rh_register_global": (C.c_int, [_dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p, C.c_int64, C.POINTER(GlobalParams), _i32p,
+                                     C.c_int, _dp, C.POINTER(GlobalResult), _i32p]),
+    "rh_register_global_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_float), C.c_int64, _i32p, _i32p, C.c_int64,
+                                         C.POINTER(GlobalParams), _i32p, C.c_int, _dp, C.POINTER(GlobalResult), _i32p]),
     "rh_remove_outliers": (C.c_int, [_dp, C.c_int64, C.POINTER(OutlierParams), C.c_int, _u8p, _i32p, C.c_int64, _i64p, _dp,
                                      C.POINTER(OutlierStats)]),
     "rh_remove_outliers_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(OutlierParams), C.c_int, _u8p, _i32p,

@@ -988,6 +988,93 @@ def register(reference, queries, normals=None, metric=None, radius=0.0, max_iter
                    rms=float(res.rms), history=dict(n_valid=nv_it[:it].copy(), rms=rms_it[:it].copy()))
 
 
+def describe(vertices, normals, k=32, radius=0.0, return_count=False, device=0):
+    """An integer point-feature histogram per point (rh_describe; include/ransac_hip.h has the definition in full): for
+    every point the angles between its normal, its neighbours' normals and the lines to them, binned 3 x 11 and summed
+    with the neighbours' own histograms.  Invariant under a rigid motion of points and normals, up to values on a bin
+    edge.  vertices, normals: (n, 3), both float32 (widened exactly) or float64; the normals are used as given.
+    k: 1 .. 63 neighbours; radius > 0 drops neighbours farther than it.
+    Returns desc (n, 33) uint16, values 0 .. 7938; then with return_count the neighbours per point (n,) int32."""
+    arrs = [np.asarray(vertices), np.asarray(normals)]
+    f32 = all(a.dtype == np.float32 for a in arrs)
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    xyz, nrm = (np.ascontiguousarray(a, dtype=t).reshape(-1, 3) for a in arrs)
+    if nrm.shape[0] != xyz.shape[0]:
+        raise ValueError("describe: %d normals for %d points" % (nrm.shape[0], xyz.shape[0]))
+    n = xyz.shape[0]
+    desc = np.zeros((n, L.DESC_DIM), dtype=np.uint16)
+    cnt = np.zeros(n, dtype=np.int32) if return_count else None
+    fn = lib().rh_describe_f32 if f32 else lib().rh_describe
+    check(fn(_p(xyz, ct), _p(nrm, ct), n, int(k), float(radius), device, _p(desc, C.c_uint16),
+             None if cnt is None else _p(cnt, C.c_int32)))
+    return (desc, cnt) if return_count else desc
+
+
+def match_features(ref_desc, qry_desc, mutual=False, return_dist=False, device=0):
+    """For every row of qry_desc the row of ref_desc with the smallest sum of squared differences (rh_match_features: an
+    exact integer, ties to the smaller index).  Both: (rows, 33) uint16 as describe returns them.  mutual: an entry is 0
+    unless the query is in turn the best query of its reference row.
+    Returns idx (m,) int32, 1-based rows of ref_desc; then with return_dist the sums (m,) uint32."""
+    ref = np.ascontiguousarray(ref_desc, dtype=np.uint16)
+    qry = np.ascontiguousarray(qry_desc, dtype=np.uint16)
+    for a in (ref, qry):
+        if a.ndim != 2 or a.shape[1] != L.DESC_DIM:
+            raise ValueError("match_features: descriptors are (rows, %d), not %r" % (L.DESC_DIM, a.shape))
+    n, m = ref.shape[0], qry.shape[0]
+    idx = np.zeros(m, dtype=np.int32)
+    dist = np.zeros(m, dtype=np.uint32) if return_dist else None
+    check(lib().rh_match_features(_p(ref, C.c_uint16), n, _p(qry, C.c_uint16), m, L.MATCH_MUTUAL if mutual else 0, device,
+                                  _p(idx, C.c_int32), None if dist is None else _p(dist, C.c_uint32)))
+    return (idx, dist) if return_dist else idx
+
+
+def register_global(reference, queries, ref_normals, qry_normals, tau, k=32, feature_radius=0.0, trials=20000, edge_ratio=0.9,
+                    min_edge=0.0, mutual=False, seed=0, triples=None, refine=True, metric=None, radius=None, device=0,
+                    return_info=False):
+    """The rigid motion that brings the cloud `queries` onto the cloud `reference` WITHOUT a start: describe() on both
+    clouds (k, feature_radius), match_features() from the queries to the reference (mutual: entries of 0 are dropped), then
+    rh_register_global -- `trials` hypotheses from three correspondences each, drawn from `seed` (or the given `triples`,
+    (trials, 3) 0-based into the correspondences), kept when their edges agree within edge_ratio and the query edges are
+    at least min_edge long, and scored by the correspondences they bring within tau.  include/ransac_hip.h has the
+    definitions in full.
+    tau: about 1.5 point spacings (the nn_median that removeoutliers reports): matches are only as exact as the sampling,
+    and a hypothesis from three of them is off by about as much.
+    refine: the result starts register(reference, queries, normals=ref_normals, metric=metric, radius=radius, init=T);
+    radius defaults to 3 tau there.
+    Returns the 4x4 float64 matrix; with return_info also a dict: coarse (the 4x4 of the best hypothesis), counts (trials,),
+    status ("ok", "no_trial"), best_trial, best_count, n_valid_trials, corr_qry and corr_ref (1-based int32) and, with
+    refine, register's info under "register"."""
+    f32, ct, (ref, qry) = _cloud_pair("register_global", reference, queries)
+    dref = describe(ref, np.asarray(ref_normals, dtype=ref.dtype), k=k, radius=feature_radius, device=device)
+    dqry = describe(qry, np.asarray(qry_normals, dtype=qry.dtype), k=k, radius=feature_radius, device=device)
+    idx = match_features(dref, dqry, mutual=mutual, device=device)
+    corr_qry = np.ascontiguousarray((np.flatnonzero(idx > 0) + 1).astype(np.int32))
+    corr_ref = np.ascontiguousarray(idx[idx > 0].astype(np.int32))
+    c, trials = len(corr_qry), int(trials)
+    tri = None
+    if triples is not None:
+        tri = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        trials = tri.shape[0]
+    prm = L.GlobalParams(trials=trials, seed=int(seed), tau=float(tau), edge_ratio=float(edge_ratio), min_edge=float(min_edge))
+    out, res = np.zeros((3, 4)), L.GlobalResult()
+    counts = np.zeros(trials if 1 <= trials <= L.GLOBAL_MAX_TRIALS else 1, dtype=np.int32)
+    fn = lib().rh_register_global_f32 if f32 else lib().rh_register_global
+    check(fn(_p(ref, ct), ref.shape[0], _p(qry, ct), qry.shape[0], _p(corr_qry, C.c_int32), _p(corr_ref, C.c_int32), c, C.byref(prm),
+             None if tri is None else _p(tri, C.c_int32), device, _p(out, C.c_double), C.byref(res), _p(counts, C.c_int32)))
+    coarse = np.vstack([out, [0.0, 0.0, 0.0, 1.0]])
+    T, reg = coarse, None
+    if refine:
+        T, reg = register(ref, qry, normals=np.asarray(ref_normals, dtype=ref.dtype), metric=metric,
+                          radius=3.0 * float(tau) if radius is None else radius, init=coarse, device=device, return_info=True)
+    if not return_info:
+        return T
+    info = dict(coarse=coarse, counts=counts, status=L.GLOB_STATUS_NAMES.get(res.status, res.status), best_trial=int(res.best_trial),
+                best_count=int(res.best_count), n_valid_trials=int(res.n_valid_trials), corr_qry=corr_qry, corr_ref=corr_ref)
+    if refine:
+        info["register"] = reg
+    return T, info
+
+
 def _rigid(who, T):
     T = np.asarray(T, dtype=np.float64)
     if T.shape not in ((3, 4), (4, 4)):
