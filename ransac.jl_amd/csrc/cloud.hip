@@ -318,15 +318,15 @@ extern "C" int rh_cloud_create(const double *xyz, const double *nrm, int64_t n, 
     CK(c->sub.alloc(6 * c->s_pad));
     CK(c->dis.alloc(6 * c->dis_stride));
     CK(c->sub_idx0.alloc(s));
-    CK(c->sub_perm.alloc(c->s_pad));   // (whole 64-lane reads of the last group stay inside the allocation: the mask pass, score4.hip)
+    CK(c->sub_perm.alloc(c->s_pad));   // (whole 64-lane reads of the last group stay inside the allocation: the mask pass, unpermute4.hip)
     CKH(hipMemsetAsync(c->sub_perm, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(c->s_pad, 1), c->stream));
     c->ngroups = (s + 63) / 64;
     c->ng_pad = ((c->ngroups + RH_G2_TG - 1) / RH_G2_TG) * RH_G2_TG + RH_G2_TG;
     CK(c->gb.alloc(7 * c->ng_pad));
     CK(c->gb32.alloc(8 * c->ng_pad));
-    c->nst = (c->ngroups + 15) / 16;
+    c->nst = (c->ngroups + RH_S4_STG - 1) / RH_S4_STG;
     CK(c->st32.alloc(8 * std::max<int64_t>(1, c->nst)));
-    c->ntile = (c->ngroups + 3) / 4;
+    c->ntile = (c->ngroups + RH_G2_TG - 1) / RH_G2_TG;
     CK(c->tile32.alloc(8 * std::max<int64_t>(1, c->ntile)));
     CK(c->gm32.alloc(4 * c->ng_pad));
     CK(c->stm32.alloc(4 * std::max<int64_t>(1, c->nst)));

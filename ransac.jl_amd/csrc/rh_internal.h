@@ -178,6 +178,12 @@ constexpr int64_t RH_G2_MIN_POINTS = 8192;               // below this the brute
 //     lists call super-tiles ARE tree nodes, and the plane order's blocks are the super-tiles.  Below 1024 points today's rule.
 // Both children are non-empty for every cnt > 64 (aligned, cnt > 1024: m = ceil(cnt / 1024) >= 2 and (m + 1) / 2 <= m - 1).
 constexpr int64_t RH_KD_NODE = 1024;
+// The groupings of the culled score path, stated once: 64 points per group, RH_G2_TG groups per tile (what a block stages),
+// RH_S4_STG groups per super-tile (what the candidate lists are cut by).  Super-tiles are whole tiles, and a super-tile is a
+// k-d node: the aligned tree and the plane order's blocks (kdorder.hip) are correct only while these agree.
+constexpr int RH_S4_STG = 16;
+static_assert(RH_KD_NODE == RH_S4_STG * 64, "a super-tile is one node of the aligned position tree");
+static_assert(RH_S4_STG % RH_G2_TG == 0, "a super-tile is a whole number of tiles");
 constexpr int64_t RH_KD_ALIGN_MIN_TILES = 1000;          // "kd_align" by size: subsets of this many 256-point tiles and more (the size from which list launches are taken with batches in flight)
 static inline int64_t kd_left_count(int64_t cnt, bool aligned)
 {
@@ -500,7 +506,10 @@ bool rh_score_v4_enabled(const rh_cloud *c);
 // w.d_occ, rows w.mstride4 apart: rhk_unpermute_masks4).  launch_info (optional): a sized launch (not open_count) leaves its
 // R, lists taken (0 / 1), rows and tiles there.
 int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t *launch_info = nullptr);
-int rhk_unpermute_masks4(rh_cloud *c, rh_batch_ws &w, int32_t b, uint64_t *d_out);   // score4.hip: w's entry lists -> dense rows
+int rhk_unpermute_masks4(rh_cloud *c, rh_batch_ws &w, int32_t b, uint64_t *d_out);   // unpermute4.hip: w's entry lists -> dense rows
+// (functions that only join the units of the score path are kept out of the library's dynamic symbols)
+#define RH_UNIT_LOCAL __attribute__((visibility("hidden")))
+RH_UNIT_LOCAL bool rhk_plane_order_wanted(const rh_cloud *c);   // score4.hip: "plane_order" -- do plane candidates walk the plane order of subset 1?
 // score nk candidates of one kind; nk_host < 0: count is only known on the device (d_nk),
 // launch for an upper bound of nk_bound candidates
 int rhk_score_kind(rh_cloud *c, int kind, const double *pts, int64_t stride, int64_t s,
@@ -511,7 +520,11 @@ int rhk_score_kind(rh_cloud *c, int kind, const float *pts, int64_t stride, int6
                    const uint64_t *enabled_words_or_null, const rh_prep *d_prep, const int32_t *d_orig,
                    const int32_t *d_nk, int32_t nk_bound, double eps, double cosa, int32_t *d_counts,
                    uint64_t *d_masks_or_null, int64_t mask_stride);
-int rhk_gb32_build(rh_cloud *c);   // (score4.hip: gb32 from gb)
+int rhk_gb32_build(rh_cloud *c);   // (boxes32.hip: gb32 / st32 / tile32 / gm32 / stm32 and nrm_len from gb and sub)
+// boxes32.hip, queued on c->stream: the binary32 boxes of ng groups from their binary64 ones (7 planes c->ng_pad apart), and
+// of the nruns runs of k consecutive groups of subset 1
+RH_UNIT_LOCAL void rhk_gb32_of(rh_cloud *c, const double *gb, int64_t ng, float *gb32);
+RH_UNIT_LOCAL void rhk_runs32_of(rh_cloud *c, const double *gb, int k, int64_t nruns, float *out);
 int rhk_store_cls(rh_cloud *c, const rh_prep *const prep[4], const int32_t n[4], const int32_t pbase[5], const double eps[4],
                   const double cosa[4], void *d_cls, float *d_box, int64_t bstride);
 int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, rh_score_job job);   // the same over dis[first, first + cnt): fills in job.points
@@ -519,7 +532,7 @@ int rhk_cloud_aabb(rh_cloud *c, const double *d_xyz, int64_t n, double lo[3], do
 int rhk_kd_order(rh_cloud *c, const double *d_xyz, const double *d_nrm, const int32_t *d_idx0);   // kdorder.hip: subset 1's k-d leaf order on the device
 int rhk_plane_order_build(rh_cloud *c);     // kdorder.hip: the plane order of subset 1 from c->sub (pl_sub, pl_src, then rhk_plane_boxes)
 int rhk_plane_enabled_sync(rh_cloud *c);    // kdorder.hip: pl_enabled from sub_enabled, on the cloud's stream (no plane order: nothing)
-int rhk_plane_boxes(rh_cloud *c);           // score4.hip: pl_gb32 / pl_gm32 / pl_st32 / pl_stm32 from pl_sub
+int rhk_plane_boxes(rh_cloud *c);           // boxes32.hip: pl_gb32 / pl_gm32 / pl_st32 / pl_stm32 from pl_sub
 int rhk_score_kind_dis(rh_cloud *c, int kind, int64_t first, int64_t cnt, const rh_prep *d_prep, const int32_t *d_orig,
                        const int32_t *d_nk, int32_t nk_bound, double eps, double cosa, int32_t *d_counts);
 int rhk_group_bounds(rh_cloud *c);

@@ -33,11 +33,9 @@
 #include <vector>
 
 #include "rh_internal.h"
-#ifdef RH_DIAG
-#include "ransac_hip_diag.h"
-#endif
 #include "score_device.h"
 #include "score4_device.h"
+#include "score4_shared.h"
 #include "wave_keys.h"
 
 namespace {
@@ -45,18 +43,11 @@ namespace {
 using namespace rhdev;
 using namespace rh4;
 
-typedef float rh_f32x4 __attribute__((ext_vector_type(4)));
-typedef float rh_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned long long rh_u64x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t rh_u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int S4_TG = 4;                 // groups per tile (8, measured in round 4 -- the per-chunk work of stage 1 paid once per 8 box tests,
-                                         // fuller batches: cfg3 0.0906 -> 0.0959 ms, cfg2 0.078 -> 0.104, cfg5 0.384 -> 0.375; R = 4 with it: worse still)
+// (S4_TG groups per tile, S4_STG per super-tile: score4_shared.h)
 constexpr int S4_GB = 2;                 // bits of the group in a pair-list entry
 constexpr unsigned S4_GM = (1u << S4_GB) - 1u;
 constexpr int S4_ROW = 65;               // padded row length of the tile arrays (bank spread of the per-lane rows)
 constexpr int S4_W = 4;                  // waves per block
-constexpr int S4_STG = 16;               // groups per super-tile (st_cull_kernel): 4 tiles = 1024 points of the k-d leaf order
 // R: 64-candidate chunks per block row -- 16 / 12 / 4 / 2 by the size of the grid (rhk_score4_all holds the rule and the
 // measurements behind it)
 template <int R, bool MASK = false, bool LIST = false>
@@ -75,11 +66,6 @@ struct S4Shared {
     int weirdw[S4_TG];                   // per group: an enabled point with a non-finite value
     int npairs, next_batch;
 };
-
-static __device__ __forceinline__ bool is_nan_bits(float v)
-{
-    return (__builtin_bit_cast(uint32_t, v) & 0x7fffffffu) > 0x7f800000u;
-}
 
 struct S4KindArgs {
     const rh_cls *cls;      // classifier records of the bin
@@ -128,15 +114,6 @@ struct S4AllArgs {
 #else
 #define S4_STAT(stats, idx, val) do { } while (0)
 #endif
-
-template <int KIND> struct S4Fields { static constexpr int NBOX = KIND == RH_PLANE ? 8 : (KIND == RH_SPHERE ? 5 : (KIND == RH_CYLINDER ? 10 : 11)); };
-
-// may a plane candidate (fields 5-7 of its culling record: the cells its inliers' normals can lie in) meet a group / super-tile
-// whose points' normals lie in the cells of gm?  (score4_device.h, normal cells)
-static __device__ __forceinline__ bool nsig_meet(const float (&B)[RH_BOX_FIELDS], const rh_u32x4 gm)
-{
-    return (((__builtin_bit_cast(uint32_t, B[5]) & gm.x) | (__builtin_bit_cast(uint32_t, B[6]) & gm.y)) | (__builtin_bit_cast(uint32_t, B[7]) & gm.z)) != 0u;
-}
 
 #define RH4_CONST_AS __attribute__((address_space(4)))
 
@@ -593,450 +570,6 @@ score4_kernel(int64_t s, const S4AllArgs A, int32_t *__restrict__ counts, int db
 #undef RH_S4_BODY
 }
 
-#ifdef RH_DIAG
-// ---- audit of the classifier's margins (tests): every (candidate, point) of a batch against subset 1.
-// a32 / b32 are what the score kernel computes (the very same functions: ua, ub of score4_device.h); a64 / b64 the same scaled
-// quantities from the reference's binary64 arithmetic.  |x32 - x64| has to stay below 1/2 for the classification to be sound; by
-// construction (RH_CLS_SAFETY) it should stay below ~1/8.  out[kind * 2 + {0, 1}] = max over the batch of |a32 - a64|,
-// |b32 - b64| (sphere / cylinder: only where the distance half is not far outside, ua64 < 2 -- the norm's error is relative
-// to the norm); out[8 + kind] = pairs looked at.
-struct S4AuditCand { rh_prep P; rh_cls C; double cNhi, wN, eDlo, wD, cosa, eps; int kind, usable; };   // (cNhi .. wD: cls_make's dbg4)
-
-__global__ void __launch_bounds__(256)
-cls_audit_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const S4AuditCand *__restrict__ cands, int ncand,
-                 unsigned long long *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c = blockIdx.y;
-    if (c >= ncand) return;
-    const S4AuditCand &Q = cands[c];
-    double ea = 0.0, eb = 0.0;
-    bool counted = false;
-    if (i < s && Q.usable) {
-        const double x = pts[i], y = pts[stride + i], z = pts[2 * stride + i];
-        const double nx = pts[3 * stride + i], ny = pts[4 * stride + i], nz = pts[5 * stride + i];
-        const rh_prep &P = Q.P;
-        float a32, b32;
-        double a64, b64;
-        if (Q.kind == RH_PLANE) {
-            cls_plane_ab(Q.C, (float)x, (float)y, (float)z, (float)nx, (float)ny, (float)nz, a32, b32);
-            const double dn = (P.f[3] * nx + P.f[4] * ny) + P.f[5] * nz;
-            const double d = (P.f[6] * (x - P.f[0]) + P.f[7] * (y - P.f[1])) + P.f[8] * (z - P.f[2]);
-            a64 = (Q.cNhi - dn) / Q.wN;
-            b64 = (fabs(d) - Q.eDlo) / Q.wD;
-            ea = fabs((double)a32 - a64);
-            eb = fabs((double)b32 - b64);
-            counted = true;
-        } else if (Q.kind == RH_SPHERE || Q.kind == RH_CYLINDER) {
-            double qx, qy, qz, R, sgn;
-            if (Q.kind == RH_SPHERE) {
-                cls_round_ab<RH_SPHERE>(Q.C, (float)x, (float)y, (float)z, (float)nx, (float)ny, (float)nz, a32, b32);
-                qx = x - P.f[0]; qy = y - P.f[1]; qz = z - P.f[2]; R = P.f[3]; sgn = P.f[4];
-            } else {
-                cls_round_ab<RH_CYLINDER>(Q.C, (float)x, (float)y, (float)z, (float)nx, (float)ny, (float)nz, a32, b32);
-                const double tx = x - P.f[3], ty = y - P.f[4], tz = z - P.f[5];
-                const double sd = (P.f[0] * tx + P.f[1] * ty) + P.f[2] * tz;
-                qx = (x - P.f[0] * sd) - P.f[3]; qy = (y - P.f[1] * sd) - P.f[4]; qz = (z - P.f[2] * sd) - P.f[5];
-                R = P.f[6]; sgn = P.f[7];
-            }
-            // the squared form (score4_device.h, "Round kinds without a square root"): dbg4 = m2, W2, mv, Wv
-            const double m2 = Q.cNhi, W2 = Q.wN, mv = Q.eDlo, Wv = Q.wD;
-            const double n2 = (qx * qx + qy * qy) + qz * qz;
-            const double qn = (qx * nx + qy * ny) + qz * nz;
-            a64 = (fabs(n2 - (R * R + Q.eps * Q.eps)) - (2.0 * R * Q.eps - m2)) / W2;
-            b64 = (mv + (Q.cosa * Q.cosa * n2 - sgn * qn * fabs(qn))) / Wv;
-            // the error of n2 is relative (3 u n2): far outside the band it exceeds any fixed margin and cannot matter
-            // (ua is a few thousand widths above 1 there); what has to hold is the bound NEAR the band
-            if (a64 < 2.0) { ea = fabs((double)a32 - a64); eb = fabs((double)b32 - b64); }
-            counted = true;
-        } else if (Q.kind == RH_CONE) {
-            // a64 / b64 from the reference's own frame (cone_frame: its dist and its normal cosine), the closed form only
-            // supplies rho for the multiplied-through angle test; points the classifier hands to the exact test because
-            // they lie next to the axis are not looked at
-            bool near_axis;
-            cls_cone_ab(Q.C, (float)x, (float)y, (float)z, (float)nx, (float)ny, (float)nz, a32, b32, near_axis);
-            if (!near_axis) {
-                double dist, dt;
-                cone_frame(P, x, y, z, nx, ny, nz, dist, dt);
-                const double an = sqrt((P.f[3] * P.f[3] + P.f[4] * P.f[4]) + P.f[5] * P.f[5]);
-                const double wx = x - P.f[0], wy = y - P.f[1], wz = z - P.f[2];
-                const double h = ((P.f[3] * wx + P.f[4] * wy) + P.f[5] * wz) / an;
-                const double qx = wx - h * (P.f[3] / an), qy = wy - h * (P.f[4] / an), qz = wz - h * (P.f[5] / an);
-                const double rho = sqrt((qx * qx + qy * qy) + qz * qz);
-                a64 = (fabs(dist) - Q.eDlo) / Q.wD;
-                b64 = 0.5 - rho * (P.f[8] * dt - Q.cosa) / Q.wN;
-                ea = fabs((double)a32 - a64);
-                eb = fabs((double)b32 - b64);
-                counted = true;
-            }
-        }
-        if (!(ea == ea)) ea = 1e30;   // a NaN on one side only is a failure
-        if (!(eb == eb)) eb = 1e30;
-    }
-    // block maximum, then one atomic per block (non-negative doubles order like their bit patterns)
-    __shared__ unsigned long long sa[4], sb[4];
-    __shared__ int sc[4];
-    unsigned long long ua = __builtin_bit_cast(unsigned long long, ea), ub = __builtin_bit_cast(unsigned long long, eb);
-    int cnt = counted ? 1 : 0;
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long va = __shfl_down(ua, off), vb = __shfl_down(ub, off);
-        ua = va > ua ? va : ua;
-        ub = vb > ub ? vb : ub;
-        cnt += __shfl_down(cnt, off);
-    }
-    if ((threadIdx.x & 63) == 0) { sa[threadIdx.x >> 6] = ua; sb[threadIdx.x >> 6] = ub; sc[threadIdx.x >> 6] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0 && Q.kind >= 0 && Q.kind < 4) {
-        unsigned long long ma = 0, mb = 0;
-        int n = 0;
-        for (int w = 0; w < 4; w++) { ma = sa[w] > ma ? sa[w] : ma; mb = sb[w] > mb ? sb[w] : mb; n += sc[w]; }
-        atomicMax(&out[Q.kind * 2], ma);
-        atomicMax(&out[Q.kind * 2 + 1], mb);
-        atomicAdd(&out[8 + Q.kind], (unsigned long long)n);
-    }
-}
-
-// ---- audit of the DECISIONS (tests, tools/fuzz_score.py): what the margin audit above argues, counted.  One wave per
-// (candidate, 64-point group of subset 1), lane = point, with the very records (cls_make) and functions (box_skip32,
-// cls_*_t) the score kernel uses, against the exact test of the cloud's element type:
-//   out[kind * 10 + 0] pairs, 1 pairs the box test skips, 2 VIOLATION: skipped pairs with an exact inlier,
-//   3 points, 4 classified surely-in, 5 surely-out, 6 VIOLATION: surely-in but the exact test rejects,
-//   7 VIOLATION: surely-out but the exact test accepts, 8 exact inliers, 9 VIOLATION: the all-zero point a disabled point
-//   is staged as comes out surely-in (plane / sphere / cylinder count what the classifier says without looking at the
-//   enabled bits; the cone masks them).
-struct S4SoundCand { rh_prep P; rh_prepf Pf; rh_cls C; float box[RH_BOX_FIELDS]; int kind; int pad; };
-struct S4SoundArgs { double eps[4], cosa[4]; int f32; };
-
-template <int KIND>
-static __device__ __forceinline__ void sound_one(const S4SoundCand &Q, const S4SoundArgs &A, double x, double y, double z, double nx, double ny,
-                                                 double nz, const uint64_t valid, const rh_box32 &G, const rh_box32 &GS, const rh_box32 &GT, const rh_u32x4 gm, const rh_u32x4 sm, const int lane, unsigned long long *__restrict__ out)
-{
-    const double eps = A.eps[KIND], cosa = A.cosa[KIND];
-    uint64_t ex;
-    if (A.f32) ex = test_point<KIND>(Q.Pf, (float)x, (float)y, (float)z, (float)nx, (float)ny, (float)nz, eps, cosa);
-    else ex = test_point<KIND>(Q.P, x, y, z, nx, ny, nz, eps, cosa);
-    ex &= valid;
-    const bool skip = box_skip32<KIND>(Q.box, G);
-    const bool stskip = box_skip32<KIND>(Q.box, GS);   // the super-tile's box (st_cull_kernel): out[48 + k] such pairs, out[52 + k] VIOLATION: with an exact inlier
-    const bool tlskip = box_skip32<KIND>(Q.box, GT);   // the tile's box (the lists the score launch walks): out[56 + k] such pairs, out[60 + k] VIOLATION: with an exact inlier
-    const bool exact_only = is_nan_bits(Q.C.f[RH_CLS_FLAG]);
-    const float fx = (float)x, fy = (float)y, fz = (float)z, fnx = (float)nx, fny = (float)ny, fnz = (float)nz;
-    float t, t0;   // (the u of score4_device.h: sign bit = surely in, 0 <= u <= 1 undecided)
-    if (KIND == RH_PLANE) { t = cls_plane_u(Q.C, fx, fy, fz, fnx, fny, fnz); t0 = cls_plane_u(Q.C, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f); }
-    else if (KIND == RH_CONE) { t = cls_cone_u(Q.C, fx, fy, fz, fnx, fny, fnz); t0 = 0.5f; }
-    else { t = cls_round_u<KIND == RH_SPHERE ? RH_SPHERE : RH_CYLINDER>(Q.C, fx, fy, fz, fnx, fny, fnz);
-           t0 = cls_round_u<KIND == RH_SPHERE ? RH_SPHERE : RH_CYLINDER>(Q.C, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f); }
-    const float sum = (fabsf(fx) + fabsf(fy)) + (fabsf(fz) + fabsf(fnx)) + (fabsf(fny) + fabsf(fnz));
-    const bool weird = WB(!(sum < __builtin_inff()) && ((valid >> lane) & 1ULL)) != 0;   // the kernel: every candidate exact-only on this tile
-    const bool decided = !exact_only && !weird;
-    // (the cone's per-point undecided bit is the sign of u - 1, not-surely-in: u = 1 exactly counts as surely out there)
-    const uint64_t sin_ = WB(decided && cls_sure(t)) & valid;
-    const uint64_t amb = (WB(!decided || (KIND == RH_CONE ? (!cls_sure(t) && cls_sure(t - 1.0f)) : cls_undecided(t)))) & valid;
-    const uint64_t sout = valid & ~sin_ & ~amb;
-    // a "band point": its DISTANCE half alone is not surely failed (the normal half aside) -- a pair whose group holds one
-    // cannot be decided by any test on the group's position box: the floor of the necessary (candidate, group) work
-    float du, dn;
-    bool near_axis = false;
-    if (KIND == RH_PLANE) cls_plane_ab(Q.C, fx, fy, fz, fnx, fny, fnz, dn, du);
-    else if (KIND == RH_CONE) cls_cone_ab(Q.C, fx, fy, fz, fnx, fny, fnz, du, dn, near_axis);
-    else cls_round_ab<KIND == RH_SPHERE ? RH_SPHERE : RH_CYLINDER>(Q.C, fx, fy, fz, fnx, fny, fnz, du, dn);
-    const uint64_t band = WB(!decided || near_axis || !(du > 1.0f)) & valid;
-    if (lane == 0) {
-        if (band != 0) atomicAdd(&out[40 + KIND], 1ULL);
-        if (ex != 0) atomicAdd(&out[44 + KIND], 1ULL);
-        if (stskip) atomicAdd(&out[48 + KIND], 1ULL);
-        if (stskip && ex != 0) atomicAdd(&out[52 + KIND], 1ULL);
-        if (tlskip) atomicAdd(&out[56 + KIND], 1ULL);
-        if (tlskip && ex != 0) atomicAdd(&out[60 + KIND], 1ULL);
-        if (KIND == RH_PLANE) {
-            // the normal-cell masks (planes): out[64] pairs the GROUP's mask rules out, out[65] VIOLATION: such a pair with an exact
-            // inlier, out[66] / out[67] the same for the SUPER-TILE's mask (the list launch)
-            const bool gskip = !nsig_meet(Q.box, gm), sskip = !nsig_meet(Q.box, sm);
-            if (gskip) atomicAdd(&out[64], 1ULL);
-            if (gskip && ex != 0) atomicAdd(&out[65], 1ULL);
-            if (sskip) atomicAdd(&out[66], 1ULL);
-            if (sskip && ex != 0) atomicAdd(&out[67], 1ULL);
-        }
-        unsigned long long *o = out + KIND * 10;
-        atomicAdd(&o[0], 1ULL);
-        if (skip) atomicAdd(&o[1], 1ULL);
-        if (skip && ex != 0) atomicAdd(&o[2], 1ULL);
-        atomicAdd(&o[3], (unsigned long long)__popcll(valid));
-        if (sin_) atomicAdd(&o[4], (unsigned long long)__popcll(sin_));
-        if (sout) atomicAdd(&o[5], (unsigned long long)__popcll(sout));
-        if (sin_ & ~ex) atomicAdd(&o[6], (unsigned long long)__popcll(sin_ & ~ex));
-        if (sout & ex) atomicAdd(&o[7], (unsigned long long)__popcll(sout & ex));
-        if (ex) atomicAdd(&o[8], (unsigned long long)__popcll(ex));
-        if (blockIdx.x == 0 && !exact_only && cls_sure(t0)) atomicAdd(&o[9], 1ULL);
-    }
-}
-
-__global__ void __launch_bounds__(64)
-cls_sound_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, const float *__restrict__ gb32, const float *__restrict__ st32, const float *__restrict__ tile32, const uint32_t *__restrict__ gm32, const uint32_t *__restrict__ stm32, const S4SoundCand *__restrict__ cands,
-                 int ncand, const S4SoundArgs A, const int kinds, unsigned long long *__restrict__ out)   // kinds: bit k = candidates of kind k count
-{
-    const int lane = threadIdx.x;
-    const int64_t g = blockIdx.x;
-    const int64_t i = g * 64 + lane;
-    const uint64_t valid = valid_mask(g * 64, s);
-    const bool on = (valid >> lane) & 1ULL;
-    const double x = on ? pts[i] : 0.0, y = on ? pts[stride + i] : 0.0, z = on ? pts[2 * stride + i] : 0.0;
-    const double nx = on ? pts[3 * stride + i] : 0.0, ny = on ? pts[4 * stride + i] : 0.0, nz = on ? pts[5 * stride + i] : 0.0;
-    rh_box32 G;
-    G.cx = gb32[g * 8 + 0]; G.cy = gb32[g * 8 + 1]; G.cz = gb32[g * 8 + 2]; G.hx = gb32[g * 8 + 3];
-    G.hy = gb32[g * 8 + 4]; G.hz = gb32[g * 8 + 5]; G.hr = gb32[g * 8 + 6];
-    rh_box32 GS;
-    {
-        const float *b = st32 + (g / S4_STG) * 8;
-        GS.cx = b[0]; GS.cy = b[1]; GS.cz = b[2]; GS.hx = b[3]; GS.hy = b[4]; GS.hz = b[5]; GS.hr = b[6];
-    }
-    rh_box32 GT;
-    {
-        const float *b = tile32 + (g / S4_TG) * 8;
-        GT.cx = b[0]; GT.cy = b[1]; GT.cz = b[2]; GT.hx = b[3]; GT.hy = b[4]; GT.hz = b[5]; GT.hr = b[6];
-    }
-    const rh_u32x4 gm = ((const rh_u32x4 *)gm32)[g], sm = ((const rh_u32x4 *)stm32)[g / S4_STG];
-    for (int c = blockIdx.y; c < ncand; c += gridDim.y) {
-        const S4SoundCand &Q = cands[c];
-        if (Q.kind < 0 || Q.kind > 3 || !((kinds >> Q.kind) & 1)) continue;
-        switch (Q.kind) {
-        case RH_PLANE: sound_one<RH_PLANE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
-        case RH_SPHERE: sound_one<RH_SPHERE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
-        case RH_CYLINDER: sound_one<RH_CYLINDER>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
-        case RH_CONE: sound_one<RH_CONE>(Q, A, x, y, z, nx, ny, nz, valid, G, GS, GT, gm, sm, lane, out); break;
-        default: break;
-        }
-    }
-}
-
-// ---- the cone's classifier on points of the caller's choice (rh_dbg_cls_cone): cls_cone_ab is device code -- its rho goes
-// through the hardware's reciprocal root --, so what it says of a point can only be asked here.  pts: 6 rows of n binary32
-// values (x y z nx ny nz), converted on the host the way the staging converts them.
-__global__ void __launch_bounds__(256)
-cls_cone_dbg_kernel(const rh_cls C, const float *__restrict__ pts, int64_t n, float *__restrict__ ua, float *__restrict__ ub,
-                    uint8_t *__restrict__ near_out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float a, b;
-    bool near_axis;
-    cls_cone_ab(C, pts[i], pts[n + i], pts[2 * n + i], pts[3 * n + i], pts[4 * n + i], pts[5 * n + i], a, b, near_axis);
-    ua[i] = a;
-    ub[i] = b;
-    near_out[i] = near_axis ? 1 : 0;
-}
-
-#endif   // RH_DIAG
-
-// ---- masks -> subset order, from the entry lists the score kernel left (round 4; round 3 wrote the words into sparse
-// internal-order rows with an occupancy byte each, and the un-permutation searched them: 1.0 ms at cfg5, a chain of
-// dependent loads per block -- occupancy -> list -> words -> positions -- at two blocks per CU).  One block per (candidate
-// row, output segment): the segment of the output row is assembled in LDS and written out once, coalesced.  The block
-// streams the row's entries (coalesced 16-byte loads, several per thread in flight), keeps of each word the bits that
-// land in ITS segment (segmask[segment][word], made once per cloud; without it -- more than 8 segments -- a range test
-// after the look-up), and its waves look the surviving bits' positions up 64 at a time through a per-wave ring.
-// a row of up to 8192 words (524 288 subset points) is ONE segment (64 KB of LDS); longer rows are cut into segments of 3072
-// words (cfg5, 24 415 words per row, masks step: 8192 -> 0.883 ms, 6144 0.851, 4096 0.848, 3072 0.828, 2560 0.839, 2048 0.847,
-// 1536 0.891: smaller segments mean more blocks per CU for a chain of dependent loads, and more passes over the entries)
-#ifndef RH_UNP_BLOCK
-#define RH_UNP_BLOCK 512      // threads per block of the multi-segment form
-#endif
-#ifndef RH_UNP_MULTI
-#define RH_UNP_MULTI 3072     // words per output segment of rows that need several
-#endif
-constexpr int S4_UNP_WORDS = 8192, S4_UNP_WORDS_MULTI = RH_UNP_MULTI;
-constexpr int S6_UNROLL = 4;
-
-// WAVEWORD (rows of one segment): a wave per entry, a lane per bit -- the word's 64 positions are one coalesced load and
-// every set bit lands in the block's segment; four entries in flight per wave (round 3's inner loop, fed from the list)
-template <bool WAVEWORD, int BLK = 512>
-__global__ void __launch_bounds__(BLK)
-unpermute6_kernel(const rh_u64x2 *__restrict__ ent, const int32_t *__restrict__ cursor, int64_t mstride, const int32_t *__restrict__ perm,
-                  int64_t swords, int64_t seg_words, const uint64_t *__restrict__ segmask, int64_t smstride, uint64_t *__restrict__ out)
-{
-    extern __shared__ unsigned long long seg[];
-    __shared__ uint32_t ring[BLK / 64][128];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t row = blockIdx.x;
-    const int64_t w0 = (int64_t)blockIdx.y * seg_words;
-    const int nw = (int)(swords - w0 < seg_words ? swords - w0 : seg_words);
-    for (int t = threadIdx.x; t < nw; t += BLK) seg[t] = 0ULL;
-    const int n = min(cursor[row], (int32_t)mstride);
-    __syncthreads();
-    const int32_t lo = (int32_t)(w0 << 6), span = nw << 6;
-    const rh_u64x2 *__restrict__ src = ent + row * mstride;
-    const uint64_t *__restrict__ sm = segmask != nullptr ? segmask + (int64_t)blockIdx.y * smstride : nullptr;
-    if (WAVEWORD) {
-        for (int i0 = wv * 4; i0 < n; i0 += (BLK / 64) * 4) {
-            rh_u64x2 e[4];
-            int32_t j[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                e[k] = src[min(i0 + k, n - 1)];
-                j[k] = perm[((int64_t)e[k].x << 6) + lane] - lo;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (i0 + k < n && ((e[k].y >> lane) & 1ULL) && j[k] >= 0 && j[k] < span) atomicOr(&seg[j[k] >> 6], 1ULL << (j[k] & 63));
-        }
-        __syncthreads();
-        uint64_t *__restrict__ dstw = out + row * swords + w0;
-        for (int t = threadIdx.x; t < nw; t += BLK) dstw[t] = seg[t];
-        return;
-    }
-    int head = 0, fill = 0;   // the wave's ring (wave-uniform)
-    auto drain = [&](int k) {
-        wave_lds_sync();
-        if (lane < k) {
-            const uint32_t e = ring[wv][(head + lane) & 127];
-            const int32_t j = perm[e] - lo;
-            if (j >= 0 && j < span) atomicOr(&seg[j >> 6], 1ULL << (j & 63));
-        }
-        head = (head + k) & 127;
-        fill -= k;
-    };
-    for (int i0 = threadIdx.x; i0 - lane < n; i0 += BLK * S6_UNROLL) {   // (whole waves stay in the loop: ballots)
-        rh_u64x2 e[S6_UNROLL];
-#pragma unroll
-        for (int k = 0; k < S6_UNROLL; k++) {
-            const int i = i0 + k * BLK;
-            e[k].x = 0; e[k].y = 0;
-            if (i < n) e[k] = src[i];
-        }
-        uint64_t m[S6_UNROLL];
-#pragma unroll
-        for (int k = 0; k < S6_UNROLL; k++) m[k] = (sm != nullptr && e[k].y != 0) ? (e[k].y & sm[e[k].x]) : e[k].y;
-#pragma unroll
-        for (int k = 0; k < S6_UNROLL; k++) {
-            const uint32_t gbase = (uint32_t)e[k].x << 6;
-            uint64_t mm = m[k];
-            for (;;) {
-                const bool has = mm != 0;
-                const uint64_t hm = WB(has);
-                if (hm == 0) break;
-                const int bit = has ? __builtin_ctzll(mm) : 0;
-                mm &= mm - 1;
-                const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0));
-                if (has) ring[wv][(head + fill + rank) & 127] = gbase + (uint32_t)bit;
-                fill += __popcll(hm);
-                if (fill >= 64) drain(64);
-            }
-        }
-    }
-    if (fill > 0) drain(fill);
-    __syncthreads();
-    uint64_t *__restrict__ dst = out + row * swords + w0;
-    for (int t = threadIdx.x; t < nw; t += BLK) dst[t] = seg[t];
-}
-
-__global__ void clear_cursors_kernel(int32_t *__restrict__ cursor, int32_t b)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < b) cursor[i] = 0;
-}
-
-// segmask[seg * smstride + g]: bit b set <=> point b of internal word g has its subset position in output segment seg
-__global__ void segmask_kernel(const int32_t *__restrict__ perm, int64_t s, int64_t ngroups, int64_t seg_bits, int nseg, int64_t smstride,
-                               uint64_t *__restrict__ segmask)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= ngroups) return;
-    for (int sgi = 0; sgi < nseg; sgi++) {
-        uint64_t m = 0;
-        for (int b = 0; b < 64; b++) {
-            const int64_t i = (g << 6) + b;
-            if (i < s && (int64_t)perm[i] / seg_bits == sgi) m |= 1ULL << b;
-        }
-        segmask[(int64_t)sgi * smstride + g] = m;
-    }
-}
-
-// binary32 boxes of the groups from the binary64 ones (7 planes of gstride doubles): 8 floats per group
-__global__ void gb32_kernel(const double *__restrict__ gb, int64_t gstride, int64_t ngroups, float *__restrict__ out)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= ngroups) return;
-    const double c[3] = { gb[g], gb[gstride + g], gb[2 * gstride + g] };
-    const double h[3] = { gb[3 * gstride + g], gb[4 * gstride + g], gb[5 * gstride + g] };
-    float o[8];
-    box_to_f32(c, h, o);
-#pragma unroll
-    for (int k = 0; k < 8; k++) out[g * 8 + k] = o[k];
-}
-
-// boxes of runs of k consecutive groups (k = S4_STG: the super-tiles, k = S4_TG: the tiles): the union of the groups' boxes,
-// widened by what the unions' own arithmetic can lose, then made binary32 like a group's.  A group box that is not finite
-// makes the union's NaN: never skipped.
-__global__ void st32_kernel(const double *__restrict__ gb, int64_t gstride, int64_t ngroups, int k_groups, int64_t nst, float *__restrict__ out)
-{
-    const int64_t st = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (st >= nst) return;
-    double lo[3] = { __builtin_inf(), __builtin_inf(), __builtin_inf() }, hi[3] = { -__builtin_inf(), -__builtin_inf(), -__builtin_inf() };
-    bool bad = false;
-    for (int64_t g = st * k_groups; g < (st + 1) * k_groups && g < ngroups; g++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const double cc = gb[k * gstride + g], hh = gb[(3 + k) * gstride + g];
-            bad |= !(fabs(cc) < __builtin_inf()) || !(fabs(hh) < __builtin_inf());
-            lo[k] = fmin(lo[k], cc - hh);
-            hi[k] = fmax(hi[k], cc + hh);
-        }
-    double c3[3], h3[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        c3[k] = 0.5 * lo[k] + 0.5 * hi[k];
-        // (cc -+ hh above and the two differences below each round once: a few ulps of the LARGEST magnitude involved, not of h)
-        h3[k] = fmax(hi[k] - c3[k], c3[k] - lo[k]) * 1.000000000001 + (fabs(lo[k]) + fabs(hi[k])) * 1e-15;
-        bad |= !(fabs(c3[k]) < __builtin_inf()) || !(h3[k] < __builtin_inf());
-    }
-    float o[8];
-    box_to_f32(c3, h3, o);
-#pragma unroll
-    for (int k = 0; k < 8; k++) out[st * 8 + k] = bad ? __builtin_nanf("") : o[k];
-}
-
-// normal-cell masks of the groups (score4_device.h): a wave per group, lane = point; every point of the group counts, enabled
-// or not.  out: 4 words per group (96 bits + 0).  maxlen: the largest finite normal length seen (bits of a non-negative double).
-__global__ void __launch_bounds__(256)
-nsig_kernel(const double *__restrict__ pts, int64_t stride, int64_t s, int64_t ngroups, uint32_t *__restrict__ out, unsigned long long *__restrict__ maxlen)
-{
-    __shared__ uint32_t m[4][4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t g = (int64_t)blockIdx.x * 4 + wv;
-    if (lane < 4) m[wv][lane] = 0u;
-    __syncthreads();
-    const int64_t i = g * 64 + lane;
-    double len = 0.0;
-    if (g < ngroups && i < s) {
-        const double nx = pts[3 * stride + i], ny = pts[4 * stride + i], nz = pts[5 * stride + i];
-        uint32_t w[3];
-        nsig_point_bits(nx, ny, nz, w);
-        if (w[0] != 0u) atomicOr(&m[wv][0], w[0]);
-        if (w[1] != 0u) atomicOr(&m[wv][1], w[1]);
-        if (w[2] != 0u) atomicOr(&m[wv][2], w[2]);
-        const double l = sqrt((nx * nx + ny * ny) + nz * nz);
-        if (l < __builtin_inf()) len = l;   // (NaN and inf: not a length; such a normal sets no bit or all of them)
-    }
-    unsigned long long lb = __builtin_bit_cast(unsigned long long, len);
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long v = __shfl_down(lb, off); lb = v > lb ? v : lb; }
-    if (lane == 0 && lb != 0ULL) atomicMax(maxlen, lb);
-    __syncthreads();
-    if (g < ngroups && lane < 4) out[g * 4 + lane] = m[wv][lane];
-}
-
-// ... of the super-tiles: the OR of their groups' masks
-__global__ void nsig_st_kernel(const uint32_t *__restrict__ gm, int64_t ngroups, int k_groups, int64_t nst, uint32_t *__restrict__ out)
-{
-    const int64_t st = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (st >= nst) return;
-    uint32_t w[4] = { 0u, 0u, 0u, 0u };
-    for (int64_t g = st * k_groups; g < (st + 1) * k_groups && g < ngroups; g++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) w[k] |= gm[g * 4 + k];
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[st * 4 + k] = w[k];
-}
-
 // ---- the super-tile lists of a batch.  One block per (super-tile, kind): the kind's candidates in bin order, 256 at a time,
 // lane = candidate, the culling record against the super-tile's box with the very test of stage 1 (box_skip32: a box that
 // holds all the points of its groups may be skipped only when none of them can pass) -- the survivors' bin slots, in order.
@@ -1113,61 +646,7 @@ st_cull_kernel(const StCullArgs A)
     }
 }
 
-inline int cdiv4(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
-
 }  // namespace
-
-int rhk_gb32_build(rh_cloud *c)
-{
-    if (c->ngroups == 0 || c->gb32 == nullptr) return RH_OK;
-    hipLaunchKernelGGL(gb32_kernel, dim3(cdiv4(c->ngroups, 256)), dim3(256), 0, c->stream, c->gb, c->ng_pad, c->ngroups, c->gb32);
-    if (c->st32 != nullptr && c->nst > 0)
-        hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->nst, 64)), dim3(64), 0, c->stream, c->gb, c->ng_pad, c->ngroups, S4_STG, c->nst, c->st32);
-    if (c->tile32 != nullptr && c->ntile > 0)
-        hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->ntile, 64)), dim3(64), 0, c->stream, c->gb, c->ng_pad, c->ngroups, S4_TG, c->ntile, c->tile32);
-    RH_HIP(hipGetLastError());
-    // the normal-cell masks of subset 1 (score4_device.h), once per cloud: the points' normals never change, and the masks
-    // do not look at the enabled bits.  The largest normal length comes back with them (one wait, at creation).
-    c->nrm_len = 0.0;
-    if (c->gm32 != nullptr && c->stm32 != nullptr && c->s > 0) {
-        rh_dev<unsigned long long> d_len;
-        RH_TRY(d_len.alloc(1));
-        RH_HIP(hipMemsetAsync(d_len, 0, sizeof(unsigned long long), c->stream));
-        hipLaunchKernelGGL(nsig_kernel, dim3(cdiv4(c->ngroups, 4)), dim3(256), 0, c->stream, c->sub, c->s_pad, c->s, c->ngroups, c->gm32, d_len);
-        hipLaunchKernelGGL(nsig_st_kernel, dim3(cdiv4(c->nst, 64)), dim3(64), 0, c->stream, c->gm32, c->ngroups, S4_STG, c->nst, c->stm32);
-        RH_HIP(hipGetLastError());
-        unsigned long long h_len = 0;
-        RH_HIP(hipMemcpyAsync(&h_len, d_len, sizeof h_len, hipMemcpyDeviceToHost, c->stream));
-        RH_HIP(hipStreamSynchronize(c->stream));
-        c->nrm_len = __builtin_bit_cast(double, h_len);
-    }
-    return RH_OK;
-}
-
-// the same for the plane order (kdorder.hip): boxes and normal-cell masks of the 64-point groups of c->pl_sub and of its
-// super-tiles, by the kernels that make the leaf order's.  Once per cloud; waits for the stream (the binary64 boxes are a
-// temporary of the call).
-int rhk_plane_boxes(rh_cloud *c)
-{
-    if (c->pl_sub == nullptr || c->ngroups == 0) return RH_OK;
-    rh_dev<double> gb;
-    rh_dev<unsigned long long> d_len;
-    RH_TRY(gb.alloc(7 * c->ng_pad));
-    RH_TRY(d_len.alloc(1));
-    RH_HIP(hipMemsetAsync(gb, 0, sizeof(double) * 7 * (size_t)c->ng_pad, c->stream));
-    RH_HIP(hipMemsetAsync(d_len, 0, sizeof(unsigned long long), c->stream));
-    RH_HIP(hipMemsetAsync(c->pl_gb32, 0, sizeof(float) * 8 * (size_t)c->ng_pad, c->stream));
-    RH_HIP(hipMemsetAsync(c->pl_gm32, 0, sizeof(uint32_t) * 4 * (size_t)c->ng_pad, c->stream));
-    RH_TRY(rhk_group_bounds_of(c, c->pl_sub, c->s_pad, c->s, c->ngroups, gb, c->ng_pad));
-    hipLaunchKernelGGL(gb32_kernel, dim3(cdiv4(c->ngroups, 256)), dim3(256), 0, c->stream, gb, c->ng_pad, c->ngroups, c->pl_gb32);
-    hipLaunchKernelGGL(nsig_kernel, dim3(cdiv4(c->ngroups, 4)), dim3(256), 0, c->stream, c->pl_sub, c->s_pad, c->s, c->ngroups, c->pl_gm32, d_len);
-    // (16 consecutive groups of the plane order are another point set than 16 of the leaf order: boxes and masks of their own)
-    hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->nst, 64)), dim3(64), 0, c->stream, gb, c->ng_pad, c->ngroups, S4_STG, c->nst, c->pl_st32);
-    hipLaunchKernelGGL(nsig_st_kernel, dim3(cdiv4(c->nst, 64)), dim3(64), 0, c->stream, c->pl_gm32, c->ngroups, S4_STG, c->nst, c->pl_stm32);
-    RH_HIP(hipGetLastError());
-    RH_HIP(hipStreamSynchronize(c->stream));
-    return RH_OK;
-}
 
 // "plane_order" (read on every launch; 0 = by size, 1 = whenever the cloud has the order, 2 = never): do plane candidates walk
 // the plane order of subset 1?  By size: from RH_PLANE_ORDER_MIN_TILES tiles on.  The order removes plane pairs -- vector
@@ -1179,7 +658,7 @@ int rhk_plane_boxes(rh_cloud *c)
 #ifndef RH_PLANE_ORDER_MIN_TILES
 #define RH_PLANE_ORDER_MIN_TILES 256
 #endif
-static bool plane_order_wanted(const rh_cloud *c)
+bool rhk_plane_order_wanted(const rh_cloud *c)
 {
     if (c->pl_sub == nullptr) return false;
     const int64_t opt = rh_opt_int(c, RH_OPT_PLANE_ORDER, 0);
@@ -1227,14 +706,14 @@ int rhk_score4_all(rh_cloud *c, rh_batch_ws &w, const rh_score_job &job, int32_t
     for (int k = 0; k < 4; k++)
         A.k[k] = { (const rh_cls *)B.cls[k], B.box[k], B.prep[k], B.orig[k], job.nk[k], job.en[k], job.eps[k], job.cosa[k],
                    PS.pts, PS.stride, PS.gb32, nsig_on ? (const uint32_t *)c->gm32 : nullptr };
-    // "plane_order" (plane_order_wanted: by size, always, never): the plane candidates of a counts-only launch on subset 1 walk the
+    // "plane_order" (rhk_plane_order_wanted: by size, always, never): the plane candidates of a counts-only launch on subset 1 walk the
     // cloud's plane order (kdorder.hip) -- the same points, inside every node of the position tree with at most 1024 points
     // grouped by their normals, so that a group's normal-cell mask holds 8 cells instead of 18 (cfg3) and a third fewer (plane,
     // group) pairs survive stage 1.  The culling rules are sound for ANY grouping of the points and a count is a sum over
     // points: the counts are the same, bit for bit.  The plane lists of the launch (st_cull_kernel) are cut by the boxes and
     // masks of the plane order's own super-tiles.  Mask launches keep the leaf order (their inlier words are numbered by it),
     // and so do the diag build's skeleton modes.  The enabled words: the cloud's plane-order twin of sub_enabled, or none.
-    const bool plane_on = on_subset && d_masks_int == nullptr && dbg == 0 && plane_order_wanted(c) &&
+    const bool plane_on = on_subset && d_masks_int == nullptr && dbg == 0 && rhk_plane_order_wanted(c) &&
                           (job.en[RH_PLANE] == nullptr || job.en[RH_PLANE] == c->sub_enabled.get());
     if (plane_on) {
         S4KindArgs &P = A.k[RH_PLANE];
@@ -1428,414 +907,8 @@ int rhk_score4_dis(rh_cloud *c, int64_t first, int64_t cnt, rh_score_job job)
     const int64_t ng = (cnt + 63) / 64;
     if (ng > c->ng_pad) { rh_set_error("rhk_score4_dis: %lld groups", (long long)ng); return RH_E_INTERNAL; }
     RH_TRY(rhk_group_bounds_of(c, c->dis + first, c->dis_stride, cnt, ng, c->dis_gb, c->ng_pad));
-    hipLaunchKernelGGL(gb32_kernel, dim3(cdiv4(ng, 256)), dim3(256), 0, c->stream, c->dis_gb, c->ng_pad, ng, c->dis_gb32);
+    rhk_gb32_of(c, c->dis_gb, ng, c->dis_gb32);
     RH_HIP(hipGetLastError());
     job.points = { c->dis + first, c->dis_stride, cnt, ng, c->dis_gb32 };
     return rhk_score4_all(c, c->ws[0], job);   // (no lists over another set than subset 1: w is not touched)
-}
-
-#ifdef RH_DIAG
-// diagnostics (tests): the classifier's worst binary32 error on a batch, in units of its margin widths (see
-// cls_audit_kernel); out[12]: per kind (plane, sphere, cylinder, -) the two maxima, then the numbers of pairs
-extern "C" int rh_dbg_cls_audit(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, double *out)
-{
-    if (c == nullptr || out == nullptr || p == nullptr || b < 0 || (b > 0 && shapes == nullptr)) { rh_set_error("rh_dbg_cls_audit: bad arguments"); return RH_E_INVALID; }
-    for (int i = 0; i < 12; i++) out[i] = 0.0;
-    if (b == 0 || c->s == 0) return RH_OK;
-    RH_HIP(hipSetDevice(c->device));
-    std::vector<S4AuditCand> h((size_t)b);
-    for (int32_t i = 0; i < b; i++) {
-        S4AuditCand &Q = h[(size_t)i];
-        Q.kind = shapes[i].kind;
-        Q.usable = 0;
-        if (Q.kind < 0 || Q.kind > 3) continue;
-        rh_prep_host(shapes[i], &Q.P);
-        double d4[4] = { 0, 0, 0, 0 };
-        cls_make(Q.P, Q.kind, p->eps[Q.kind], p->cos_alpha[Q.kind], c->coord_mag, c->nrm_mag, Q.C, nullptr, 0, d4, c->f32);
-        Q.cNhi = d4[0]; Q.wN = d4[1]; Q.eDlo = d4[2]; Q.wD = d4[3]; Q.cosa = p->cos_alpha[Q.kind]; Q.eps = p->eps[Q.kind];
-        Q.usable = !(Q.C.f[RH_CLS_FLAG] != Q.C.f[RH_CLS_FLAG]) && Q.wN > 0 && Q.wD > 0;
-    }
-    rh_dev<S4AuditCand> d_c;
-    rh_dev<unsigned long long> d_o;
-    RH_TRY(d_c.alloc(b));
-    RH_TRY(d_o.alloc(12));
-    RH_HIP(hipMemcpyAsync(d_c, h.data(), sizeof(S4AuditCand) * (size_t)b, hipMemcpyHostToDevice, c->stream));
-    RH_HIP(hipMemsetAsync(d_o, 0, sizeof(unsigned long long) * 12, c->stream));
-    for (int32_t c0 = 0; c0 < b; c0 += 32768) {
-        const int32_t nb = std::min<int32_t>(32768, b - c0);
-        hipLaunchKernelGGL(cls_audit_kernel, dim3((unsigned)cdiv4(c->s, 256), (unsigned)nb), dim3(256), 0, c->stream, c->sub, c->s_pad,
-                           c->s, d_c + c0, nb, d_o);
-    }
-    unsigned long long ho[12];
-    RH_HIP(hipMemcpyAsync(ho, d_o, sizeof ho, hipMemcpyDeviceToHost, c->stream));
-    RH_HIP(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 8; i++) out[i] = __builtin_bit_cast(double, ho[i]);
-    for (int i = 8; i < 12; i++) out[i] = (double)ho[i];
-    return RH_OK;
-}
-
-// diagnostics (tests, tools/fuzz_score.py): the decisions of the box test and of the classifier against the exact test
-// on every (candidate, point) of a batch x subset 1 (all points taken as enabled): 72 counters, layout at sound_one.
-// rh_dbg_cls_soundness hands out the first 56 (its callers' buffers hold that many), rh_dbg_cls_soundness_tiles the 8 of the
-// tile level, rh_dbg_cls_soundness_nsig the 4 of the normal-cell masks.
-static int cls_soundness_run(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out, const int first, const int nout)
-{
-    if (c == nullptr || out == nullptr || p == nullptr || b < 0 || (b > 0 && shapes == nullptr)) { rh_set_error("rh_dbg_cls_soundness: bad arguments"); return RH_E_INVALID; }
-    for (int i = 0; i < nout; i++) out[i] = 0;
-    if (b == 0 || c->s == 0 || c->ngroups == 0 || c->gb32 == nullptr || c->st32 == nullptr || c->tile32 == nullptr || c->gm32 == nullptr || c->stm32 == nullptr) return RH_OK;
-    RH_HIP(hipSetDevice(c->device));
-    std::vector<S4SoundCand> h((size_t)b);
-    for (int32_t i = 0; i < b; i++) {
-        S4SoundCand &Q = h[(size_t)i];
-        Q.kind = shapes[i].kind;
-        Q.pad = 0;
-        if (Q.kind < 0 || Q.kind > 3) { Q.kind = -1; continue; }
-        rh_prep_host(shapes[i], &Q.P);
-        Q.Pf = prepf_of_kind(Q.P, Q.kind);
-        cls_make(Q.P, Q.kind, p->eps[Q.kind], p->cos_alpha[Q.kind], c->coord_mag, c->nrm_mag, Q.C, Q.box, 1, nullptr, c->f32, c->nrm_len);
-    }
-    S4SoundArgs A;
-    for (int k = 0; k < 4; k++) { A.eps[k] = p->eps[k]; A.cosa[k] = p->cos_alpha[k]; }
-    A.f32 = c->f32 ? 1 : 0;
-    rh_dev<S4SoundCand> d_c;
-    rh_dev<unsigned long long> d_o;
-    RH_TRY(d_c.alloc(b));
-    RH_TRY(d_o.alloc(72));
-    RH_HIP(hipMemcpyAsync(d_c, h.data(), sizeof(S4SoundCand) * (size_t)b, hipMemcpyHostToDevice, c->stream));
-    RH_HIP(hipMemsetAsync(d_o, 0, sizeof(unsigned long long) * 72, c->stream));
-    // The census describes what the score kernel walks: with the plane order in use ("plane_order"), the plane candidates meet
-    // the plane-order groups -- their points, boxes and masks, those of the plane order's super-tiles, and the boxes of runs of
-    // S4_TG of them, made here -- and the other kinds the leaf order's.
-    const bool pl = plane_order_wanted(c);
-    const dim3 grid((unsigned)c->ngroups, (unsigned)std::min<int32_t>(b, 64));
-    hipLaunchKernelGGL(cls_sound_kernel, grid, dim3(64), 0, c->stream, c->sub, c->s_pad, c->s, c->gb32, c->st32, c->tile32, c->gm32, c->stm32, d_c, b, A,
-                       pl ? 0xe : 0xf, d_o);
-    rh_dev<double> pl_gb;
-    rh_dev<float> pl_tile32;
-    if (pl) {
-        RH_TRY(pl_gb.alloc(7 * c->ng_pad));
-        RH_TRY(pl_tile32.alloc(8 * std::max<int64_t>(1, c->ntile)));
-        RH_HIP(hipMemsetAsync(pl_gb, 0, sizeof(double) * 7 * (size_t)c->ng_pad, c->stream));
-        RH_TRY(rhk_group_bounds_of(c, c->pl_sub, c->s_pad, c->s, c->ngroups, pl_gb, c->ng_pad));
-        hipLaunchKernelGGL(st32_kernel, dim3(cdiv4(c->ntile, 64)), dim3(64), 0, c->stream, pl_gb, c->ng_pad, c->ngroups, S4_TG, c->ntile, pl_tile32);
-        hipLaunchKernelGGL(cls_sound_kernel, grid, dim3(64), 0, c->stream, c->pl_sub, c->s_pad, c->s, c->pl_gb32, c->pl_st32, pl_tile32, c->pl_gm32, c->pl_stm32, d_c,
-                           b, A, 0x1, d_o);
-    }
-    RH_HIP(hipGetLastError());
-    unsigned long long ho[72];
-    RH_HIP(hipMemcpyAsync(ho, d_o, sizeof ho, hipMemcpyDeviceToHost, c->stream));
-    RH_HIP(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < nout; i++) out[i] = (uint64_t)ho[first + i];
-    return RH_OK;
-}
-
-extern "C" int rh_dbg_cls_soundness(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out)
-{
-    return cls_soundness_run(c, shapes, b, p, out, 0, 56);
-}
-
-// the tile level of the same census: out[k] = pairs (candidate, group) whose TILE's box rules the candidate out -- the pairs the
-// tile lists keep from the score launch --, out[4 + k] = VIOLATION: such a pair with an exact inlier
-extern "C" int rh_dbg_cls_soundness_tiles(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out)
-{
-    return cls_soundness_run(c, shapes, b, p, out, 56, 8);
-}
-
-// the normal-cell masks in the same census (planes): out[0] = pairs (candidate, group) the group's mask rules out, out[1] =
-// VIOLATION: such a pair with an exact inlier, out[2] / out[3] = the same for the super-tile's mask
-extern "C" int rh_dbg_cls_soundness_nsig(rh_cloud *c, const rh_shape *shapes, int32_t b, const rh_params *p, uint64_t *out)
-{
-    return cls_soundness_run(c, shapes, b, p, out, 64, 4);
-}
-
-// the candidate mask as the host builds it (cls_make on rh_prep_host's record: what the staged path uploads), and the cell
-// function on `ndirs` directions (-1: a zero or NaN vector, -2: an infinite component).  Host only: needs no GPU.
-extern "C" int rh_dbg_nsig(const rh_shape *shape, const rh_params *p, double M, double Nm, double Ln, int f32, uint32_t *mask_out,
-                           const double *dirs, int64_t ndirs, int32_t *cells_out)
-{
-    if (p == nullptr || ndirs < 0 || (ndirs > 0 && (dirs == nullptr || cells_out == nullptr)) || (shape != nullptr && mask_out == nullptr)) {
-        rh_set_error("rh_dbg_nsig: bad arguments");
-        return RH_E_INVALID;
-    }
-    if (shape != nullptr) {
-        if (shape->kind != RH_PLANE) { rh_set_error("rh_dbg_nsig: planes only"); return RH_E_INVALID; }
-        rh_prep P;
-        rh_prep_host(*shape, &P);
-        rh_cls C;
-        float box[RH_BOX_FIELDS];
-        cls_make(P, RH_PLANE, p->eps[RH_PLANE], p->cos_alpha[RH_PLANE], M, Nm, C, box, 1, nullptr, f32 != 0, Ln);
-        for (int k = 0; k < 3; k++) mask_out[k] = __builtin_bit_cast(uint32_t, box[5 + k]);
-    }
-    for (int64_t i = 0; i < ndirs; i++) {
-        uint32_t w[3];
-        nsig_point_bits(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], w);
-        if ((w[0] & w[1] & w[2]) == 0xffffffffu) cells_out[i] = -2;
-        else if ((w[0] | w[1] | w[2]) == 0u) cells_out[i] = -1;
-        else cells_out[i] = nsig_cell(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
-    }
-    return RH_OK;
-}
-
-// the binary64 boxes of the 64-point groups of subset 1, in group order: out[6 g ..] = centre, half extents; *ngroups_out: how
-// many there are (out = null or cap too small: only the number)
-extern "C" int rh_dbg_group_boxes(rh_cloud *c, double *out, int64_t cap, int64_t *ngroups_out)
-{
-    if (c == nullptr || ngroups_out == nullptr || cap < 0) { rh_set_error("rh_dbg_group_boxes: bad arguments"); return RH_E_INVALID; }
-    *ngroups_out = c->gb == nullptr ? 0 : c->ngroups;
-    if (out == nullptr || cap < *ngroups_out || *ngroups_out == 0) return RH_OK;
-    RH_HIP(hipSetDevice(c->device));
-    std::vector<double> h((size_t)c->ngroups * 6);
-    const double *gb = c->gb;
-    for (int k = 0; k < 6; k++)
-        RH_HIP(hipMemcpyAsync(h.data() + (size_t)k * c->ngroups, gb + (int64_t)k * c->ng_pad, sizeof(double) * (size_t)c->ngroups, hipMemcpyDeviceToHost, c->stream));
-    RH_HIP(hipStreamSynchronize(c->stream));
-    for (int64_t g = 0; g < c->ngroups; g++)
-        for (int k = 0; k < 6; k++) out[6 * g + k] = h[(size_t)k * c->ngroups + g];
-    return RH_OK;
-}
-
-// the cylinder's box test as the host runs it: the culling record cls_make builds for the shape (fields_out[RH_BOX_FIELDS]), and
-// for each of the n binary64 boxes (centre, half extents: boxes[6 i ..]), converted by box_to_f32 like a group's, the decision
-// of the kernel's own function (skip_out) and of its two ball clauses alone (ball_out).  Host only: needs no GPU.
-extern "C" int rh_dbg_cylbox(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, const double *boxes, int64_t n,
-                             uint8_t *skip_out, uint8_t *ball_out, float *fields_out)
-{
-    if (shape == nullptr || p == nullptr || n < 0 || (n > 0 && (boxes == nullptr || skip_out == nullptr || ball_out == nullptr))) {
-        rh_set_error("rh_dbg_cylbox: bad arguments");
-        return RH_E_INVALID;
-    }
-    if (shape->kind != RH_CYLINDER) { rh_set_error("rh_dbg_cylbox: cylinders only"); return RH_E_INVALID; }
-    rh_prep P;
-    rh_prep_host(*shape, &P);
-    rh_cls C;
-    float box[RH_BOX_FIELDS];
-    cls_make(P, RH_CYLINDER, p->eps[RH_CYLINDER], p->cos_alpha[RH_CYLINDER], M, Nm, C, box, 1, nullptr, f32 != 0);
-    if (fields_out != nullptr)
-        for (int k = 0; k < RH_BOX_FIELDS; k++) fields_out[k] = box[k];
-    for (int64_t i = 0; i < n; i++) {
-        float o[8];
-        box_to_f32(boxes + 6 * i, boxes + 6 * i + 3, o);
-        rh_box32 G;
-        G.cx = o[0]; G.cy = o[1]; G.cz = o[2]; G.hx = o[3]; G.hy = o[4]; G.hz = o[5]; G.hr = o[6];
-        skip_out[i] = cyl_box_skip32<true>(box, G) ? 1 : 0;
-        ball_out[i] = cyl_box_skip32<false>(box, G) ? 1 : 0;
-    }
-    return RH_OK;
-}
-
-// the classifier of a round candidate as the host runs it: the record cls_make builds for the shape, its margins (dbg4: m2, W2,
-// mv, Wv) and the kernel's own cls_round_ab on n points.  Host only: needs no GPU.
-extern "C" int rh_dbg_cls_round(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
-                                const double *nrm, float *ua_out, float *ub_out, float *rec_out, double *dbg4_out)
-{
-    if (shape == nullptr || p == nullptr || n < 0 || (n > 0 && (xyz == nullptr || nrm == nullptr || ua_out == nullptr || ub_out == nullptr))) {
-        rh_set_error("rh_dbg_cls_round: bad arguments");
-        return RH_E_INVALID;
-    }
-    if (shape->kind != RH_SPHERE && shape->kind != RH_CYLINDER) { rh_set_error("rh_dbg_cls_round: spheres and cylinders only"); return RH_E_INVALID; }
-    rh_prep P;
-    rh_prep_host(*shape, &P);
-    rh_cls C;
-    double d4[4] = { 0, 0, 0, 0 };
-    cls_make(P, shape->kind, p->eps[shape->kind], p->cos_alpha[shape->kind], M, Nm, C, nullptr, 0, d4, f32 != 0);
-    if (rec_out != nullptr)
-        for (int k = 0; k < 16; k++) rec_out[k] = C.f[k];
-    if (dbg4_out != nullptr)
-        for (int k = 0; k < 4; k++) dbg4_out[k] = d4[k];
-    for (int64_t i = 0; i < n; i++) {
-        const float x = (float)xyz[3 * i], y = (float)xyz[3 * i + 1], z = (float)xyz[3 * i + 2];
-        const float nx = (float)nrm[3 * i], ny = (float)nrm[3 * i + 1], nz = (float)nrm[3 * i + 2];
-        if (shape->kind == RH_SPHERE) cls_round_ab<RH_SPHERE>(C, x, y, z, nx, ny, nz, ua_out[i], ub_out[i]);
-        else cls_round_ab<RH_CYLINDER>(C, x, y, z, nx, ny, nz, ua_out[i], ub_out[i]);
-    }
-    return RH_OK;
-}
-
-// the two-bit books of the score kernel's point loops as the host runs them (score4_device.h, "Two-bit books": books2_push and
-// the four read-outs, the very statements of score4_batch): nseq sequences of 64 values u' each, pushed in point order.  Host
-// only: needs no GPU.
-extern "C" int rh_dbg_books2(const float *u2, int64_t nseq, int32_t *sure_count_out, uint64_t *sure_word_out, uint64_t *und_word_out,
-                             uint8_t *any_und_out)
-{
-    if (nseq < 0 || (nseq > 0 && (u2 == nullptr || sure_count_out == nullptr || sure_word_out == nullptr || und_word_out == nullptr || any_und_out == nullptr))) {
-        rh_set_error("rh_dbg_books2: bad arguments");
-        return RH_E_INVALID;
-    }
-    for (int64_t s = 0; s < nseq; s++) {
-        uint32_t w[4] = { 0u, 0u, 0u, 0u };
-        for (int q = 0; q < 4; q++)
-            for (int j = 0; j < 16; j++) w[q] = books2_push(w[q], u2[64 * s + 16 * q + j]);
-        sure_count_out[s] = books2_sure_count(w);
-        sure_word_out[s] = books2_sure64(w);
-        und_word_out[s] = books2_und64(w);
-        any_und_out[s] = books2_any_undecided(w) ? 1 : 0;
-    }
-    return RH_OK;
-}
-
-// u and u' of a plane, sphere or cylinder candidate on n points, on the host: u = max(ua, ub) by the functions every other caller
-// uses on the record cls_make builds, u' by the point loops' own path -- that record doubled by cls_double, then cls_u2.  Host
-// only: needs no GPU.
-extern "C" int rh_dbg_cls_u2(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
-                             const double *nrm, float *u_out, float *u2_out, float *rec_out)
-{
-    if (shape == nullptr || p == nullptr || n < 0 || (n > 0 && (xyz == nullptr || nrm == nullptr || u_out == nullptr || u2_out == nullptr))) {
-        rh_set_error("rh_dbg_cls_u2: bad arguments");
-        return RH_E_INVALID;
-    }
-    const int kind = shape->kind;
-    if (kind != RH_PLANE && kind != RH_SPHERE && kind != RH_CYLINDER) { rh_set_error("rh_dbg_cls_u2: planes, spheres and cylinders only"); return RH_E_INVALID; }
-    rh_prep P;
-    rh_prep_host(*shape, &P);
-    rh_cls C;
-    cls_make(P, kind, p->eps[kind], p->cos_alpha[kind], M, Nm, C, nullptr, 0, nullptr, f32 != 0);
-    if (rec_out != nullptr)
-        for (int k = 0; k < 16; k++) rec_out[k] = C.f[k];
-    rh_cls D = C;
-    if (kind == RH_PLANE) cls_double<RH_PLANE>(D);
-    else if (kind == RH_SPHERE) cls_double<RH_SPHERE>(D);
-    else cls_double<RH_CYLINDER>(D);
-    for (int64_t i = 0; i < n; i++) {
-        const float x = (float)xyz[3 * i], y = (float)xyz[3 * i + 1], z = (float)xyz[3 * i + 2];
-        const float nx = (float)nrm[3 * i], ny = (float)nrm[3 * i + 1], nz = (float)nrm[3 * i + 2];
-        if (kind == RH_PLANE) { u_out[i] = cls_plane_u(C, x, y, z, nx, ny, nz); u2_out[i] = cls_u2<RH_PLANE>(D, x, y, z, nx, ny, nz); }
-        else if (kind == RH_SPHERE) { u_out[i] = cls_round_u<RH_SPHERE>(C, x, y, z, nx, ny, nz); u2_out[i] = cls_u2<RH_SPHERE>(D, x, y, z, nx, ny, nz); }
-        else { u_out[i] = cls_round_u<RH_CYLINDER>(C, x, y, z, nx, ny, nz); u2_out[i] = cls_u2<RH_CYLINDER>(D, x, y, z, nx, ny, nz); }
-    }
-    return RH_OK;
-}
-
-// the cone's box test as the host runs it: the culling record cls_make builds for the shape (fields_out[RH_BOX_FIELDS]), and for
-// each of the n binary64 boxes (centre, half extents: boxes[6 i ..]), converted by box_to_f32 like a group's, the decision of
-// the kernel's own function.  Host only: needs no GPU.
-extern "C" int rh_dbg_conebox(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, const double *boxes, int64_t n,
-                              uint8_t *skip_out, float *fields_out)
-{
-    if (shape == nullptr || p == nullptr || n < 0 || (n > 0 && (boxes == nullptr || skip_out == nullptr))) {
-        rh_set_error("rh_dbg_conebox: bad arguments");
-        return RH_E_INVALID;
-    }
-    if (shape->kind != RH_CONE) { rh_set_error("rh_dbg_conebox: cones only"); return RH_E_INVALID; }
-    rh_prep P;
-    rh_prep_host(*shape, &P);
-    rh_cls C;
-    float box[RH_BOX_FIELDS];
-    cls_make(P, RH_CONE, p->eps[RH_CONE], p->cos_alpha[RH_CONE], M, Nm, C, box, 1, nullptr, f32 != 0);
-    if (fields_out != nullptr)
-        for (int k = 0; k < RH_BOX_FIELDS; k++) fields_out[k] = box[k];
-    for (int64_t i = 0; i < n; i++) {
-        float o[8];
-        box_to_f32(boxes + 6 * i, boxes + 6 * i + 3, o);
-        rh_box32 G;
-        G.cx = o[0]; G.cy = o[1]; G.cz = o[2]; G.hx = o[3]; G.hy = o[4]; G.hz = o[5]; G.hr = o[6];
-        skip_out[i] = cone_box_skip32(box, G) ? 1 : 0;
-    }
-    return RH_OK;
-}
-
-// the classifier of a cone candidate: the record cls_make builds for the shape on the host, its thresholds and widths (dbg4:
-// 0, wL, eD_lo, wD) and the kernel's own cls_cone_ab on n points, on the device (cls_cone_dbg_kernel).  Synchronous.
-extern "C" int rh_dbg_cls_cone(const rh_shape *shape, const rh_params *p, double M, double Nm, int f32, int64_t n, const double *xyz,
-                               const double *nrm, int device, float *ua_out, float *ub_out, uint8_t *near_out, float *rec_out, double *dbg4_out)
-{
-    if (shape == nullptr || p == nullptr || n < 0 || n > (int64_t)1 << 24 ||
-        (n > 0 && (xyz == nullptr || nrm == nullptr || ua_out == nullptr || ub_out == nullptr || near_out == nullptr))) {
-        rh_set_error("rh_dbg_cls_cone: bad arguments");
-        return RH_E_INVALID;
-    }
-    if (shape->kind != RH_CONE) { rh_set_error("rh_dbg_cls_cone: cones only"); return RH_E_INVALID; }
-    rh_prep P;
-    rh_prep_host(*shape, &P);
-    rh_cls C;
-    double d4[4] = { 0, 0, 0, 0 };
-    cls_make(P, RH_CONE, p->eps[RH_CONE], p->cos_alpha[RH_CONE], M, Nm, C, nullptr, 0, d4, f32 != 0);
-    if (rec_out != nullptr)
-        for (int k = 0; k < 16; k++) rec_out[k] = C.f[k];
-    if (dbg4_out != nullptr)
-        for (int k = 0; k < 4; k++) dbg4_out[k] = d4[k];
-    if (n == 0) return RH_OK;
-    std::vector<float> h((size_t)n * 6);
-    for (int64_t i = 0; i < n; i++)
-        for (int k = 0; k < 3; k++) {
-            h[(size_t)(k * n + i)] = (float)xyz[3 * i + k];
-            h[(size_t)((3 + k) * n + i)] = (float)nrm[3 * i + k];
-        }
-    RH_HIP(hipSetDevice(device));
-    rh_dev<float> d_p, d_a, d_b;
-    rh_dev<uint8_t> d_n;
-    RH_TRY(d_p.alloc(n * 6));
-    RH_TRY(d_a.alloc(n));
-    RH_TRY(d_b.alloc(n));
-    RH_TRY(d_n.alloc(n));
-    RH_HIP(hipMemcpy(d_p, h.data(), sizeof(float) * (size_t)n * 6, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(cls_cone_dbg_kernel, dim3((unsigned)cdiv4(n, 256)), dim3(256), 0, 0, C, (const float *)d_p, n, (float *)d_a, (float *)d_b, (uint8_t *)d_n);
-    RH_HIP(hipGetLastError());
-    RH_HIP(hipMemcpy(ua_out, d_a, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    RH_HIP(hipMemcpy(ub_out, d_b, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    RH_HIP(hipMemcpy(near_out, d_n, (size_t)n, hipMemcpyDeviceToHost));
-    return RH_OK;
-}
-
-#endif   // RH_DIAG
-
-#ifdef RH_DIAG
-// diagnostics: the event counters of the score launches on this cloud (layout: S4_STAT above).  mode 0: read (out[128], null:
-// nothing), 1: switch the counting on and zero the counters, 2: switch it off.  Synchronises the cloud's stream.
-extern "C" int rh_dbg_s4_stats(rh_cloud *c, int mode, uint64_t *out)
-{
-    if (c == nullptr || mode < 0 || mode > 2) { rh_set_error("rh_dbg_s4_stats: bad arguments"); return RH_E_INVALID; }
-    RH_HIP(hipSetDevice(c->device));
-    RH_HIP(hipStreamSynchronize(c->stream));
-    if (mode == 1) {
-        if (c->s4_stats == nullptr) RH_TRY(c->s4_stats.alloc(128));
-        RH_HIP(hipMemset(c->s4_stats, 0, sizeof(unsigned long long) * 128));
-    } else if (mode == 2) {
-        c->s4_stats.reset();
-    } else if (out != nullptr) {
-        for (int i = 0; i < 128; i++) out[i] = 0;
-        if (c->s4_stats != nullptr) RH_HIP(hipMemcpy(out, c->s4_stats, sizeof(unsigned long long) * 128, hipMemcpyDeviceToHost));
-    }
-    return RH_OK;
-}
-#endif   // RH_DIAG
-
-// the entry lists the v4 score kernel left in the workspace (rows of mstride4 16-byte entries, one cursor per row in d_occ) ->
-// dense rows in subset order; the cursors are zero again afterwards
-int rhk_unpermute_masks4(rh_cloud *c, rh_batch_ws &w, int32_t b, uint64_t *d_out)
-{
-    if (b == 0 || c->swords == 0) return RH_OK;
-    const uint64_t *d_in = w.d_masks_int;
-    uint8_t *d_occ = w.d_occ;
-    const int64_t mstride = w.mstride4;
-    const int env_words = (int)rh_opt_int(c, RH_OPT_UNP_WORDS, 0);   // rh_set_option(.., "unp_words", n) (tests; read per call): segments of n words, so that a small cloud's rows span several / many
-    const int64_t seg_words = std::min<int64_t>(c->swords, env_words > 0 ? std::min(env_words, 16384) : (c->swords <= S4_UNP_WORDS ? S4_UNP_WORDS : S4_UNP_WORDS_MULTI));
-    const int nseg = cdiv4(c->swords, seg_words);
-    static bool attr_set = false;
-    if (!attr_set) {
-        RH_HIP(hipFuncSetAttribute((const void *)unpermute6_kernel<false, RH_UNP_BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(uint64_t) * 16384)));
-        RH_HIP(hipFuncSetAttribute((const void *)unpermute6_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(uint64_t) * 16384)));
-        attr_set = true;
-    }
-    const uint64_t *sm = nullptr;
-    if (nseg > 1 && nseg <= 16) {   // which bits of a word belong to which segment: made once per workspace and segment width, on its stream
-        if (w.d_segmask == nullptr || w.segmask_words != seg_words) {
-            w.segmask_words = 0;
-            RH_TRY(w.d_segmask.grow(c->stream, (int64_t)nseg * c->ng_pad));
-            w.segmask_words = seg_words;
-            hipLaunchKernelGGL(segmask_kernel, dim3((unsigned)cdiv4(c->ngroups, 256)), dim3(256), 0, c->stream, c->sub_perm, c->s, c->ngroups,
-                               seg_words * 64, nseg, c->ng_pad, w.d_segmask);
-            RH_HIP(hipGetLastError());
-        }
-        sm = w.d_segmask;
-    }
-    const bool waveword = nseg == 1;
-    if (waveword)
-        hipLaunchKernelGGL(unpermute6_kernel<true>, dim3((unsigned)b, (unsigned)nseg), dim3(512), sizeof(uint64_t) * (size_t)seg_words, c->stream,
-                           (const rh_u64x2 *)d_in, (const int32_t *)d_occ, mstride, c->sub_perm, c->swords, seg_words, sm, c->ng_pad, d_out);
-    else
-        hipLaunchKernelGGL((unpermute6_kernel<false, RH_UNP_BLOCK>), dim3((unsigned)b, (unsigned)nseg), dim3(RH_UNP_BLOCK), sizeof(uint64_t) * (size_t)seg_words, c->stream,
-                           (const rh_u64x2 *)d_in, (const int32_t *)d_occ, mstride, c->sub_perm, c->swords, seg_words, sm, c->ng_pad, d_out);
-    hipLaunchKernelGGL(clear_cursors_kernel, dim3((unsigned)cdiv4(b, 256)), dim3(256), 0, c->stream, (int32_t *)d_occ, b);
-    RH_HIP(hipGetLastError());
-    return RH_OK;
 }

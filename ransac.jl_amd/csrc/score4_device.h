@@ -31,7 +31,7 @@
 //             with G = sqrt(3) Nm (|c'| + |s'|) + |c| + 1/4 and rho, |h| <= sqrt(3) T.  Points next to the axis
 //             (rho^2 <= alpha |w|^2 + beta), where the reference's own frame is ill-conditioned, are always undecided.
 // Every margin is the first-order bound x RH_CLS_SAFETY (2) plus the conversion error of the threshold itself; the
-// binary64 side's own rounding (~1e-15 relative) disappears in that factor.  rh_dbg_cls_audit (score4.hip) evaluates
+// binary64 side's own rounding (~1e-15 relative) disappears in that factor.  rh_dbg_cls_audit (score4_diag.hip) evaluates
 // max |q32 - q64| / (width of the ambiguity band = 2 m) over real batches with these very functions: sound below 1/2,
 // by construction below 1/4 (measured worst 0.21 = 0.84 of the first-order bound); tests/test_parity_gpu.py and
 // tools/cls_audit.py hold it below 0.3.  (Round 3 started with a safety factor of 4 and widths rounded up to powers of
@@ -89,7 +89,7 @@ __host__ __device__ inline double cls_slack64(const rh_prep &P, double M) { retu
 // ---- Normal cells (planes).  The boxes of stage 1 know where a group's points lie, not where their normals point: three
 // quarters of the plane pairs that survive the boxes fail on the normal half of the test in every point.  The unit sphere
 // of directions is cut into RH_NSIG_CELLS = 96 cells (a cube map: 6 faces x 4 x 4); a group of subset 1 carries the set of
-// cells its points' normals fall in (96 bits, made once per cloud: nsig_kernel, score4.hip -- ALL points, enabled or not, so
+// cells its points' normals fall in (96 bits, made once per cloud: nsig_kernel, boxes32.hip -- ALL points, enabled or not, so
 // that the set stays a superset through every extraction), a plane candidate the set of cells that can hold the normal of a
 // point it accepts (cls_make, fields 5-7 of the culling record).  A pair whose two sets do not meet is not walked.
 // Soundness -- a skipped pair holds no inlier:

@@ -1,5 +1,5 @@
 """The census of the box tests on the hostile batch of test_cylbox_gpu.py (diag build: rh_dbg_cls_soundness / _tiles,
-csrc/score4.hip sound_one): no pair that a group's, a tile's or a super-tile's box rules out holds an exact inlier, for any kind;
+csrc/score4_diag.hip sound_one): no pair that a group's, a tile's or a super-tile's box rules out holds an exact inlier, for any kind;
 and the cylinder's box test skips no fewer pairs than its two ball clauses alone, counted on the host with the kernel's own
 function (rh_dbg_cylbox) over the library's group boxes (rh_dbg_group_boxes)."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""The census of the normal-cell masks (diag build: rh_dbg_cls_soundness_nsig, csrc/score4.hip sound_one): over every (plane
+"""The census of the normal-cell masks (diag build: rh_dbg_cls_soundness_nsig, csrc/score4_diag.hip sound_one): over every (plane
 candidate, 64-point group) pair of the hostile batch of test_nsig_gpu.py, the pairs that the group's mask and the super-tile's
 mask rule out, and of those the pairs that hold an exact inlier -- the masks must skip something, and never an inlier."""
 import ctypes as C

@@ -1,5 +1,5 @@
-"""The normal-cell masks of the culled score kernel (csrc/score4_device.h, "normal cells"; score4.hip: nsig_kernel, stage 1 of
-score4_segment, st_cull_kind<plane>; rh_set_option "nsig"): a (plane candidate, 64-point group) pair is not walked when no point
+"""The normal-cell masks of the culled score kernel (csrc/score4_device.h, "normal cells"; boxes32.hip: nsig_kernel; score4.hip: stage 1
+of score4_segment, st_cull_kind<plane>; rh_set_option "nsig"): a (plane candidate, 64-point group) pair is not walked when no point
 of the group has its normal in a cell the candidate can accept, and the list launch drops a plane from a super-tile's list the
 same way.  That changes which pairs are walked, never what a walked pair computes: counts and dense masks must equal the
 oracle's bit for bit, and each other with the masks on ("nsig" = 0) and off (2), with and without lists ("st_cull" 1 / 2), in

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Soundness of the v4 score kernel's shortcuts as a COUNT (rh_dbg_cls_soundness, csrc/score4.hip): over random clouds,
+"""Soundness of the v4 score kernel's shortcuts as a COUNT (rh_dbg_cls_soundness, csrc/score4_diag.hip): over random clouds,
 coordinate scales 1 .. 1e6, eps 1e-6 .. 50, alpha 0.5 .. 120 degrees, candidates from jittered ground truth to
 arbitrary / degenerate / far-away-point shapes (tools/fuzz_score.py's generator), Float64 and Float32 clouds --
   (i)   (candidate, group) pairs the binary32 box test skips although the exact test finds an inlier in the group,
