@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RH_VERSION 124
+#define RH_VERSION 125
 
 enum {
     RH_OK = 0,
@@ -775,6 +775,74 @@ int rh_orient_normals(const double *xyz_aos, const double *nrm_aos, int64_t n, c
                       double *nrm_out_aos, int32_t *flip_out_or_null, int32_t *comp_out_or_null, rh_orient_stats *stats_or_null);
 int rh_orient_normals_f32(const float *xyz_aos, const float *nrm_aos, int64_t n, const rh_orient_params *p, int device,
                           float *nrm_out_aos, int32_t *flip_out_or_null, int32_t *comp_out_or_null, rh_orient_stats *stats_or_null);
+
+/* ---- region growing by smoothness for a cloud with normals (Rabbani et al. 2006: the second detector of PCL and CGAL
+ *      beside RANSAC; no counterpart in the reference, which finds shapes by RANSAC alone) ----
+ * Splits a cloud by its SURFACES where rh_cluster splits it by gaps in space: a detector of its own for piecewise-smooth
+ * scenes, a pre-segmentation with rh_ransac run per region, the points rh_assign_points left without a label into sheets.
+ * The textbook algorithm grows one region after another from a sorted seed list, and its result depends on the seed order
+ * and on which region reaches a point first.  This statement follows rh_cluster's three kinds and depends on no order:
+ * seeds play the core points, smooth neighbour pairs play the eps-neighbourhood, the border rule is "nearest".
+ * Points p_0 .. p_(n-1), normals n_i (binary64 array-of-structures, used as given, not renormalised), optional curvature
+ * c_i (double [n] or null: rh_estimate_normals' curv_out), parameters below.
+ *  1. V = the points whose normal is not (0, 0, 0) (all three components == 0.0).  The degenerate points of
+ *     rh_estimate_normals are outside V, take no part and come back with label 0;
+ *  2. NEIGHBOURS.  N(i) = rh_knn's neighbour list of i for (k, radius), searched over all n points.  i ~ j when j is in
+ *     N(i) or i is in N(j): the undirected graph of rh_orient_normals, step 2;
+ *  3. SMOOTH PAIR, for i ~ j with both in V.  dot = (ni.x*nj.x + ni.y*nj.y) + ni.z*nj.z, each operation rounded on its
+ *     own, no contraction (bit-symmetric in i and j); a = fabs(dot) with RH_SEG_UNSIGNED, dot otherwise.  The pair is
+ *     smooth when a >= cos_angle and, with dist_max > 0, both tangent-plane distances pass: with dx = pj.x - pi.x (dy, dz
+ *     likewise), e_i = (ni.x*dx + ni.y*dy) + ni.z*dz and e_j = (nj.x*(-dx) + nj.y*(-dy)) + nj.z*(-dz) -- negation is
+ *     exact, so the test is symmetric -- fabs(e_i) <= dist_max and fabs(e_j) <= dist_max.  The distance test is what
+ *     separates parallel sheets a step apart, whose normals agree;
+ *  4. SEED.  i in V is a seed when no curvature is given or c_i <= curv_max.  A NaN curvature makes no seed;
+ *  5. REGION.  A region is a connected component of the graph on the seeds whose edges are the smooth pairs.  Two regions
+ *     are never joined through a point that is no seed;
+ *  6. BORDER.  i in V that is no seed and forms a smooth pair with at least one seed j is a border point; it belongs to
+ *     the region of that j with the smallest d2(i, j) (rh_knn's expression), ties to the smaller j.  j may list i without
+ *     i listing j: those pairs count;
+ *  7. every other point has label 0 and kind RH_PT_NOISE.  The kinds are rh_cluster's, RH_PT_CORE meaning seed; after the
+ *     min_size drop a point's kind is what it was before the drop;
+ *  8. min_size and the numbering are rh_cluster's steps 6 and 7, "smallest core point" reading "smallest seed";
+ *  9. labels_out, kind_out, cap, counts, offsets, idx and *n_regions_out behave as in rh_cluster, RH_E_CAPACITY included.
+ *     stats (optional): n_regions = M; n_seed + n_border + n_unassigned + n_invalid = n, where n_invalid = n - |V| and
+ *     n_unassigned = the points of V that are neither a seed nor have a seed to attach to; n_small = the seeds and border
+ *     points of the regions dropped by min_size; largest = the size of the largest region left, 0 when M = 0;
+ * 10. RH_E_INVALID, decided before the device is touched: a null xyz / nrm / params / labels_out / n_regions_out, n < 1,
+ *     n >= 2^31 - 1, n*k >= 2^31, k outside 1 .. RH_KNN_MAX_K, radius negative or not finite, cos_angle not finite or
+ *     outside [-1, 1], curv_max NaN, dist_max negative or not finite, min_size < 1, an unknown order or flag bit, cap < 0;
+ *     found on the device, nothing is written: a coordinate that is not finite, a normal component that is not finite or
+ *     exceeds 2 in magnitude;
+ * 11. the _f32 entry widens coordinates, normals and curvature exactly and decides everything in binary64: its outputs
+ *     equal those of the binary64 call on the widened input.
+ * Every decision is a comparison of binary64 values of fixed expressions or integer arithmetic: the same bits on every run,
+ * whatever the order of processing.  The caller takes the cosine: the library never calls cos().  The array arguments may
+ * be host or device pointers (the copies are hipMemcpyDefault); params, scalars and stats are host memory.  The neighbour
+ * lists never leave the device. */
+#define RH_SEG_UNSIGNED 1
+typedef struct {
+    int32_t k;               /* 1 .. RH_KNN_MAX_K */
+    int32_t flags;           /* RH_SEG_UNSIGNED or 0 */
+    double radius;           /* 0 = no limit (rh_knn's) */
+    double cos_angle;        /* finite, in [-1, 1] */
+    double curv_max;         /* not NaN; ignored without curvature */
+    double dist_max;         /* 0 = no distance test; otherwise finite and > 0 */
+    int32_t min_size;        /* >= 1 */
+    int32_t order;           /* RH_CLUSTER_BY_* */
+} rh_segment_params;
+typedef struct {
+    int64_t n_regions, n_seed, n_border, n_unassigned, n_invalid;
+    int64_t n_small;         /* points of regions below min_size */
+    int64_t largest;
+} rh_segment_stats;
+int rh_segment_smooth(const double *xyz_aos, const double *nrm_aos, const double *curv_or_null, int64_t n,
+                      const rh_segment_params *p, int device, int32_t *labels_out, uint8_t *kind_out_or_null, int64_t cap,
+                      int64_t *counts_out_or_null, int64_t *offsets_out_or_null, int64_t *idx_out_or_null,
+                      int64_t *n_regions_out, rh_segment_stats *stats_or_null);
+int rh_segment_smooth_f32(const float *xyz_aos, const float *nrm_aos, const float *curv_or_null, int64_t n,
+                          const rh_segment_params *p, int device, int32_t *labels_out, uint8_t *kind_out_or_null, int64_t cap,
+                          int64_t *counts_out_or_null, int64_t *offsets_out_or_null, int64_t *idx_out_or_null,
+                          int64_t *n_regions_out, rh_segment_stats *stats_or_null);
 
 /* ---- nearest neighbours of query points in ANOTHER cloud, and cloud-to-cloud distances on them (no counterpart in the
  *      reference, which works on one cloud) ----

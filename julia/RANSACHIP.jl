@@ -739,6 +739,82 @@ function cluster(vertices::AbstractVector{SVector{3,T}}, eps::Real; min_pts::Int
     return resize!(labels, n), resize!(kind, n), resize!(counts, m[] + 1), resize!(offsets, m[] + 2), resize!(idx, n), st[]
 end
 
+# ---- region growing by smoothness for a cloud with normals (rh_segment_smooth) ----
+# typedef struct { int32_t k, flags; double radius, cos_angle, curv_max, dist_max; int32_t min_size, order; } rh_segment_params;   (48 bytes)
+struct RhSegmentParams
+    k::Cint
+    flags::Cint
+    radius::Cdouble
+    cos_angle::Cdouble
+    curv_max::Cdouble
+    dist_max::Cdouble
+    min_size::Cint
+    order::Cint
+end
+# typedef struct { int64_t n_regions, n_seed, n_border, n_unassigned, n_invalid, n_small, largest; } rh_segment_stats;   (56 bytes)
+struct RhSegmentStats
+    n_regions::Int64
+    n_seed::Int64
+    n_border::Int64
+    n_unassigned::Int64
+    n_invalid::Int64
+    n_small::Int64
+    largest::Int64
+end
+
+"""
+    segment_smooth(vertices, normals; curvature = nothing, k = 16, radius = 0, angle = deg2rad(25), curv_max = 0.05,
+                   dist_max = 0, unsigned = false, min_size = 1, order = :size)
+        -> (labels, kind, counts, offsets, idx, stats)
+
+Splits a cloud with normals into its smooth sheets (`rh_segment_smooth`: region growing by smoothness, stated so that
+nothing depends on an order; include/ransac_hip.h has the definition in full).  Two points are linked when one is among
+the other's `k` nearest neighbours, their normals differ by at most `angle` (radians; `unsigned`: up to sign) and, with
+`dist_max > 0`, each lies within `dist_max` of the other's tangent plane.  A point whose curvature is at most `curv_max`
+is a seed (every point with a normal, without `curvature`); regions are the connected components of the seeds, any other
+point joins the region of its nearest linked seed (ties to the smaller index) or has no label, and neither have regions
+below `min_size` points nor points whose normal is (0, 0, 0).  The cosine of `angle` is taken here.  `labels[i]`: 0 for
+none, else 1 to M, by descending size (`:size`) or by the smallest seed's index (`:index`); `kind[i]`: 0 none, 1 border,
+2 seed; `counts`, `offsets` and `idx` as in `cluster`; `stats`: an `RhSegmentStats`.
+"""
+function segment_smooth(vertices::AbstractVector{SVector{3,T}}, normals::AbstractVector{SVector{3,T}};
+                        curvature::Union{Nothing,AbstractVector{T}} = nothing, k::Integer = 16, radius::Real = 0.0,
+                        angle::Real = deg2rad(25.0), curv_max::Real = 0.05, dist_max::Real = 0.0, unsigned::Bool = false,
+                        min_size::Integer = 1, order::Symbol = :size, device::Integer = 0) where {T<:Union{Float32,Float64}}
+    order in (:index, :size) || error("segment_smooth: order is :index or :size")
+    length(normals) == length(vertices) || error("segment_smooth: as many normals as vertices")
+    curvature === nothing || length(curvature) == length(vertices) || error("segment_smooth: as many curvatures as vertices")
+    p = RhSegmentParams(k, unsigned ? 1 : 0, radius, cos(Float64(angle)), curv_max, dist_max, min_size, order === :index ? 0 : 1)
+    vs = convert(Vector{SVector{3,T}}, vertices)
+    ns = convert(Vector{SVector{3,T}}, normals)
+    cs = curvature === nothing ? T[] : convert(Vector{T}, curvature)
+    n = length(vs)
+    labels = zeros(Int32, max(n, 1))
+    kind = zeros(UInt8, max(n, 1))
+    counts = zeros(Int64, n + 1)
+    offsets = zeros(Int64, n + 2)
+    idx = zeros(Int64, max(n, 1))
+    m = Ref{Int64}(0)
+    st = Ref(RhSegmentStats(0, 0, 0, 0, 0, 0, 0))
+    GC.@preserve vs ns cs labels kind counts offsets idx begin
+        pc = curvature === nothing ? Ptr{T}(C_NULL) : pointer(cs)
+        if T == Float32
+            check(ccall((:rh_segment_smooth_f32, LIB), Cint,
+                (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Ref{RhSegmentParams}, Cint, Ptr{Int32}, Ptr{UInt8}, Int64, Ptr{Int64},
+                 Ptr{Int64}, Ptr{Int64}, Ref{Int64}, Ref{RhSegmentStats}),
+                pointer(reinterpret(Float32, vs)), pointer(reinterpret(Float32, ns)), pc, n, p, device, labels, kind, n, counts,
+                offsets, idx, m, st))
+        else
+            check(ccall((:rh_segment_smooth, LIB), Cint,
+                (Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ref{RhSegmentParams}, Cint, Ptr{Int32}, Ptr{UInt8}, Int64, Ptr{Int64},
+                 Ptr{Int64}, Ptr{Int64}, Ref{Int64}, Ref{RhSegmentStats}),
+                pointer(reinterpret(Float64, vs)), pointer(reinterpret(Float64, ns)), pc, n, p, device, labels, kind, n, counts,
+                offsets, idx, m, st))
+        end
+    end
+    return resize!(labels, n), resize!(kind, n), resize!(counts, m[] + 1), resize!(offsets, m[] + 2), resize!(idx, n), st[]
+end
+
 # ---- nearest neighbours of query points in another cloud, and cloud distances (rh_knn_query, rh_cloud_distance) ----
 # typedef struct { double radius; double threshold; int32_t metric; int32_t reserved; } rh_distance_params;   (24 bytes)
 struct RhDistanceParams

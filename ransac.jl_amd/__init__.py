@@ -11,7 +11,8 @@ from .api import (DEFAULT_PARAMETERS, DEFAULT_SHAPE_DICT, ConfidenceInterval, E,
                   notsoconfident, params_to_c, prob, ransac, ransacparameters, MpGroup, refit, refit_component, refit_lsq, score_batch,
                   scorecandidate, select_enabled, sample_sets, fit_sets, shape_f32, shape_from_c, strt, buildoctree, octreedepth, findleaf,
                   getnthcell, iswithinrectangle, cell_enabled_points, shape_extents, OctreeCell, set_option, get_option, option,
-                  voxeldownsample, expand_inpoints, assign_points, assign_cloud, lists_from_assignment, cluster, cluster_inpoints)
+                  voxeldownsample, expand_inpoints, assign_points, assign_cloud, lists_from_assignment, cluster, cluster_inpoints,
+                  segment_smooth, segment_inpoints)
 
 from .io import exportJSON, readconfig, toDict
 

@@ -87,6 +87,18 @@ class ClusterStats(C.Structure):
                 ("n_small", C.c_int64), ("largest", C.c_int64)]
 
 
+class SegmentParams(C.Structure):
+    """rh_segment_params (include/ransac_hip.h)"""
+    _fields_ = [("k", C.c_int32), ("flags", C.c_int32), ("radius", C.c_double), ("cos_angle", C.c_double),
+                ("curv_max", C.c_double), ("dist_max", C.c_double), ("min_size", C.c_int32), ("order", C.c_int32)]
+
+
+class SegmentStats(C.Structure):
+    """rh_segment_stats (include/ransac_hip.h)"""
+    _fields_ = [("n_regions", C.c_int64), ("n_seed", C.c_int64), ("n_border", C.c_int64), ("n_unassigned", C.c_int64),
+                ("n_invalid", C.c_int64), ("n_small", C.c_int64), ("largest", C.c_int64)]
+
+
 class OrientParams(C.Structure):
     """rh_orient_params (include/ransac_hip.h)"""
     _fields_ = [("k", C.c_int32), ("anchor", C.c_int32), ("radius", C.c_double), ("up", C.c_double * 3)]
@@ -146,6 +158,7 @@ OUT_BLOCK_POINTS = 1024
 OUT_STATISTICAL, OUT_ABSOLUTE, OUT_RADIUS = 0, 1, 2
 CLUSTER_BY_INDEX, CLUSTER_BY_SIZE = 0, 1
 PT_NOISE, PT_BORDER, PT_CORE = 0, 1, 2
+SEG_UNSIGNED = 1
 ORI_ANCHOR_FIRST, ORI_ANCHOR_TOP = 0, 1
 VOX_FIRST, VOX_CENTROID = 0, 1
 VOX_ALIGN_NORMALS = 1
@@ -265,6 +278,11 @@ SIGNATURES = {
                              C.POINTER(ClusterStats)]),
     "rh_cluster_f32": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.POINTER(ClusterParams), C.c_int, _i32p, _u8p, C.c_int64, _i64p,
                                  _i64p, _i64p, _i64p, C.POINTER(ClusterStats)]),
+    "rh_segment_smooth": (C.c_int, [_dp, _dp, _dp, C.c_int64, C.POINTER(SegmentParams), C.c_int, _i32p, _u8p, C.c_int64, _i64p, _i64p,
+                                    _i64p, _i64p, C.POINTER(SegmentStats)]),
+    "rh_segment_smooth_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64,
+                                        C.POINTER(SegmentParams), C.c_int, _i32p, _u8p, C.c_int64, _i64p, _i64p, _i64p, _i64p,
+                                        C.POINTER(SegmentStats)]),
     "rh_orient_normals": (C.c_int, [_dp, _dp, C.c_int64, C.POINTER(OrientParams), C.c_int, _dp, _i32p, _i32p, C.POINTER(OrientStats)]),
     "rh_orient_normals_f32": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64, C.POINTER(OrientParams), C.c_int,
                                         C.POINTER(C.c_float), _i32p, _i32p, C.POINTER(OrientStats)]),

@@ -1200,6 +1200,80 @@ def cluster_inpoints(vertices, inpoints, eps, **kw):
     return [sel[part - 1] for part in lists_from_assignment(offsets, idx)[1:]]
 
 
+def segment_smooth(vertices, normals, curvature=None, k=16, radius=0.0, angle=math.radians(25.0), curv_max=0.05, dist_max=0.0,
+                   unsigned=False, min_size=1, order="size", device=0, return_kind=False, return_counts=False,
+                   return_lists=False, return_stats=False, cos_angle=None):
+    """Split a cloud with normals into its smooth sheets (rh_segment_smooth: region growing by smoothness, restated so
+    that nothing depends on an order; include/ransac_hip.h has the definition in full).  Two points are linked when one is
+    among the other's k nearest neighbours (within radius, when radius > 0), their normals differ by at most `angle`
+    (radians; unsigned: up to sign) and, with dist_max > 0, each lies within dist_max of the other's tangent plane.  A
+    point whose curvature is at most curv_max is a seed (every point with a normal, when no curvature is given); the
+    regions are the connected components of the seeds, a point that is no seed joins the region of its nearest linked
+    seed (ties to the smaller index), the rest has no label, and neither have regions of fewer than min_size points nor
+    points whose normal is (0, 0, 0).  order "size" numbers the regions by descending size, "index" by their smallest
+    seed's index.  The cosine of `angle` is taken here and handed on; cos_angle= gives it directly instead.
+    vertices, normals: (n, 3) float64 or float32 (widened exactly; the normals and the curvature take the dtype of the
+    vertices), curvature: (n,), e.g. estimatenormals(..., return_curvature=True).
+    Returns labels (int32, 0 = none, 1 .. M), then on request: return_kind uint8 per point (_lib.PT_NOISE / PT_BORDER /
+    PT_CORE = seed), return_counts int64[M + 1] (label 0 first), return_lists (offsets[M + 2], idx[n]): the 1-based indices
+    grouped by label, ascending within a label (lists_from_assignment splits them), return_stats a dict n_regions, n_seed,
+    n_border, n_unassigned, n_invalid, n_small, largest."""
+    orders = {"index": L.CLUSTER_BY_INDEX, "size": L.CLUSTER_BY_SIZE}
+    if isinstance(order, str) and order not in orders:
+        raise ValueError("segment_smooth: order %r is neither 'index' nor 'size'" % (order,))
+    f32 = np.asarray(vertices).dtype == np.float32
+    t, ct = (np.float32, C.c_float) if f32 else (np.float64, C.c_double)
+    xyz = np.ascontiguousarray(vertices, dtype=t).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, dtype=t).reshape(-1, 3)
+    n = xyz.shape[0]
+    if nrm.shape[0] != n:
+        raise ValueError("segment_smooth: %d normals for %d points" % (nrm.shape[0], n))
+    curv = None
+    if curvature is not None:
+        curv = np.ascontiguousarray(curvature, dtype=t).reshape(-1)
+        if curv.shape[0] != n:
+            raise ValueError("segment_smooth: %d curvatures for %d points" % (curv.shape[0], n))
+    prm = L.SegmentParams(k=int(k), flags=L.SEG_UNSIGNED if unsigned else 0, radius=float(radius),
+                          cos_angle=math.cos(float(angle)) if cos_angle is None else float(cos_angle), curv_max=float(curv_max),
+                          dist_max=float(dist_max), min_size=int(min_size), order=int(orders.get(order, order)))
+    labels = np.zeros(max(n, 1), dtype=np.int32)
+    kind = np.zeros(max(n, 1), dtype=np.uint8) if return_kind else None
+    counts = np.zeros(n + 1, dtype=np.int64) if return_counts else None
+    offsets = np.zeros(n + 2, dtype=np.int64) if return_lists else None
+    idx = np.zeros(max(n, 1), dtype=np.int64) if return_lists else None
+    st, m = L.SegmentStats(), C.c_int64(0)
+    fn = lib().rh_segment_smooth_f32 if f32 else lib().rh_segment_smooth
+    check(fn(_p(xyz, ct), _p(nrm, ct), None if curv is None else _p(curv, ct), n, C.byref(prm), device, _p(labels, C.c_int32),
+             None if kind is None else _p(kind, C.c_uint8), n, None if counts is None else _p(counts, C.c_int64),
+             None if offsets is None else _p(offsets, C.c_int64), None if idx is None else _p(idx, C.c_int64), C.byref(m), C.byref(st)))
+    m = int(m.value)
+    out = (labels[:n],) + ((kind[:n],) if return_kind else ()) + ((counts[:m + 1].copy(),) if return_counts else ())
+    out += ((offsets[:m + 2].copy(), idx[:n]) if return_lists else ())
+    out += (({f: int(getattr(st, f)) for f, _ in L.SegmentStats._fields_},) if return_stats else ())
+    return out[0] if len(out) == 1 else out
+
+
+def segment_inpoints(vertices, normals, inpoints, curvature=None, **kw):
+    """The smooth regions of the points vertices[inpoints - 1] (inpoints: 1-based indices, e.g. the unlabelled list of
+    assign_points): a list of int64 arrays, one per region in the order of segment_smooth(...), each holding that region's
+    members as 1-based indices into `vertices` -- the caller's indexing -- in the order in which inpoints lists them.
+    Points without a label are left out.  kw: k, radius, angle, cos_angle, curv_max, dist_max, unsigned, min_size, order,
+    device of segment_smooth()."""
+    bad = [k for k in kw if k not in ("k", "radius", "angle", "cos_angle", "curv_max", "dist_max", "unsigned", "min_size", "order", "device")]
+    if bad:
+        raise TypeError("segment_inpoints: unexpected argument %s" % bad[0])
+    v = np.asarray(vertices).reshape(-1, 3)
+    nrm = np.asarray(normals).reshape(-1, 3)
+    sel = np.asarray(inpoints, dtype=np.int64).reshape(-1)
+    if sel.size == 0:
+        return []
+    if sel.min() < 1 or sel.max() > v.shape[0]:
+        raise ValueError("segment_inpoints: an index outside 1 .. %d" % v.shape[0])
+    curv = None if curvature is None else np.asarray(curvature).reshape(-1)[sel - 1]
+    _, offsets, idx = segment_smooth(v[sel - 1], nrm[sel - 1], curv, return_lists=True, **kw)
+    return [sel[part - 1] for part in lists_from_assignment(offsets, idx)[1:]]
+
+
 def voxeldownsample(vertices, beta, normals=None, mode="centroid", align_normals=False, device=0, return_index=False,
                     return_counts=False, return_map=False):
     """Thin a raw cloud on a voxel grid of width beta (rh_voxel_downsample, include/ransac_hip.h has the definition in

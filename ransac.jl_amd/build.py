@@ -23,7 +23,7 @@ CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libransac_hip.so")
 SO_DIAG = os.path.join(HERE, "libransac_hip_diag.so")
 OBJDIR = os.path.join(HERE, "_build")
-SOURCES = ["kernels.hip", "enabled.hip", "score4.hip", "boxes32.hip", "unpermute4.hip", "score4_diag.hip", "cloud.hip", "kdorder.hip", "korder.hip", "driver.hip", "driver_extract.hip", "driver_windows.hip", "driver_store.hip", "mp.hip", "sampler.hip", "lsq.hip", "cc.hip", "component.hip", "extent.hip", "assign.hip", "octree.hip", "normals.hip", "knn.hip", "knn_query.hip", "register.hip", "describe.hip", "match.hip", "register_global.hip", "cluster.hip", "orient.hip", "voxel.hip", "comm.hip", "options.cpp", "fit.cpp"]
+SOURCES = ["kernels.hip", "enabled.hip", "score4.hip", "boxes32.hip", "unpermute4.hip", "score4_diag.hip", "cloud.hip", "kdorder.hip", "korder.hip", "driver.hip", "driver_extract.hip", "driver_windows.hip", "driver_store.hip", "mp.hip", "sampler.hip", "lsq.hip", "cc.hip", "component.hip", "extent.hip", "assign.hip", "octree.hip", "normals.hip", "knn.hip", "knn_query.hip", "register.hip", "describe.hip", "match.hip", "register_global.hip", "cluster.hip", "segment.hip", "orient.hip", "voxel.hip", "comm.hip", "options.cpp", "fit.cpp"]
 # -ffp-contract=off: never fuse a*b+c -- inlier sets must match the CPU path bit for bit.
 # -fno-slp-vectorize: the vectoriser pairs binary32 operations into v_pk_fma_f32 / v_pk_mul_f32 -- no faster than two
 # plain ones on gfx950 (4.2 against 2 x 2.3 issue cycles, profiles/r3/ubench_valu_rates.txt) and every pair pays v_mov

@@ -1,5 +1,5 @@
 // call_scope.h -- what an entry point on raw host arrays (rh_voxel_downsample, rh_knn, rh_remove_outliers, rh_knn_query,
-// rh_cloud_distance, rh_register, rh_describe, rh_match_features, rh_register_global, rh_cluster, rh_orient_normals, rh_estimate_normals, rh_assign_points, rh_largestconncomp) owns for the length of the call: the device, a stream of its
+// rh_cloud_distance, rh_register, rh_describe, rh_match_features, rh_register_global, rh_cluster, rh_segment_smooth, rh_orient_normals, rh_estimate_normals, rh_assign_points, rh_largestconncomp) owns for the length of the call: the device, a stream of its
 // own and its device buffers, released on every way out -- among them the ONE scratch block of the call's hipcub
 // launches (cub) -- and the read-back of the call's scalars (fetch).  The cloud-bound paths do not come here: a cloud has
 // its stream and its grown buffers (rh_dev::grow, RH_HIP).

@@ -14,12 +14,11 @@
 //                       by ORIGINAL point index, so that a cluster's root is its smallest core index
 //              2 root   a point that is no core point keeps its best (d2, index) core candidate and takes that one's root;
 //                       a core point looks its own root up.  -> root[], kind[]
-//   sizes    integer atomicAdd per root (one per distinct root of a wave), the min_size filter, an exclusive scan over the
-//            root flags in index order for the numbering; BY_SIZE: a radix sort of the M keys (~size, root)
-//   lists    a stable radix sort of (label, index): label 0 first, indices ascending within a label
+//   tail     root_labels.h: sizes, the min_size filter, the numbering, labels, stats and lists
 // Nothing waits on another block; uf_unite's retry loop (union_find.h) is the only loop without a static bound.  No
 // floating-point atomics: every output is a comparison of binary64 values or an integer.
 #include "knn_grid.h"
+#include "root_labels.h"
 #include "union_find.h"
 #include "wave_keys.h"
 
@@ -150,85 +149,6 @@ __global__ __launch_bounds__(CL_BLOCK) void cl_walk_kernel(const ClJob J)
     }
 }
 
-// the call's scalars on the device
-struct ClScal {
-    unsigned long long n_core, n_border, n_noise, n_small;
-    int32_t largest, m;
-    int32_t nitems, pad;
-};
-
-// size[r] = the points whose root is r: the first lane of every distinct root of a wave adds the wave's count
-__global__ void cl_size_kernel(const int32_t *__restrict__ root, int64_t n, int32_t *__restrict__ size)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const int32_t r = i < n ? root[i] : -1;
-    wave_each_key(r >= 0 && (int64_t)r < n, r, [&](int leader, int32_t R, uint64_t same) {
-        if (lane == leader) atomicAdd(&size[R], (int32_t)__popcll(same));
-    });
-}
-
-// flag[r] = r is the root of a cluster that stays
-__global__ void cl_keep_kernel(const int32_t *__restrict__ root, const int32_t *__restrict__ size, int64_t n, int32_t min_size,
-                               int32_t *__restrict__ flag)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flag[i] = root[i] == (int32_t)i && size[i] >= min_size;
-}
-
-// BY_INDEX: lab[r] = num[r] + 1.  BY_SIZE: the sort key of cluster num[r], descending size and then ascending root
-__global__ void cl_number_kernel(const int32_t *__restrict__ flag, const int32_t *__restrict__ num, const int32_t *__restrict__ size,
-                                 int64_t n, int by_size, int32_t *__restrict__ lab, uint64_t *__restrict__ key)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !flag[i]) return;
-    if (by_size) key[num[i]] = ((uint64_t)(~(uint32_t)size[i]) << 32) | (uint64_t)(uint32_t)i;
-    else lab[i] = num[i] + 1;
-}
-
-__global__ void cl_rank_kernel(const uint64_t *__restrict__ sorted, int64_t m, int64_t n, int32_t *__restrict__ lab)
-{
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= m) return;
-    const uint64_t r = sorted[k] & 0xFFFFFFFFULL;
-    if (r < (uint64_t)n) lab[r] = (int32_t)(k + 1);
-}
-
-// labels, the counters of the stats, the list keys; counts[label] (when wanted) from the roots
-__global__ void cl_label_kernel(const int32_t *__restrict__ root, const int32_t *__restrict__ flag, const int32_t *__restrict__ lab,
-                                const int32_t *__restrict__ size, const uint8_t *__restrict__ kind, int64_t n, int64_t cap,
-                                int32_t *__restrict__ labels, int64_t *__restrict__ one_based, int64_t *__restrict__ counts, ClScal *sc)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool in = i < n;
-    const int32_t r = in ? root[i] : -1;
-    const bool has = r >= 0 && (int64_t)r < n;
-    const int32_t l = has && flag[r] ? lab[r] : 0;
-    const int k = in ? kind[i] : -1;
-    if (in) {
-        labels[i] = l;
-        if (one_based) one_based[i] = i + 1;
-        if (r == (int32_t)i && l > 0) {
-            if (counts && (int64_t)l <= cap) counts[l] = size[i];
-            atomicMax(&sc->largest, size[i]);
-        }
-    }
-    const uint64_t bc = __builtin_amdgcn_ballot_w64(k == RH_PT_CORE), bb = __builtin_amdgcn_ballot_w64(k == RH_PT_BORDER),
-                   bn = __builtin_amdgcn_ballot_w64(k == RH_PT_NOISE), bs = __builtin_amdgcn_ballot_w64(in && k != RH_PT_NOISE && l == 0);
-    if ((threadIdx.x & 63) == 0) {
-        if (bc) atomicAdd(&sc->n_core, (unsigned long long)__popcll(bc));
-        if (bb) atomicAdd(&sc->n_border, (unsigned long long)__popcll(bb));
-        if (bn) atomicAdd(&sc->n_noise, (unsigned long long)__popcll(bn));
-        if (bs) atomicAdd(&sc->n_small, (unsigned long long)__popcll(bs));
-    }
-}
-
-// counts[0] = the points without a label; the slot behind the last count stays 0 (the scan's last offset = n)
-__global__ void cl_count0_kernel(const ClScal *sc, int64_t *counts)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0) counts[0] = (int64_t)(sc->n_noise + sc->n_small);
-}
-
 template <int PASS>
 void launch_walk(hipStream_t st, const ClJob &J)
 {
@@ -248,8 +168,6 @@ int cluster(const char *who, const T *xyz_aos, int64_t n, const rh_cluster_param
     CallScope S;
     RH_TRY(S.open(who, device));
     const hipStream_t st = S.st;
-    const bool tally = counts_out != nullptr || offsets_out != nullptr;
-    cap = std::min(cap, n);                                      // (there are n clusters at most: nothing is written beyond)
 
     // grid
     double *d_xyz = nullptr;
@@ -260,29 +178,24 @@ int cluster(const char *who, const T *xyz_aos, int64_t n, const rh_cluster_param
     RH_TRY(ix.build(p->eps * (1.0 + CL_SLACK)));
 
     // items
-    ClScal *d_sc = nullptr, h;
+    RootScal *d_sc = nullptr, h;
     uint8_t *d_flag8 = nullptr;
-    int32_t *d_items = nullptr, *d_size = nullptr, *d_flag = nullptr, *d_num = nullptr, *d_lab = nullptr, *d_labels = nullptr;
+    int32_t *d_items = nullptr;
     RH_TRY(S.alloc(&d_sc, 1));
     RH_TRY(S.alloc(&d_flag8, n));
     RH_TRY(S.alloc(&d_items, n));
-    RH_TRY(S.alloc(&d_size, n)); RH_TRY(S.alloc(&d_flag, n)); RH_TRY(S.alloc(&d_num, n)); RH_TRY(S.alloc(&d_lab, n));
-    RH_TRY(S.alloc(&d_labels, n));
-    int64_t *d_one = nullptr, *d_idx = nullptr, *d_counts = nullptr, *d_offsets = nullptr;
-    int32_t *d_lsorted = nullptr;
-    if (idx_out) { RH_TRY(S.alloc(&d_one, n)); RH_TRY(S.alloc(&d_idx, n)); RH_TRY(S.alloc(&d_lsorted, n)); }
     hipcub::CountingInputIterator<int32_t> zero_based(0);
-    uint64_t *d_mkey = ix.d_key[0], *d_msorted = nullptr;       // (the grid's unsorted keys are free once it is built)
-    SCOPE_HIP(S, hipMemsetAsync(d_sc, 0, sizeof(ClScal), st));
+    SCOPE_HIP(S, hipMemsetAsync(d_sc, 0, sizeof(RootScal), st));
     hipLaunchKernelGGL(cl_chunk_flag_kernel, dim3(blocks_for(n)), dim3(256), 0, st, ix.g, ix.d_key[1], n, d_flag8);
     SCOPE_HIP(S, hipGetLastError());
-    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceSelect::Flagged(t, b, zero_based, d_flag8, d_items, &d_sc->nitems, (int)n, st); }));
+    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceSelect::Flagged(t, b, zero_based, d_flag8, d_items, &d_sc->aux, (int)n, st); }));
     RH_TRY(S.fetch(&h, d_sc));
-    if (h.nitems < 1 || (int64_t)h.nitems > n) { rh_set_error("%s: %d work items for %lld points", who, h.nitems, (long long)n); return RH_E_INTERNAL; }
+    const int64_t nitems = h.aux;
+    if (nitems < 1 || nitems > n) { rh_set_error("%s: %lld work items for %lld points", who, (long long)nitems, (long long)n); return RH_E_INTERNAL; }
 
     // the three passes
     ClJob J;
-    J.g = ix.g; J.skey = ix.d_key[1]; J.items = d_items; J.n = n; J.nitems = h.nitems;
+    J.g = ix.g; J.skey = ix.d_key[1]; J.items = d_items; J.n = n; J.nitems = nitems;
     J.eps2 = p->eps * p->eps;
     J.need = p->min_pts - 1;
     J.core_s = d_flag8;                                          // (the chunk flags are spent: pass 0 writes every position)
@@ -293,65 +206,21 @@ int cluster(const char *who, const T *xyz_aos, int64_t n, const rh_cluster_param
     launch_walk<2>(st, J);
     SCOPE_HIP(S, hipGetLastError());
 
-    // sizes, the min_size filter, the numbering
-    SCOPE_HIP(S, hipMemsetAsync(d_size, 0, sizeof(int32_t) * (size_t)n, st));
-    hipLaunchKernelGGL(cl_size_kernel, dim3(blocks_for(n)), dim3(256), 0, st, J.root, n, d_size);
-    hipLaunchKernelGGL(cl_keep_kernel, dim3(blocks_for(n)), dim3(256), 0, st, J.root, d_size, n, p->min_size, d_flag);
-    SCOPE_HIP(S, hipGetLastError());
-    RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_flag, d_num, (int)n, st); }));
-    hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(64), 0, st, d_flag, d_num, n, &d_sc->m);   // the clusters that stay
-    const int by_size = p->order == RH_CLUSTER_BY_SIZE;
-    hipLaunchKernelGGL(cl_number_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_flag, d_num, d_size, n, by_size, d_lab, d_mkey);
-    SCOPE_HIP(S, hipGetLastError());
-    RH_TRY(S.fetch(&h, d_sc));
-    const int64_t m = h.m;
-    if (m < 0 || m > n) { rh_set_error("%s: %lld clusters of %lld points", who, (long long)m, (long long)n); return RH_E_INTERNAL; }
-    if (by_size && m > 0) {
-        d_msorted = ix.d_key[1];                                // (the walk is over: the sorted cell keys are spent)
-        RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortKeys(t, b, d_mkey, d_msorted, (int)m, 0, 64, st); }));
-        hipLaunchKernelGGL(cl_rank_kernel, dim3(blocks_for(m)), dim3(256), 0, st, d_msorted, m, n, d_lab);
-    }
-
-    // labels and stats; they are written even when the lists do not fit
-    const bool fits = !tally || m <= cap;
-    if (tally && fits) {
-        RH_TRY(S.alloc(&d_counts, cap + 2));
-        RH_TRY(S.alloc(&d_offsets, cap + 2));
-        SCOPE_HIP(S, hipMemsetAsync(d_counts, 0, sizeof(int64_t) * (size_t)(cap + 2), st));
-    }
-    hipLaunchKernelGGL(cl_label_kernel, dim3(blocks_for(n)), dim3(256), 0, st, J.root, d_flag, d_lab, d_size, J.kind, n, cap, d_labels,
-                       d_one, d_counts, d_sc);
-    SCOPE_HIP(S, hipGetLastError());
-    SCOPE_HIP(S, hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, st));
-    SCOPE_HIP(S, hipMemcpyAsync(labels_out, d_labels, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, st));
-    if (kind_out) SCOPE_HIP(S, hipMemcpyAsync(kind_out, J.kind, (size_t)n, hipMemcpyDefault, st));
-    SCOPE_HIP(S, hipStreamSynchronize(st));
-    *n_clusters_out = m;
-    if (stats) {
-        stats->n_clusters = m;
-        stats->n_core = (int64_t)h.n_core; stats->n_border = (int64_t)h.n_border; stats->n_noise = (int64_t)h.n_noise;
-        stats->n_small = (int64_t)h.n_small; stats->largest = h.largest;
-    }
-    if (!fits) {
-        rh_set_error("%s: %lld clusters, counts / offsets hold %lld", who, (long long)m, (long long)cap);
-        return RH_E_CAPACITY;
-    }
-
-    // lists
-    if (tally) {
-        hipLaunchKernelGGL(cl_count0_kernel, dim3(1), dim3(64), 0, st, d_sc, d_counts);
-        SCOPE_HIP(S, hipGetLastError());
-        RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_counts, d_offsets, (int)(cap + 2), st); }));
-        if (counts_out) SCOPE_HIP(S, hipMemcpyAsync(counts_out, d_counts, sizeof(int64_t) * (size_t)(cap + 1), hipMemcpyDefault, st));
-        if (offsets_out) SCOPE_HIP(S, hipMemcpyAsync(offsets_out, d_offsets, sizeof(int64_t) * (size_t)(cap + 2), hipMemcpyDefault, st));
-    }
-    if (idx_out) {
-        const int bits = sort_bits((uint64_t)m + 1);            // (the labels are 0 .. m)
-        RH_TRY(S.cub([&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, d_labels, d_lsorted, d_one, d_idx, (int)n, 0, bits, st); }));
-        SCOPE_HIP(S, hipMemcpyAsync(idx_out, d_idx, sizeof(int64_t) * (size_t)n, hipMemcpyDefault, st));
-    }
-    SCOPE_HIP(S, hipStreamSynchronize(st));
-    return RH_OK;
+    // the tail; the grid's unsorted keys are free once it is built, the sorted ones now that the walk is over
+    RootTail tl;
+    tl.what = "clusters";
+    tl.d_root = J.root; tl.d_kind = J.kind; tl.n = n;
+    tl.min_size = p->min_size; tl.by_size = p->order == RH_CLUSTER_BY_SIZE; tl.cap = cap;
+    tl.d_sc = d_sc; tl.d_mkey = ix.d_key[0]; tl.d_msorted = ix.d_key[1];
+    tl.labels_out = labels_out; tl.kind_out = kind_out; tl.counts_out = counts_out; tl.offsets_out = offsets_out; tl.idx_out = idx_out;
+    return root_labels(S, tl, [&](const RootScal &r, int64_t m) {
+        *n_clusters_out = m;
+        if (stats) {
+            stats->n_clusters = m;
+            stats->n_core = (int64_t)r.n_core; stats->n_border = (int64_t)r.n_border; stats->n_noise = (int64_t)r.n_noise;
+            stats->n_small = (int64_t)r.n_small; stats->largest = r.largest;
+        }
+    });
 }
 
 }  // namespace

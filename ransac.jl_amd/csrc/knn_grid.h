@@ -1,5 +1,5 @@
 // knn_grid.h -- the uniform grid of the exact k-nearest-neighbour search (knn_device.h has the query), shared by
-// normals.hip (rh_estimate_normals), knn.hip (rh_knn, rh_remove_outliers), orient.hip (rh_orient_normals), knn_query.hip and register.hip (rh_knn_query,
+// normals.hip (rh_estimate_normals), knn.hip (rh_knn, rh_remove_outliers), orient.hip (rh_orient_normals), segment.hip (rh_segment_smooth), knn_query.hip and register.hip (rh_knn_query,
 // rh_cloud_distance, rh_register: the grid holds the reference cloud) and cluster.hip (rh_cluster, which walks the cells itself):
 //   points radix-sorted by cell key, an open-addressing hash table key -> [start, end) of the occupied cells only (empty
 //   space costs nothing; table and bounding box are cell_grid.h's), the coordinates gathered into cell order.  KnnIndex

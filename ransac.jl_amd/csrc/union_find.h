@@ -1,5 +1,5 @@
 // union_find.h -- lock-free union-find on the device, over an array of parents L (cc.hip: pixels, component.hip: the slots
-// of the cell table, cluster.hip: the points).  A root points at itself and is the smallest index of its set, parents only ever go down, so a link
+// of the cell table, cluster.hip: the points, segment.hip: the seeds).  A root points at itself and is the smallest index of its set, parents only ever go down, so a link
 // to any ancestor is a valid link.  Flatten with atomicMin(&L[i], root), never a plain store: a neighbour's path halving
 // may write L[i] at the same time.
 #pragma once
