@@ -94,6 +94,13 @@ int rh_dbg_cls_round(const rh_shape *shape, const rh_params *p, double M, double
  * i.e. bit 30 clear; a NaN with a clear sign is "out"); any_und_out[s]: 1 = some point is undecided.  Needs no GPU. */
 int rh_dbg_books2(const float *u2, int64_t nseq, int32_t *sure_count_out, uint64_t *sure_word_out, uint64_t *und_word_out,
                   uint8_t *any_und_out);
+/* The undecided word of a pair as the counts-only launches read it off the books IN PLACE (csrc/score4_device.h, "Books in
+ * place"), on the host, by the very functions of the kernel.  u2: as for rh_dbg_books2.  packed_out[s]: the undecided points of
+ * sequence s in the books' own bit order; pi_out[L], L = 0 .. 63: the point that bit L of such a word stands for (a permutation
+ * of 0 .. 63).  point_words / deposit_out (both or neither NULL): deposit_out[s] = the point-ordered word point_words[s] brought
+ * into the books' order (the pairs that ignore their books queue their group's enabled word so).  Needs no GPU. */
+int rh_dbg_books2_inplace(const float *u2, int64_t nseq, uint64_t *packed_out, int32_t *pi_out /* [64] */, const uint64_t *point_words,
+                          uint64_t *deposit_out);
 /* u and u' of a plane, sphere or cylinder candidate on the n points xyz[3 i ..] with normals nrm[3 i ..] (converted to binary32
  * as the kernel's staging converts them), on the host: u_out[i] = max(ua, ub) from the record cls_make builds, by the functions
  * the audits use; u2_out[i] = what the kernel's point loops compute, from that record doubled in registers (cls_double) with

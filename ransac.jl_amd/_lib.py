@@ -338,6 +338,7 @@ DIAG_SIGNATURES = {
     "rh_dbg_cls_round": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), _dp]),
     "rh_dbg_books2": (C.c_int, [C.POINTER(C.c_float), C.c_int64, _i32p, _u64p, _u64p, _u8p]),
+    "rh_dbg_books2_inplace": (C.c_int, [C.POINTER(C.c_float), C.c_int64, _u64p, _i32p, _u64p, _u64p]),
     "rh_dbg_cls_u2": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_int, C.c_int64, _dp, _dp, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                 C.POINTER(C.c_float)]),
     "rh_dbg_conebox": (C.c_int, [_sp, _pp, C.c_double, C.c_double, C.c_int, _dp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_float)]),

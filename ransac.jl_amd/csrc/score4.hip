@@ -116,6 +116,14 @@ struct S4AllArgs {
 #endif
 
 #define RH4_CONST_AS __attribute__((address_space(4)))
+// score4_kernel's explicit arguments as they lie in its kernarg segment (each at its natural alignment)
+struct S4KernArgs {
+    int64_t s;
+    S4AllArgs A;
+    int32_t *counts;
+    int dbg;
+};
+static_assert(offsetof(S4KernArgs, A) == 8 && alignof(S4AllArgs) == 8 && offsetof(S4KernArgs, counts) == 8 + sizeof(S4AllArgs), "kernarg layout of score4_kernel");
 
 // lane i <- lane i - 1 (lane 0 <- 0) / lane i <- lane i + 1 (lane 63 <- 0): DPP moves across the whole wave, no trip through LDS
 static __device__ __forceinline__ int wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
@@ -138,7 +146,7 @@ static __device__ __forceinline__ int run_total(int v, int key, int lane)
 // one batch: the 64 pairs of the block's list from `head` on (n of them valid), one per lane
 template <int KIND, int R, bool MASK, bool F32, bool LIST>
 static __device__ __forceinline__ void
-score4_batch(S4Shared<R, MASK, LIST> &sh, const int wv, const int lane, const int head, const int n, const int cbase, const double *__restrict__ pts,
+score4_batch(S4Shared<R, MASK, LIST> &sh, const int wv, const int lane, const int pil, const int head, const int n, const int cbase, const double *__restrict__ pts,
              int64_t stride, const int64_t p0, const rh_prep *__restrict__ prep, const rh_cls *__restrict__ cls,
              const int32_t *__restrict__ orig, double eps, double cosa, int32_t *__restrict__ counts, const bool weird,
              uint64_t *__restrict__ masks, uint8_t *__restrict__ occ, const int64_t mstride, const int64_t g0, unsigned long long *__restrict__ stats)
@@ -212,7 +220,7 @@ score4_batch(S4Shared<R, MASK, LIST> &sh, const int wv, const int lane, const in
         total = (act && !exact_only) ? books2_sure_count(w) : 0;
         if (MASK) word = (act && !exact_only) ? books2_sure64(w) : 0ULL;
         // Pairs with an undecided point (a percent of them): the owning lane's books say WHICH points are undecided; a
-        // wave-uniform loop over those pairs puts them on the ring with lane = point -- two v_readlane of the owner's word, a
+        // wave-uniform loop over those pairs puts them on the ring, a lane per bit of the word -- two v_readlane of the owner's word, a
         // rank, a store; no record, no point and no classifier a second time -- and only they take the exact test, 64 at a
         // time, whatever pair they belong to.  (Until round 12 the loop evaluated the classifier again with lane = point to
         // find them: 36-48 vector and 53-56 scalar instructions per pair behind a scalar-load round trip.  Round 3 ran the
@@ -220,8 +228,20 @@ score4_batch(S4Shared<R, MASK, LIST> &sh, const int wv, const int lane, const in
         uint64_t redo = WB(amb);
         S4_STAT(stats, 24 * KIND + 9, __popcll(redo));
         if (redo != 0) {
-            const uint64_t lg = sh.len[g];
-            const uint64_t und = exact_only ? lg : (books2_und64(w) & lg);   // (exact-only: every enabled point; read of the amb lanes only)
+            uint64_t und;   // (read of the amb lanes only)
+            if (MASK) {
+                const uint64_t lg = sh.len[g];
+                und = exact_only ? lg : (books2_und64(w) & lg);   // (exact-only: every enabled point; point order, as the inlier words are)
+            } else {
+                // Counts-only: the books' own bit order (score4_device.h, "Books in place") -- bit L of the word is point pil
+                // of lane L, four instructions instead of four compressions.  No mask by the group's enabled word: a disabled
+                // or out-of-range point is staged as zeros, and cls_make's guards make the zero point surely out for every
+                // record whose books are read (the note behind the point loops) -- its two bits never read "undecided".
+                und = books2_und64_inplace(w);
+                // pairs that ignore their books take every enabled point: the enabled word, deposited into the books' order
+                // (wave-uniform branch: rare -- an exact-only record or a tile with a non-finite value)
+                if (WB(amb && exact_only) != 0) { if (exact_only) und = books2_deposit64(sh.len[g]); }
+            }
             const uint32_t undlo = (uint32_t)und, undhi = (uint32_t)(und >> 32);
             sh.cntb[wv][lane] = 0;
             if (MASK) sh.maskb[wv][lane] = 0ULL;
@@ -232,7 +252,7 @@ score4_batch(S4Shared<R, MASK, LIST> &sh, const int wv, const int lane, const in
                 const uint64_t uk = ((uint64_t)uhi << 32) | ulo;
                 const bool has = (uk >> lane) & 1ULL;
                 const int rank = __builtin_amdgcn_mbcnt_hi(uhi, __builtin_amdgcn_mbcnt_lo(ulo, 0));
-                if (has) sh.qb[wv][(qbh + qbn + rank) & 127] = (uint16_t)((k << 6) | lane);
+                if (has) sh.qb[wv][(qbh + qbn + rank) & 127] = (uint16_t)((k << 6) | pil);   // (pil: the point lane's bit stands for)
                 qbn += __popcll(uk);
                 S4_STAT(stats, 24 * KIND + 10, __popcll(uk));
                 if (qbn >= 64) drain_b(64);
@@ -335,7 +355,7 @@ score4_batch(S4Shared<R, MASK, LIST> &sh, const int wv, const int lane, const in
 // pairs from the list until it is empty.
 template <int KIND, int R, bool MASK, bool F32, bool LIST>
 static __device__ __forceinline__ void
-score4_segment(S4Shared<R, MASK, LIST> &sh, const S4KindArgs &K, const int32_t *__restrict__ nkp, const uint16_t *__restrict__ list, const int64_t bstride, const int lo, const int hi,
+score4_segment(S4Shared<R, MASK, LIST> &sh, const RH4_CONST_AS S4KindArgs *K, const int pil, const int32_t *__restrict__ nkp, const uint16_t *__restrict__ list, const int64_t bstride, const int lo, const int hi,
                const double *__restrict__ pts, int64_t stride, const int64_t g0, const unsigned live, const bool weird,
                int32_t *__restrict__ counts, int dbg, uint64_t *__restrict__ masks, uint8_t *__restrict__ occ, const int64_t mstride,
                unsigned long long *__restrict__ stats)
@@ -367,7 +387,7 @@ score4_segment(S4Shared<R, MASK, LIST> &sh, const S4KindArgs &K, const int32_t *
     {
         const int cil = LIST ? slot[0] : clamped(0);
 #pragma unroll
-        for (int f = 0; f < NB; f++) B[0][f] = K.box[(int64_t)f * bstride + cil];
+        for (int f = 0; f < NB; f++) B[0][f] = K->box[(int64_t)f * bstride + cil];
     }
 #pragma unroll
     for (int h = 0; h < CPW; h++) {
@@ -377,7 +397,7 @@ score4_segment(S4Shared<R, MASK, LIST> &sh, const S4KindArgs &K, const int32_t *
         if (h + 1 < CPW) {   // the next chunk's records: in flight during this chunk's tests
             const int cinl = LIST ? slot[h + 1 < CPW ? h + 1 : 0] : clamped(h + 1);
 #pragma unroll
-            for (int f = 0; f < NB; f++) B[(h + 1) & 1][f] = K.box[(int64_t)f * bstride + cinl];
+            for (int f = 0; f < NB; f++) B[(h + 1) & 1][f] = K->box[(int64_t)f * bstride + cinl];
         }
         unsigned surv = 0;
 #pragma unroll
@@ -423,8 +443,8 @@ score4_segment(S4Shared<R, MASK, LIST> &sh, const S4KindArgs &K, const int32_t *
         if (lane == 0) bt = atomicAdd(&sh.next_batch, 1);
         bt = __builtin_amdgcn_readfirstlane(bt);
         if (bt * 64 >= npairs) break;
-        score4_batch<KIND, R, MASK, F32, LIST>(sh, wv, lane, bt * 64, min(64, npairs - bt * 64), lo << 6, pts, stride, g0 * 64, K.prep, K.cls, K.orig,
-                                         K.eps, K.cosa, counts, weird, masks, occ, mstride, g0, stats);
+        score4_batch<KIND, R, MASK, F32, LIST>(sh, wv, lane, pil, bt * 64, min(64, npairs - bt * 64), lo << 6, pts, stride, g0 * 64, K->prep, K->cls, K->orig,
+                                         K->eps, K->cosa, counts, weird, masks, occ, mstride, g0, stats);
     }
 }
 
@@ -484,7 +504,8 @@ static __device__ __forceinline__ void s4_stage(SH &sh, const double *__restrict
 // segment(s) of its row (almost always one) on its tile.
 // TAIL: the launch that picks up what a sized-before-the-count-was-known launch leaves over (rhk_score4_all, `open`):
 // its blocks walk the rows from A.row0 on grid-stride.  A separate instantiation -- the loop around the four per-kind
-// bodies costs the register allocation dearly (96 scalar + 40 vector registers spilled), the one-row form none.
+// bodies costs the register allocation dearly (10 to 17 vector registers spilled; until the bodies read their arguments where
+// they start, 114 to 192 scalar ones as well), the one-row form none.
 template <int R, bool MASK, bool F32, bool TAIL = false, bool LIST = false>
 // 7 blocks of four waves per CU = 7 waves per SIMD = 72 vector registers (measured against 8 / 64 registers: cfg3 0.0816 ->
 // 0.0807 ms, cfg5 0.3006 -> 0.2973; 6 / 80 registers is slower: profiles/r4/experiments.txt)
@@ -527,15 +548,27 @@ score4_kernel(int64_t s, const S4AllArgs A, int32_t *__restrict__ counts, int db
     const double *staged_pts = nullptr;
     (void)staged_en;
     (void)staged_pts;
+    const RH4_CONST_AS S4KernArgs *const kargs = (const RH4_CONST_AS S4KernArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    // counts-only: the point that this lane's bit of a pair's undecided word stands for (score4_device.h, "Books in place")
+    const int pil = MASK ? (int)(threadIdx.x & 63) : books2_point_of_bit((int)(threadIdx.x & 63));
+    // Every per-kind body takes its arguments from the kernarg segment where it starts, through a constant-address-space pointer
+    // behind an empty asm: the loads can neither be hoisted to the kernel's start nor merged across the bodies.  (Read from the
+    // by-value A they were all requested in the prologue and stayed live across the four bodies -- 37 to 52 scalar registers of
+    // the list instantiations spilled into vector lanes, 30 v_writelane per wave up front and a v_readlane wherever one was used.)
 #define RH_S4_BODY(K)                                                                                                  \
     {                                                                                                                  \
         const int slo = max(lo, base) - base, shi = min(hi, base + nch[K]) - base;                                     \
         if (slo < shi) {                                                                                               \
+            const RH4_CONST_AS S4KernArgs *ka = kargs;                                                                 \
+            asm volatile("" : "+s"(ka));                                                                               \
+            const RH4_CONST_AS S4KindArgs *Kb = &ka->A.k[K];                                                           \
+            const uint64_t *const en_k = Kb->en;                                                                       \
+            const double *const pts_k = Kb->pts;                                                                       \
             if (ran) __syncthreads();   /* the previous segment's waves are done with the tile and the list */        \
-            if (!ran || A.k[K].en != staged_en || A.k[K].pts != staged_pts) {   /* (another point set: its own boxes and masks too) */ \
-                s4_stage(sh, A.k[K].pts, A.k[K].stride, s, A.k[K].en, g0 * 64, A.k[K].gb32, A.k[K].gm32, A.ngroups);   \
-                staged_en = A.k[K].en;                                                                                 \
-                staged_pts = A.k[K].pts;                                                                               \
+            if (!ran || en_k != staged_en || pts_k != staged_pts) {   /* (another point set: its own boxes and masks too) */ \
+                s4_stage(sh, pts_k, Kb->stride, s, en_k, g0 * 64, Kb->gb32, Kb->gm32, ka->A.ngroups);                  \
+                staged_en = en_k;                                                                                      \
+                staged_pts = pts_k;                                                                                    \
                 S4_STAT(A.stats, 96 + 1, 1);                                                                           \
             } else { S4_STAT(A.stats, 96 + 2, 1); if (threadIdx.x == 0) { sh.npairs = 0; sh.next_batch = 0; } }   /* same tile, same enabled words */   \
             __syncthreads();                                                                                           \
@@ -543,7 +576,7 @@ score4_kernel(int64_t s, const S4AllArgs A, int32_t *__restrict__ counts, int db
             for (int g = 0; g < S4_TG; g++) live |= sh.len[g] != 0 ? (1u << g) : 0u;                                   \
             live = __builtin_amdgcn_readfirstlane(live);                                                               \
             { int ww = 0; for (int g = 0; g < S4_TG; g++) ww |= sh.weirdw[g]; weird = __builtin_amdgcn_readfirstlane(ww) != 0; }  \
-            if (live != 0) score4_segment<K, R, MASK, F32, LIST>(sh, A.k[K], LIST ? A.stcount + (st4 + K) : A.k[K].nk, LIST ? A.stlist + (st4 + K) * A.stcap : nullptr, A.bstride, slo, shi, A.k[K].pts, A.k[K].stride, g0, live, weird, counts, dbg, A.masks, A.occ, A.mstride, A.stats); \
+            if (live != 0) score4_segment<K, R, MASK, F32, LIST>(sh, Kb, pil, LIST ? ka->A.stcount + (st4 + K) : Kb->nk, LIST ? ka->A.stlist + (st4 + K) * ka->A.stcap : nullptr, ka->A.bstride, slo, shi, pts_k, Kb->stride, g0, live, weird, counts, dbg, ka->A.masks, ka->A.occ, ka->A.mstride, A.stats); \
             else S4_STAT(A.stats, 96 + 3, 1);                                                                         \
             ran = true;                                                                                                \
         }                                                                                                              \

@@ -735,6 +735,40 @@ static __host__ __device__ __forceinline__ uint64_t books2_sure64(const uint32_t
     const uint32_t hi = books2_compress(w[2] & RH_BOOKS2_SIGN) | (books2_compress(w[3] & RH_BOOKS2_SIGN) << 16);
     return ((uint64_t)hi << 32) | lo;
 }
+
+// ---- Books in place (counts-only launches).  Nothing behind the point loops needs the undecided bits of a pair in point order:
+// the ring entry names its point itself.  The words' undecided bits sit at the sign places (odd bits), so two words interleave
+// into one without a compression: lo = U0 | (U1 >> 1), hi = U2 | (U3 >> 1) with Uq = books2_und_bits(w[q]) -- bit 31 - 2 j of
+// a half holds point j of its first word, bit 30 - 2 j point 16 + j of its second.  Bit L of the 64-bit word therefore stands
+// for point books2_point_of_bit(L), a fixed permutation of 0 .. 63 (a lane constant in the kernel), and popcounts, ranks and
+// "any" read the same off either form.  Host and device run these very statements (rh_dbg_books2_inplace).
+static __host__ __device__ __forceinline__ uint64_t books2_und64_inplace(const uint32_t (&w)[4])
+{
+    const uint32_t lo = books2_und_bits(w[0]) | (books2_und_bits(w[1]) >> 1);
+    const uint32_t hi = books2_und_bits(w[2]) | (books2_und_bits(w[3]) >> 1);
+    return ((uint64_t)hi << 32) | lo;
+}
+static __host__ __device__ __forceinline__ int books2_point_of_bit(int L)
+{
+    return (L & 32) + ((~L & 1) << 4) + ((31 - (L & 31)) >> 1);
+}
+// a point-ordered word (bit p = point p: the group's enabled word) in the books' order -- the inverse of books2_compress per
+// 16 points; for the rare pairs that ignore their books (exact-only records, tiles with a non-finite value)
+static __host__ __device__ __forceinline__ uint32_t books2_expand(uint32_t x)
+{
+    x = (x | (x << 8)) & 0x00ff00ffu;
+    x = (x | (x << 4)) & 0x0f0f0f0fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    x = (x | (x << 1)) & 0x55555555u;              // point j at bit 2 j
+    return __builtin_bitreverse32(x);              // point j at bit 31 - 2 j
+}
+static __host__ __device__ __forceinline__ uint64_t books2_deposit64(uint64_t v)
+{
+    const uint32_t a = (uint32_t)v, b = (uint32_t)(v >> 32);
+    const uint32_t lo = books2_expand(a & 0xffffu) | (books2_expand(a >> 16) >> 1);
+    const uint32_t hi = books2_expand(b & 0xffffu) | (books2_expand(b >> 16) >> 1);
+    return ((uint64_t)hi << 32) | lo;
+}
 #endif   // __HIPCC__
 
 }  // namespace rh4

@@ -515,6 +515,27 @@ extern "C" int rh_dbg_books2(const float *u2, int64_t nseq, int32_t *sure_count_
     return RH_OK;
 }
 
+// the undecided word of the counts-only launches as the host runs it (score4_device.h, "Books in place"): per sequence of 64
+// values u' the packed word in the books' own bit order; pi_out[L] = the point that bit L stands for; and, for point-ordered
+// words (may be null), what books2_deposit64 makes of them -- the form the pairs that ignore their books queue.  Host only.
+extern "C" int rh_dbg_books2_inplace(const float *u2, int64_t nseq, uint64_t *packed_out, int32_t *pi_out, const uint64_t *point_words,
+                                     uint64_t *deposit_out)
+{
+    if (nseq < 0 || pi_out == nullptr || (nseq > 0 && (u2 == nullptr || packed_out == nullptr)) || ((point_words == nullptr) != (deposit_out == nullptr))) {
+        rh_set_error("rh_dbg_books2_inplace: bad arguments");
+        return RH_E_INVALID;
+    }
+    for (int L = 0; L < 64; L++) pi_out[L] = books2_point_of_bit(L);
+    for (int64_t s = 0; s < nseq; s++) {
+        uint32_t w[4] = { 0u, 0u, 0u, 0u };
+        for (int q = 0; q < 4; q++)
+            for (int j = 0; j < 16; j++) w[q] = books2_push(w[q], u2[64 * s + 16 * q + j]);
+        packed_out[s] = books2_und64_inplace(w);
+        if (point_words != nullptr) deposit_out[s] = books2_deposit64(point_words[s]);
+    }
+    return RH_OK;
+}
+
 // u and u' of a plane, sphere or cylinder candidate on n points, on the host: u = max(ua, ub) by the functions every other caller
 // uses on the record cls_make builds, u' by the point loops' own path -- that record doubled by cls_double, then cls_u2.  Host
 // only: needs no GPU.
